@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the HIP backend on the reference's headline workloads (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it stages the scene, renders W untimed steps, times K steps, writes the
+outputs of the last timed step when --dump-outputs is given (dump_outputs below) and prints the line. Everything else
+moves behind `--full`: the roofline (a counters frame of its own), the sustained rate, the plugin path, the parity legs
+of all three builds against the CPU oracle, the CPU baseline, and for N > 1 the bit-for-bit check against one GPU.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself, as a child process
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...`, rendezvous on 127.0.0.1) -- decided before
@@ -20,14 +25,14 @@ timed region; nothing is read back to the host inside it.
 (25 camera paths are traced per pixel per pass, renderer/cpu/Renderer.cpp:21,38; depth limit 8, MIS on.)
 
 value = Msamples/s = camera paths of all ranks / max-over-ranks wall time. Rank 0 prints ONE
-JSON line. The oracle / compiled reference are used ONLY for the cpu_baseline and parity legs, never inside the timed
-region.
+JSON line. The oracle / compiled reference are used ONLY for the cpu_baseline and parity legs of --full, never inside the
+timed region.
 
 Which numerics build is timed (round 5): EXACT -- the one of the three (include/kajo_hip.h: fast, strict, exact) that is the
 fastest to meet BASELINE.json's "per-pixel RMSE < 1e-4 vs reference" on the frame being timed. `value`, `roofline` and
-`config.numerics` are that build's; the parity leg renders the WHOLE timed frame (1920 x 1080 x 16 passes) with the CPU
-oracle (~25 s of the host's cores, outside the timed region) and compares every build with it; the other two builds are
-reported beside it (`fast_mode`, `strict_mode`). `--fast` / `--strict` time those instead.
+`config.numerics` are that build's; with --full the parity leg renders the WHOLE timed frame (1920 x 1080 x 16 passes) with
+the CPU oracle (~25 s of the host's cores, outside the timed region) and compares every build with it; the other two builds
+are reported beside it (`fast_mode`, `strict_mode`). `--fast` / `--strict` time those instead.
 """
 import argparse
 import ctypes as C
@@ -261,6 +266,27 @@ def scheduler_run_leg(scene, W, H, passes, numerics, frames=8):
             "command": "kajo_render -w %d -h %d -r hip --passes %d --batch %d --gpus 1 --json --scene-pod <spheres.json fixture> --%s" % (W, H, passes * (frames + 2), passes, numerics)}
 
 
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, argb, W, H):
+    """--dump-outputs: what the last timed step hands its caller -- the ARGB8 image it resolved on the device (Image::pixels,
+    renderer/Image.h:18-20) -- as DIR/argb8.npy, float32 (H, W, 4): channels A, R, G, B (0-255), row 0 = top; 33 MB at
+    1920 x 1080. A frame that would exceed DUMP_BYTES (3840 x 2160) is written as a fixed sample of 2^20 pixels (seed 0),
+    (2^20, 4), with their row-major indices in pixel_index.npy (float64).
+    The scene, seed and pass count follow from the arguments alone, so two runs with the same arguments can be compared file
+    for file."""
+    os.makedirs(out_dir, exist_ok=True)
+    px = argb.cpu().numpy().view(np.uint32).reshape(-1)
+    shape = (H, W)
+    if W * H * 4 * 4 > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(W * H, 1 << 20, replace=False))
+        px, shape = px[idx], (len(idx),)
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+    argb8 = np.stack([(px >> s) & 0xFF for s in (24, 16, 8, 0)], -1).astype(np.float32)
+    np.save(os.path.join(out_dir, "argb8.npy"), argb8.reshape(shape + (4,)))
+
+
 STAGE_TAG = "KAJO_BENCH_STAGE"
 
 
@@ -307,14 +333,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)  # (the first launches of a handle measure and order its blocks: five untimed steps leave them behind)
     ap.add_argument("--workload", default="auto", choices=["auto", "c2", "c3"],
                     help="auto: c2 (1080p, 16 passes) on one GPU, c3 (4K, 64 passes, strong scaling) on several")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the cpu_baseline / parity / other-mode legs")
+    ap.add_argument("--full", action="store_true", help="besides the headline: roofline, sustained rate, plugin path, parity legs of all "
+                    "three builds, CPU baseline; N > 1: the bit-for-bit check against one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the outputs of the last one as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline / parity / other-mode legs")
     ap.add_argument("--exact", action="store_true", help="time the EXACT kernels (the default: the fastest build that meets BASELINE.json's RMSE < 1e-4)")
     ap.add_argument("--strict", action="store_true", help="time the STRICT kernels (bit-identical to the oracle)")
     ap.add_argument("--fast", action="store_true", help="time the FAST kernels (1.6 x the rate; RMSE ~6e-4 on the timed frame)")
-    ap.add_argument("--sustain-seconds", type=float, default=3.0, help="N = 1: after the K timed steps, this many seconds of back-to-back "
-                    "frames of the same build, reported as `sustained` (0 = skip)")
+    ap.add_argument("--sustain-seconds", type=float, default=3.0, help="--full, N = 1: after the K timed steps, this many seconds of "
+                    "back-to-back frames of the same build, reported as `sustained` (0 = skip)")
     ap.add_argument("--passes-per-launch", type=int, default=0)
-    ap.add_argument("--no-check", action="store_true", help="N > 1: skip the bit-for-bit check against a one-GPU frame")
+    ap.add_argument("--no-check", action="store_true", help="--full, N > 1: skip the bit-for-bit check against a one-GPU frame")
     ap.add_argument("--separate-compose", action="store_true",
                     help="N > 1: rank 0 composes the whole float frame and resolves that (two passes over the data, rounds 1-3) instead "
                          "of resolving straight from the gathered tile buffers")
@@ -327,6 +356,8 @@ def main():
                          "there because memory the library allocated is foreign to the process group's allocator: this switch lets a run on "
                          "real hardware tell whether it is needed)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -393,7 +424,7 @@ def main():
 def run_ranks(args, world, rank, local_rank):
     numerics = "fast" if args.fast else ("strict" if args.strict else "exact")
     sched_leg = None
-    if world == 1 and not args.no_cpu_baseline and args.workload in ("auto", "c2") and torch.cuda.device_count() > 0:
+    if args.full and world == 1 and not args.no_cpu_baseline and args.workload in ("auto", "c2") and torch.cuda.device_count() > 0:
         # the plugin path, in a child process, BEFORE this process initialises the GPU (device_count() does not)
         from kajo_amd.scene import Scene as _Scene
         _z = np.load(os.path.join(ROOT, "tests", "golden", "scenes.npz"))
@@ -501,10 +532,13 @@ def run_ranks(args, world, rank, local_rank):
     dt_local = time.perf_counter() - t0
     c1 = r.counters()
     dt = dt_local
+    if args.dump_outputs and rank == 0:
+        note_stage(rank, "dump outputs")
+        dump_outputs(args.dump_outputs, argb, W, H)
     # The K timed steps are a fraction of a second of GPU time. The same loop for a few seconds more, OUTSIDE the timed region
     # and reported beside it: clocks, power and temperature have settled by then.
     sustained = None
-    if world == 1 and args.sustain_seconds > 0 and args.steps > 0:
+    if args.full and world == 1 and args.sustain_seconds > 0:
         per_step = dt_local / args.steps
         k = max(args.steps, int(args.sustain_seconds / max(per_step, 1e-6)))
         ts = time.perf_counter()
@@ -531,7 +565,7 @@ def run_ranks(args, world, rank, local_rank):
 
     # ---- N > 1: the composed frame against ONE GPU rendering the same frame alone, bit for bit (2 steps) ---------
     check = None
-    if world > 1 and not args.no_check:
+    if args.full and world > 1 and not args.no_check:
         note_stage(rank, "bit-for-bit check against one GPU")
         r.reset()
         for _ in range(2):
@@ -562,39 +596,11 @@ def run_ranks(args, world, rank, local_rank):
     note_stage(rank, "report")
     out = None
     if rank == 0:
-        kernel = "kajo_render_" + numerics
-        # work per path from the device counters of a separate, untimed frame (deterministic)
-        rc = factory(W, H, tile_index=0, tile_count=world, counters=True)
-        cc = rc.render(min(PASSES, 16)).counters()
-        rc.close()
-        trav = cc["traversals"] / cc["paths"]
-        vert = cc["vertices"] / cc["paths"]
-        fpp = flops_per_path(scene.n_planes, scene.n_spheres, trav, vert)
         launches = c1["launches"] - c0["launches"]
         kernel_ms = (c1["kernelMs"] - c0["kernelMs"]) / max(launches, 1)
         paths_per_launch = (c1["paths"] - c0["paths"]) / max(launches, 1)
-        achieved = fpp * paths_per_launch / (kernel_ms * 1e-3) / 1e12
-        owned_px = (c1["paths"] - c0["paths"]) / (n * n * PASSES * args.steps)
-        hbm_gbs = 32.0 * owned_px / (kernel_ms * 1e-3) / 1e9  # float4 read + write per pixel per launch
         workload = ("data/spheres.json (parsed-scene fixture), %dx%d, %d spp = %d passes x S=32 (25 camera paths/px/pass), "
                     "depth 8, MIS on; %s" % (W, H, PASSES * SPP, PASSES, wl_label))
-        pc = profile_counters(kernel, wl) if world == 1 else None
-        roof = {"bound": "valu", "achieved": achieved, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
-                "frac": achieved / PEAK_FP32_TFLOPS,
-                "traffic": pc["hbm_bytes_per_launch"] if pc else None,
-                "traffic_source": (pc["source"] + " (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE over this command, on kernels with this source hash)") if pc
-                                  else "no counters file for these kernels (tools/profile_round.sh <round> writes profiles/r<NN>_counters.json; the newest one collected on this source hash is used)",
-                "kernel": kernel, "kernel_ms_per_launch": kernel_ms, "launches_per_step": launches / args.steps,
-                "passes_per_launch": ppl,
-                "flops_per_path": fpp, "traversals_per_path": trav, "vertices_per_path": vert,
-                "lane_efficiency": cc["traversals"] / max(cc["laneSlots"], 1),
-                "hbm": {"achieved": hbm_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": hbm_gbs / PEAK_HBM_GBS,
-                        "algorithmic_bytes_per_launch": 32.0 * owned_px}}
-        if pc:
-            # FP32 work the launch really executed: the PMC FLOP count x the share of lanes that were active
-            roof["executed_flops"] = {"per_launch": pc["executed_fp32_flops_per_launch"],
-                                      "tflops": pc["executed_fp32_flops_per_launch"] / (kernel_ms * 1e-3) / 1e12,
-                                      "valu_lane_utilisation": pc["valu_lane_utilisation"], "source": pc["source"]}
         out = {
             "metric": "Msamples/s", "value": value, "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
@@ -612,11 +618,40 @@ def run_ranks(args, world, rank, local_rank):
                        # launch-shaping knobs are compile-time constants of libkajo_hip.so (no getenv in it); a tools' twin
                        # selected with KAJO_HIP_LIB reads them from the environment, so whatever was set is recorded
                        "tuning_env": {k: v for k, v in sorted(os.environ.items()) if k.startswith("KAJO_") and k != "KAJO_HIP_LIB"}},
-            "roofline": roof,
             "in_kernel_value": paths_per_launch / (kernel_ms * 1e-3) / 1e6 * world,
-            "mtraversals_per_s": value * trav,
             "nominal_rays_x_spp_x_bounces_per_s_M": W * H * n * n * PASSES * DEPTH * args.steps / dt / 1e6,
         }
+        if args.full:
+            kernel = "kajo_render_" + numerics
+            # work per path from the device counters of a separate, untimed frame (deterministic)
+            rc = factory(W, H, tile_index=0, tile_count=world, counters=True)
+            cc = rc.render(min(PASSES, 16)).counters()
+            rc.close()
+            trav = cc["traversals"] / cc["paths"]
+            vert = cc["vertices"] / cc["paths"]
+            fpp = flops_per_path(scene.n_planes, scene.n_spheres, trav, vert)
+            achieved = fpp * paths_per_launch / (kernel_ms * 1e-3) / 1e12
+            owned_px = (c1["paths"] - c0["paths"]) / (n * n * PASSES * args.steps)
+            hbm_gbs = 32.0 * owned_px / (kernel_ms * 1e-3) / 1e9  # float4 read + write per pixel per launch
+            pc = profile_counters(kernel, wl) if world == 1 else None
+            roof = {"bound": "valu", "achieved": achieved, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
+                    "frac": achieved / PEAK_FP32_TFLOPS,
+                    "traffic": pc["hbm_bytes_per_launch"] if pc else None,
+                    "traffic_source": (pc["source"] + " (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE over this command, on kernels with this source hash)") if pc
+                                      else "no counters file for these kernels (tools/profile_round.sh <round> writes profiles/r<NN>_counters.json; the newest one collected on this source hash is used)",
+                    "kernel": kernel, "kernel_ms_per_launch": kernel_ms, "launches_per_step": launches / args.steps,
+                    "passes_per_launch": ppl,
+                    "flops_per_path": fpp, "traversals_per_path": trav, "vertices_per_path": vert,
+                    "lane_efficiency": cc["traversals"] / max(cc["laneSlots"], 1),
+                    "hbm": {"achieved": hbm_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": hbm_gbs / PEAK_HBM_GBS,
+                            "algorithmic_bytes_per_launch": 32.0 * owned_px}}
+            if pc:
+                # FP32 work the launch really executed: the PMC FLOP count x the share of lanes that were active
+                roof["executed_flops"] = {"per_launch": pc["executed_fp32_flops_per_launch"],
+                                          "tflops": pc["executed_fp32_flops_per_launch"] / (kernel_ms * 1e-3) / 1e12,
+                                          "valu_lane_utilisation": pc["valu_lane_utilisation"], "source": pc["source"]}
+            out["roofline"] = roof
+            out["mtraversals_per_s"] = value * trav
         if sustained:
             sustained["value"] = paths_per_step * sustained["steps"] / sustained["seconds"] / 1e6
             sustained["unit"] = "Msamples/s"
@@ -633,7 +668,7 @@ def run_ranks(args, world, rank, local_rank):
             if check:
                 out["multi_gpu"].update(check)
     r.close()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the parity legs first, the timed CPU baseline last (its libraries are built with the reference's fast-math flags)
         if sched_leg:
             # hip::Scheduler::run() on the same frame with the same numerics build, next to ms_per_step: the difference is the 8 MB

@@ -56,7 +56,7 @@ def test_scene_staging(san, scenes):
 
 def test_scene_loader(san):
     files = [os.path.join(ROOT, "kajo_amd", "data", n) for n in ("caustics.json", "dialect.json")]
-    files += [p for p in (os.path.join("/root/reference/data", n) for n in ("spheres.json", "test.json")) if os.path.exists(p)]
+    files += [os.path.join(ROOT, "tests", "golden", "scenes", n) for n in ("spheres.json", "test.json")]  # the reference's own scene files
     for aspect in (1.0, 1920.0 / 1080.0, 640.0 / 480.0):  # (the aspects of the six parsed scenes of tests/golden/scenes.npz)
         out = san("parse", aspect, *files)
         assert out.count(" spheres ") == len(files)

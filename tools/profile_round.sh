@@ -17,7 +17,7 @@ OUT=gpurun_out/${R}prof
 mkdir -p $OUT
 case $STAGE in
 a)
-  python3 bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench done"
+  python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench done"
   for m in exact fast strict; do
     flag=$([ $m = exact ] && echo "" || echo "--$m")
     rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$m -- python3 bench.py $flag --steps 40 --warmup 5 --no-cpu-baseline --sustain-seconds 0 > $OUT/stats_$m.log 2>&1
@@ -41,7 +41,7 @@ b)
   echo "block profiles done"
   ;;
 c)
-  python3 bench.py --steps 20 --warmup 5 > $OUT/bench_final.json 2> $OUT/bench_final.err; echo "final bench done"
+  python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench_final.json 2> $OUT/bench_final.err; echo "final bench done"
   (echo "== EXACT"; python3 tools/configs.py exact; echo "== FAST"; python3 tools/configs.py; echo "== STRICT"; python3 tools/configs.py strict) > $OUT/configs.txt 2>&1
   python3 tools/configs_roofline.py $OUT/configs_roofline.json > $OUT/configs_roofline.txt 2>&1
   echo "configs done"

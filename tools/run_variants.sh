@@ -6,6 +6,6 @@ for lib in kajo_amd/libkajo_hip.so kajo_amd/libkajo_hip_r02*.so kajo_amd/libkajo
   [ -f "$lib" ] || continue
   echo "== $lib"
   for mode in "" "--strict"; do
-  KAJO_HIP_LIB=$PWD/$lib python bench.py $mode --steps 8 --warmup 2 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('  %-8s %9.1f Msamples/s  kernel %6.2f ms' % ('$mode' or 'fast', d['value'], d['roofline']['kernel_ms_per_launch']))"
+  KAJO_HIP_LIB=$PWD/$lib python bench.py $mode --steps 8 --warmup 2 --full --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('  %-8s %9.1f Msamples/s  kernel %6.2f ms' % ('$mode' or 'fast', d['value'], d['roofline']['kernel_ms_per_launch']))"
   done
 done
