@@ -22,6 +22,8 @@
  *   kajo_hip_read_radiance   the radianceMap local of Renderer.cpp:36 (not observable in the
  *                            reference; exported here for parity tests)
  *   kajo_hip_counters        the samples/s bookkeeping of Preview::update (Preview.cpp:79-98)
+ *   kajo_hip_read_aov        (no counterpart: the reference has no AOVs) the first-hit albedo, normal and depth a denoiser
+ *                            takes beside the beauty image, over the beauty render's own camera samples (KAJO_FLAG_AOV)
  *   kajo_hip_destroy         the unique_ptr members of cpu::Scheduler (cpu/Scheduler.h:29-31)
  *
  * Pixels are dealt to GPUs as fixed-size tiles: a handle created with
@@ -91,6 +93,10 @@ extern "C" {
                                    (kajo_render_*_lights) instead of the one that samples the BSDF in the light's visit (same results in the
                                    FAST and EXACT builds bit for bit and in the STRICT build, which stays the oracle; the hold thresholds
                                    stay those of the scene's own instance; for A/B runs and tests) */
+#define KAJO_FLAG_AOV 1024u   /* first-hit AOVs for denoisers (kajo_hip_read_aov): create() allocates and zeroes two whole-frame float4 buffers
+                                   (2 x W x H x 16 bytes) and every kajo_hip_render enqueues one more kernel per render launch, on the handle's
+                                   stream, over the same passes' camera samples. Whole frame on one handle only: with tileCount != 1 create()
+                                   refuses the flag (KAJO_E_INVALID). Without it nothing is allocated or launched. */
 
 typedef struct KajoParams {
     int32_t samplesPerPass; /* S: nominal samples per pixel per pass (reference: 32, Renderer.cpp:21);
@@ -113,7 +119,8 @@ typedef struct KajoCounters {
     uint64_t primitiveTests; /* traversals * (nPlanes + nSpheres): what walking every object costs; with
                                 the uniform grid of large scenes the spheres actually tested are fewer */
     uint64_t laneSlots;      /* 64 * wave-iterations of the trace loop: traversals / laneSlots = lane efficiency */
-    double kernelMs;         /* summed device time of the render kernels (HIP events on the handle's stream) */
+    double kernelMs;         /* summed device time of the render kernels (HIP events on the handle's stream; not the AOV kernel of
+                                KAJO_FLAG_AOV, which runs outside them) */
     uint64_t launches;       /* render kernel launches */
     uint64_t shadowQueries;  /* large scenes: shadow rays answered from the lights' visibility lists inside the light loop (they
                                 are not among `traversals`, which then counts camera and extension rays only) */
@@ -139,14 +146,15 @@ int kajo_hip_destroy(kajo_hip_t h); /* NULL is accepted */
    (1-4, 5-8, ...): a group is summed from zero in pass order, then added to the total; a group in progress is added last. */
 int kajo_hip_render(kajo_hip_t h, int passes);
 int kajo_hip_wait(kajo_hip_t h);
-/* Zero the accumulation and restart the pass numbering at 1. */
+/* Zero the accumulation (and the AOV buffers and their sample count) and restart the pass numbering at 1. */
 int kajo_hip_reset(kajo_hip_t h);
 /* Continue a progressive session from pass `passesDone`: the next pass rendered is passesDone + 1 (the reference's loop
    `for (pass = 1;; pass++)`, Renderer.cpp:44, has no end). The call does not touch the accumulation buffer and DECLARES
    that it holds the sum of `passesDone` passes: kajo_hip_resolve_* divide by the pass count and kajo_hip_counters reports
    it, so the caller restores the buffer of the session being continued through kajo_hip_tile_buffer() first (or calls
    kajo_hip_reset() and set_pass_count(0)). FAST / EXACT: a passesDone inside a group of four continues from the buffer as
-   one sum (the passes of the group so far are not known apart). Pass numbers run to 2^31 - 2. */
+   one sum (the passes of the group so far are not known apart). Pass numbers run to 2^31 - 2. The AOV buffers of KAJO_FLAG_AOV are not
+   touched: later passes are traced with their own pass numbers' streams and added to them. */
 int kajo_hip_set_pass_count(kajo_hip_t h, int passesDone);
 
 /* Whole-frame outputs; valid when tileCount == 1, or on a handle that has been composed.
@@ -171,6 +179,28 @@ int kajo_hip_compose(kajo_hip_t h, const void* gathered);
    one pass over the data, without the whole-frame float buffer (renderer/cpu/Renderer.cpp:70-75 per pixel, as
    kajo_hip_resolve_argb8_device). kajo_hip_compose stays for kajo_hip_read_radiance. */
 int kajo_hip_resolve_gathered_argb8_device(kajo_hip_t h, const void* gathered, void* dst);
+
+/* First-hit AOVs (KAJO_FLAG_AOV), the buffers a denoiser takes beside the beauty image. The samples are the beauty render's camera samples
+   and no others: every pass rendered into the handle, every stratum (sx, sy) of n = floor(sqrt(S)), the same jittered ray from the same
+   stream key (include/kajo_stream.h; renderer/cpu/Renderer.cpp:51-64). Per sample, h = the kernels' own closest-hit walk of that ray:
+     hit     1 if h hit an object, else 0
+     albedo  hit: min(max((diffuse + specular) + transparency, 0), 1) per RGB channel of the hit object's material, in that order of
+             operations (the three lobe colours of Shader.cpp:129-131); miss: backgroundColor.rgb, unclamped (what the path returns,
+             Shader.cpp:116-117)
+     normal  hit: the world-space normal of the hit as kajo_hip_kat_trace reports it (not flipped towards the ray); miss: 0
+     depth   hit: the ray's maxDistance (t of the unit-length camera direction); miss: 0
+   Per pixel two float4 sums, A = (sum albedo.rgb, sum hit) and B = (sum normal.xyz, sum depth), formed in float32 one sample at a time, in
+   pass order and then stratum order sy * n + sx. So the buffers are a function of (scene, parameters, passes rendered), not of how the
+   passes were cut into render() calls or launches. The hit count is exact up to 2^24 samples per pixel.
+   STRICT handles give the oracle's walk and normals bit for bit; EXACT handles compute the AOVs with STRICT's arithmetic (its walk and
+   normals are STRICT's); FAST handles with FAST's.
+   albedoHits, normalDepth: HOST pointers to width*height*4 floats (row 0 = top), A and B; either may be NULL. *samples (may be NULL):
+   n^2 x the passes rendered into the buffers since create() or kajo_hip_reset() (mean albedo = A.rgb / samples, mean normal =
+   B.xyz / samples, mean depth of the hits = B.w / A.w). Waits for outstanding work. KAJO_E_STATE on a handle created without the flag. */
+int kajo_hip_read_aov(kajo_hip_t h, float* albedoHits, float* normalDepth, int64_t* samples);
+/* Name of the AOV kernel instance the handle launches (one per scene class, as the render kernels: the whole scene in LDS; the grid's cell
+   lists in LDS or in global memory; with or without visibility lists), or NULL without KAJO_FLAG_AOV. For tests and profiles. */
+const char* kajo_hip_aov_kernel(kajo_hip_t h);
 
 /* Use an existing HIP stream (hipStream_t passed as void*) instead of the handle's own. */
 int kajo_hip_set_stream(kajo_hip_t h, void* stream);

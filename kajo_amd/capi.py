@@ -33,6 +33,7 @@ KAJO_FLAG_DEFERRED = 64  # experiment library libkajo_hip_exp.so only
 KAJO_FLAG_NO_SHADOW_LISTS = 128
 KAJO_FLAG_NO_ONE_LIGHT = 256  # every numerics build: the any-number-of-lights instance for a one-light scene (A/B, tests)
 KAJO_FLAG_EXACT = 512  # decision-exact numerics: STRICT's decisions, FAST's radiance arithmetic
+KAJO_FLAG_AOV = 1024  # first-hit albedo / normal / depth buffers over the beauty render's camera samples (kajo_hip_read_aov)
 
 # every symbol include/kajo_hip.h declares
 EXPORTS = [
@@ -41,7 +42,7 @@ EXPORTS = [
     "kajo_hip_tile_buffer", "kajo_hip_compose", "kajo_hip_set_stream", "kajo_hip_counters",
     "kajo_hip_stage_scene", "kajo_hip_last_error", "kajo_hip_version", "kajo_hip_kat_trace", "kajo_hip_kat_shade",
     "kajo_hip_kat_strictmath", "kajo_hip_stage_shadow_lists", "kajo_hip_resolve_gathered_argb8_device", "kajo_hip_stage_info",
-    "kajo_hip_launch_order",
+    "kajo_hip_launch_order", "kajo_hip_read_aov", "kajo_hip_aov_kernel",
 ]
 
 
@@ -116,6 +117,10 @@ def lib():
             L.kajo_hip_stage_info.argtypes = [C.POINTER(KajoScene), C.POINTER(KajoStageInfo)]
         if hasattr(L, "kajo_hip_launch_order"):  # (round 6)
             L.kajo_hip_launch_order.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+        if hasattr(L, "kajo_hip_read_aov"):  # (the experiment libraries of earlier rounds do not have it)
+            L.kajo_hip_read_aov.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+            L.kajo_hip_aov_kernel.argtypes = [C.c_void_p]
+            L.kajo_hip_aov_kernel.restype = C.c_char_p
         L.kajo_hip_kat_trace.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
         L.kajo_hip_kat_shade.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.kajo_hip_kat_strictmath.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

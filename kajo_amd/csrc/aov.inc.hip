@@ -1,0 +1,184 @@
+// aov.inc.hip -- first-hit AOVs for denoisers (KAJO_FLAG_AOV, include/kajo_hip.h kajo_hip_read_aov), included by kernel_strict.hip and
+// kernel_fast.hip behind integrator.inc.hip: the SAME device functions (stageToLds, trace, hitNormal) on the beauty render's own camera
+// samples. The STRICT instance serves STRICT and EXACT handles: EXACT's camera rays, walk and normals are STRICT's arithmetic.
+//
+// Shape: one wave per 8x8 pixel block and one lane per pixel, as in the render kernels, so that a wave's camera rays stay coherent. A lane
+// reads its pixel's two float4 sums, adds its samples one at a time -- pass order, then stratum sy * n + sx -- and writes them back: the
+// sequential loop is what fixes the summation order, so the buffers do not depend on how the passes were cut into launches.
+// Per sample: hit = id != 0; albedo = clamp((diffuse + specular) + transparency, 0, 1) of the hit object's material (the three lobe colours
+// of Shader.cpp:129-131), the background colour on a miss (Shader.cpp:116-117); the world normal hitNormal gives (no flip), 0 on a miss;
+// depth = the ray's maxDistance, 0 on a miss.
+#define KAJO_AOV_CAT2(a, b) a##b
+#define KAJO_AOV_CAT(a, b) KAJO_AOV_CAT2(a, b)
+
+namespace
+{
+
+// The camera block of renderBody (integrator.inc.hip, MODE_NEW; Renderer.cpp:51-64), restated: the stream key of (pixel, stratum, pass),
+// one generator step, the jittered point on the image plane and the normalised direction. Same operations on the same operands in the
+// same order, so the same bits in the STRICT build (tests/test_hip_aov.py replays them against the oracle).
+KDEV void aovCameraRay(const AovArgs& args, const LdsScene& lds, int spx, int spy, int sampleX, int sampleY, int pass, F3& O, F3& d)
+{
+    const float curPixX = spx * args.pixelWidth, curPixY = (args.H - spy) * args.pixelHeight;
+    uint32_t a = (uint32_t)(spy * args.W + spx) ^ 0x61707865u, c = ((uint32_t)args.seed ^ 0x79622d32u) ^ ((uint32_t)pass >> 16),
+             dd = (uint32_t)(args.seed >> 32) ^ 0x6b206574u;
+    uint32_t b = ((uint32_t)(sampleY * args.n + sampleX) | ((uint32_t)pass << 16)) ^ 0x3320646eu;
+    KAJO_QUARTER_ROUND(a, b, c, dd);
+    KAJO_QUARTER_ROUND(a, b, c, dd);
+    KAJO_QUARTER_ROUND(a, b, c, dd);
+    Rng fresh;
+    fresh.lo = (uint64_t)a | ((uint64_t)b << 32);
+    fresh.hi = (uint64_t)c | ((uint64_t)dd << 32);
+    rngStep(fresh);
+    const float offX = unitBits((uint32_t)fresh.lo);
+    const float offY = unitBits((uint32_t)(fresh.lo >> 32));
+    const float sx = curPixX + sampleX * args.sampleWidth + offX * args.sampleWidth;
+    const float sy = curPixY + sampleY * args.sampleHeight + offY * args.sampleHeight;
+    const DFloat4 c0 = lds.camera[0], c1 = lds.camera[1], c2 = lds.camera[2], c3 = lds.camera[3];
+    O = f3(c3.x, c3.y, c3.z);
+    d = normalize(f3(c0.x, c0.y, c0.z) + f3(c1.x, c1.y, c1.z) * sx + f3(c2.x, c2.y, c2.z) * sy - O);
+}
+
+// COLD_LDS, LISTS, GHOME: as renderBody's (the instance of the scene class; capi.cpp picks it at create)
+template <bool COLD_LDS, bool LISTS = false, int GHOME = 0>
+KDEV void aovBody(const AovArgs& args, unsigned char* ldsRaw)
+{
+    const DSceneView& sc = args.scene;
+    const LdsScene lds = stageToLds<COLD_LDS>(sc, ldsRaw);
+    const int lane = threadIdx.x & 63;
+    const int block = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6))); // (wave-uniform)
+    const int blocksX = (args.W + 7) >> 3;
+    if (block >= blocksX * ((args.H + 7) >> 3)) // (the grid's last workgroup may have waves beyond the frame: past the last barrier)
+        return;
+    const int px = (block % blocksX) * 8 + (lane & 7), py = (block / blocksX) * 8 + (lane >> 3);
+    const bool inImage = px < args.W && py < args.H;
+    const size_t at = inImage ? (size_t)py * args.W + px : 0;
+    float4* const albedoHits = static_cast<float4*>(args.albedoHits);
+    float4* const normalDepth = static_cast<float4*>(args.normalDepth);
+    float4 A = make_float4(0.0f, 0.0f, 0.0f, 0.0f), B = A;
+    if (inImage) {
+        A = albedoHits[at];
+        B = normalDepth[at];
+    }
+    const F3 bg = f3(sc.background[0], sc.background[1], sc.background[2]);
+    const int n = args.n, endPass = args.firstPass + args.nPasses;
+    for (int pass = args.firstPass; pass < endPass; pass++) {
+        for (int sampleY = 0; sampleY < n; sampleY++) {
+            for (int sampleX = 0; sampleX < n; sampleX++) {
+                F3 O, d;
+                aovCameraRay(args, lds, px, py, sampleX, sampleY, pass, O, d);
+                // (lanes outside the frame trace nothing through the grid; their sums are never written)
+                const Hit h = trace<!COLD_LDS, GHOME, LISTS>(sc, lds, O, d, inImage);
+                F3 albedo = bg, N = f3(0.0f, 0.0f, 0.0f);
+                float depth = 0.0f, hit = 0.0f;
+                if (h.id != 0) {
+                    const DMaterial& m = lds.material[h.id - 1];
+                    const float r = (m.diffuse[0] + m.specular[0]) + m.transparency[0];
+                    const float g = (m.diffuse[1] + m.specular[1]) + m.transparency[1];
+                    const float bl = (m.diffuse[2] + m.specular[2]) + m.transparency[2];
+                    albedo = f3(fminf(fmaxf(r, 0.0f), 1.0f), fminf(fmaxf(g, 0.0f), 1.0f), fminf(fmaxf(bl, 0.0f), 1.0f));
+                    N = hitNormal<LISTS>(sc, lds, h, O, d);
+                    depth = h.t;
+                    hit = 1.0f;
+                }
+                // (a miss adds zeros: every sample is one addition per word, as the definition sums them)
+                A.x += albedo.x;
+                A.y += albedo.y;
+                A.z += albedo.z;
+                A.w += hit;
+                B.x += N.x;
+                B.y += N.y;
+                B.z += N.z;
+                B.w += depth;
+            }
+        }
+    }
+    if (inImage) {
+        albedoHits[at] = A;
+        normalDepth[at] = B;
+    }
+}
+
+} // namespace
+
+// whole scene in LDS
+extern "C" __global__ void __launch_bounds__(256) KAJO_AOV_NAME(const AovArgs args)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ldsRaw[];
+    aovBody<true>(args, ldsRaw);
+}
+
+// hot records in LDS, cold ones in global memory: an instance per home of the grid's cell lists (LDS: _lg), as the render kernels
+extern "C" __global__ void __launch_bounds__(256) KAJO_AOV_CAT(KAJO_AOV_NAME, _big)(const AovArgs args)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ldsRaw[];
+    aovBody<false, false, 2>(args, ldsRaw);
+}
+
+extern "C" __global__ void __launch_bounds__(256) KAJO_AOV_CAT(KAJO_AOV_NAME, _big_lg)(const AovArgs args)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ldsRaw[];
+    aovBody<false, false, 1>(args, ldsRaw);
+}
+
+// scenes with visibility lists: the walk of a closed room of (centre, radius) spheres, nothing else compiled in
+extern "C" __global__ void __launch_bounds__(256) KAJO_AOV_CAT(KAJO_AOV_NAME, _biglist)(const AovArgs args)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ldsRaw[];
+    aovBody<false, true, 2>(args, ldsRaw);
+}
+
+extern "C" __global__ void __launch_bounds__(256) KAJO_AOV_CAT(KAJO_AOV_NAME, _biglist_lg)(const AovArgs args)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ldsRaw[];
+    aovBody<false, true, 1>(args, ldsRaw);
+}
+
+namespace
+{
+const void* aovKernel(int instance)
+{
+    switch (instance) {
+    case KAJO_AOV_BIG: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, _big));
+    case KAJO_AOV_BIG_LG: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, _big_lg));
+    case KAJO_AOV_BIGLIST: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, _biglist));
+    case KAJO_AOV_BIGLIST_LG: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, _biglist_lg));
+    default: return reinterpret_cast<const void*>(KAJO_AOV_NAME);
+    }
+}
+} // namespace
+
+// 256 threads = four pixel blocks per workgroup; `grid` = ceil(blocks / 4). ldsBytes: the scene copy of the instance.
+extern "C" int KAJO_AOV_CAT(KAJO_AOV_NAME, _launch)(const AovArgs* args, int instance, unsigned grid, size_t ldsBytes, void* stream)
+{
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (instance) {
+    case KAJO_AOV_BIG: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, _big), dim3(grid), dim3(256), ldsBytes, st, *args); break;
+    case KAJO_AOV_BIG_LG: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, _big_lg), dim3(grid), dim3(256), ldsBytes, st, *args); break;
+    case KAJO_AOV_BIGLIST: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, _biglist), dim3(grid), dim3(256), ldsBytes, st, *args); break;
+    case KAJO_AOV_BIGLIST_LG: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, _biglist_lg), dim3(grid), dim3(256), ldsBytes, st, *args); break;
+    default: hipLaunchKernelGGL(KAJO_AOV_NAME, dim3(grid), dim3(256), ldsBytes, st, *args); break;
+    }
+    return (int)hipGetLastError();
+}
+
+// Dynamic LDS above the default: the opt-in per function and device, only ever raised (see the render kernels' _set_lds, launch.inc.hip).
+extern "C" int KAJO_AOV_CAT(KAJO_AOV_NAME, _set_lds)(int instance, size_t ldsBytes)
+{
+    static size_t highWaterOfDevice[64][KAJO_AOV_INSTANCES] = {};
+    static std::mutex guard;
+    int device = 0;
+    hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess)
+        return (int)e;
+    if (device < 0 || device >= 64 || instance < 0 || instance >= KAJO_AOV_INSTANCES)
+        return (int)hipErrorInvalidValue;
+    std::lock_guard<std::mutex> lock(guard);
+    size_t& highWater = highWaterOfDevice[device][instance];
+    if (ldsBytes <= highWater)
+        return (int)hipSuccess;
+    e = hipFuncSetAttribute(aovKernel(instance), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
+    if (e == hipSuccess)
+        highWater = ldsBytes;
+    return (int)e;
+}

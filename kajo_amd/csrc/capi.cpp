@@ -48,6 +48,10 @@ int kajo_kat_shade_strict_launch(const RenderArgs*, unsigned grid, size_t lds, v
 int kajo_kat_trace_fast_launch(const KatTraceArgs*, unsigned grid, size_t lds, void* stream);
 int kajo_kat_trace_strict_launch(const KatTraceArgs*, unsigned grid, size_t lds, void* stream);
 int kajo_kat_math_launch(int fn, int n, const void* x, const void* y, void* out, void* stream);
+int kajo_aov_fast_launch(const AovArgs*, int instance, unsigned grid, size_t lds, void* stream);
+int kajo_aov_strict_launch(const AovArgs*, int instance, unsigned grid, size_t lds, void* stream);
+int kajo_aov_fast_set_lds(int instance, size_t lds);
+int kajo_aov_strict_set_lds(int instance, size_t lds);
 }
 
 namespace
@@ -156,6 +160,11 @@ struct KajoHip
     std::vector<hipEvent_t> eventPool;
     double kernelMs = 0.0;
     uint64_t launches = 0;
+    // first-hit AOVs (KAJO_FLAG_AOV; aov.inc.hip): float4 [2][W * H], albedo + hits then normal + depth, row-major; the passes summed into them
+    void* aov = nullptr;
+    int aovInstance = KAJO_AOV_SMALL; // render_args.h KajoAovInstance: the scene class, as the render kernel is chosen
+    size_t aovLds = 0;                // the instance's scene copy
+    long long aovPasses = 0;
 
     // numerics build the handle runs (include/kajo_hip.h): 0 FAST, 1 STRICT, 2 EXACT
     int numerics() const { return (params.flags & KAJO_FLAG_STRICT) ? 1 : ((params.flags & KAJO_FLAG_EXACT) ? 2 : 0); }
@@ -176,6 +185,11 @@ struct KajoHip
         case 2: return kajo_render_exact_split_launch(a, grid, block, lds, stream);
         default: return kajo_render_fast_split_launch(a, grid, block, lds, stream);
         }
+    }
+    // (the STRICT instance serves STRICT and EXACT handles: EXACT's camera rays, walk and normals are STRICT's arithmetic)
+    int launchAov(const AovArgs* a, unsigned grid) const
+    {
+        return strict() ? kajo_aov_strict_launch(a, aovInstance, grid, aovLds, stream) : kajo_aov_fast_launch(a, aovInstance, grid, aovLds, stream);
     }
     int setLds(size_t lds) const
     {
@@ -278,6 +292,8 @@ void destroy(KajoHip* h)
         (void)hipFree(h->side);
     if (h->carry)
         (void)hipFree(h->carry);
+    if (h->aov)
+        (void)hipFree(h->aov);
     if (h->ownStream && h->stream)
         (void)hipStreamDestroy(h->stream);
     delete h;
@@ -509,6 +525,8 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
         return fail(KAJO_E_INVALID, "tile size must be multiples of 8 with tileW*tileH a multiple of 256");
     if (p.tileCount < 1 || p.tileIndex < 0 || p.tileIndex >= p.tileCount)
         return fail(KAJO_E_INVALID, "tileIndex/tileCount out of range");
+    if ((p.flags & KAJO_FLAG_AOV) && p.tileCount != 1)
+        return fail(KAJO_E_INVALID, "first-hit AOVs need the whole frame on one handle (tileCount 1)");
 
     if (p.flags & (KAJO_FLAG_STRICT | KAJO_FLAG_EXACT)) {
         // integrator.inc.hip kdiv / ksqrt: the IEEE quotient and root without the compiler's range scaling are exact while operands stay
@@ -742,6 +760,22 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
             CREATE_TRY((hipError_t)h->setLds(ldsTotal));
         }
     }
+    if (p.flags & KAJO_FLAG_AOV) {
+        // the AOV kernel of the scene's class -- small scenes: everything in LDS; large ones: the hot records (and the grid's cell lists where
+        // create() put them in LDS), per home of the cell lists and with or without visibility lists, as launch.inc.hip picks the render kernel
+        if (h->coldInLds)
+            h->aovInstance = KAJO_AOV_SMALL;
+        else if (v.shadow.enabled)
+            h->aovInstance = v.grid.inLds ? KAJO_AOV_BIGLIST_LG : KAJO_AOV_BIGLIST;
+        else
+            h->aovInstance = v.grid.inLds ? KAJO_AOV_BIG_LG : KAJO_AOV_BIG;
+        h->aovLds = h->coldInLds ? h->ldsBytes : h->hotBytes;
+        if (h->aovLds > 48 * 1024)
+            CREATE_TRY((hipError_t)(h->strict() ? kajo_aov_strict_set_lds(h->aovInstance, h->aovLds) : kajo_aov_fast_set_lds(h->aovInstance, h->aovLds)));
+        const size_t bytes = 2 * (size_t)width * height * 16;
+        CREATE_TRY(hipMalloc(&h->aov, bytes));
+        CREATE_TRY(hipMemsetAsync(h->aov, 0, bytes, h->stream));
+    }
     CREATE_TRY(hipStreamSynchronize(h->stream));
 #undef CREATE_TRY
     *out = h;
@@ -932,6 +966,27 @@ int kajo_hip_render(kajo_hip_t h, int passes)
         }
         HIP_TRY(hipEventRecord(e1, h->stream));
         h->pending.emplace_back(e0, e1);
+        if (h->aov) {
+            // the first-hit AOVs of the same passes, behind the render launch and outside its timing events (KajoCounters.kernelMs)
+            AovArgs g;
+            std::memset(&g, 0, sizeof g);
+            g.scene = h->view;
+            g.albedoHits = h->aov;
+            g.normalDepth = static_cast<char*>(h->aov) + (size_t)h->W * h->H * 16;
+            g.W = h->W;
+            g.H = h->H;
+            g.n = a.n;
+            g.pixelWidth = a.pixelWidth;
+            g.pixelHeight = a.pixelHeight;
+            g.sampleWidth = a.sampleWidth;
+            g.sampleHeight = a.sampleHeight;
+            g.firstPass = a.firstPass;
+            g.nPasses = now;
+            g.seed = a.seed;
+            const unsigned long long blocks = (unsigned long long)((h->W + 7) / 8) * ((h->H + 7) / 8);
+            HIP_TRY((hipError_t)h->launchAov(&g, (unsigned)((blocks + 3) / 4)));
+            h->aovPasses += now;
+        }
         if (a.waveTrips && split == 1 && chunks == 1) {
             h->tripsPending = true;
             a.waveTrips = nullptr; // later launches of this call keep the first measurement
@@ -968,7 +1023,10 @@ int kajo_hip_reset(kajo_hip_t h)
     HIP_TRY(hipMemsetAsync(h->tiles, 0, h->tileBytes, h->stream));
     if (h->counters)
         HIP_TRY(hipMemsetAsync(h->counters, 0, 32 * sizeof(unsigned long long), h->stream));
+    if (h->aov)
+        HIP_TRY(hipMemsetAsync(h->aov, 0, 2 * (size_t)h->W * h->H * 16, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    h->aovPasses = 0;
     h->passesDone = 0;
     h->carryValid = false;
     h->frameValid = false;
@@ -1084,6 +1142,39 @@ int kajo_hip_read_radiance(kajo_hip_t h, float* dst)
         return rc;
     HIP_TRY(hipMemcpyAsync(dst, h->frame, (size_t)h->W * h->H * 16, hipMemcpyDeviceToHost, h->stream));
     return kajo_hip_wait(h);
+}
+
+int kajo_hip_read_aov(kajo_hip_t h, float* albedoHits, float* normalDepth, int64_t* samples)
+{
+    if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    if (!h->aov)
+        return fail(KAJO_E_STATE, "the handle was created without the AOV flag: no first-hit AOVs to read");
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    const size_t bytes = (size_t)h->W * h->H * 16;
+    if (albedoHits)
+        HIP_TRY(hipMemcpyAsync(albedoHits, h->aov, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (normalDepth)
+        HIP_TRY(hipMemcpyAsync(normalDepth, static_cast<char*>(h->aov) + bytes, bytes, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = kajo_hip_wait(h)))
+        return rc;
+    if (samples) {
+        const long long n = (long long)std::sqrt((double)(unsigned)h->params.samplesPerPass);
+        *samples = (int64_t)(n * n * h->aovPasses);
+    }
+    return KAJO_OK;
+}
+
+const char* kajo_hip_aov_kernel(kajo_hip_t h)
+{
+    if (!h || !h->aov)
+        return nullptr;
+    static const char* const names[2][KAJO_AOV_INSTANCES] = {
+        {"kajo_aov_fast", "kajo_aov_fast_big", "kajo_aov_fast_big_lg", "kajo_aov_fast_biglist", "kajo_aov_fast_biglist_lg"},
+        {"kajo_aov_strict", "kajo_aov_strict_big", "kajo_aov_strict_big_lg", "kajo_aov_strict_biglist", "kajo_aov_strict_biglist_lg"}};
+    return names[h->strict() ? 1 : 0][h->aovInstance];
 }
 
 namespace

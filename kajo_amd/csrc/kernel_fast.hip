@@ -27,3 +27,6 @@
 #define KAJO_RESOLVE_TILES_NAME kajo_resolve_tiles_fast
 #include "integrator.inc.hip"
 #include "launch.inc.hip"
+// first-hit AOVs (KAJO_FLAG_AOV)
+#define KAJO_AOV_NAME kajo_aov_fast
+#include "aov.inc.hip"

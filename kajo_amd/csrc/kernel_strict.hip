@@ -24,6 +24,9 @@
 #define KAJO_RESOLVE_TILES_NAME kajo_resolve_tiles_strict
 #include "integrator.inc.hip"
 #include "launch.inc.hip"
+// first-hit AOVs (KAJO_FLAG_AOV): this instance serves the STRICT and the EXACT handles
+#define KAJO_AOV_NAME kajo_aov_strict
+#include "aov.inc.hip"
 
 // include/kajo_strictmath.h element-wise on the device (kajo_hip_kat_strictmath): the claim that these
 // functions give identical bits on x86-64 and gfx950 is checked directly.

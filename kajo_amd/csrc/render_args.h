@@ -70,6 +70,32 @@ struct KatTraceArgs
     float* out;        // [count][13]: t, position, normal, tangent, binormal
 };
 
+// First-hit AOVs (aov.inc.hip, KAJO_FLAG_AOV): the camera samples of passes [firstPass, firstPass + nPasses) traced once more, without
+// shading. Two whole-frame buffers, row-major, row 0 = top: albedoHits (sum of albedo.rgb, number of hits) and normalDepth (sum of
+// normal.xyz, sum of depth).
+struct AovArgs
+{
+    DSceneView scene;
+    void* albedoHits;    // float4 [W * H]
+    void* normalDepth;   // float4 [W * H]
+    int32_t W, H;
+    int32_t n;           // strata per axis
+    float pixelWidth, pixelHeight, sampleWidth, sampleHeight; // Renderer.cpp:39-42, as RenderArgs
+    int32_t firstPass, nPasses;
+    uint64_t seed;
+};
+
+// AOV kernel instances (aov.inc.hip), one per scene class the render kernels tell apart (capi.cpp picks one at create)
+enum KajoAovInstance
+{
+    KAJO_AOV_SMALL = 0,      // whole scene in LDS, every object walked
+    KAJO_AOV_BIG = 1,        // hot records in LDS, cold ones global; the grid's cell lists (if any) in global memory
+    KAJO_AOV_BIG_LG = 2,     // ... the cell lists in LDS
+    KAJO_AOV_BIGLIST = 3,    // scenes with visibility lists (closed room, (centre, radius) spheres only): lists global
+    KAJO_AOV_BIGLIST_LG = 4, // ... in LDS
+    KAJO_AOV_INSTANCES = 5
+};
+
 // tile-buffer slot of pixel (x, y): tiles are dealt round-robin to `tileCount` owners; inside a
 // tile pixels are grouped in 8x8 blocks (one wave each) so that a wave's 64 float4 are
 // contiguous (1 KiB per store instruction).

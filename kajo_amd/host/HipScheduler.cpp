@@ -130,6 +130,8 @@ struct Scheduler::Impl
         }
         if (opt.gpus < 1)
             throw std::runtime_error("hip::Scheduler: no GPU visible (this backend has no CPU path)");
+        if (opt.aov && opt.gpus != 1)
+            throw std::runtime_error("hip::Scheduler: first-hit AOVs need the whole frame on one GPU (gpus = 1)");
         if (opt.sameDevice && opt.gather != Options::Copy)
             throw std::runtime_error("hip::Scheduler: sameDevice needs gather = Copy (RCCL wants one rank per device)");
         Options::Numerics numerics = opt.strict ? Options::Strict : opt.numerics;
@@ -150,7 +152,8 @@ struct Scheduler::Impl
             p.samplesPerPass = opt.samplesPerPass;
             p.depthLimit = opt.depthLimit;
             p.seed = opt.seed;
-            p.flags = (numerics == Options::Strict ? KAJO_FLAG_STRICT : numerics == Options::Exact ? KAJO_FLAG_EXACT : 0u) | (opt.counters ? KAJO_FLAG_COUNTERS : 0u);
+            p.flags = (numerics == Options::Strict ? KAJO_FLAG_STRICT : numerics == Options::Exact ? KAJO_FLAG_EXACT : 0u) | (opt.counters ? KAJO_FLAG_COUNTERS : 0u) |
+                      (opt.aov ? KAJO_FLAG_AOV : 0u);
             p.device = opt.sameDevice ? 0 : g;
             p.tileIndex = g;
             p.tileCount = opt.gpus;
@@ -260,6 +263,15 @@ void Scheduler::readRadiance(float* dst)
         d.composed = true;
     }
     check(kajo_hip_read_radiance(d.handles[0], dst), "kajo_hip_read_radiance");
+}
+
+void Scheduler::readAov(float* albedoHits, float* normalDepth, long long* samples)
+{
+    Impl& d = *m_impl;
+    int64_t n = 0;
+    check(kajo_hip_read_aov(d.handles[0], albedoHits, normalDepth, &n), "kajo_hip_read_aov");
+    if (samples)
+        *samples = (long long)n;
 }
 
 void Scheduler::run()

@@ -56,6 +56,7 @@ struct Options
     bool sameDevice = false;      // all tile owners on device 0 (needs gather = Copy)
     bool forceGather = false;     // run the gather + compose step with ONE owner too (a one-rank communicator whose
                                   // rank sends its tile buffer to itself): the multi-GPU call sequence on a one-GPU box
+    bool aov = false;             // also accumulate the first-hit albedo / normal / depth (KAJO_FLAG_AOV; readAov): one GPU only
 };
 
 struct Statistics
@@ -84,6 +85,8 @@ public:
     const Statistics& statistics() const;
     // whole-frame float accumulation (W*H*4, sum over passes of radiance / S) after run()
     void readRadiance(float* dst);
+    // first-hit AOV sums after run() (Options::aov; include/kajo_hip.h kajo_hip_read_aov): W*H*4 floats each, either may be null
+    void readAov(float* albedoHits, float* normalDepth, long long* samples);
 
 private:
     struct Impl;

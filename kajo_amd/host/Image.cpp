@@ -109,3 +109,28 @@ bool Image::save(const std::string& fileName) const
     ok = std::fclose(f) == 0 && ok;
     return ok;
 }
+
+bool writePfm(const std::string& fileName, int width, int height, int channels, const float* topRowFirst)
+{
+    if (channels != 1 && channels != 3)
+        return false;
+    FILE* f = std::fopen(fileName.c_str(), "wb");
+    if (!f) {
+        std::cerr << "PFM encode failure: cannot open " << fileName << std::endl;
+        return false;
+    }
+    // (a negative scale says little-endian, the byte order of the floats below)
+    bool ok = std::fprintf(f, "%s\n%d %d\n-1.0\n", channels == 3 ? "PF" : "Pf", width, height) > 0;
+    const uint16_t probe = 1;
+    const bool little = *reinterpret_cast<const unsigned char*>(&probe) == 1;
+    std::vector<unsigned char> row((size_t)width * channels * 4);
+    for (int y = height - 1; ok && y >= 0; y--) {
+        const unsigned char* src = reinterpret_cast<const unsigned char*>(topRowFirst + (size_t)y * width * channels);
+        for (size_t i = 0; i < row.size(); i += 4)
+            for (int k = 0; k < 4; k++)
+                row[i + k] = src[i + (little ? k : 3 - k)];
+        ok = std::fwrite(row.data(), 1, row.size(), f) == row.size();
+    }
+    ok = std::fclose(f) == 0 && ok;
+    return ok;
+}

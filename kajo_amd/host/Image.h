@@ -24,4 +24,8 @@ public:
     bool save(const std::string& path) const;
 };
 
+// Writes a little-endian PFM ("PF" for channels = 3, "Pf" for 1): width * height * channels floats given top row first, stored bottom row
+// first as the format requires; false on I/O failure.
+bool writePfm(const std::string& path, int width, int height, int channels, const float* topRowFirst);
+
 #endif

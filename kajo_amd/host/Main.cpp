@@ -17,7 +17,7 @@
 int main(int argc, char** argv)
 {
     std::vector<std::string> args(argv, argv + argc);
-    std::string rendererName = "hip", out = "out.png", rawOut, scenePath;
+    std::string rendererName = "hip", out = "out.png", rawOut, aovPrefix, scenePath;
     int width = 640, height = 480;
     hip::Options opt;
     opt.passes = 16;
@@ -55,6 +55,9 @@ int main(int argc, char** argv)
                         "                    --passes passes (16 when 0) in launches planned for half a second at most\n"
                         "    -o FILE         PNG output (out.png)\n"
                         "    --raw FILE      also dump the float4 accumulation (W*H*4 floats)\n"
+                        "    --aov PREFIX    also write the first-hit AOVs a denoiser takes, averaged over the render's camera samples:\n"
+                        "                    PREFIX_albedo.pfm, PREFIX_normal.pfm (3 channels), PREFIX_depth.pfm (1; mean over the hits)\n"
+                        "                    (one GPU only)\n"
                         "    --json          print run statistics as one JSON line\n"
                         "    -v              progress on stderr\n",
                         args[0].c_str());
@@ -80,6 +83,7 @@ int main(int argc, char** argv)
         else if (a == "--scene-pod" && more) podPath = args[++i];
         else if (a == "-o" && more) out = args[++i];
         else if (a == "--raw" && more) rawOut = args[++i];
+        else if (a == "--aov" && more) aovPrefix = args[++i];
         else if (a == "--json") json = true;
         else if (a == "-v") verbose = true;
         else if (!a.empty() && a[0] != '-') scenePath = a;
@@ -87,6 +91,14 @@ int main(int argc, char** argv)
     if (width <= 0 || height <= 0) {
         std::cerr << "Bad image size" << std::endl;
         return 1;
+    }
+    if (!aovPrefix.empty()) {
+        // (before any device is opened: the AOV buffers are whole-frame buffers of ONE handle, include/kajo_hip.h KAJO_FLAG_AOV)
+        if (opt.gpus != 1 || threeArg) {
+            std::cerr << "kajo_render: --aov needs the whole frame on one GPU (--gpus 1, without --three-arg)" << std::endl;
+            return 1;
+        }
+        opt.aov = true;
     }
 
     scene::Scene scene;
@@ -141,6 +153,24 @@ int main(int argc, char** argv)
             hipScheduler->readRadiance(acc.data());
             std::ofstream f(rawOut, std::ios::binary);
             f.write(reinterpret_cast<const char*>(acc.data()), (std::streamsize)(acc.size() * sizeof(float)));
+        }
+        if (!aovPrefix.empty()) {
+            // the means: albedo and normal over every sample, depth over the samples that hit (0 where none did)
+            const size_t count = (size_t)width * height;
+            std::vector<float> a(count * 4), b(count * 4), albedo(count * 3), normal(count * 3), depth(count);
+            long long samples = 0;
+            hipScheduler->readAov(a.data(), b.data(), &samples);
+            const float s = samples > 0 ? (float)samples : 1.0f;
+            for (size_t i = 0; i < count; i++) {
+                for (int k = 0; k < 3; k++) {
+                    albedo[3 * i + k] = a[4 * i + k] / s;
+                    normal[3 * i + k] = b[4 * i + k] / s;
+                }
+                depth[i] = a[4 * i + 3] > 0.0f ? b[4 * i + 3] / a[4 * i + 3] : 0.0f;
+            }
+            if (!writePfm(aovPrefix + "_albedo.pfm", width, height, 3, albedo.data()) || !writePfm(aovPrefix + "_normal.pfm", width, height, 3, normal.data()) ||
+                !writePfm(aovPrefix + "_depth.pfm", width, height, 1, depth.data()))
+                return 3;
         }
     } catch (const std::exception& e) {
         std::cerr << "kajo_render: " << e.what() << std::endl;

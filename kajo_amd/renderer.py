@@ -17,7 +17,8 @@ from .scene import Scene
 class HipRenderer:
     def __init__(self, scene: Scene, width: int, height: int, spp: int = 32, depth_limit: int = 8,
                  seed: int = 0o715517, strict: bool = False, exact: bool = False, counters: bool = False, device: int = 0,
-                 tile=(64, 16), tile_index: int = 0, tile_count: int = 1, passes_per_launch: int = 0, flags: int = 0):
+                 tile=(64, 16), tile_index: int = 0, tile_count: int = 1, passes_per_launch: int = 0, flags: int = 0,
+                 aov: bool = False):
         L = capi.lib()
         self._L = L
         self.scene = scene
@@ -29,6 +30,7 @@ class HipRenderer:
         p.depthLimit = depth_limit
         p.seed = seed
         p.flags = (capi.KAJO_FLAG_STRICT if strict else 0) | (capi.KAJO_FLAG_EXACT if exact else 0) | (capi.KAJO_FLAG_COUNTERS if counters else 0) | int(flags)
+        p.flags |= capi.KAJO_FLAG_AOV if aov else 0
         p.device = device
         p.tileW, p.tileH = tile
         p.tileIndex, p.tileCount = tile_index, tile_count
@@ -97,6 +99,25 @@ class HipRenderer:
         c = capi.KajoCounters()
         capi.check(self._L.kajo_hip_counters(self._h, C.byref(c)))
         return {k: getattr(c, k) for k, _ in capi.KajoCounters._fields_}
+
+    def aov(self) -> dict:
+        """First-hit AOVs (include/kajo_hip.h kajo_hip_read_aov; the handle needs aov=True): raw=(A, B), both (H, W, 4) float32 sums --
+        A = (albedo.rgb, hits), B = (normal.xyz, depth) -- and the means a denoiser takes: albedo = A.rgb / samples, normal = B.xyz /
+        samples, depth = B.w / hits (0 where no sample hit)."""
+        A = np.empty((self.height, self.width, 4), np.float32)
+        B = np.empty((self.height, self.width, 4), np.float32)
+        samples = C.c_int64()
+        capi.check(self._L.kajo_hip_read_aov(self._h, A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), C.byref(samples)))
+        s = np.float32(max(samples.value, 1))
+        hits = A[..., 3].copy()
+        depth = np.zeros_like(hits)
+        np.divide(B[..., 3], hits, out=depth, where=hits > 0)
+        return dict(raw=(A, B), samples=samples.value, albedo=A[..., :3] / s, normal=B[..., :3] / s, depth=depth, hits=hits)
+
+    def aov_kernel(self):
+        """Name of the AOV kernel instance the handle launches (None without aov=True)."""
+        name = self._L.kajo_hip_aov_kernel(self._h)
+        return name.decode() if name else None
 
     # -- known-answer hooks ----------------------------------------------------------------
     def kat_trace(self, origins, dirs):
