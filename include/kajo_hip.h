@@ -24,6 +24,8 @@
  *   kajo_hip_counters        the samples/s bookkeeping of Preview::update (Preview.cpp:79-98)
  *   kajo_hip_read_aov        (no counterpart: the reference has no AOVs) the first-hit albedo, normal and depth a denoiser
  *                            takes beside the beauty image, over the beauty render's own camera samples (KAJO_FLAG_AOV)
+ *   kajo_hip_denoise         (no counterpart: the reference has no denoiser) an edge-aware A-trous filter of the frame guided by
+ *                            those AOVs, into buffers of its own; kajo_hip_default_denoise_params gives its defaults
  *   kajo_hip_destroy         the unique_ptr members of cpu::Scheduler (cpu/Scheduler.h:29-31)
  *
  * Pixels are dealt to GPUs as fixed-size tiles: a handle created with
@@ -201,6 +203,49 @@ int kajo_hip_read_aov(kajo_hip_t h, float* albedoHits, float* normalDepth, int64
 /* Name of the AOV kernel instance the handle launches (one per scene class, as the render kernels: the whole scene in LDS; the grid's cell
    lists in LDS or in global memory; with or without visibility lists), or NULL without KAJO_FLAG_AOV. For tests and profiles. */
 const char* kajo_hip_aov_kernel(kajo_hip_t h);
+
+/* Edge-aware A-trous denoiser (Dammertz et al. 2010) guided by the first-hit AOVs, its luminance weight scaled by a spatial variance
+   estimate (the spatial part of SVGF, Schied et al. 2017). A post-process over the handle's whole frame, in kernels of its own
+   (kajo_amd/csrc/denoise.hip) on the handle's stream, in float32 IEEE arithmetic without contraction in every numerics build: only its
+   inputs depend on FAST / EXACT / STRICT. Definition -- P = the handle's pass count, s = kajo_hip_read_aov's *samples (1 where no AOV
+   sample was taken); per pixel p:
+     c = sum.rgb / P                      mean radiance (sum: the accumulation, kajo_hip_read_radiance)
+     a = A.rgb / s                        albedo (A, B: kajo_hip_read_aov)
+     N = normalize(B.xyz), 0 where |B.xyz| = 0;  z = B.w / A.w, 0 where A.w = 0
+     e = c / max(a, 1e-3) per channel     (demodulation; with KAJO_DENOISE_NO_DEMODULATE e = c)
+     l(e) = 0.2126 r + 0.7152 g + 0.0722 b
+   A pixel COUNTS where e is finite (all three channels). v0(p) = the variance of l over the 3x3 window around p, over the counted
+   pixels inside the image (E[l^2] - E[l]^2, formed about the window's mean; 0 at a pixel that does not count). Iteration i = 0 .. K-1,
+   step d = 2^i, taps q = p + d (dx, dy), dx, dy in -2..2, h = [1/16, 1/4, 3/8, 1/4, 1/16]:
+     w   = h[dx] h[dy] w_z w_n w_l
+     w_z = exp(-|z_p - z_q| / (sigmaDepth * max(z_p, z_q, 1e-4) * |(dx, dy)| * d / max(W, H)));  1 at the centre tap
+     w_n = max(0, dot(N_p, N_q))^sigmaNormal;  1 where either normal is 0 (no hit)
+     w_l = exp(-|l_p - l_q| / (sigmaLuminance * sqrt(g(v_i)(p)) + 1e-6)), g = the 3x3 [1/4, 1/2, 1/4] blur of v_i over the counted
+           pixels inside the image, renormalised over them;  1 where p does not count
+     (an exp whose numerator is 0 is 1)
+     e_{i+1}(p) = sum(w e_i(q)) / sum(w),   v_{i+1}(p) = sum(w^2 v_i(q)) / sum(w)^2
+   over the taps inside the image that count (no edge clamping; the weights are renormalised over the taps that remain). A pixel that
+   does not count takes the weighted mean of the taps that do, its own tap skipped: the denoiser repairs NaN / Inf pixels and never
+   spreads them. Where no tap counts (sum(w) = 0) e is NaN and v 0. Output: e_K * max(a, 1e-3) * P (demodulated) or e_K * P, in the
+   units of kajo_hip_read_radiance (sums over passes), .w copied from the accumulation. K = 0: a copy of the accumulation (no
+   demodulation), so its ARGB8 equals kajo_hip_resolve_argb8 bit for bit.
+   radiance: HOST pointer to width*height*4 floats (row 0 = top); argb8: HOST pointer to width*height words, the output resolved by the
+   handle's own resolve kernel with P passes, as kajo_hip_resolve_argb8; either may be NULL. Waits for outstanding work. The
+   accumulation, the AOV buffers, the pass count and the counters (kernelMs included) are not touched. Scratch (three float4 frames and
+   one ARGB8 frame) is allocated on the first call and freed by kajo_hip_destroy.
+   KAJO_E_INVALID: a NULL handle or params, iterations outside 0..8, a negative or non-finite sigma. KAJO_E_STATE: a handle created
+   without KAJO_FLAG_AOV, or with no pass rendered. */
+#define KAJO_DENOISE_NO_DEMODULATE 1u /* filter the mean radiance itself instead of radiance / albedo */
+typedef struct KajoDenoiseParams {
+    int32_t iterations;   /* K, 0..8 (default 5) */
+    uint32_t flags;       /* KAJO_DENOISE_* (default 0) */
+    float sigmaLuminance; /* default 4 */
+    float sigmaNormal;    /* default 128 */
+    float sigmaDepth;     /* default 1 (the quality sweep) */
+    float reserved[3];    /* 0 */
+} KajoDenoiseParams;
+void kajo_hip_default_denoise_params(KajoDenoiseParams* p); /* NULL is accepted */
+int kajo_hip_denoise(kajo_hip_t h, const KajoDenoiseParams* p, float* radiance, uint32_t* argb8);
 
 /* Use an existing HIP stream (hipStream_t passed as void*) instead of the handle's own. */
 int kajo_hip_set_stream(kajo_hip_t h, void* stream);

@@ -34,6 +34,7 @@ KAJO_FLAG_NO_SHADOW_LISTS = 128
 KAJO_FLAG_NO_ONE_LIGHT = 256  # every numerics build: the any-number-of-lights instance for a one-light scene (A/B, tests)
 KAJO_FLAG_EXACT = 512  # decision-exact numerics: STRICT's decisions, FAST's radiance arithmetic
 KAJO_FLAG_AOV = 1024  # first-hit albedo / normal / depth buffers over the beauty render's camera samples (kajo_hip_read_aov)
+KAJO_DENOISE_NO_DEMODULATE = 1  # KajoDenoiseParams.flags: filter the mean radiance itself, not radiance / albedo
 
 # every symbol include/kajo_hip.h declares
 EXPORTS = [
@@ -42,13 +43,18 @@ EXPORTS = [
     "kajo_hip_tile_buffer", "kajo_hip_compose", "kajo_hip_set_stream", "kajo_hip_counters",
     "kajo_hip_stage_scene", "kajo_hip_last_error", "kajo_hip_version", "kajo_hip_kat_trace", "kajo_hip_kat_shade",
     "kajo_hip_kat_strictmath", "kajo_hip_stage_shadow_lists", "kajo_hip_resolve_gathered_argb8_device", "kajo_hip_stage_info",
-    "kajo_hip_launch_order", "kajo_hip_read_aov", "kajo_hip_aov_kernel",
+    "kajo_hip_launch_order", "kajo_hip_read_aov", "kajo_hip_aov_kernel", "kajo_hip_default_denoise_params", "kajo_hip_denoise",
 ]
 
 
 class KajoStageInfo(C.Structure):
     _fields_ = [("closedRoom", C.c_int32), ("grid", C.c_int32), ("shadowLists", C.c_int32), ("reserved", C.c_int32),
                 ("room", C.c_float * 6), ("gridCenter", C.c_float * 3), ("gridReach", C.c_float)]
+
+
+class KajoDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("flags", C.c_uint32), ("sigmaLuminance", C.c_float), ("sigmaNormal", C.c_float),
+                ("sigmaDepth", C.c_float), ("reserved", C.c_float * 3)]
 
 
 class KajoParams(C.Structure):
@@ -121,6 +127,10 @@ def lib():
             L.kajo_hip_read_aov.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
             L.kajo_hip_aov_kernel.argtypes = [C.c_void_p]
             L.kajo_hip_aov_kernel.restype = C.c_char_p
+        if hasattr(L, "kajo_hip_denoise"):  # (nor the denoiser)
+            L.kajo_hip_default_denoise_params.argtypes = [C.POINTER(KajoDenoiseParams)]
+            L.kajo_hip_default_denoise_params.restype = None
+            L.kajo_hip_denoise.argtypes = [C.c_void_p, C.POINTER(KajoDenoiseParams), C.c_void_p, C.c_void_p]
         L.kajo_hip_kat_trace.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
         L.kajo_hip_kat_shade.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.kajo_hip_kat_strictmath.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

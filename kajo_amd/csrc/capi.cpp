@@ -52,6 +52,9 @@ int kajo_aov_fast_launch(const AovArgs*, int instance, unsigned grid, size_t lds
 int kajo_aov_strict_launch(const AovArgs*, int instance, unsigned grid, size_t lds, void* stream);
 int kajo_aov_fast_set_lds(int instance, size_t lds);
 int kajo_aov_strict_set_lds(int instance, size_t lds);
+int kajo_denoise_launch(const void* tiles, const TileMap* map, const void* albedoHits, const void* normalDepth, float passes, float samples,
+                        int iterations, int demodulate, float sigmaLuminance, float sigmaNormal, float sigmaDepth, void* scratch, void** result,
+                        void* stream);
 }
 
 namespace
@@ -165,6 +168,8 @@ struct KajoHip
     int aovInstance = KAJO_AOV_SMALL; // render_args.h KajoAovInstance: the scene class, as the render kernel is chosen
     size_t aovLds = 0;                // the instance's scene copy
     long long aovPasses = 0;
+    // the denoiser's scratch (denoise.hip; kajo_hip_denoise), on its first call: float4 [3][W * H] (guide, two colour frames) + uint32 [W * H]
+    void* denoise = nullptr;
 
     // numerics build the handle runs (include/kajo_hip.h): 0 FAST, 1 STRICT, 2 EXACT
     int numerics() const { return (params.flags & KAJO_FLAG_STRICT) ? 1 : ((params.flags & KAJO_FLAG_EXACT) ? 2 : 0); }
@@ -294,6 +299,8 @@ void destroy(KajoHip* h)
         (void)hipFree(h->carry);
     if (h->aov)
         (void)hipFree(h->aov);
+    if (h->denoise)
+        (void)hipFree(h->denoise);
     if (h->ownStream && h->stream)
         (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1175,6 +1182,67 @@ const char* kajo_hip_aov_kernel(kajo_hip_t h)
         {"kajo_aov_fast", "kajo_aov_fast_big", "kajo_aov_fast_big_lg", "kajo_aov_fast_biglist", "kajo_aov_fast_biglist_lg"},
         {"kajo_aov_strict", "kajo_aov_strict_big", "kajo_aov_strict_big_lg", "kajo_aov_strict_biglist", "kajo_aov_strict_biglist_lg"}};
     return names[h->strict() ? 1 : 0][h->aovInstance];
+}
+
+void kajo_hip_default_denoise_params(KajoDenoiseParams* p)
+{
+    if (!p)
+        return;
+    std::memset(p, 0, sizeof *p);
+    p->iterations = 5;
+    p->flags = 0;
+    p->sigmaLuminance = 4.0f;
+    p->sigmaNormal = 128.0f;
+    p->sigmaDepth = 1.0f;
+}
+
+int kajo_hip_denoise(kajo_hip_t h, const KajoDenoiseParams* p, float* radiance, uint32_t* argb8)
+{
+    // (the parameters first: their refusals do not need a handle)
+    if (!p)
+        return fail(KAJO_E_INVALID, "null denoise parameters");
+    if (p->iterations < 0 || p->iterations > 8)
+        return fail(KAJO_E_INVALID, "denoise iterations must be in [0, 8]");
+    for (float sigma : {p->sigmaLuminance, p->sigmaNormal, p->sigmaDepth})
+        if (!std::isfinite(sigma) || sigma < 0.0f)
+            return fail(KAJO_E_INVALID, "denoise sigmas must be finite and not negative");
+    if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    if (!h->aov)
+        return fail(KAJO_E_STATE, "the handle was created without the AOV flag: nothing to guide the denoiser");
+    if (h->passesDone < 1)
+        return fail(KAJO_E_STATE, "nothing rendered yet");
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    const size_t count = (size_t)h->W * h->H;
+    if (!h->denoise)
+        HIP_TRY(hipMalloc(&h->denoise, count * (3 * 16 + 4)));
+    char* scratch = static_cast<char*>(h->denoise);
+    void* argb = scratch + 3 * count * 16;
+    void* out = scratch + count * 16;
+    if (p->iterations == 0) {
+        // the accumulation itself (one owner: tileCount is 1 with the AOV flag)
+        HIP_TRY((hipError_t)kajo_compose_launch(h->tiles, &h->map, out, h->stream));
+    } else {
+        const long long n = (long long)std::sqrt((double)(unsigned)h->params.samplesPerPass);
+        const long long samples = std::max(n * n * h->aovPasses, 1LL);
+        hipError_t le = (hipError_t)kajo_denoise_launch(h->tiles, &h->map, h->aov, static_cast<char*>(h->aov) + count * 16, (float)h->passesDone,
+                                                        (float)samples, p->iterations, (p->flags & KAJO_DENOISE_NO_DEMODULATE) ? 0 : 1,
+                                                        p->sigmaLuminance, p->sigmaNormal, p->sigmaDepth, scratch, &out, h->stream);
+        if (le != hipSuccess)
+            return failHip(le, "denoise kernel launch");
+    }
+    if (argb8) {
+        hipError_t le = (hipError_t)(h->strict() ? kajo_resolve_strict_launch(out, (int)count, (float)h->passesDone, argb, h->stream)
+                                                 : kajo_resolve_fast_launch(out, (int)count, (float)h->passesDone, argb, h->stream));
+        if (le != hipSuccess)
+            return failHip(le, "resolve kernel launch");
+        HIP_TRY(hipMemcpyAsync(argb8, argb, count * 4, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (radiance)
+        HIP_TRY(hipMemcpyAsync(radiance, out, count * 16, hipMemcpyDeviceToHost, h->stream));
+    return kajo_hip_wait(h);
 }
 
 namespace

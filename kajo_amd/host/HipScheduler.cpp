@@ -274,6 +274,14 @@ void Scheduler::readAov(float* albedoHits, float* normalDepth, long long* sample
         *samples = (long long)n;
 }
 
+void Scheduler::readDenoised(const KajoDenoiseParams* params, float* radiance, uint32_t* argb8)
+{
+    Impl& d = *m_impl;
+    KajoDenoiseParams p;
+    kajo_hip_default_denoise_params(&p);
+    check(kajo_hip_denoise(d.handles[0], params ? params : &p, radiance, argb8), "kajo_hip_denoise");
+}
+
 void Scheduler::run()
 {
     Impl& d = *m_impl;

@@ -18,6 +18,7 @@
 
 class Image;
 class Preview;
+struct KajoDenoiseParams; // include/kajo_hip.h
 
 namespace scene
 {
@@ -87,6 +88,9 @@ public:
     void readRadiance(float* dst);
     // first-hit AOV sums after run() (Options::aov; include/kajo_hip.h kajo_hip_read_aov): W*H*4 floats each, either may be null
     void readAov(float* albedoHits, float* normalDepth, long long* samples);
+    // the frame denoised with the AOVs as guides after run() (Options::aov; include/kajo_hip.h kajo_hip_denoise): W*H*4 float sums and
+    // W*H ARGB8 words, either may be null; params null = kajo_hip_default_denoise_params
+    void readDenoised(const KajoDenoiseParams* params, float* radiance, uint32_t* argb8);
 
 private:
     struct Impl;

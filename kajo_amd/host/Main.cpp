@@ -11,14 +11,16 @@
 
 #include "HipScheduler.h"
 #include "Image.h"
+#include "kajo_hip.h"
 #include "Preview.h"
 #include "scene/Scene.h"
 
 int main(int argc, char** argv)
 {
     std::vector<std::string> args(argv, argv + argc);
-    std::string rendererName = "hip", out = "out.png", rawOut, aovPrefix, scenePath;
+    std::string rendererName = "hip", out = "out.png", rawOut, aovPrefix, denoiseOut, scenePath;
     int width = 640, height = 480;
+    int denoiseIterations = 5;
     hip::Options opt;
     opt.passes = 16;
     opt.gpus = 1;
@@ -58,6 +60,9 @@ int main(int argc, char** argv)
                         "    --aov PREFIX    also write the first-hit AOVs a denoiser takes, averaged over the render's camera samples:\n"
                         "                    PREFIX_albedo.pfm, PREFIX_normal.pfm (3 channels), PREFIX_depth.pfm (1; mean over the hits)\n"
                         "                    (one GPU only)\n"
+                        "    --denoise FILE  also write the frame denoised with those AOVs as guides, as a PNG (edge-aware A-trous filter,\n"
+                        "                    include/kajo_hip.h kajo_hip_denoise; collects the AOVs; one GPU only)\n"
+                        "    --denoise-iterations K  the filter's iterations, 0..8 (5)\n"
                         "    --json          print run statistics as one JSON line\n"
                         "    -v              progress on stderr\n",
                         args[0].c_str());
@@ -84,6 +89,8 @@ int main(int argc, char** argv)
         else if (a == "-o" && more) out = args[++i];
         else if (a == "--raw" && more) rawOut = args[++i];
         else if (a == "--aov" && more) aovPrefix = args[++i];
+        else if (a == "--denoise" && more) denoiseOut = args[++i];
+        else if (a == "--denoise-iterations" && more) denoiseIterations = std::atoi(args[++i].c_str());
         else if (a == "--json") json = true;
         else if (a == "-v") verbose = true;
         else if (!a.empty() && a[0] != '-') scenePath = a;
@@ -96,6 +103,18 @@ int main(int argc, char** argv)
         // (before any device is opened: the AOV buffers are whole-frame buffers of ONE handle, include/kajo_hip.h KAJO_FLAG_AOV)
         if (opt.gpus != 1 || threeArg) {
             std::cerr << "kajo_render: --aov needs the whole frame on one GPU (--gpus 1, without --three-arg)" << std::endl;
+            return 1;
+        }
+        opt.aov = true;
+    }
+    if (!denoiseOut.empty()) {
+        // (the denoiser reads the AOV buffers of the one handle: the same condition as --aov, checked before any device is opened)
+        if (opt.gpus != 1 || threeArg) {
+            std::cerr << "kajo_render: --denoise needs the whole frame on one GPU (--gpus 1, without --three-arg)" << std::endl;
+            return 1;
+        }
+        if (denoiseIterations < 0 || denoiseIterations > 8) {
+            std::cerr << "kajo_render: --denoise-iterations must be in 0..8" << std::endl;
             return 1;
         }
         opt.aov = true;
@@ -170,6 +189,15 @@ int main(int argc, char** argv)
             }
             if (!writePfm(aovPrefix + "_albedo.pfm", width, height, 3, albedo.data()) || !writePfm(aovPrefix + "_normal.pfm", width, height, 3, normal.data()) ||
                 !writePfm(aovPrefix + "_depth.pfm", width, height, 1, depth.data()))
+                return 3;
+        }
+        if (!denoiseOut.empty()) {
+            KajoDenoiseParams p;
+            kajo_hip_default_denoise_params(&p);
+            p.iterations = denoiseIterations;
+            Image denoised(width, height);
+            hipScheduler->readDenoised(&p, nullptr, denoised.pixels.get());
+            if (!denoised.save(denoiseOut))
                 return 3;
         }
     } catch (const std::exception& e) {

@@ -114,6 +114,23 @@ class HipRenderer:
         np.divide(B[..., 3], hits, out=depth, where=hits > 0)
         return dict(raw=(A, B), samples=samples.value, albedo=A[..., :3] / s, normal=B[..., :3] / s, depth=depth, hits=hits)
 
+    def denoise(self, iterations: int = 5, sigma_luminance: float = None, sigma_normal: float = None, sigma_depth: float = None,
+                demodulate: bool = True) -> dict:
+        """Edge-aware A-trous denoise of the frame guided by the first-hit AOVs (include/kajo_hip.h kajo_hip_denoise; the handle needs
+        aov=True): radiance = (H, W, 4) float32 sums over passes, as radiance(); argb8 = (H, W) uint32, as argb8(). Sigmas left None take
+        kajo_hip_default_denoise_params' values. The accumulation and the AOVs are not touched."""
+        p = capi.KajoDenoiseParams()
+        self._L.kajo_hip_default_denoise_params(C.byref(p))
+        p.iterations = int(iterations)
+        p.flags = 0 if demodulate else capi.KAJO_DENOISE_NO_DEMODULATE
+        for field, value in (("sigmaLuminance", sigma_luminance), ("sigmaNormal", sigma_normal), ("sigmaDepth", sigma_depth)):
+            if value is not None:
+                setattr(p, field, float(value))
+        radiance = np.empty((self.height, self.width, 4), np.float32)
+        argb8 = np.empty((self.height, self.width), np.uint32)
+        capi.check(self._L.kajo_hip_denoise(self._h, C.byref(p), radiance.ctypes.data_as(C.c_void_p), argb8.ctypes.data_as(C.c_void_p)))
+        return dict(radiance=radiance, argb8=argb8)
+
     def aov_kernel(self):
         """Name of the AOV kernel instance the handle launches (None without aov=True)."""
         name = self._L.kajo_hip_aov_kernel(self._h)
