@@ -26,6 +26,9 @@
  *                            takes beside the beauty image, over the beauty render's own camera samples (KAJO_FLAG_AOV)
  *   kajo_hip_denoise         (no counterpart: the reference has no denoiser) an edge-aware A-trous filter of the frame guided by
  *                            those AOVs, into buffers of its own; kajo_hip_default_denoise_params gives its defaults
+ *   kajo_hip_tonemap_argb8   Image::linearToSRGB / colorToRGBA8 (renderer/Image.cpp:14-27) with an exposure, a tone curve and automatic
+ *                            exposure in front of the clamp; kajo_hip_tonemap_gathered_argb8_device is its twin over gathered tile
+ *                            buffers, kajo_hip_tone_scale reports the scale applied, kajo_hip_default_tone_params gives the defaults
  *   kajo_hip_destroy         the unique_ptr members of cpu::Scheduler (cpu/Scheduler.h:29-31)
  *
  * Pixels are dealt to GPUs as fixed-size tiles: a handle created with
@@ -246,6 +249,54 @@ typedef struct KajoDenoiseParams {
 } KajoDenoiseParams;
 void kajo_hip_default_denoise_params(KajoDenoiseParams* p); /* NULL is accepted */
 int kajo_hip_denoise(kajo_hip_t h, const KajoDenoiseParams* p, float* radiance, uint32_t* argb8);
+
+/* Exposure, tone curves and automatic exposure in the image resolve: a post-process over the handle's whole frame, in kernels of its own
+   (kajo_amd/csrc/tonemap.inc.hip) on the handle's stream, compiled into each numerics build so that the mean and the display transform are
+   the resolve's own expressions (EXACT handles use the STRICT build's, as for the resolve). Definition -- P = the handle's pass count; per
+   pixel:
+     m = sum.rgb / P                  the build's division, as the resolve forms it (sum: the accumulation, or the denoised frame)
+     the pixel COUNTS where all three channels of m are finite
+     l(x) = 0.2126 x.r + 0.7152 x.g + 0.0722 x.b
+     a = key / Lavg, Lavg = exp(mean of log(1e-4 + max(l(m), 0)) over the counting pixels of the whole frame), with
+         KAJO_TONE_AUTO_EXPOSURE; 1 without the flag or where no pixel counts
+     s = 2^exposure * a               (exactly 1 with exposure 0 and no automatic exposure)
+     x = m * s, then y per curve:
+       CLAMP     min(max(x, 0), 1) per channel (NaN gives 0)
+       REINHARD  L = l(x), Ld = L (1 + L / white^2) / (1 + L), or L / (1 + L) with white = 0 (Reinhard et al. 2002, eq. 4, on
+                 luminance); y = min(max(x Ld / L, 0), 1) where L > 0, else 0
+       ACES      min(max(x (2.51 x + 0.03) / (x (2.43 x + 0.59) + 0.14), 0), 1) per channel (Narkowicz 2015, no pre-scale)
+     a pixel that does not count is mapped by CLAMP under every curve (NaN / Inf as the resolve maps them)
+     out = (int)(pow(y, 1 / 2.2) * 255 + .5) per channel with the build's pow, alpha 255 (the resolve's expression)
+   The default parameters are the resolve bit for bit: kajo_hip_resolve_argb8, kajo_hip_resolve_gathered_argb8_device, and with denoise
+   kajo_hip_denoise's argb8. The log-average is summed in float64 over fixed 64x16 rectangles of the image in image order and the
+   rectangles' sums in a fixed order, with no atomics: image and scale are the same bits from run to run and for any number of tile owners.
+   Refusals (KAJO_E_INVALID, before any device work): NULL params or handle; an unknown curve or flag bit; an exposure that is not finite
+   or outside -32..32; a white point that is negative or not finite; with KAJO_TONE_AUTO_EXPOSURE a key that is not finite or not above
+   0; non-zero reserved words. The accumulation, the AOV buffers, the pass count and the counters (kernelMs included) are not touched;
+   scratch (the log-average's partial sums and the scale word) is allocated on first use and freed by kajo_hip_destroy. */
+#define KAJO_TONE_CLAMP 0              /* the reference's: clamp to [0, 1] (the default) */
+#define KAJO_TONE_REINHARD 1           /* Reinhard et al. 2002, eq. 4, on luminance, with a white point */
+#define KAJO_TONE_ACES 2               /* Narkowicz 2015 fit of the ACES RRT + ODT, per channel, no pre-scale */
+#define KAJO_TONE_AUTO_EXPOSURE 1u     /* KajoToneParams.flags */
+typedef struct KajoToneParams {
+    int32_t curve;     /* KAJO_TONE_* (default CLAMP) */
+    uint32_t flags;    /* KAJO_TONE_* flags (default 0) */
+    float exposure;    /* EV added, -32 .. 32: a linear factor 2^exposure (default 0) */
+    float white;       /* REINHARD: the exposed luminance mapped to 1; 0 = none, i.e. L / (1 + L) (default 0) */
+    float key;         /* AUTO_EXPOSURE: the grey the log-average luminance is mapped to, > 0 (default 0.18) */
+    float reserved[3]; /* 0 */
+} KajoToneParams;
+void kajo_hip_default_tone_params(KajoToneParams* p); /* NULL is accepted */
+/* The whole frame (tileCount 1, or a composed handle, as kajo_hip_resolve_argb8) tone-mapped. denoise == NULL maps the accumulation;
+   otherwise the frame kajo_hip_denoise with those parameters produces, formed on the device by the denoiser's kernels (its refusals and
+   KAJO_E_STATE rules apply). argb8: HOST pointer to width*height words (row 0 = top); *scale: the s applied; either may be NULL. Waits. */
+int kajo_hip_tonemap_argb8(kajo_hip_t h, const KajoToneParams* p, const KajoDenoiseParams* denoise, uint32_t* argb8, float* scale);
+/* The tone-mapped twin of kajo_hip_resolve_gathered_argb8_device (the same `gathered` buffers, NULL = the handle's own when tileCount == 1),
+   into DEVICE memory, asynchronous on the handle's stream: the log-average reaches the mapping kernel through a device word, no host
+   synchronisation. */
+int kajo_hip_tonemap_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoToneParams* p, void* dst);
+/* The s of the handle's most recent tone mapping; waits for it. KAJO_E_STATE before the first one. */
+int kajo_hip_tone_scale(kajo_hip_t h, float* scale);
 
 /* Use an existing HIP stream (hipStream_t passed as void*) instead of the handle's own. */
 int kajo_hip_set_stream(kajo_hip_t h, void* stream);

@@ -35,6 +35,8 @@ KAJO_FLAG_NO_ONE_LIGHT = 256  # every numerics build: the any-number-of-lights i
 KAJO_FLAG_EXACT = 512  # decision-exact numerics: STRICT's decisions, FAST's radiance arithmetic
 KAJO_FLAG_AOV = 1024  # first-hit albedo / normal / depth buffers over the beauty render's camera samples (kajo_hip_read_aov)
 KAJO_DENOISE_NO_DEMODULATE = 1  # KajoDenoiseParams.flags: filter the mean radiance itself, not radiance / albedo
+KAJO_TONE_CLAMP, KAJO_TONE_REINHARD, KAJO_TONE_ACES = 0, 1, 2  # KajoToneParams.curve
+KAJO_TONE_AUTO_EXPOSURE = 1  # KajoToneParams.flags: scale the frame's log-average luminance to `key`
 
 # every symbol include/kajo_hip.h declares
 EXPORTS = [
@@ -44,6 +46,7 @@ EXPORTS = [
     "kajo_hip_stage_scene", "kajo_hip_last_error", "kajo_hip_version", "kajo_hip_kat_trace", "kajo_hip_kat_shade",
     "kajo_hip_kat_strictmath", "kajo_hip_stage_shadow_lists", "kajo_hip_resolve_gathered_argb8_device", "kajo_hip_stage_info",
     "kajo_hip_launch_order", "kajo_hip_read_aov", "kajo_hip_aov_kernel", "kajo_hip_default_denoise_params", "kajo_hip_denoise",
+    "kajo_hip_default_tone_params", "kajo_hip_tonemap_argb8", "kajo_hip_tonemap_gathered_argb8_device", "kajo_hip_tone_scale",
 ]
 
 
@@ -55,6 +58,11 @@ class KajoStageInfo(C.Structure):
 class KajoDenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("flags", C.c_uint32), ("sigmaLuminance", C.c_float), ("sigmaNormal", C.c_float),
                 ("sigmaDepth", C.c_float), ("reserved", C.c_float * 3)]
+
+
+class KajoToneParams(C.Structure):
+    _fields_ = [("curve", C.c_int32), ("flags", C.c_uint32), ("exposure", C.c_float), ("white", C.c_float), ("key", C.c_float),
+                ("reserved", C.c_float * 3)]
 
 
 class KajoParams(C.Structure):
@@ -131,6 +139,13 @@ def lib():
             L.kajo_hip_default_denoise_params.argtypes = [C.POINTER(KajoDenoiseParams)]
             L.kajo_hip_default_denoise_params.restype = None
             L.kajo_hip_denoise.argtypes = [C.c_void_p, C.POINTER(KajoDenoiseParams), C.c_void_p, C.c_void_p]
+        if hasattr(L, "kajo_hip_tonemap_argb8"):  # (nor the tone mapping)
+            L.kajo_hip_default_tone_params.argtypes = [C.POINTER(KajoToneParams)]
+            L.kajo_hip_default_tone_params.restype = None
+            L.kajo_hip_tonemap_argb8.argtypes = [C.c_void_p, C.POINTER(KajoToneParams), C.POINTER(KajoDenoiseParams), C.c_void_p,
+                                                 C.POINTER(C.c_float)]
+            L.kajo_hip_tonemap_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoToneParams), C.c_void_p]
+            L.kajo_hip_tone_scale.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.kajo_hip_kat_trace.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
         L.kajo_hip_kat_shade.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.kajo_hip_kat_strictmath.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -55,7 +55,12 @@ int kajo_aov_strict_set_lds(int instance, size_t lds);
 int kajo_denoise_launch(const void* tiles, const TileMap* map, const void* albedoHits, const void* normalDepth, float passes, float samples,
                         int iterations, int demodulate, float sigmaLuminance, float sigmaNormal, float sigmaDepth, void* scratch, void** result,
                         void* stream);
+int kajo_tone_fast_launch(const void* src, const TileMap* map, int fromTiles, float passes, const ToneArgs* t, void* scratch, void* dst, void* stream);
+int kajo_tone_strict_launch(const void* src, const TileMap* map, int fromTiles, float passes, const ToneArgs* t, void* scratch, void* dst, void* stream);
 }
+
+static_assert(KAJO_TONE_CLAMP == KAJO_TONE_CURVE_CLAMP && KAJO_TONE_REINHARD == KAJO_TONE_CURVE_REINHARD && KAJO_TONE_ACES == KAJO_TONE_CURVE_ACES,
+              "tonemap.inc.hip numbers the curves as include/kajo_hip.h does");
 
 namespace
 {
@@ -170,6 +175,10 @@ struct KajoHip
     long long aovPasses = 0;
     // the denoiser's scratch (denoise.hip; kajo_hip_denoise), on its first call: float4 [3][W * H] (guide, two colour frames) + uint32 [W * H]
     void* denoise = nullptr;
+    // tone mapping (tonemap.inc.hip; kajo_hip_tonemap_*), on its first call: the scale word + the logavg partials (toneScratchBytes)
+    void* tone = nullptr;
+    int toneScaleState = 0; // the s of the most recent tone mapping: 0 none yet, 1 toneScale, 2 the scale word (auto exposure)
+    float toneScale = 1.0f;
 
     // numerics build the handle runs (include/kajo_hip.h): 0 FAST, 1 STRICT, 2 EXACT
     int numerics() const { return (params.flags & KAJO_FLAG_STRICT) ? 1 : ((params.flags & KAJO_FLAG_EXACT) ? 2 : 0); }
@@ -301,6 +310,8 @@ void destroy(KajoHip* h)
         (void)hipFree(h->aov);
     if (h->denoise)
         (void)hipFree(h->denoise);
+    if (h->tone)
+        (void)hipFree(h->tone);
     if (h->ownStream && h->stream)
         (void)hipStreamDestroy(h->stream);
     delete h;
@@ -1196,9 +1207,14 @@ void kajo_hip_default_denoise_params(KajoDenoiseParams* p)
     p->sigmaDepth = 1.0f;
 }
 
-int kajo_hip_denoise(kajo_hip_t h, const KajoDenoiseParams* p, float* radiance, uint32_t* argb8)
+} // extern "C"
+
+namespace
 {
-    // (the parameters first: their refusals do not need a handle)
+
+// kajo_hip_denoise's refusals of the parameters (before the handle is looked at) and of the handle
+int checkDenoise(kajo_hip_t h, const KajoDenoiseParams* p)
+{
     if (!p)
         return fail(KAJO_E_INVALID, "null denoise parameters");
     if (p->iterations < 0 || p->iterations > 8)
@@ -1212,27 +1228,96 @@ int kajo_hip_denoise(kajo_hip_t h, const KajoDenoiseParams* p, float* radiance, 
         return fail(KAJO_E_STATE, "the handle was created without the AOV flag: nothing to guide the denoiser");
     if (h->passesDone < 1)
         return fail(KAJO_E_STATE, "nothing rendered yet");
-    int rc = bind(h);
-    if (rc)
-        return rc;
+    return KAJO_OK;
+}
+
+// The denoised frame (sums over passes, row-major) on the handle's stream, in the denoiser's scratch: *out points into it. Checked by
+// checkDenoise, device bound.
+int denoiseFrame(KajoHip* h, const KajoDenoiseParams* p, void** out)
+{
     const size_t count = (size_t)h->W * h->H;
     if (!h->denoise)
         HIP_TRY(hipMalloc(&h->denoise, count * (3 * 16 + 4)));
     char* scratch = static_cast<char*>(h->denoise);
-    void* argb = scratch + 3 * count * 16;
-    void* out = scratch + count * 16;
+    *out = scratch + count * 16;
     if (p->iterations == 0) {
         // the accumulation itself (one owner: tileCount is 1 with the AOV flag)
-        HIP_TRY((hipError_t)kajo_compose_launch(h->tiles, &h->map, out, h->stream));
+        HIP_TRY((hipError_t)kajo_compose_launch(h->tiles, &h->map, *out, h->stream));
     } else {
         const long long n = (long long)std::sqrt((double)(unsigned)h->params.samplesPerPass);
         const long long samples = std::max(n * n * h->aovPasses, 1LL);
         hipError_t le = (hipError_t)kajo_denoise_launch(h->tiles, &h->map, h->aov, static_cast<char*>(h->aov) + count * 16, (float)h->passesDone,
                                                         (float)samples, p->iterations, (p->flags & KAJO_DENOISE_NO_DEMODULATE) ? 0 : 1,
-                                                        p->sigmaLuminance, p->sigmaNormal, p->sigmaDepth, scratch, &out, h->stream);
+                                                        p->sigmaLuminance, p->sigmaNormal, p->sigmaDepth, scratch, out, h->stream);
         if (le != hipSuccess)
             return failHip(le, "denoise kernel launch");
     }
+    return KAJO_OK;
+}
+
+// KajoToneParams -> the kernels' ToneArgs, or a refusal (KAJO_E_INVALID) before any device work
+int toneArgsOf(const KajoToneParams* p, ToneArgs* t)
+{
+    if (!p)
+        return fail(KAJO_E_INVALID, "null tone parameters");
+    if (p->curve != KAJO_TONE_CLAMP && p->curve != KAJO_TONE_REINHARD && p->curve != KAJO_TONE_ACES)
+        return fail(KAJO_E_INVALID, "unknown tone curve");
+    if (p->flags & ~KAJO_TONE_AUTO_EXPOSURE)
+        return fail(KAJO_E_INVALID, "unknown tone flag");
+    if (!std::isfinite(p->exposure) || p->exposure < -32.0f || p->exposure > 32.0f)
+        return fail(KAJO_E_INVALID, "tone exposure must be finite and in [-32, 32]");
+    if (!std::isfinite(p->white) || p->white < 0.0f)
+        return fail(KAJO_E_INVALID, "tone white point must be finite and not negative");
+    if ((p->flags & KAJO_TONE_AUTO_EXPOSURE) && !(std::isfinite(p->key) && p->key > 0.0f))
+        return fail(KAJO_E_INVALID, "tone key must be finite and positive");
+    for (float r : p->reserved)
+        if (r != 0.0f)
+            return fail(KAJO_E_INVALID, "tone reserved fields must be 0");
+    t->curve = p->curve;
+    t->autoExposure = (p->flags & KAJO_TONE_AUTO_EXPOSURE) ? 1 : 0;
+    t->exposureScale = std::exp2(p->exposure);
+    t->white = p->white;
+    t->key = p->key;
+    return KAJO_OK;
+}
+
+size_t toneScratchBytes(const KajoHip* h)
+{
+    const size_t rects = (size_t)((h->W + 63) / 64) * (size_t)((h->H + 15) / 16); // tonemap.inc.hip kToneRectW x kToneRectH
+    return KAJO_TONE_PARTIALS_OFFSET + rects * 16;
+}
+
+// Enqueue the tone mapping of `src` (tiles through h->map's geometry with `gathered`'s base, or the row-major frame) into dst (device)
+int toneLaunch(KajoHip* h, const void* src, const TileMap* map, bool fromTiles, const ToneArgs& t, void* dst)
+{
+    if (t.autoExposure && !h->tone)
+        HIP_TRY(hipMalloc(&h->tone, toneScratchBytes(h)));
+    hipError_t le = (hipError_t)(h->strict() ? kajo_tone_strict_launch(src, map, fromTiles ? 1 : 0, (float)h->passesDone, &t, h->tone, dst, h->stream)
+                                             : kajo_tone_fast_launch(src, map, fromTiles ? 1 : 0, (float)h->passesDone, &t, h->tone, dst, h->stream));
+    if (le != hipSuccess)
+        return failHip(le, "tone mapping kernel launch");
+    h->toneScaleState = t.autoExposure ? 2 : 1;
+    h->toneScale = t.exposureScale;
+    return KAJO_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int kajo_hip_denoise(kajo_hip_t h, const KajoDenoiseParams* p, float* radiance, uint32_t* argb8)
+{
+    // (the parameters first: their refusals do not need a handle)
+    int rc = checkDenoise(h, p);
+    if (rc)
+        return rc;
+    if ((rc = bind(h)))
+        return rc;
+    const size_t count = (size_t)h->W * h->H;
+    void* out = nullptr;
+    if ((rc = denoiseFrame(h, p, &out)))
+        return rc;
+    void* argb = static_cast<char*>(h->denoise) + 3 * count * 16;
     if (argb8) {
         hipError_t le = (hipError_t)(h->strict() ? kajo_resolve_strict_launch(out, (int)count, (float)h->passesDone, argb, h->stream)
                                                  : kajo_resolve_fast_launch(out, (int)count, (float)h->passesDone, argb, h->stream));
@@ -1243,6 +1328,92 @@ int kajo_hip_denoise(kajo_hip_t h, const KajoDenoiseParams* p, float* radiance, 
     if (radiance)
         HIP_TRY(hipMemcpyAsync(radiance, out, count * 16, hipMemcpyDeviceToHost, h->stream));
     return kajo_hip_wait(h);
+}
+
+void kajo_hip_default_tone_params(KajoToneParams* p)
+{
+    if (!p)
+        return;
+    std::memset(p, 0, sizeof *p);
+    p->curve = KAJO_TONE_CLAMP;
+    p->flags = 0;
+    p->exposure = 0.0f;
+    p->white = 0.0f;
+    p->key = 0.18f;
+}
+
+int kajo_hip_tonemap_argb8(kajo_hip_t h, const KajoToneParams* p, const KajoDenoiseParams* denoise, uint32_t* argb8, float* scale)
+{
+    // (every refusal before any device work: the parameters, the denoiser's, then the handle)
+    ToneArgs t{};
+    int rc = toneArgsOf(p, &t);
+    if (rc)
+        return rc;
+    if (denoise) {
+        if ((rc = checkDenoise(h, denoise)))
+            return rc;
+    } else if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    if ((rc = bind(h)))
+        return rc;
+    if (h->passesDone < 1)
+        return fail(KAJO_E_STATE, "nothing rendered yet");
+    const size_t count = (size_t)h->W * h->H;
+    if (!h->argb)
+        HIP_TRY(hipMalloc(&h->argb, count * 4));
+    if (denoise) {
+        void* out = nullptr;
+        if ((rc = denoiseFrame(h, denoise, &out)) || (rc = toneLaunch(h, out, &h->map, false, t, h->argb)))
+            return rc;
+    } else if (!h->frameValid && h->map.tileCount == 1) {
+        // one owner and no composed frame at hand: straight from the tile buffer, as kajo_hip_resolve_argb8_device
+        if ((rc = toneLaunch(h, h->tiles, &h->map, true, t, h->argb)))
+            return rc;
+    } else {
+        if ((rc = composeOwn(h)) || (rc = toneLaunch(h, h->frame, &h->map, false, t, h->argb)))
+            return rc;
+    }
+    if (argb8)
+        HIP_TRY(hipMemcpyAsync(argb8, h->argb, count * 4, hipMemcpyDeviceToHost, h->stream));
+    return scale ? kajo_hip_tone_scale(h, scale) : kajo_hip_wait(h);
+}
+
+int kajo_hip_tonemap_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoToneParams* p, void* dst)
+{
+    ToneArgs t{};
+    int rc = toneArgsOf(p, &t);
+    if (rc)
+        return rc;
+    if (!h || !dst)
+        return fail(KAJO_E_INVALID, "null argument");
+    if ((rc = bind(h)))
+        return rc;
+    if (h->passesDone < 1)
+        return fail(KAJO_E_STATE, "nothing rendered yet");
+    if (!gathered) {
+        if (h->map.tileCount != 1)
+            return fail(KAJO_E_STATE, "a handle that owns part of the frame needs the gathered tile buffers");
+        gathered = h->tiles;
+    }
+    return toneLaunch(h, gathered, &h->map, true, t, dst);
+}
+
+int kajo_hip_tone_scale(kajo_hip_t h, float* scale)
+{
+    if (!h || !scale)
+        return fail(KAJO_E_INVALID, "null argument");
+    if (h->toneScaleState == 0)
+        return fail(KAJO_E_STATE, "nothing tone-mapped yet");
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    float s = h->toneScale;
+    if (h->toneScaleState == 2)
+        HIP_TRY(hipMemcpyAsync(&s, h->tone, sizeof s, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = kajo_hip_wait(h)))
+        return rc;
+    *scale = s;
+    return KAJO_OK;
 }
 
 namespace

@@ -30,3 +30,6 @@
 // first-hit AOVs (KAJO_FLAG_AOV)
 #define KAJO_AOV_NAME kajo_aov_fast
 #include "aov.inc.hip"
+// exposure, tone curves and automatic exposure in the resolve (kajo_hip_tonemap_argb8)
+#define KAJO_TONE_SUFFIX _fast
+#include "tonemap.inc.hip"

@@ -27,6 +27,9 @@
 // first-hit AOVs (KAJO_FLAG_AOV): this instance serves the STRICT and the EXACT handles
 #define KAJO_AOV_NAME kajo_aov_strict
 #include "aov.inc.hip"
+// exposure, tone curves and automatic exposure in the resolve (kajo_hip_tonemap_argb8): these instances serve the STRICT and the EXACT handles
+#define KAJO_TONE_SUFFIX _strict
+#include "tonemap.inc.hip"
 
 // include/kajo_strictmath.h element-wise on the device (kajo_hip_kat_strictmath): the claim that these
 // functions give identical bits on x86-64 and gfx950 is checked directly.

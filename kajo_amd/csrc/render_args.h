@@ -120,6 +120,20 @@ static inline void kajoTileSlot(const TileMap& m, int x, int y, int* owner, uint
     *slot = (uint32_t)(((tile / m.tileCount) * wavesPerTile + wb) * 64 + lane);
 }
 
+// One tone mapping (tonemap.inc.hip; include/kajo_hip.h KajoToneParams, validated by capi.cpp)
+#define KAJO_TONE_CURVE_CLAMP 0    // = KAJO_TONE_CLAMP
+#define KAJO_TONE_CURVE_REINHARD 1 // = KAJO_TONE_REINHARD
+#define KAJO_TONE_CURVE_ACES 2     // = KAJO_TONE_ACES
+#define KAJO_TONE_PARTIALS_OFFSET 256 // scratch: the scale word (float) at 0, the logavg rectangles' double2 (sum, count) from here
+struct ToneArgs
+{
+    int32_t curve;        // KAJO_TONE_CURVE_*
+    int32_t autoExposure; // 1: s = exposureScale * key / Lavg of the frame (logavg + scale kernels); 0: s = exposureScale
+    float exposureScale;  // 2^exposure
+    float white;          // REINHARD: the white point, 0 = none
+    float key;            // auto exposure: the grey Lavg is mapped to
+};
+
 // Launch tail: slot of thread `tid` of physical workgroup `physical` -- part `part` > 0 of a parted block -- in the compact side buffers
 // (RenderArgs::side): buffer part - 1, behind the slots of the parted blocks before it in the order. The fold kernel reads the same
 // place as (part - 1) * sideStride + j * threads + tid for the j-th parted block.

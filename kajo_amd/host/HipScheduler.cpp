@@ -73,6 +73,10 @@ struct Scheduler::Impl
     void* argbDevice = nullptr;       // on device 0: the resolved image of a gathered frame, before it goes to Image::pixels
     size_t tileBytes = 0;
     Statistics stats;
+    float toneScale = 1; // Statistics::toneScale of the last image
+
+    // Options::tone is the identity (include/kajo_hip.h: s = 1 and the clamp, whatever white and key say): the plain resolve
+    bool toneIsIdentity() const { return opt.tone.curve == KAJO_TONE_CLAMP && opt.tone.flags == 0 && opt.tone.exposure == 0.0f; }
 
     ~Impl()
     {
@@ -190,7 +194,10 @@ struct Scheduler::Impl
     {
         if (opt.gpus == 1 && !opt.forceGather) {
             // single owner: the library resolves from its own tile buffer
-            check(kajo_hip_resolve_argb8(handles[0], image->pixels.get()), "kajo_hip_resolve_argb8");
+            if (toneIsIdentity())
+                check(kajo_hip_resolve_argb8(handles[0], image->pixels.get()), "kajo_hip_resolve_argb8");
+            else
+                check(kajo_hip_tonemap_argb8(handles[0], &opt.tone, nullptr, image->pixels.get(), &toneScale), "kajo_hip_tonemap_argb8");
             return;
         }
         const size_t count = tileBytes / sizeof(float);
@@ -217,11 +224,16 @@ struct Scheduler::Impl
             }
         }
         composed = false;
-        check(kajo_hip_resolve_gathered_argb8_device(handles[0], gathered, argbDevice), "kajo_hip_resolve_gathered_argb8_device");
+        if (toneIsIdentity())
+            check(kajo_hip_resolve_gathered_argb8_device(handles[0], gathered, argbDevice), "kajo_hip_resolve_gathered_argb8_device");
+        else
+            check(kajo_hip_tonemap_gathered_argb8_device(handles[0], gathered, &opt.tone, argbDevice), "kajo_hip_tonemap_gathered_argb8_device");
         checkHip(hipSetDevice(devices[0]), "hipSetDevice");
         checkHip(hipMemcpyAsync(image->pixels.get(), argbDevice, (size_t)image->width * image->height * 4, hipMemcpyDeviceToHost, streams[0]),
                  "hipMemcpyAsync(image)");
         checkHip(hipStreamSynchronize(streams[0]), "hipStreamSynchronize");
+        if (!toneIsIdentity())
+            check(kajo_hip_tone_scale(handles[0], &toneScale), "kajo_hip_tone_scale"); // (the stream is drained: no wait left)
     }
     bool composed = false;
 };
@@ -280,6 +292,14 @@ void Scheduler::readDenoised(const KajoDenoiseParams* params, float* radiance, u
     KajoDenoiseParams p;
     kajo_hip_default_denoise_params(&p);
     check(kajo_hip_denoise(d.handles[0], params ? params : &p, radiance, argb8), "kajo_hip_denoise");
+}
+
+void Scheduler::readDenoisedTonemapped(const KajoDenoiseParams* params, const KajoToneParams* tone, uint32_t* argb8, float* scale)
+{
+    Impl& d = *m_impl;
+    KajoDenoiseParams p;
+    kajo_hip_default_denoise_params(&p);
+    check(kajo_hip_tonemap_argb8(d.handles[0], tone ? tone : &d.opt.tone, params ? params : &p, argb8, scale), "kajo_hip_tonemap_argb8");
 }
 
 void Scheduler::run()
@@ -347,6 +367,7 @@ void Scheduler::run()
     d.stats.gpus = o.gpus;
     d.stats.batchMs = batchMs;
     d.stats.batchPasses = batchPasses;
+    d.stats.toneScale = d.toneScale;
     d.stats.wallSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     for (kajo_hip_t h : d.handles) {
         KajoCounters c;

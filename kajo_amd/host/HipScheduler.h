@@ -15,10 +15,10 @@
 #include <vector>
 
 #include "Scheduler.h"
+#include "kajo_hip.h" // KajoToneParams (Options::tone)
 
 class Image;
 class Preview;
-struct KajoDenoiseParams; // include/kajo_hip.h
 
 namespace scene
 {
@@ -58,6 +58,9 @@ struct Options
     bool forceGather = false;     // run the gather + compose step with ONE owner too (a one-rank communicator whose
                                   // rank sends its tile buffer to itself): the multi-GPU call sequence on a one-GPU box
     bool aov = false;             // also accumulate the first-hit albedo / normal / depth (KAJO_FLAG_AOV; readAov): one GPU only
+    // Exposure, tone curve and automatic exposure of the image run() writes (include/kajo_hip.h kajo_hip_tonemap_argb8; with one owner
+    // or after the gather). The default is the identity: every frame then takes the plain resolve, exactly as without this field.
+    KajoToneParams tone = {KAJO_TONE_CLAMP, 0u, 0.0f, 0.0f, 0.18f, {0.0f, 0.0f, 0.0f}};
 };
 
 struct Statistics
@@ -69,6 +72,7 @@ struct Statistics
     int gpus = 0;          // tile owners the frame was dealt to
     std::vector<double> batchMs; // wall time of every refresh: render launch .. Image::pixels filled (host), in run() order
     std::vector<int> batchPasses;
+    float toneScale = 1;   // the scale s the last image was tone-mapped with (Options::tone; 1 with the identity)
 };
 
 class Scheduler : public ::Scheduler
@@ -91,6 +95,9 @@ public:
     // the frame denoised with the AOVs as guides after run() (Options::aov; include/kajo_hip.h kajo_hip_denoise): W*H*4 float sums and
     // W*H ARGB8 words, either may be null; params null = kajo_hip_default_denoise_params
     void readDenoised(const KajoDenoiseParams* params, float* radiance, uint32_t* argb8);
+    // the same frame tone-mapped (include/kajo_hip.h kajo_hip_tonemap_argb8 with denoise = params): W*H ARGB8 words; tone null = Options::tone;
+    // *scale (may be null) = the s applied
+    void readDenoisedTonemapped(const KajoDenoiseParams* params, const KajoToneParams* tone, uint32_t* argb8, float* scale);
 
 private:
     struct Impl;

@@ -1,6 +1,7 @@
 // Main.cpp -- headless driver with the reference's command line (renderer/Main.cpp:97-146):
 //   kajo_render [-w SIZE] [-h SIZE] [-r hip] [options] SCENE.json     (no SCENE: the built-in test scene)
 // plus what a window-less run needs: a pass budget, an output name and the backend's options.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -15,10 +16,29 @@
 #include "Preview.h"
 #include "scene/Scene.h"
 
+namespace
+{
+
+// a float option's value, whole and finite, or false
+bool parseFloat(const std::string& text, float* out)
+{
+    char* end = nullptr;
+    const float v = std::strtof(text.c_str(), &end);
+    if (text.empty() || *end != '\0' || !std::isfinite(v))
+        return false;
+    *out = v;
+    return true;
+}
+
+} // namespace
+
 int main(int argc, char** argv)
 {
     std::vector<std::string> args(argv, argv + argc);
-    std::string rendererName = "hip", out = "out.png", rawOut, aovPrefix, denoiseOut, scenePath;
+    std::string rendererName = "hip", out = "out.png", rawOut, aovPrefix, denoiseOut, hdrOut, scenePath;
+    // tone options (include/kajo_hip.h KajoToneParams): the raw text, checked after the loop; toneGiven = any of them was given
+    std::string toneCurve, toneExposure, toneWhite, toneKey;
+    bool toneAuto = false, toneGiven = false;
     int width = 640, height = 480;
     int denoiseIterations = 5;
     hip::Options opt;
@@ -57,13 +77,20 @@ int main(int argc, char** argv)
                         "                    --passes passes (16 when 0) in launches planned for half a second at most\n"
                         "    -o FILE         PNG output (out.png)\n"
                         "    --raw FILE      also dump the float4 accumulation (W*H*4 floats)\n"
+                        "    --hdr FILE      also write the mean radiance (the accumulation / passes) as a 3-channel PFM, no exposure or curve\n"
+                        "    --tonemap CURVE the image's tone curve (-o and --denoise; include/kajo_hip.h kajo_hip_tonemap_argb8): clamp (the\n"
+                        "                    reference's, default) | reinhard (on luminance, Reinhard et al. 2002) | aces (Narkowicz 2015)\n"
+                        "    --exposure EV   exposure in stops, -32..32: the mean radiance is scaled by 2^EV before the curve (0)\n"
+                        "    --white W       reinhard: the exposed luminance mapped to white, >= 0 (0 = none: L / (1 + L))\n"
+                        "    --auto-exposure scale the frame's log-average luminance to --key (on top of --exposure)\n"
+                        "    --key K         --auto-exposure: the grey the log-average is mapped to, > 0 (0.18)\n"
                         "    --aov PREFIX    also write the first-hit AOVs a denoiser takes, averaged over the render's camera samples:\n"
                         "                    PREFIX_albedo.pfm, PREFIX_normal.pfm (3 channels), PREFIX_depth.pfm (1; mean over the hits)\n"
                         "                    (one GPU only)\n"
                         "    --denoise FILE  also write the frame denoised with those AOVs as guides, as a PNG (edge-aware A-trous filter,\n"
                         "                    include/kajo_hip.h kajo_hip_denoise; collects the AOVs; one GPU only)\n"
                         "    --denoise-iterations K  the filter's iterations, 0..8 (5)\n"
-                        "    --json          print run statistics as one JSON line\n"
+                        "    --json          print run statistics as one JSON line (with a tone option: the scale applied, tone_scale)\n"
                         "    -v              progress on stderr\n",
                         args[0].c_str());
             return 1;
@@ -88,6 +115,12 @@ int main(int argc, char** argv)
         else if (a == "--scene-pod" && more) podPath = args[++i];
         else if (a == "-o" && more) out = args[++i];
         else if (a == "--raw" && more) rawOut = args[++i];
+        else if (a == "--hdr" && more) hdrOut = args[++i];
+        else if (a == "--tonemap" && more) { toneCurve = args[++i]; toneGiven = true; }
+        else if (a == "--exposure" && more) { toneExposure = args[++i]; toneGiven = true; }
+        else if (a == "--white" && more) { toneWhite = args[++i]; toneGiven = true; }
+        else if (a == "--auto-exposure") { toneAuto = true; toneGiven = true; }
+        else if (a == "--key" && more) { toneKey = args[++i]; toneGiven = true; }
         else if (a == "--aov" && more) aovPrefix = args[++i];
         else if (a == "--denoise" && more) denoiseOut = args[++i];
         else if (a == "--denoise-iterations" && more) denoiseIterations = std::atoi(args[++i].c_str());
@@ -98,6 +131,33 @@ int main(int argc, char** argv)
     if (width <= 0 || height <= 0) {
         std::cerr << "Bad image size" << std::endl;
         return 1;
+    }
+    if (toneGiven) {
+        // (before any device is opened: the refusals of kajo_hip_tonemap_argb8, with the option's name)
+        if (threeArg) {
+            std::cerr << "kajo_render: the tone options need the backend's options (without --three-arg)" << std::endl;
+            return 1;
+        }
+        if (toneCurve == "clamp" || toneCurve.empty()) opt.tone.curve = KAJO_TONE_CLAMP;
+        else if (toneCurve == "reinhard") opt.tone.curve = KAJO_TONE_REINHARD;
+        else if (toneCurve == "aces") opt.tone.curve = KAJO_TONE_ACES;
+        else {
+            std::cerr << "kajo_render: --tonemap must be clamp, reinhard or aces" << std::endl;
+            return 1;
+        }
+        if (!toneExposure.empty() && (!parseFloat(toneExposure, &opt.tone.exposure) || opt.tone.exposure < -32.0f || opt.tone.exposure > 32.0f)) {
+            std::cerr << "kajo_render: --exposure must be a number in -32..32" << std::endl;
+            return 1;
+        }
+        if (!toneWhite.empty() && (!parseFloat(toneWhite, &opt.tone.white) || opt.tone.white < 0.0f)) {
+            std::cerr << "kajo_render: --white must be a finite number >= 0" << std::endl;
+            return 1;
+        }
+        if (!toneKey.empty() && (!parseFloat(toneKey, &opt.tone.key) || opt.tone.key <= 0.0f)) {
+            std::cerr << "kajo_render: --key must be a finite number > 0" << std::endl;
+            return 1;
+        }
+        opt.tone.flags = toneAuto ? KAJO_TONE_AUTO_EXPOSURE : 0u;
     }
     if (!aovPrefix.empty()) {
         // (before any device is opened: the AOV buffers are whole-frame buffers of ONE handle, include/kajo_hip.h KAJO_FLAG_AOV)
@@ -173,6 +233,18 @@ int main(int argc, char** argv)
             std::ofstream f(rawOut, std::ios::binary);
             f.write(reinterpret_cast<const char*>(acc.data()), (std::streamsize)(acc.size() * sizeof(float)));
         }
+        if (!hdrOut.empty()) {
+            // the estimate itself: sum / P in float32, RGB
+            const size_t count = (size_t)width * height;
+            std::vector<float> acc(count * 4), rgb(count * 3);
+            hipScheduler->readRadiance(acc.data());
+            const float passes = (float)hipScheduler->statistics().passes;
+            for (size_t i = 0; i < count; i++)
+                for (int k = 0; k < 3; k++)
+                    rgb[3 * i + k] = acc[4 * i + k] / passes;
+            if (!writePfm(hdrOut, width, height, 3, rgb.data()))
+                return 3;
+        }
         if (!aovPrefix.empty()) {
             // the means: albedo and normal over every sample, depth over the samples that hit (0 where none did)
             const size_t count = (size_t)width * height;
@@ -196,7 +268,10 @@ int main(int argc, char** argv)
             kajo_hip_default_denoise_params(&p);
             p.iterations = denoiseIterations;
             Image denoised(width, height);
-            hipScheduler->readDenoised(&p, nullptr, denoised.pixels.get());
+            if (toneGiven)
+                hipScheduler->readDenoisedTonemapped(&p, nullptr, denoised.pixels.get(), nullptr);
+            else
+                hipScheduler->readDenoised(&p, nullptr, denoised.pixels.get());
             if (!denoised.save(denoiseOut))
                 return 3;
         }
@@ -225,7 +300,10 @@ int main(int argc, char** argv)
             std::printf("%s%d", i ? ", " : "", preview->updates()[i].pass);
             onOwner = onOwner && preview->updates()[i].onCreatingThread;
         }
-        std::printf("], \"preview_updates_on_owning_thread\": %s, \"preview_event_calls\": %d}\n", onOwner ? "true" : "false", preview->eventCalls());
+        std::printf("], \"preview_updates_on_owning_thread\": %s, \"preview_event_calls\": %d", onOwner ? "true" : "false", preview->eventCalls());
+        if (toneGiven)
+            std::printf(", \"tone_scale\": %.9g", (double)s.toneScale);
+        std::printf("}\n");
     }
     return 0;
 }

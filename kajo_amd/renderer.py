@@ -114,11 +114,8 @@ class HipRenderer:
         np.divide(B[..., 3], hits, out=depth, where=hits > 0)
         return dict(raw=(A, B), samples=samples.value, albedo=A[..., :3] / s, normal=B[..., :3] / s, depth=depth, hits=hits)
 
-    def denoise(self, iterations: int = 5, sigma_luminance: float = None, sigma_normal: float = None, sigma_depth: float = None,
-                demodulate: bool = True) -> dict:
-        """Edge-aware A-trous denoise of the frame guided by the first-hit AOVs (include/kajo_hip.h kajo_hip_denoise; the handle needs
-        aov=True): radiance = (H, W, 4) float32 sums over passes, as radiance(); argb8 = (H, W) uint32, as argb8(). Sigmas left None take
-        kajo_hip_default_denoise_params' values. The accumulation and the AOVs are not touched."""
+    def _denoise_params(self, iterations: int = 5, sigma_luminance: float = None, sigma_normal: float = None, sigma_depth: float = None,
+                        demodulate: bool = True):
         p = capi.KajoDenoiseParams()
         self._L.kajo_hip_default_denoise_params(C.byref(p))
         p.iterations = int(iterations)
@@ -126,10 +123,47 @@ class HipRenderer:
         for field, value in (("sigmaLuminance", sigma_luminance), ("sigmaNormal", sigma_normal), ("sigmaDepth", sigma_depth)):
             if value is not None:
                 setattr(p, field, float(value))
+        return p
+
+    def denoise(self, iterations: int = 5, sigma_luminance: float = None, sigma_normal: float = None, sigma_depth: float = None,
+                demodulate: bool = True) -> dict:
+        """Edge-aware A-trous denoise of the frame guided by the first-hit AOVs (include/kajo_hip.h kajo_hip_denoise; the handle needs
+        aov=True): radiance = (H, W, 4) float32 sums over passes, as radiance(); argb8 = (H, W) uint32, as argb8(). Sigmas left None take
+        kajo_hip_default_denoise_params' values. The accumulation and the AOVs are not touched."""
+        p = self._denoise_params(iterations, sigma_luminance, sigma_normal, sigma_depth, demodulate)
         radiance = np.empty((self.height, self.width, 4), np.float32)
         argb8 = np.empty((self.height, self.width), np.uint32)
         capi.check(self._L.kajo_hip_denoise(self._h, C.byref(p), radiance.ctypes.data_as(C.c_void_p), argb8.ctypes.data_as(C.c_void_p)))
         return dict(radiance=radiance, argb8=argb8)
+
+    def tonemap(self, curve: str = "clamp", exposure: float = 0.0, white: float = 0.0, auto_exposure: bool = False, key: float = 0.18,
+                denoise: dict = None):
+        """Exposure, tone curve and automatic exposure in the resolve (include/kajo_hip.h kajo_hip_tonemap_argb8): -> (argb8, scale), argb8
+        = (H, W) uint32 as argb8(), scale = the linear factor s applied to the mean radiance. curve: "clamp" | "reinhard" | "aces".
+        denoise: None maps the accumulation; a dict of denoise()'s keyword arguments maps the frame denoise() would give (aov=True). The
+        defaults are argb8() bit for bit. The accumulation, the AOVs and the counters are not touched."""
+        curves = {"clamp": capi.KAJO_TONE_CLAMP, "reinhard": capi.KAJO_TONE_REINHARD, "aces": capi.KAJO_TONE_ACES}
+        if curve not in curves:
+            raise ValueError("curve must be one of %s" % ", ".join(curves))
+        p = capi.KajoToneParams()
+        self._L.kajo_hip_default_tone_params(C.byref(p))
+        p.curve = curves[curve]
+        p.flags = capi.KAJO_TONE_AUTO_EXPOSURE if auto_exposure else 0
+        p.exposure, p.white, p.key = float(exposure), float(white), float(key)
+        d = None
+        if denoise is not None:
+            d = self._denoise_params(**denoise)
+        argb8 = np.empty((self.height, self.width), np.uint32)
+        scale = C.c_float()
+        capi.check(self._L.kajo_hip_tonemap_argb8(self._h, C.byref(p), None if d is None else C.byref(d), argb8.ctypes.data_as(C.c_void_p),
+                                                  C.byref(scale)))
+        return argb8, scale.value
+
+    def tone_scale(self) -> float:
+        """The scale s of the most recent tone mapping (include/kajo_hip.h kajo_hip_tone_scale)."""
+        scale = C.c_float()
+        capi.check(self._L.kajo_hip_tone_scale(self._h, C.byref(scale)))
+        return scale.value
 
     def aov_kernel(self):
         """Name of the AOV kernel instance the handle launches (None without aov=True)."""
