@@ -21,9 +21,7 @@
 #include "render_args.h"
 #include "stage.h"
 #include "launch_order.h"
-#include "tuning.h"
-
-constexpr int kMaxParts = 8; // workgroups a block of the launch tail is rendered in: one per group of a launch of 2 .. 8 groups
+#include "launch_plan.h"
 
 // launchers defined next to their kernels (kernel_fast.hip, kernel_strict.hip, kernel_exact.hip, aux_kernels.hip)
 extern "C" {
@@ -62,6 +60,37 @@ int kajo_tone_strict_launch(const void* src, const TileMap* map, int fromTiles, 
 static_assert(KAJO_TONE_CLAMP == KAJO_TONE_CURVE_CLAMP && KAJO_TONE_REINHARD == KAJO_TONE_CURVE_REINHARD && KAJO_TONE_ACES == KAJO_TONE_CURVE_ACES,
               "tonemap.inc.hip numbers the curves as include/kajo_hip.h does");
 
+// One numerics build's launchers
+struct KernelSet
+{
+    int (*render)(const RenderArgs*, int coldInLds, unsigned grid, unsigned block, size_t lds, void* stream);
+    int (*split)(const RenderArgs*, unsigned grid, unsigned block, size_t lds, void* stream);
+    int (*setLds)(int coldInLds, size_t lds);
+    int (*resolve)(const void* frame, int count, float passes, void* dst, void* stream);
+    int (*resolveTiles)(const void* gathered, const TileMap* map, float passes, void* dst, void* stream);
+    int (*tone)(const void* src, const TileMap* map, int fromTiles, float passes, const ToneArgs* t, void* scratch, void* dst, void* stream);
+    int (*aov)(const AovArgs*, int instance, unsigned grid, size_t lds, void* stream);
+    int (*aovSetLds)(int instance, size_t lds);
+    int (*katTrace)(const KatTraceArgs*, unsigned grid, size_t lds, void* stream);
+    int (*katShade)(const RenderArgs*, unsigned grid, size_t lds, void* stream);
+    const char* aovNames[KAJO_AOV_INSTANCES]; // kajo_hip_aov_kernel
+};
+
+static const KernelSet kFastKernels = {kajo_render_fast_launch, kajo_render_fast_split_launch, kajo_render_fast_set_lds, kajo_resolve_fast_launch,
+                                       kajo_resolve_tiles_fast_launch, kajo_tone_fast_launch, kajo_aov_fast_launch, kajo_aov_fast_set_lds,
+                                       kajo_kat_trace_fast_launch, kajo_kat_shade_fast_launch,
+                                       {"kajo_aov_fast", "kajo_aov_fast_big", "kajo_aov_fast_big_lg", "kajo_aov_fast_biglist", "kajo_aov_fast_biglist_lg"}};
+static const KernelSet kStrictKernels = {kajo_render_strict_launch, kajo_render_strict_split_launch, kajo_render_strict_set_lds, kajo_resolve_strict_launch,
+                                         kajo_resolve_tiles_strict_launch, kajo_tone_strict_launch, kajo_aov_strict_launch, kajo_aov_strict_set_lds,
+                                         kajo_kat_trace_strict_launch, kajo_kat_shade_strict_launch,
+                                         {"kajo_aov_strict", "kajo_aov_strict_big", "kajo_aov_strict_big_lg", "kajo_aov_strict_biglist", "kajo_aov_strict_biglist_lg"}};
+// The oracle's arithmetic in everything that decides (STRICT and EXACT): which walk, which hold policy, whose resolve. EXACT has render
+// and shading kernels of its own; the STRICT instances serve it for the rest (EXACT's camera rays, walk and normals are STRICT's arithmetic).
+static const KernelSet kExactKernels = {kajo_render_exact_launch, kajo_render_exact_split_launch, kajo_render_exact_set_lds, kajo_resolve_strict_launch,
+                                        kajo_resolve_tiles_strict_launch, kajo_tone_strict_launch, kajo_aov_strict_launch, kajo_aov_strict_set_lds,
+                                        kajo_kat_trace_strict_launch, kajo_kat_shade_exact_launch,
+                                        {"kajo_aov_strict", "kajo_aov_strict_big", "kajo_aov_strict_big_lg", "kajo_aov_strict_biglist", "kajo_aov_strict_biglist_lg"}};
+
 namespace
 {
 
@@ -85,23 +114,42 @@ int failHip(hipError_t e, const char* what)
             return failHip(e_, #expr);                                                                                 \
     } while (0)
 
-template <class T>
-hipError_t upload(const std::vector<T>& v, const T** out, std::vector<void*>& owned)
+// A device allocation, freed with its owner (KajoHip's members: by destroy(), with the handle's device current)
+struct DeviceBuffer
 {
-    *out = nullptr;
-    const size_t bytes = (v.empty() ? 1 : v.size()) * sizeof(T);
     void* p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess)
-        return e;
-    owned.push_back(p);
-    if (!v.empty()) {
-        e = hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-        if (e != hipSuccess)
-            return e;
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    ~DeviceBuffer() { reset(); }
+    void reset()
+    {
+        if (p)
+            (void)hipFree(p);
+        p = nullptr;
     }
-    *out = static_cast<const T*>(p);
-    return hipSuccess;
+    hipError_t alloc(size_t bytes)
+    {
+        reset();
+        return hipMalloc(&p, bytes ? bytes : 1);
+    }
+    // allocated on first need, kept after
+    hipError_t ensure(size_t bytes) { return p ? hipSuccess : alloc(bytes); }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+    explicit operator bool() const { return p != nullptr; }
+};
+
+template <class T>
+hipError_t upload(const std::vector<T>& v, const T** out, std::vector<DeviceBuffer>& owned)
+{
+    owned.emplace_back();
+    DeviceBuffer& b = owned.back();
+    hipError_t e = b.alloc((v.empty() ? 1 : v.size()) * sizeof(T));
+    if (e == hipSuccess && !v.empty())
+        e = hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    *out = b.as<const T>();
+    return e;
 }
 
 } // namespace
@@ -113,106 +161,55 @@ struct KajoHip
     bool ownStream = false;
     int W = 0, H = 0;
     KajoParams params{};
+    Numerics numerics = Numerics::Fast;
+    const KernelSet* k = &kFastKernels; // the launchers of that build
     kajo::StagedScene staged;
     DSceneView view{};
-    std::vector<void*> sceneBuffers;
+    std::vector<DeviceBuffer> sceneBuffers;
+    KajoLdsPlan lds; // launch_plan.h
     TileMap map{};
     int tilesY = 0, nTiles = 0, nTilesOwned = 0, tilesPerOwner = 0;
     size_t tileBytes = 0;
-    void* tiles = nullptr;   // float4[slotsPerOwner]
-    void* frame = nullptr;   // float4[W*H], lazily
-    void* argb = nullptr;    // uint32[W*H], lazily
+    DeviceBuffer tiles; // float4[slotsPerOwner]
+    DeviceBuffer frame; // float4[W*H], lazily
+    DeviceBuffer argb;  // uint32[W*H], lazily
     bool frameValid = false;
-    unsigned long long* counters = nullptr; // device [4]
+    DeviceBuffer counters; // unsigned long long [32]: [4] work counters, then the block profile of diagnostic builds
     // launch-order feedback (render_args.h): per-wave loop trips of the last launch, block order for the next
-    uint32_t* waveTrips = nullptr;   // device [grid * 4]
-    uint32_t* blockOrder = nullptr;  // device [grid]
+    DeviceBuffer waveTrips;  // uint32 [grid * wavesPerBlock]
+    DeviceBuffer blockOrder; // uint32 [grid]
     bool orderValid = false, tripsPending = false;
     unsigned gridBlocks = 0;
     // launch tail (updateBlockOrder / partTheTail): the cost-sorted order on the host, how many of its last (cheapest) blocks are rendered in
     // parts, those blocks, and per number of parts G = 2 .. 8 the order with each of them expanded into G workgroups (built on first use)
     std::vector<uint32_t> hostOrder;
-    uint32_t* partedOrder[kMaxParts + 1] = {}; // device [gridBlocks + (G - 1) * nParted]
-    uint32_t* partedBlocks = nullptr;               // device [nParted]
+    DeviceBuffer partedOrder[kMaxParts + 1]; // uint32 [gridBlocks + (G - 1) * nParted]
+    DeviceBuffer partedBlocks;               // uint32 [nParted]
     unsigned nParted = 0;
-    void* side = nullptr;        // float4 [kMaxParts - 1][nParted * block threads]: the later parts' group sums of one launch
-    bool partsAllowed = false;   // FAST / EXACT handle of a small scene that orders its launches and may divide them
+    DeviceBuffer side;         // float4 [kMaxParts - 1][nParted * block threads]: the later parts' group sums of one launch
+    bool partsAllowed = false; // FAST / EXACT handle of a small scene that orders its launches and may divide them
     // FAST / EXACT, small scenes (render_args.h): a launch that ends inside a group of four passes leaves the group so far and the total of
     // the complete groups here
-    void* carry = nullptr;       // float4 [2][slotsPerOwner], on first need
+    DeviceBuffer carry;          // float4 [2][slotsPerOwner], on first need
     bool carryValid = false;     // ... and they are those of passesDone
     int waveSlots = 0;           // waves the chip holds at once with this handle's kernel (updateBlockOrder)
     unsigned lastTailGroups = 0; // KajoCounters.tailGroups
-    unsigned wavesPerBlock = 1; // workgroup = 64 * wavesPerBlock threads: single-wave groups dispatch and retire
-                                // independently (measured +2.3 % over 4-wave groups)
     int passesDone = 0;
-    size_t ldsBytes = 0, hotBytes = 0;
-    int stealWindow = 4; // render_args.h; 1 when a large scene needs the LDS for its grid
-    int thrL = 1, holdTrips = 1; // integrator.inc.hip MODE_HOLD
-    int ldsExtra = 0;    // (KAJO_TUNING builds only) unused bytes per wave, to study a launch at a lower occupancy
-    int helpBytes = 0;   // list scenes: [64] owner lanes + [64] blocker flags of the cooperative list walk (integrator.inc.hip), behind the mailbox
-    int accBytes = 0;    // FAST / EXACT, small scenes: [64] float4, the lanes' running totals behind the mailbox (integrator.inc.hip GROUPS)
-    size_t perWaveBytes(bool withMailbox) const
-    {
-        return (size_t)ldsExtra + (size_t)helpBytes + (withMailbox ? (size_t)64 * stealWindow * 16 + (size_t)accBytes : 0);
-    }
-    void fillWaveLds(RenderArgs& a, size_t perWaveOffset, bool withMailbox) const
-    {
-        a.perWaveOffset = (uint32_t)perWaveOffset;
-        a.perWaveBytes = (uint32_t)perWaveBytes(withMailbox);
-        a.thrL = thrL;
-        a.holdTrips = holdTrips;
-    }
-    int coldInLds = 1;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; // kernel timing
     std::vector<hipEvent_t> eventPool;
     double kernelMs = 0.0;
     uint64_t launches = 0;
     // first-hit AOVs (KAJO_FLAG_AOV; aov.inc.hip): float4 [2][W * H], albedo + hits then normal + depth, row-major; the passes summed into them
-    void* aov = nullptr;
+    DeviceBuffer aov;
     int aovInstance = KAJO_AOV_SMALL; // render_args.h KajoAovInstance: the scene class, as the render kernel is chosen
     size_t aovLds = 0;                // the instance's scene copy
     long long aovPasses = 0;
     // the denoiser's scratch (denoise.hip; kajo_hip_denoise), on its first call: float4 [3][W * H] (guide, two colour frames) + uint32 [W * H]
-    void* denoise = nullptr;
-    // tone mapping (tonemap.inc.hip; kajo_hip_tonemap_*), on its first call: the scale word + the logavg partials (toneScratchBytes)
-    void* tone = nullptr;
+    DeviceBuffer denoise;
+    // tone mapping (tonemap.inc.hip; kajo_hip_tonemap_*), on its first call: the scale word + the logavg partials (toneLaunch)
+    DeviceBuffer tone;
     int toneScaleState = 0; // the s of the most recent tone mapping: 0 none yet, 1 toneScale, 2 the scale word (auto exposure)
     float toneScale = 1.0f;
-
-    // numerics build the handle runs (include/kajo_hip.h): 0 FAST, 1 STRICT, 2 EXACT
-    int numerics() const { return (params.flags & KAJO_FLAG_STRICT) ? 1 : ((params.flags & KAJO_FLAG_EXACT) ? 2 : 0); }
-    // the oracle's arithmetic in everything that decides (STRICT and EXACT): which walk, which hold policy, whose resolve
-    bool strict() const { return numerics() != 0; }
-    int launchRender(const RenderArgs* a, int home, unsigned grid, unsigned block, size_t lds) const
-    {
-        switch (numerics()) {
-        case 1: return kajo_render_strict_launch(a, home, grid, block, lds, stream);
-        case 2: return kajo_render_exact_launch(a, home, grid, block, lds, stream);
-        default: return kajo_render_fast_launch(a, home, grid, block, lds, stream);
-        }
-    }
-    int launchSplit(const RenderArgs* a, unsigned grid, unsigned block, size_t lds) const
-    {
-        switch (numerics()) {
-        case 1: return kajo_render_strict_split_launch(a, grid, block, lds, stream);
-        case 2: return kajo_render_exact_split_launch(a, grid, block, lds, stream);
-        default: return kajo_render_fast_split_launch(a, grid, block, lds, stream);
-        }
-    }
-    // (the STRICT instance serves STRICT and EXACT handles: EXACT's camera rays, walk and normals are STRICT's arithmetic)
-    int launchAov(const AovArgs* a, unsigned grid) const
-    {
-        return strict() ? kajo_aov_strict_launch(a, aovInstance, grid, aovLds, stream) : kajo_aov_fast_launch(a, aovInstance, grid, aovLds, stream);
-    }
-    int setLds(size_t lds) const
-    {
-        switch (numerics()) {
-        case 1: return kajo_render_strict_set_lds(coldInLds, lds);
-        case 2: return kajo_render_exact_set_lds(coldInLds, lds);
-        default: return kajo_render_fast_set_lds(coldInLds, lds);
-        }
-    }
 };
 
 namespace
@@ -248,13 +245,6 @@ int getEvent(KajoHip* h, hipEvent_t* ev)
     return KAJO_OK;
 }
 
-int ensureFrame(KajoHip* h)
-{
-    if (!h->frame)
-        HIP_TRY(hipMalloc(&h->frame, (size_t)h->W * h->H * 16));
-    return KAJO_OK;
-}
-
 // whole frame from this handle's own tiles (single-owner case)
 int composeOwn(KajoHip* h)
 {
@@ -262,10 +252,8 @@ int composeOwn(KajoHip* h)
         return KAJO_OK;
     if (h->map.tileCount != 1)
         return fail(KAJO_E_STATE, "whole-frame output needs kajo_hip_compose() when tileCount > 1");
-    int rc = ensureFrame(h);
-    if (rc)
-        return rc;
-    HIP_TRY((hipError_t)kajo_compose_launch(h->tiles, &h->map, h->frame, h->stream));
+    HIP_TRY(h->frame.ensure((size_t)h->W * h->H * 16));
+    HIP_TRY((hipError_t)kajo_compose_launch(h->tiles.p, &h->map, h->frame.p, h->stream));
     h->frameValid = true;
     return KAJO_OK;
 }
@@ -283,35 +271,6 @@ void destroy(KajoHip* h)
     }
     for (hipEvent_t e : h->eventPool)
         (void)hipEventDestroy(e);
-    for (void* p : h->sceneBuffers)
-        (void)hipFree(p);
-    if (h->tiles)
-        (void)hipFree(h->tiles);
-    if (h->frame)
-        (void)hipFree(h->frame);
-    if (h->argb)
-        (void)hipFree(h->argb);
-    if (h->counters)
-        (void)hipFree(h->counters);
-    if (h->waveTrips)
-        (void)hipFree(h->waveTrips);
-    if (h->blockOrder)
-        (void)hipFree(h->blockOrder);
-    for (uint32_t* o : h->partedOrder)
-        if (o)
-            (void)hipFree(o);
-    if (h->partedBlocks)
-        (void)hipFree(h->partedBlocks);
-    if (h->side)
-        (void)hipFree(h->side);
-    if (h->carry)
-        (void)hipFree(h->carry);
-    if (h->aov)
-        (void)hipFree(h->aov);
-    if (h->denoise)
-        (void)hipFree(h->denoise);
-    if (h->tone)
-        (void)hipFree(h->tone);
     if (h->ownStream && h->stream)
         (void)hipStreamDestroy(h->stream);
     delete h;
@@ -334,29 +293,22 @@ int partTheTail(KajoHip* h)
     if (!h->waveSlots) {
         int cus = 0;
         HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
-        h->waveSlots = cus * 4 * (h->coldInLds ? 5 : 4); // (launch bounds of the small-scene / large-scene kernels)
+        h->waveSlots = cus * 4 * (h->lds.coldInLds ? 5 : 4); // (launch bounds of the small-scene / large-scene kernels)
     }
     int q4 = 4; // how many blocks, in eighths of the slots (measured: tools/tail_sweep.sh)
     KAJO_TUNE_INT("KAJO_TAIL_Q4", 0, 64, q4);
-    const unsigned nParted = kajoTailBlocks(n, (unsigned)h->waveSlots / h->wavesPerBlock, q4);
+    const unsigned nParted = kajoTailBlocks(n, (unsigned)h->waveSlots / h->lds.wavesPerBlock, q4);
     if (nParted == 0)
         return KAJO_OK;
-    const unsigned block = 64 * h->wavesPerBlock;
-    for (uint32_t*& o : h->partedOrder) {
-        if (o)
-            (void)hipFree(o);
-        o = nullptr;
-    }
-    if (h->partedBlocks)
-        (void)hipFree(h->partedBlocks);
-    if (h->side)
-        (void)hipFree(h->side);
-    h->partedBlocks = nullptr;
-    h->side = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->partedBlocks), (size_t)nParted * sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(h->partedBlocks, h->hostOrder.data() + (n - nParted), (size_t)nParted * sizeof(uint32_t), hipMemcpyHostToDevice));
+    const unsigned block = 64 * h->lds.wavesPerBlock;
+    for (DeviceBuffer& o : h->partedOrder)
+        o.reset();
+    h->partedBlocks.reset();
+    h->side.reset();
+    HIP_TRY(h->partedBlocks.alloc((size_t)nParted * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(h->partedBlocks.p, h->hostOrder.data() + (n - nParted), (size_t)nParted * sizeof(uint32_t), hipMemcpyHostToDevice));
     // the later parts' group sums of one launch: compact, a workgroup's worth of slots per parted block and part (18 MB at 1920x1080)
-    HIP_TRY(hipMalloc(&h->side, (size_t)(kMaxParts - 1) * nParted * block * 16));
+    HIP_TRY(h->side.alloc((size_t)(kMaxParts - 1) * nParted * block * 16));
     h->nParted = nParted;
     return KAJO_OK;
 }
@@ -368,8 +320,8 @@ int partedOrderFor(KajoHip* h, int parts)
         return KAJO_OK;
     std::vector<uint32_t> parted;
     kajoPartedOrder(h->hostOrder, h->nParted, parts, parted);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&h->partedOrder[parts]), parted.size() * sizeof(uint32_t)));
-    HIP_TRY(hipMemcpy(h->partedOrder[parts], parted.data(), parted.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(h->partedOrder[parts].alloc(parted.size() * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(h->partedOrder[parts].p, parted.data(), parted.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     return KAJO_OK;
 }
 
@@ -379,16 +331,71 @@ int updateBlockOrder(KajoHip* h)
 {
     h->tripsPending = false;
     const unsigned n = h->gridBlocks;
-    const unsigned w = h->wavesPerBlock;
+    const unsigned w = h->lds.wavesPerBlock;
     std::vector<uint32_t> trips((size_t)n * w);
-    HIP_TRY(hipMemcpy(trips.data(), h->waveTrips, trips.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(trips.data(), h->waveTrips.p, trips.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     std::vector<uint32_t> cost, order;
     kajoBlockCosts(trips.data(), n, w, cost);
     kajoCostOrder(cost, order);
-    HIP_TRY(hipMemcpy(h->blockOrder, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->blockOrder.p, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
     h->orderValid = true;
     h->hostOrder.swap(order);
     return partTheTail(h);
+}
+
+int samplesPerAxis(const KajoParams& p)
+{
+    return (int)std::sqrt((double)(unsigned)p.samplesPerPass); // Renderer.cpp:38
+}
+
+// camera samples summed into the AOVs
+long long aovSamples(const KajoHip* h)
+{
+    const long long n = samplesPerAxis(h->params);
+    return n * n * h->aovPasses;
+}
+
+// An image to resolve or tone-map: a tile buffer through h->map's geometry, or the row-major frame
+struct Image
+{
+    const void* src;
+    bool fromTiles;
+};
+
+// The preamble of the image outputs, after the caller's null checks, in the order of its refusals: the device bound, something rendered,
+// and the image -- with `fromGathered` the caller's gathered tile buffers (null: this handle's own, which must be the whole frame); otherwise
+// this handle's own tiles while it is the frame's one owner and no composed frame is at hand (the frame is composed when somebody asks for
+// the float radiance), else the composed frame.
+int imageOf(KajoHip* h, bool fromGathered, const void* gathered, Image* img)
+{
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (h->passesDone < 1)
+        return fail(KAJO_E_STATE, "nothing rendered yet");
+    if (fromGathered || (!h->frameValid && h->map.tileCount == 1)) {
+        if (!gathered) {
+            if (h->map.tileCount != 1)
+                return fail(KAJO_E_STATE, "a handle that owns part of the frame needs the gathered tile buffers");
+            gathered = h->tiles.p;
+        }
+        *img = Image{gathered, true};
+        return KAJO_OK;
+    }
+    if ((rc = composeOwn(h)))
+        return rc;
+    *img = Image{h->frame.p, false};
+    return KAJO_OK;
+}
+
+// Enqueue the display transform of the reference (the mean, clamp, 1/2.2) of an image into dst (device, ARGB8)
+int resolve(KajoHip* h, Image img, void* dst)
+{
+    hipError_t le = (hipError_t)(img.fromTiles ? h->k->resolveTiles(img.src, &h->map, (float)h->passesDone, dst, h->stream)
+                                               : h->k->resolve(img.src, h->W * h->H, (float)h->passesDone, dst, h->stream));
+    if (le != hipSuccess)
+        return failHip(le, "resolve kernel launch");
+    return KAJO_OK;
 }
 
 } // namespace
@@ -574,6 +581,8 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
     h->params = p;
     h->W = width;
     h->H = height;
+    h->numerics = (p.flags & KAJO_FLAG_STRICT) ? Numerics::Strict : (p.flags & KAJO_FLAG_EXACT) ? Numerics::Exact : Numerics::Fast;
+    h->k = h->numerics == Numerics::Strict ? &kStrictKernels : h->numerics == Numerics::Exact ? &kExactKernels : &kFastKernels;
 #define CREATE_TRY(expr)                                                                                               \
     do {                                                                                                               \
         hipError_t e_ = (expr);                                                                                        \
@@ -598,43 +607,26 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
     CREATE_TRY(upload(st.sphereCold, &v.sphereCold, h->sceneBuffers));
     CREATE_TRY(upload(st.material, &v.material, h->sceneBuffers));
     CREATE_TRY(upload(st.light, &v.light, h->sceneBuffers));
-    {
-        const uint32_t* cellStart = nullptr;
-        const uint16_t* items = nullptr;
-        CREATE_TRY(upload(st.gridCellStart, &cellStart, h->sceneBuffers));
-        CREATE_TRY(upload(st.gridItems, &items, h->sceneBuffers));
-        v.grid.enabled = st.gridEnabled;
-        v.grid.nCells = st.gridEnabled ? (int32_t)st.gridCellStart.size() - 1 : 0;
-        v.grid.nItems = (int32_t)st.gridItems.size();
-        v.grid.inLds = 0;
-        v.grid.cellStart = cellStart;
-        v.grid.items = items;
-        for (int k = 0; k < 3; k++) {
-            v.grid.dim[k] = st.gridDim[k];
-            v.grid.bmin[k] = st.gridEnabled ? st.gridMin[k] : 0.f;
-            v.grid.bmax[k] = st.gridEnabled ? st.gridMax[k] : 0.f;
-            v.grid.cell[k] = st.gridEnabled ? st.gridCell[k] : 1.f;
-            v.grid.invCell[k] = st.gridEnabled ? 1.f / st.gridCell[k] : 1.f;
-            v.grid.center[k] = st.gridCenter[k];
-        }
-        v.grid.reach2 = st.gridReach2;
+    CREATE_TRY(upload(st.gridCellStart, &v.grid.cellStart, h->sceneBuffers));
+    CREATE_TRY(upload(st.gridItems, &v.grid.items, h->sceneBuffers));
+    v.grid.enabled = st.gridEnabled;
+    v.grid.nCells = st.gridEnabled ? (int32_t)st.gridCellStart.size() - 1 : 0;
+    v.grid.nItems = (int32_t)st.gridItems.size();
+    for (int k = 0; k < 3; k++) {
+        v.grid.dim[k] = st.gridDim[k];
+        v.grid.bmin[k] = st.gridEnabled ? st.gridMin[k] : 0.f;
+        v.grid.bmax[k] = st.gridEnabled ? st.gridMax[k] : 0.f;
+        v.grid.cell[k] = st.gridEnabled ? st.gridCell[k] : 1.f;
+        v.grid.invCell[k] = st.gridEnabled ? 1.f / st.gridCell[k] : 1.f;
+        v.grid.center[k] = st.gridCenter[k];
     }
-    {
-        const uint32_t* rowBase = nullptr;
-        const uint16_t* off16 = nullptr;
-        const uint32_t* items = nullptr;
-        const float* invKeyScale = nullptr;
-        CREATE_TRY(upload(st.shadowRowBase, &rowBase, h->sceneBuffers));
-        CREATE_TRY(upload(st.shadowOff16, &off16, h->sceneBuffers));
-        CREATE_TRY(upload(st.shadowPacked, &items, h->sceneBuffers));
-        CREATE_TRY(upload(st.shadowInvKeyScale, &invKeyScale, h->sceneBuffers));
-        v.shadow.enabled = st.shadowEnabled ? 1 : 0;
-        v.shadow.n = st.shadowN;
-        v.shadow.rowBase = rowBase;
-        v.shadow.off16 = off16;
-        v.shadow.items = items;
-        v.shadow.invKeyScale = invKeyScale;
-    }
+    v.grid.reach2 = st.gridReach2;
+    CREATE_TRY(upload(st.shadowRowBase, &v.shadow.rowBase, h->sceneBuffers));
+    CREATE_TRY(upload(st.shadowOff16, &v.shadow.off16, h->sceneBuffers));
+    CREATE_TRY(upload(st.shadowPacked, &v.shadow.items, h->sceneBuffers));
+    CREATE_TRY(upload(st.shadowInvKeyScale, &v.shadow.invKeyScale, h->sceneBuffers));
+    v.shadow.enabled = st.shadowEnabled ? 1 : 0;
+    v.shadow.n = st.shadowN;
     v.nPlanes = st.nPlanes;
     v.nSpheres = st.nSpheres;
     v.nSphereHot = (int)st.sphereHot.size();
@@ -648,91 +640,10 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
         v.dp3[i] = st.p3[i] - st.p1[i];
         v.origin[i] = st.origin[i];
     }
-    // LDS budget per workgroup (device_scene.h / integrator.inc.hip renderBody): hot records always,
-    // cold records too while the total stays small enough for four workgroups per CU (160 KiB / 4).
-    // (integrator.inc.hip stageToLds: the 4-byte arrays are padded to a 16-byte boundary before the light records)
-    const size_t hotBytes = (size_t)v.nPlanes * 16 + (size_t)v.nSphereHot * 16 +
-                            ((((size_t)v.nPlanes + (v.allTranslated ? 0 : v.nSpheres) + v.nLights) * 4 + 15) & ~(size_t)15) + (size_t)v.nLights * (64 + 16) +
-                            ((((size_t)v.nLights * v.nPlanes) * 4 + 15) & ~(size_t)15) + 8 * 16;
-    const size_t coldBytes = (size_t)v.nPlanes * 48 + (size_t)v.nSpheres * 64 + (size_t)(v.nPlanes + v.nSpheres) * sizeof(DMaterial);
-    // What every wave adds to the scene copy (render_args.h): the mailbox of taken-over passes.
-    // The sizes below are constants of the product library. A -DKAJO_TUNING build (libkajo_hip_tune.so, tools/ only) reads
-    // overrides from the environment (tuning.h); libkajo_hip.so contains no getenv.
-    const bool big = st.gridEnabled || hotBytes + coldBytes > 40 * 1024;
-    h->stealWindow = 4;
-    h->helpBytes = st.shadowEnabled ? 512 : 0;
-    KAJO_TUNE_INT("KAJO_STEAL_WINDOW", 1, 16, h->stealWindow);
-    KAJO_TUNE_INT("KAJO_LDS_EXTRA", 0, 64 * 1024, h->ldsExtra);
-    h->ldsExtra &= ~15;
-    // integrator.inc.hip MODE_HOLD: lanes that must want the light / BSDF blocks before they run without any lane having
-    // waited a trip; 1 = every trip. Large scenes run them every trip (16 lights: most lanes are in them anyway).
-    h->thrL = big ? 1 : (h->strict() ? 28 : 20);
-    h->holdTrips = 1;
-    if (!big && h->strict()) {
-        // the STRICT loop of small scenes with several lights walks its shadow rays inside the light loop (KAJO_INLINE_SHADOW): a heavier
-        // block, worth waiting longer for (three lights: 11.6 -> 13.4 G paths/s at 48 lanes / three trips). One light (its own instance:
-        // one visit per vertex, the shadow ray in a trip of its own): 20.5-20.7 at 32-44 lanes / two trips (profiles/r04_presample.txt).
-        h->thrL = v.nLights > 1 ? 48 : 36;
-        h->holdTrips = v.nLights > 1 ? 3 : 2;
-    }
-    if (st.shadowEnabled) {
-        // Large scenes with visibility lists: the light loop runs to its end inside one trip (16 lights: ~10 rounds of light
-        // sample + shadow query) and is the expensive block of a trip, with a third of the lanes in it. It runs when 60 lanes
-        // have a vertex waiting or it has been put off six trips in a row; the walk loses lanes to the waiting (lane
-        // efficiency 0.975 -> 0.64) -- lanes without a ray skip the grid walk, so that costs the walk nothing but the slots -- and
-        // the launch gains: FAST 2.35 -> 4.34 G paths/s on the 1000-sphere scene at 4K x 32 passes with 48 lanes / three trips,
-        // 5.38 -> 5.54 from there to 60 / six once the idle lanes stopped walking stale rays (profiles/r04_c5_notes.txt).
-        h->thrL = 60;
-        h->holdTrips = 6;
-    }
-    KAJO_TUNE_INT("KAJO_THR_L", 1, 65, h->thrL);
-    KAJO_TUNE_INT("KAJO_HOLD_TRIPS", 1, 16, h->holdTrips);
-    size_t gridBytes = 0;
-    const size_t gridHeaderBytes = st.gridEnabled ? 5 * 16 : 0; // always in LDS (integrator.inc.hip gridWalk)
-    if (st.gridEnabled) {
-        gridBytes = ((st.gridCellStart.size() * sizeof(uint32_t) + st.gridItems.size() * sizeof(uint16_t)) + 15) & ~(size_t)15;
-        // The DDA reads a cell record and an item per step, each a dependent load: ~64 cycles from LDS, ~500 from L2. But the
-        // walk is latency-bound and wants its workgroups per CU (measured on the 1000-sphere scene in round 2: the grid in LDS
-        // at three workgroups per CU is 12 % SLOWER than the grid in L2 at four), so the grid moves into LDS only while hot
-        // records + grid + the four waves' areas stay within the limit.
-        int gridLimit = 40 * 1024;
-        KAJO_TUNE_INT("KAJO_GRID_LDS_LIMIT", 0, 160 * 1024, gridLimit); // bytes
-        // ... with the mailboxes shrunk to a one-pass steal window if need be
-        const int wanted = h->stealWindow;
-        for (int window : {4, 2, 1}) {
-            if (window > wanted)
-                continue;
-            h->stealWindow = window;
-            if (hotBytes + gridHeaderBytes + gridBytes + 4 * h->perWaveBytes(true) <= (size_t)gridLimit) {
-                v.grid.inLds = 1;
-                break;
-            }
-        }
-        if (!v.grid.inLds) {
-            h->stealWindow = wanted;
-            gridBytes = 0;
-        }
-    }
-    h->hotBytes = hotBytes + gridHeaderBytes + gridBytes; // what the big-scene staging (and the known-answer kernels) put in LDS
-    h->coldInLds = !big;
-    if (h->coldInLds && h->numerics() != 1) {
-        // (the lanes' running totals take the room of one pass of the mailbox: three passes to take over instead of four costs nothing,
-        // tools/steal_window_sweep.sh, and the scene copy + a wave's area of BASELINE's scenes stays within a fifth wave per SIMD's share)
-        h->accBytes = 64 * 16;
-        h->stealWindow = 3;
-        KAJO_TUNE_INT("KAJO_STEAL_WINDOW", 1, 16, h->stealWindow);
-    }
-    h->ldsBytes = hotBytes + (h->coldInLds ? coldBytes : 0) + gridHeaderBytes + gridBytes;
-    // every workgroup stages its own LDS copy of the scene: single-wave groups only while that copy is small
-    h->wavesPerBlock = h->ldsBytes <= 6 * 1024 ? 1 : 4;
-    {
-        int w = 0;
-        KAJO_TUNE_INT("KAJO_WAVES_PER_BLOCK", 1, 4, w); // 1, 2 or 4
-        if (w == 1 || w == 2 || w == 4)
-            h->wavesPerBlock = (unsigned)w;
-    }
-    // the one check, with the final values: scene copy + the waves' areas must fit a CU
-    if (((h->ldsBytes + 15) & ~(size_t)15) + (size_t)h->wavesPerBlock * h->perWaveBytes(true) > 160 * 1024) {
+    const KajoSceneLds bytes = kajoSceneLds(st);
+    h->lds = kajoLdsPlan(bytes.hotBytes, bytes.coldBytes, bytes.gridHeaderBytes, bytes.gridBytes, st.gridEnabled, st.shadowEnabled, v.nLights, h->numerics);
+    v.grid.inLds = h->lds.gridInLds ? 1 : 0;
+    if (!h->lds.fits) {
         destroy(h);
         return fail(KAJO_E_INVALID, "scene exceeds the LDS staging limit: scene records + the waves' mailboxes must fit 160 KiB");
     }
@@ -753,46 +664,43 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
     m.slotsPerOwner = h->tilesPerOwner * p.tileW * p.tileH;
     h->tileBytes = (size_t)m.slotsPerOwner * 16;
     // (FAST / EXACT handles of small scenes that order their launches render the tail of a launch in parts: partTheTail)
-    h->partsAllowed = h->coldInLds && h->numerics() != 1 && !(p.flags & (KAJO_FLAG_NO_SPLIT | KAJO_FLAG_NO_REORDER));
-    CREATE_TRY(hipMalloc(&h->tiles, h->tileBytes));
-    CREATE_TRY(hipMemsetAsync(h->tiles, 0, h->tileBytes, h->stream));
+    h->partsAllowed = h->lds.coldInLds && h->numerics != Numerics::Strict && !(p.flags & (KAJO_FLAG_NO_SPLIT | KAJO_FLAG_NO_REORDER));
+    CREATE_TRY(h->tiles.alloc(h->tileBytes));
+    CREATE_TRY(hipMemsetAsync(h->tiles.p, 0, h->tileBytes, h->stream));
     if (p.flags & KAJO_FLAG_COUNTERS) {
-        CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->counters), 32 * sizeof(unsigned long long)));
-        CREATE_TRY(hipMemsetAsync(h->counters, 0, 32 * sizeof(unsigned long long), h->stream));
+        CREATE_TRY(h->counters.alloc(32 * sizeof(unsigned long long)));
+        CREATE_TRY(hipMemsetAsync(h->counters.p, 0, 32 * sizeof(unsigned long long), h->stream));
     }
     {
+        const unsigned wavesPerBlock = h->lds.wavesPerBlock;
         const int wavesPerTile = (p.tileW / 8) * (p.tileH / 8);
-        h->gridBlocks = (unsigned)((long long)h->nTilesOwned * wavesPerTile / h->wavesPerBlock);
-        if ((long long)h->nTilesOwned * wavesPerTile / h->wavesPerBlock >= (1ll << 28)) { // (render_args.h: an order word has 28 bits for the block)
+        h->gridBlocks = (unsigned)((long long)h->nTilesOwned * wavesPerTile / wavesPerBlock);
+        if ((long long)h->nTilesOwned * wavesPerTile / wavesPerBlock >= (1ll << 28)) { // (render_args.h: an order word has 28 bits for the block)
             destroy(h);
             return fail(KAJO_E_INVALID, "frame too large: 2^28 pixel blocks per handle at most");
         }
         if (h->gridBlocks && !(p.flags & KAJO_FLAG_NO_REORDER)) {
-            CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->waveTrips), (size_t)h->gridBlocks * h->wavesPerBlock * sizeof(uint32_t)));
-            CREATE_TRY(hipMalloc(reinterpret_cast<void**>(&h->blockOrder), (size_t)h->gridBlocks * sizeof(uint32_t)));
+            CREATE_TRY(h->waveTrips.alloc((size_t)h->gridBlocks * wavesPerBlock * sizeof(uint32_t)));
+            CREATE_TRY(h->blockOrder.alloc((size_t)h->gridBlocks * sizeof(uint32_t)));
         }
     }
-    {
-        const size_t ldsTotal = ((h->ldsBytes + 15) & ~(size_t)15) + (size_t)h->wavesPerBlock * h->perWaveBytes(true);
-        if (ldsTotal > 48 * 1024) {
-            CREATE_TRY((hipError_t)h->setLds(ldsTotal));
-        }
-    }
+    if (h->lds.ldsTotal() > 48 * 1024)
+        CREATE_TRY((hipError_t)h->k->setLds(h->lds.coldInLds, h->lds.ldsTotal()));
     if (p.flags & KAJO_FLAG_AOV) {
         // the AOV kernel of the scene's class -- small scenes: everything in LDS; large ones: the hot records (and the grid's cell lists where
         // create() put them in LDS), per home of the cell lists and with or without visibility lists, as launch.inc.hip picks the render kernel
-        if (h->coldInLds)
+        if (h->lds.coldInLds)
             h->aovInstance = KAJO_AOV_SMALL;
         else if (v.shadow.enabled)
             h->aovInstance = v.grid.inLds ? KAJO_AOV_BIGLIST_LG : KAJO_AOV_BIGLIST;
         else
             h->aovInstance = v.grid.inLds ? KAJO_AOV_BIG_LG : KAJO_AOV_BIG;
-        h->aovLds = h->coldInLds ? h->ldsBytes : h->hotBytes;
+        h->aovLds = h->lds.coldInLds ? h->lds.ldsBytes : h->lds.hotBytes;
         if (h->aovLds > 48 * 1024)
-            CREATE_TRY((hipError_t)(h->strict() ? kajo_aov_strict_set_lds(h->aovInstance, h->aovLds) : kajo_aov_fast_set_lds(h->aovInstance, h->aovLds)));
+            CREATE_TRY((hipError_t)h->k->aovSetLds(h->aovInstance, h->aovLds));
         const size_t bytes = 2 * (size_t)width * height * 16;
-        CREATE_TRY(hipMalloc(&h->aov, bytes));
-        CREATE_TRY(hipMemsetAsync(h->aov, 0, bytes, h->stream));
+        CREATE_TRY(h->aov.alloc(bytes));
+        CREATE_TRY(hipMemsetAsync(h->aov.p, 0, bytes, h->stream));
     }
     CREATE_TRY(hipStreamSynchronize(h->stream));
 #undef CREATE_TRY
@@ -837,13 +745,14 @@ int kajo_hip_render(kajo_hip_t h, int passes)
         return KAJO_OK;
     }
     const KajoParams& p = h->params;
+    const KajoLdsPlan& lds = h->lds;
     RenderArgs a;
     std::memset(&a, 0, sizeof a);
     a.scene = h->view;
-    a.tiles = h->tiles;
+    a.tiles = h->tiles.p;
     a.W = h->W;
     a.H = h->H;
-    a.n = (int)std::sqrt((double)(unsigned)p.samplesPerPass); // Renderer.cpp:38
+    a.n = samplesPerAxis(p);
     a.S = (float)(unsigned)p.samplesPerPass;
     a.pixelWidth = 1.f / h->W;   // Renderer.cpp:39-42
     a.pixelHeight = 1.f / h->H;
@@ -858,124 +767,73 @@ int kajo_hip_render(kajo_hip_t h, int passes)
     a.tileIndex = p.tileIndex;
     a.tileCount = p.tileCount;
     a.nTilesOwned = h->nTilesOwned;
-    a.counters = h->counters;
-    a.mailboxOffset = (uint32_t)((h->ldsBytes + 15) & ~(size_t)15);
-    a.stealWindow = h->stealWindow;
+    a.counters = h->counters.as<unsigned long long>();
+    a.mailboxOffset = (uint32_t)lds.mailboxOffset();
+    a.stealWindow = lds.stealWindow;
+    a.carrySlots = (uint32_t)h->map.slotsPerOwner;
+    a.blockOrder = h->orderValid ? h->blockOrder.as<const uint32_t>() : nullptr;
+    a.waveTrips = (h->waveTrips && !h->orderValid) ? h->waveTrips.as<uint32_t>() : nullptr; // measure once, on the first launch
+    lds.fillWaveLds(a, a.mailboxOffset, true);
 
-    const unsigned block = 64 * h->wavesPerBlock;
+    const unsigned block = 64 * lds.wavesPerBlock;
     const unsigned grid = h->gridBlocks;
-    a.blockOrder = h->orderValid ? h->blockOrder : nullptr;
-    a.waveTrips = (h->waveTrips && !h->orderValid) ? h->waveTrips : nullptr; // measure once, on the first launch
-    // scene copy + every wave's mailbox
-    h->fillWaveLds(a, a.mailboxOffset, true);
-    const size_t ldsTotal = a.mailboxOffset + (size_t)h->wavesPerBlock * a.perWaveBytes;
+    const unsigned long long pixelBlocks = (unsigned long long)grid * lds.wavesPerBlock;
+    const bool grouped = lds.coldInLds && h->numerics != Numerics::Strict; // (integrator.inc.hip GROUPS: FAST / EXACT kernels of small scenes)
+    // (coldInLds 2: the small-scene instance of any number of lights although the scene has one, KAJO_FLAG_NO_ONE_LIGHT)
+    const int home = (lds.coldInLds && (p.flags & KAJO_FLAG_NO_ONE_LIGHT)) ? 2 : lds.coldInLds;
     const int perLaunch = p.passesPerLaunch > 0 ? p.passesPerLaunch : 16;
     int left = passes;
     while (left > 0) {
         const int now = left < perLaunch ? left : perLaunch;
         a.firstPass = h->passesDone + 1;
         a.nPasses = now;
-        // (integrator.inc.hip GROUPS, FAST / EXACT kernels of small scenes: the total takes the passes in groups of four by their absolute
-        // numbers. A launch that begins or ends inside a group hands the group over through `carry`: render_args.h)
-        const bool grouped = h->coldInLds && h->numerics() != 1;
-        const bool startsInside = grouped && h->passesDone % KAJO_GROUP_PASSES != 0, endsInside = grouped && (h->passesDone + now) % KAJO_GROUP_PASSES != 0;
-        if ((startsInside || endsInside) && !h->carry)
-            HIP_TRY(hipMalloc(&h->carry, 2 * h->tileBytes));
-        a.carry = h->carry;
-        a.carrySlots = (uint32_t)h->map.slotsPerOwner;
+        const KajoLaunchShape s = kajoLaunchShape(pixelBlocks, now, a.n, lds.coldInLds, p.flags & KAJO_FLAG_NO_SPLIT, a.mailboxOffset,
+                                                  lds.perWaveBytes(false), h->passesDone, grouped, h->orderValid, h->nParted);
+        if (s.startsInside || s.endsInside)
+            HIP_TRY(h->carry.ensure(2 * h->tileBytes));
+        a.carry = h->carry.p;
         // (a group whose first passes this handle did not render -- kajo_hip_set_pass_count to the middle of one -- continues from the
         // buffer as it stands: the restored sum counts as complete groups)
-        a.carryIn = startsInside && h->carryValid;
-        a.carryOut = endsInside;
-        const int launchGroups = (!startsInside && !endsInside) ? now / KAJO_GROUP_PASSES : 0; // whole groups, or 0
+        a.carryIn = s.startsInside && h->carryValid;
+        a.carryOut = s.endsInside;
         hipEvent_t e0, e1;
         if ((rc = getEvent(h, &e0)) || (rc = getEvent(h, &e1)))
             return rc;
         HIP_TRY(hipEventRecord(e0, h->stream));
-        // Small frames: fewer pixel blocks than a few rounds of the chip's 4096 wave slots. 2 or 4 waves then share a
-        // block and divide the passes of the launch (when they divide evenly); the per-pass terms meet in LDS.
-        unsigned split = 1;
-        const unsigned long long pixelBlocks = (unsigned long long)grid * h->wavesPerBlock;
-        if (h->coldInLds && !(p.flags & KAJO_FLAG_NO_SPLIT)) {
-            // measured (tools/size_sweep.py with KAJO_SPLIT=1..16, 256x144 ... 1920x1080): frames of fewer than three
-            // rounds of the 4096 wave slots run best with the largest power of two -- up to 16 waves per block, as far
-            // as the passes divide -- that keeps the launch within 8 rounds: many short waves pack the tail of the
-            // launch better than few long ones. From 1280x720 on the unsplit kernel is 3-8 % faster.
-            while (pixelBlocks < 3 * 4096 && split < 16 && now % (int)(split * 2) == 0 && pixelBlocks * split * 2 <= 8 * 4096)
-                split *= 2;
-            int v = 0;
-            KAJO_TUNE_INT("KAJO_SPLIT", 1, 16, v);
-            if (v >= 1 && (v & (v - 1)) == 0 && now % v == 0)
-                split = (unsigned)v;
-        }
-        while (split > 1 && a.mailboxOffset + (size_t)now * 64 * 16 + split * h->perWaveBytes(false) > 48 * 1024)
-            split /= 2; // the table and the waves' areas would need the large-LDS opt-in: not worth it
-        // Launches of FEW passes (BASELINE configs[0] is one pass of 16 samples on 1024 pixel blocks: a quarter of the chip's SIMDs,
-        // one wave each): the waves of a block divide the SAMPLES of every pass instead -- `chunks` per pass, now * chunks waves
-        // per block -- and the paths' radiances meet in the table [pass][sample][pixel]. Chosen when it puts more waves on a
-        // block than dividing the passes does.
-        unsigned chunks = 1;
-        if (h->coldInLds && !(p.flags & KAJO_FLAG_NO_SPLIT) && pixelBlocks < 3 * 4096) {
-            const unsigned nn = (unsigned)(a.n * a.n);
-            // the smallest division that gives the launch one round of the chip's wave slots (measured on configs[0], 1024 blocks:
-            // 4 chunks 18.0, 8 chunks 17.4, 16 chunks 15.5 G paths/s against 8.3 undivided; profiles/r03_configs.txt)
-            for (unsigned q = 2; q <= nn && (unsigned)now * q <= 16; q++)
-                if (nn % q == 0 && pixelBlocks * now * q <= 8 * 4096 && a.mailboxOffset + (size_t)now * nn * 64 * 16 + (size_t)now * q * h->perWaveBytes(false) <= 48 * 1024) {
-                    chunks = q;
-                    if (pixelBlocks * now * q >= 4096)
-                        break;
-                }
-            int v = 0;
-            KAJO_TUNE_INT("KAJO_SAMPLE_CHUNKS", 1, 16, v); // (held to the same 48 KiB bound as the automatic choice, the waves' areas included)
-            if (v >= 1 && nn % (unsigned)v == 0 && (unsigned)now * v <= 16 &&
-                a.mailboxOffset + (size_t)now * nn * 64 * 16 + (size_t)now * v * h->perWaveBytes(false) <= 48 * 1024)
-                chunks = (unsigned)v;
-            if ((unsigned)now * chunks <= split)
-                chunks = 1;
-        }
         hipError_t le;
         h->lastTailGroups = 0;
-        if (chunks > 1) {
+        if (s.chunks > 1 || s.split > 1) {
+            // the waves of a block divide the samples of every pass (behind the [pass][sample][pixel] table) or the passes (behind the
+            // [pass][pixel] term table); one round or two: the launch order does not matter
             RenderArgs b = a;
             b.blockOrder = nullptr;
             b.waveTrips = nullptr;
-            b.sampleChunks = (int32_t)chunks;
-            const unsigned waves = (unsigned)now * chunks;
-            h->fillWaveLds(b, a.mailboxOffset + (size_t)now * a.n * a.n * 64 * 16, false); // behind the [pass][sample][pixel] table
-            b.thrL = 1; // (short waves: holding a vertex only lengthens their tail -- configs[0] 18.9 against 16.5 G paths/s)
-            const size_t ldsSplit = b.perWaveOffset + (size_t)waves * b.perWaveBytes;
-            le = (hipError_t)h->launchSplit(&b, (unsigned)pixelBlocks, 64 * waves, ldsSplit);
-        } else if (split > 1) {
-            RenderArgs b = a;
-            b.blockOrder = nullptr; // one round or two: the launch order does not matter
-            b.waveTrips = nullptr;
-            h->fillWaveLds(b, a.mailboxOffset + (size_t)now * 64 * 16, false); // behind the [pass][pixel] term table
-            b.thrL = 1; // (as above: 1-3 % on frames below 720p)
-            const size_t ldsSplit = b.perWaveOffset + (size_t)split * b.perWaveBytes;
-            le = (hipError_t)h->launchSplit(&b, (unsigned)pixelBlocks, 64 * split, ldsSplit);
-        } else {
-            // (coldInLds 2: the small-scene instance of any number of lights although the scene has one, KAJO_FLAG_NO_ONE_LIGHT)
-            const int home = (h->coldInLds && (h->params.flags & KAJO_FLAG_NO_ONE_LIGHT)) ? 2 : h->coldInLds;
+            if (s.chunks > 1)
+                b.sampleChunks = (int32_t)s.chunks;
+            const unsigned waves = s.chunks > 1 ? (unsigned)now * s.chunks : s.split;
+            lds.fillWaveLds(b, a.mailboxOffset + (size_t)now * (s.chunks > 1 ? a.n * a.n : 1) * 64 * 16, false);
+            b.thrL = 1; // (short waves: holding a vertex only lengthens their tail -- configs[0] 18.9 against 16.5 G paths/s; 1-3 % on
+                        // split frames below 720p)
+            le = (hipError_t)h->k->split(&b, (unsigned)pixelBlocks, 64 * waves, b.perWaveOffset + (size_t)waves * b.perWaveBytes, h->stream);
+        } else if (s.parted) {
             // the launch tail: the cheapest blocks as one workgroup per group of the launch (partTheTail)
-            const bool parted = grouped && h->orderValid && h->nParted && launchGroups >= 2 && launchGroups <= kMaxParts;
-            if (parted) {
-                if ((rc = partedOrderFor(h, launchGroups))) {
-                    h->eventPool.push_back(e0);
-                    h->eventPool.push_back(e1);
-                    return rc;
-                }
-                h->lastTailGroups = h->nParted * (unsigned)(launchGroups - 1);
-                RenderArgs b = a;
-                b.blockOrder = h->partedOrder[launchGroups];
-                b.side = h->side;
-                b.sideStride = h->nParted * block;
-                b.partedFirst = grid - h->nParted;
-                le = (hipError_t)h->launchRender(&b, home, grid + h->lastTailGroups, block, ldsTotal);
-                if (le == hipSuccess)
-                    le = (hipError_t)kajo_fold_parts_launch(h->tiles, h->side, b.sideStride, h->partedBlocks, h->nParted, block, launchGroups, h->stream);
-            } else {
-                le = (hipError_t)h->launchRender(&a, home, grid, block, ldsTotal);
+            if ((rc = partedOrderFor(h, s.launchGroups))) {
+                h->eventPool.push_back(e0);
+                h->eventPool.push_back(e1);
+                return rc;
             }
+            h->lastTailGroups = h->nParted * (unsigned)(s.launchGroups - 1);
+            RenderArgs b = a;
+            b.blockOrder = h->partedOrder[s.launchGroups].as<const uint32_t>();
+            b.side = h->side.p;
+            b.sideStride = h->nParted * block;
+            b.partedFirst = grid - h->nParted;
+            le = (hipError_t)h->k->render(&b, home, grid + h->lastTailGroups, block, lds.ldsTotal(), h->stream);
+            if (le == hipSuccess)
+                le = (hipError_t)kajo_fold_parts_launch(h->tiles.p, h->side.p, b.sideStride, h->partedBlocks.as<const uint32_t>(), h->nParted, block,
+                                                        s.launchGroups, h->stream);
+        } else {
+            le = (hipError_t)h->k->render(&a, home, grid, block, lds.ldsTotal(), h->stream);
         }
         if (le != hipSuccess) {
             h->eventPool.push_back(e0);
@@ -989,8 +847,8 @@ int kajo_hip_render(kajo_hip_t h, int passes)
             AovArgs g;
             std::memset(&g, 0, sizeof g);
             g.scene = h->view;
-            g.albedoHits = h->aov;
-            g.normalDepth = static_cast<char*>(h->aov) + (size_t)h->W * h->H * 16;
+            g.albedoHits = h->aov.p;
+            g.normalDepth = h->aov.as<char>() + (size_t)h->W * h->H * 16;
             g.W = h->W;
             g.H = h->H;
             g.n = a.n;
@@ -1002,16 +860,16 @@ int kajo_hip_render(kajo_hip_t h, int passes)
             g.nPasses = now;
             g.seed = a.seed;
             const unsigned long long blocks = (unsigned long long)((h->W + 7) / 8) * ((h->H + 7) / 8);
-            HIP_TRY((hipError_t)h->launchAov(&g, (unsigned)((blocks + 3) / 4)));
+            HIP_TRY((hipError_t)h->k->aov(&g, h->aovInstance, (unsigned)((blocks + 3) / 4), h->aovLds, h->stream));
             h->aovPasses += now;
         }
-        if (a.waveTrips && split == 1 && chunks == 1) {
+        if (a.waveTrips && s.split == 1 && s.chunks == 1) {
             h->tripsPending = true;
             a.waveTrips = nullptr; // later launches of this call keep the first measurement
         }
         h->launches++;
         h->passesDone += now;
-        h->carryValid = endsInside;
+        h->carryValid = s.endsInside;
         left -= now;
     }
     h->frameValid = false;
@@ -1038,11 +896,11 @@ int kajo_hip_reset(kajo_hip_t h)
     int rc = kajo_hip_wait(h);
     if (rc)
         return rc;
-    HIP_TRY(hipMemsetAsync(h->tiles, 0, h->tileBytes, h->stream));
+    HIP_TRY(hipMemsetAsync(h->tiles.p, 0, h->tileBytes, h->stream));
     if (h->counters)
-        HIP_TRY(hipMemsetAsync(h->counters, 0, 32 * sizeof(unsigned long long), h->stream));
+        HIP_TRY(hipMemsetAsync(h->counters.p, 0, 32 * sizeof(unsigned long long), h->stream));
     if (h->aov)
-        HIP_TRY(hipMemsetAsync(h->aov, 0, 2 * (size_t)h->W * h->H * 16, h->stream));
+        HIP_TRY(hipMemsetAsync(h->aov.p, 0, 2 * (size_t)h->W * h->H * 16, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->aovPasses = 0;
     h->passesDone = 0;
@@ -1070,7 +928,7 @@ int kajo_hip_tile_buffer(kajo_hip_t h, void** devicePtr, size_t* bytes)
 {
     if (!h || !devicePtr || !bytes)
         return fail(KAJO_E_INVALID, "null argument");
-    *devicePtr = h->tiles;
+    *devicePtr = h->tiles.p;
     *bytes = h->tileBytes;
     return KAJO_OK;
 }
@@ -1082,9 +940,8 @@ int kajo_hip_compose(kajo_hip_t h, const void* gathered)
     int rc = bind(h);
     if (rc)
         return rc;
-    if ((rc = ensureFrame(h)))
-        return rc;
-    HIP_TRY((hipError_t)kajo_compose_launch(gathered, &h->map, h->frame, h->stream));
+    HIP_TRY(h->frame.ensure((size_t)h->W * h->H * 16));
+    HIP_TRY((hipError_t)kajo_compose_launch(gathered, &h->map, h->frame.p, h->stream));
     h->frameValid = true;
     return KAJO_OK;
 }
@@ -1093,44 +950,18 @@ int kajo_hip_resolve_gathered_argb8_device(kajo_hip_t h, const void* gathered, v
 {
     if (!h || !dst)
         return fail(KAJO_E_INVALID, "null argument");
-    int rc = bind(h);
-    if (rc)
-        return rc;
-    if (h->passesDone < 1)
-        return fail(KAJO_E_STATE, "nothing rendered yet");
-    if (!gathered) {
-        if (h->map.tileCount != 1)
-            return fail(KAJO_E_STATE, "a handle that owns part of the frame needs the gathered tile buffers");
-        gathered = h->tiles;
-    }
-    hipError_t le = (hipError_t)(h->strict() ? kajo_resolve_tiles_strict_launch(gathered, &h->map, (float)h->passesDone, dst, h->stream)
-                                             : kajo_resolve_tiles_fast_launch(gathered, &h->map, (float)h->passesDone, dst, h->stream));
-    if (le != hipSuccess)
-        return failHip(le, "resolve kernel launch");
-    return KAJO_OK;
+    Image img;
+    int rc = imageOf(h, true, gathered, &img);
+    return rc ? rc : resolve(h, img, dst);
 }
 
 int kajo_hip_resolve_argb8_device(kajo_hip_t h, void* dst)
 {
     if (!h || !dst)
         return fail(KAJO_E_INVALID, "null argument");
-    int rc = bind(h);
-    if (rc)
-        return rc;
-    if (h->passesDone < 1)
-        return fail(KAJO_E_STATE, "nothing rendered yet");
-    // one owner and no composed frame at hand: resolve straight from the tile buffer (the frame is composed when somebody
-    // asks for the float radiance)
-    if (!h->frameValid && h->map.tileCount == 1)
-        return kajo_hip_resolve_gathered_argb8_device(h, nullptr, dst);
-    if ((rc = composeOwn(h)))
-        return rc;
-    const int count = h->W * h->H;
-    hipError_t le = (hipError_t)(h->strict() ? kajo_resolve_strict_launch(h->frame, count, (float)h->passesDone, dst, h->stream)
-                                             : kajo_resolve_fast_launch(h->frame, count, (float)h->passesDone, dst, h->stream));
-    if (le != hipSuccess)
-        return failHip(le, "resolve kernel launch");
-    return KAJO_OK;
+    Image img;
+    int rc = imageOf(h, false, nullptr, &img);
+    return rc ? rc : resolve(h, img, dst);
 }
 
 int kajo_hip_resolve_argb8(kajo_hip_t h, uint32_t* dst)
@@ -1141,11 +972,10 @@ int kajo_hip_resolve_argb8(kajo_hip_t h, uint32_t* dst)
     if (rc)
         return rc;
     const size_t bytes = (size_t)h->W * h->H * 4;
-    if (!h->argb)
-        HIP_TRY(hipMalloc(&h->argb, bytes));
-    if ((rc = kajo_hip_resolve_argb8_device(h, h->argb)))
+    HIP_TRY(h->argb.ensure(bytes));
+    if ((rc = kajo_hip_resolve_argb8_device(h, h->argb.p)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(dst, h->argb, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(dst, h->argb.p, bytes, hipMemcpyDeviceToHost, h->stream));
     return kajo_hip_wait(h);
 }
 
@@ -1158,7 +988,7 @@ int kajo_hip_read_radiance(kajo_hip_t h, float* dst)
         return rc;
     if ((rc = composeOwn(h)))
         return rc;
-    HIP_TRY(hipMemcpyAsync(dst, h->frame, (size_t)h->W * h->H * 16, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(dst, h->frame.p, (size_t)h->W * h->H * 16, hipMemcpyDeviceToHost, h->stream));
     return kajo_hip_wait(h);
 }
 
@@ -1173,15 +1003,13 @@ int kajo_hip_read_aov(kajo_hip_t h, float* albedoHits, float* normalDepth, int64
         return rc;
     const size_t bytes = (size_t)h->W * h->H * 16;
     if (albedoHits)
-        HIP_TRY(hipMemcpyAsync(albedoHits, h->aov, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(albedoHits, h->aov.p, bytes, hipMemcpyDeviceToHost, h->stream));
     if (normalDepth)
-        HIP_TRY(hipMemcpyAsync(normalDepth, static_cast<char*>(h->aov) + bytes, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(normalDepth, h->aov.as<char>() + bytes, bytes, hipMemcpyDeviceToHost, h->stream));
     if ((rc = kajo_hip_wait(h)))
         return rc;
-    if (samples) {
-        const long long n = (long long)std::sqrt((double)(unsigned)h->params.samplesPerPass);
-        *samples = (int64_t)(n * n * h->aovPasses);
-    }
+    if (samples)
+        *samples = (int64_t)aovSamples(h);
     return KAJO_OK;
 }
 
@@ -1189,10 +1017,7 @@ const char* kajo_hip_aov_kernel(kajo_hip_t h)
 {
     if (!h || !h->aov)
         return nullptr;
-    static const char* const names[2][KAJO_AOV_INSTANCES] = {
-        {"kajo_aov_fast", "kajo_aov_fast_big", "kajo_aov_fast_big_lg", "kajo_aov_fast_biglist", "kajo_aov_fast_biglist_lg"},
-        {"kajo_aov_strict", "kajo_aov_strict_big", "kajo_aov_strict_big_lg", "kajo_aov_strict_biglist", "kajo_aov_strict_biglist_lg"}};
-    return names[h->strict() ? 1 : 0][h->aovInstance];
+    return h->k->aovNames[h->aovInstance];
 }
 
 void kajo_hip_default_denoise_params(KajoDenoiseParams* p)
@@ -1236,17 +1061,15 @@ int checkDenoise(kajo_hip_t h, const KajoDenoiseParams* p)
 int denoiseFrame(KajoHip* h, const KajoDenoiseParams* p, void** out)
 {
     const size_t count = (size_t)h->W * h->H;
-    if (!h->denoise)
-        HIP_TRY(hipMalloc(&h->denoise, count * (3 * 16 + 4)));
-    char* scratch = static_cast<char*>(h->denoise);
+    HIP_TRY(h->denoise.ensure(count * (3 * 16 + 4)));
+    char* scratch = h->denoise.as<char>();
     *out = scratch + count * 16;
     if (p->iterations == 0) {
         // the accumulation itself (one owner: tileCount is 1 with the AOV flag)
-        HIP_TRY((hipError_t)kajo_compose_launch(h->tiles, &h->map, *out, h->stream));
+        HIP_TRY((hipError_t)kajo_compose_launch(h->tiles.p, &h->map, *out, h->stream));
     } else {
-        const long long n = (long long)std::sqrt((double)(unsigned)h->params.samplesPerPass);
-        const long long samples = std::max(n * n * h->aovPasses, 1LL);
-        hipError_t le = (hipError_t)kajo_denoise_launch(h->tiles, &h->map, h->aov, static_cast<char*>(h->aov) + count * 16, (float)h->passesDone,
+        const long long samples = std::max(aovSamples(h), 1LL);
+        hipError_t le = (hipError_t)kajo_denoise_launch(h->tiles.p, &h->map, h->aov.p, h->aov.as<char>() + count * 16, (float)h->passesDone,
                                                         (float)samples, p->iterations, (p->flags & KAJO_DENOISE_NO_DEMODULATE) ? 0 : 1,
                                                         p->sigmaLuminance, p->sigmaNormal, p->sigmaDepth, scratch, out, h->stream);
         if (le != hipSuccess)
@@ -1281,24 +1104,29 @@ int toneArgsOf(const KajoToneParams* p, ToneArgs* t)
     return KAJO_OK;
 }
 
-size_t toneScratchBytes(const KajoHip* h)
+// Enqueue the tone mapping of an image (tiles through h->map's geometry, or the row-major frame) into dst (device)
+int toneLaunch(KajoHip* h, Image img, const ToneArgs& t, void* dst)
 {
-    const size_t rects = (size_t)((h->W + 63) / 64) * (size_t)((h->H + 15) / 16); // tonemap.inc.hip kToneRectW x kToneRectH
-    return KAJO_TONE_PARTIALS_OFFSET + rects * 16;
-}
-
-// Enqueue the tone mapping of `src` (tiles through h->map's geometry with `gathered`'s base, or the row-major frame) into dst (device)
-int toneLaunch(KajoHip* h, const void* src, const TileMap* map, bool fromTiles, const ToneArgs& t, void* dst)
-{
-    if (t.autoExposure && !h->tone)
-        HIP_TRY(hipMalloc(&h->tone, toneScratchBytes(h)));
-    hipError_t le = (hipError_t)(h->strict() ? kajo_tone_strict_launch(src, map, fromTiles ? 1 : 0, (float)h->passesDone, &t, h->tone, dst, h->stream)
-                                             : kajo_tone_fast_launch(src, map, fromTiles ? 1 : 0, (float)h->passesDone, &t, h->tone, dst, h->stream));
+    const size_t scratch = KAJO_TONE_PARTIALS_OFFSET + (size_t)((h->W + 63) / 64) * (size_t)((h->H + 15) / 16) * 16; // tonemap.inc.hip kToneRect*
+    if (t.autoExposure)
+        HIP_TRY(h->tone.ensure(scratch));
+    hipError_t le = (hipError_t)h->k->tone(img.src, &h->map, img.fromTiles ? 1 : 0, (float)h->passesDone, &t, h->tone.p, dst, h->stream);
     if (le != hipSuccess)
         return failHip(le, "tone mapping kernel launch");
     h->toneScaleState = t.autoExposure ? 2 : 1;
     h->toneScale = t.exposureScale;
     return KAJO_OK;
+}
+
+// the rays of the known-answer entry points as the kernels read them: float [n][6], origin then direction
+std::vector<float> packRays(int n, const float* origins, const float* dirs)
+{
+    std::vector<float> rays(6 * (size_t)n);
+    for (int i = 0; i < n; i++) {
+        std::memcpy(&rays[6 * (size_t)i], origins + 3 * (size_t)i, 12);
+        std::memcpy(&rays[6 * (size_t)i + 3], dirs + 3 * (size_t)i, 12);
+    }
+    return rays;
 }
 
 } // namespace
@@ -1317,12 +1145,10 @@ int kajo_hip_denoise(kajo_hip_t h, const KajoDenoiseParams* p, float* radiance, 
     void* out = nullptr;
     if ((rc = denoiseFrame(h, p, &out)))
         return rc;
-    void* argb = static_cast<char*>(h->denoise) + 3 * count * 16;
+    void* argb = h->denoise.as<char>() + 3 * count * 16;
     if (argb8) {
-        hipError_t le = (hipError_t)(h->strict() ? kajo_resolve_strict_launch(out, (int)count, (float)h->passesDone, argb, h->stream)
-                                                 : kajo_resolve_fast_launch(out, (int)count, (float)h->passesDone, argb, h->stream));
-        if (le != hipSuccess)
-            return failHip(le, "resolve kernel launch");
+        if ((rc = resolve(h, Image{out, false}, argb)))
+            return rc;
         HIP_TRY(hipMemcpyAsync(argb8, argb, count * 4, hipMemcpyDeviceToHost, h->stream));
     }
     if (radiance)
@@ -1354,27 +1180,22 @@ int kajo_hip_tonemap_argb8(kajo_hip_t h, const KajoToneParams* p, const KajoDeno
             return rc;
     } else if (!h)
         return fail(KAJO_E_INVALID, "null handle");
-    if ((rc = bind(h)))
+    // (with the AOV flag, which the denoiser needs, the handle is the frame's one owner: nothing is composed here)
+    Image img;
+    if ((rc = imageOf(h, false, nullptr, &img)))
         return rc;
-    if (h->passesDone < 1)
-        return fail(KAJO_E_STATE, "nothing rendered yet");
     const size_t count = (size_t)h->W * h->H;
-    if (!h->argb)
-        HIP_TRY(hipMalloc(&h->argb, count * 4));
+    HIP_TRY(h->argb.ensure(count * 4));
     if (denoise) {
         void* out = nullptr;
-        if ((rc = denoiseFrame(h, denoise, &out)) || (rc = toneLaunch(h, out, &h->map, false, t, h->argb)))
+        if ((rc = denoiseFrame(h, denoise, &out)))
             return rc;
-    } else if (!h->frameValid && h->map.tileCount == 1) {
-        // one owner and no composed frame at hand: straight from the tile buffer, as kajo_hip_resolve_argb8_device
-        if ((rc = toneLaunch(h, h->tiles, &h->map, true, t, h->argb)))
-            return rc;
-    } else {
-        if ((rc = composeOwn(h)) || (rc = toneLaunch(h, h->frame, &h->map, false, t, h->argb)))
-            return rc;
+        img = Image{out, false};
     }
+    if ((rc = toneLaunch(h, img, t, h->argb.p)))
+        return rc;
     if (argb8)
-        HIP_TRY(hipMemcpyAsync(argb8, h->argb, count * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(argb8, h->argb.p, count * 4, hipMemcpyDeviceToHost, h->stream));
     return scale ? kajo_hip_tone_scale(h, scale) : kajo_hip_wait(h);
 }
 
@@ -1386,16 +1207,8 @@ int kajo_hip_tonemap_gathered_argb8_device(kajo_hip_t h, const void* gathered, c
         return rc;
     if (!h || !dst)
         return fail(KAJO_E_INVALID, "null argument");
-    if ((rc = bind(h)))
-        return rc;
-    if (h->passesDone < 1)
-        return fail(KAJO_E_STATE, "nothing rendered yet");
-    if (!gathered) {
-        if (h->map.tileCount != 1)
-            return fail(KAJO_E_STATE, "a handle that owns part of the frame needs the gathered tile buffers");
-        gathered = h->tiles;
-    }
-    return toneLaunch(h, gathered, &h->map, true, t, dst);
+    Image img;
+    return (rc = imageOf(h, true, gathered, &img)) ? rc : toneLaunch(h, img, t, dst);
 }
 
 int kajo_hip_tone_scale(kajo_hip_t h, float* scale)
@@ -1409,44 +1222,24 @@ int kajo_hip_tone_scale(kajo_hip_t h, float* scale)
         return rc;
     float s = h->toneScale;
     if (h->toneScaleState == 2)
-        HIP_TRY(hipMemcpyAsync(&s, h->tone, sizeof s, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(&s, h->tone.p, sizeof s, hipMemcpyDeviceToHost, h->stream));
     if ((rc = kajo_hip_wait(h)))
         return rc;
     *scale = s;
     return KAJO_OK;
 }
 
-namespace
-{
-
-struct DeviceBuffer // scratch for the known-answer entry points
-{
-    void* p = nullptr;
-    ~DeviceBuffer()
-    {
-        if (p)
-            (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-};
-
-} // namespace
-
 int kajo_hip_kat_trace(kajo_hip_t h, int n, const float* origins, const float* dirs, int32_t* objIndex, float* t,
                        float* position, float* normal, float* tangent, float* binormal)
 {
     if (!h || n < 0 || !origins || !dirs || !objIndex || !t || !position || !normal || !tangent || !binormal)
         return fail(KAJO_E_INVALID, "null argument");
-    if (h->hotBytes > 48 * 1024)
+    if (h->lds.hotBytes > 48 * 1024)
         return fail(KAJO_E_INVALID, "known-answer entry points are limited to scenes whose hot records fit 48 KiB of LDS");
     int rc = bind(h);
     if (rc || n == 0)
         return rc;
-    std::vector<float> rays(6 * (size_t)n);
-    for (int i = 0; i < n; i++) {
-        std::memcpy(&rays[6 * i], origins + 3 * i, 12);
-        std::memcpy(&rays[6 * i + 3], dirs + 3 * i, 12);
-    }
+    const std::vector<float> rays = packRays(n, origins, dirs);
     DeviceBuffer dRays, dIdx, dOut;
     HIP_TRY(dRays.alloc(rays.size() * 4));
     HIP_TRY(dIdx.alloc((size_t)n * 4));
@@ -1454,13 +1247,12 @@ int kajo_hip_kat_trace(kajo_hip_t h, int n, const float* origins, const float* d
     HIP_TRY(hipMemcpyAsync(dRays.p, rays.data(), rays.size() * 4, hipMemcpyHostToDevice, h->stream));
     KatTraceArgs a;
     a.scene = h->view;
-    a.rays = static_cast<const float*>(dRays.p);
+    a.rays = dRays.as<const float>();
     a.count = n;
-    a.idx = static_cast<int32_t*>(dIdx.p);
-    a.out = static_cast<float*>(dOut.p);
+    a.idx = dIdx.as<int32_t>();
+    a.out = dOut.as<float>();
     const unsigned grid = (unsigned)((n + 255) / 256);
-    hipError_t le = (hipError_t)(h->strict() ? kajo_kat_trace_strict_launch(&a, grid, h->hotBytes, h->stream)
-                                             : kajo_kat_trace_fast_launch(&a, grid, h->hotBytes, h->stream));
+    hipError_t le = (hipError_t)h->k->katTrace(&a, grid, h->lds.hotBytes, h->stream);
     if (le != hipSuccess)
         return failHip(le, "kat trace launch");
     std::vector<float> out((size_t)n * 13);
@@ -1482,16 +1274,12 @@ int kajo_hip_kat_shade(kajo_hip_t h, int n, const float* origins, const float* d
 {
     if (!h || n < 0 || !origins || !dirs || !states || !rgb || !finalStates)
         return fail(KAJO_E_INVALID, "null argument");
-    if (h->hotBytes > 48 * 1024)
+    if (h->lds.hotBytes > 48 * 1024)
         return fail(KAJO_E_INVALID, "known-answer entry points are limited to scenes whose hot records fit 48 KiB of LDS");
     int rc = bind(h);
     if (rc || n == 0)
         return rc;
-    std::vector<float> rays(6 * (size_t)n);
-    for (int i = 0; i < n; i++) {
-        std::memcpy(&rays[6 * i], origins + 3 * i, 12);
-        std::memcpy(&rays[6 * i + 3], dirs + 3 * i, 12);
-    }
+    const std::vector<float> rays = packRays(n, origins, dirs);
     DeviceBuffer dRays, dStates, dRgb, dFinal;
     HIP_TRY(dRays.alloc(rays.size() * 4));
     HIP_TRY(dStates.alloc((size_t)n * 16));
@@ -1510,21 +1298,19 @@ int kajo_hip_kat_shade(kajo_hip_t h, int n, const float* origins, const float* d
     a.tileH = 16;
     a.tilesX = a.tilesY = 1;
     a.tileCount = 1;
-    a.katRays = static_cast<const float*>(dRays.p);
-    a.katStates = static_cast<const uint64_t*>(dStates.p);
-    a.katRgb = static_cast<float*>(dRgb.p);
-    a.katFinal = static_cast<uint64_t*>(dFinal.p);
+    a.katRays = dRays.as<const float>();
+    a.katStates = dStates.as<const uint64_t>();
+    a.katRgb = dRgb.as<float>();
+    a.katFinal = dFinal.as<uint64_t>();
     a.katCount = n;
     a.stealWindow = 1;
-    a.mailboxOffset = (uint32_t)((h->hotBytes + 15) & ~(size_t)15);
-    h->fillWaveLds(a, a.mailboxOffset, false);
+    a.mailboxOffset = (uint32_t)((h->lds.hotBytes + 15) & ~(size_t)15);
+    h->lds.fillWaveLds(a, a.mailboxOffset, false);
     const size_t ldsKat = a.mailboxOffset + 4 * (size_t)a.perWaveBytes;
     if (ldsKat > 64 * 1024)
         return fail(KAJO_E_INVALID, "known-answer entry points are limited to scenes whose hot records and wave areas fit 64 KiB of LDS");
     const unsigned grid = (unsigned)((n + 255) / 256);
-    hipError_t le = (hipError_t)(h->numerics() == 1 ? kajo_kat_shade_strict_launch(&a, grid, ldsKat, h->stream)
-                                 : h->numerics() == 2 ? kajo_kat_shade_exact_launch(&a, grid, ldsKat, h->stream)
-                                                      : kajo_kat_shade_fast_launch(&a, grid, ldsKat, h->stream));
+    hipError_t le = (hipError_t)h->k->katShade(&a, grid, ldsKat, h->stream);
     if (le != hipSuccess)
         return failHip(le, "kat shade launch");
     std::vector<float> out4((size_t)n * 4);
@@ -1565,7 +1351,7 @@ extern "C" int kajo_hip_debug_profile(kajo_hip_t h, unsigned long long* out28)
     int rc = kajo_hip_wait(h);
     if (rc)
         return rc;
-    HIP_TRY(hipMemcpy(out28, h->counters + 4, 28 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out28, h->counters.as<unsigned long long>() + 4, 28 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return KAJO_OK;
 }
 
@@ -1577,7 +1363,7 @@ int kajo_hip_counters(kajo_hip_t h, KajoCounters* out)
     if (rc)
         return rc;
     std::memset(out, 0, sizeof *out);
-    const int n = (int)std::sqrt((double)(unsigned)h->params.samplesPerPass);
+    const int n = samplesPerAxis(h->params);
     // pixels this handle owns
     unsigned long long pixels = 0;
     for (int t = h->params.tileIndex; t < h->nTiles; t += h->params.tileCount) {
@@ -1593,7 +1379,7 @@ int kajo_hip_counters(kajo_hip_t h, KajoCounters* out)
     out->tailGroups = h->lastTailGroups;
     if (h->counters) {
         unsigned long long c[4];
-        HIP_TRY(hipMemcpy(c, h->counters, sizeof c, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c, h->counters.p, sizeof c, hipMemcpyDeviceToHost));
         out->traversals = c[0];
         out->vertices = c[1];
         out->laneSlots = c[2];

@@ -1,8 +1,8 @@
 """The host side under AddressSanitizer + UBSan (SURVEY.md section 5 "race detection / sanitizers"; CPU only: GPU sanitizers are not
 available on the pool). tools/host_san.cpp is compiled from the PRODUCT's own sources -- kajo_amd/csrc/stage.cpp (object records, grid,
 visibility lists), kajo_amd/host/scene/SceneLoader.cpp (Kajo's JSON dialect), kajo_amd/csrc/launch_order.h (cost order, parted launch
-tail) and render_args.h (tile slots, side-buffer slots) -- with -fsanitize=address,undefined and run on the tests' scenes; the launch order
-and the side-buffer slots are also checked against a model written here."""
+tail), launch_plan.h (LDS plan, launch shape) and render_args.h (tile slots, side-buffer slots) -- with -fsanitize=address,undefined and run
+on the tests' scenes; the launch order, the launch shape and the side-buffer slots are also checked against a model written here."""
 import os
 import shutil
 import subprocess
@@ -38,7 +38,9 @@ def san(tmp_path_factory):
     return run
 
 
-def test_scene_staging(san, scenes):
+@pytest.fixture(scope="module")
+def stage_pods(san, scenes):
+    """the tests' scenes as .pod files: -> their paths"""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from kajo_amd.scene import stress_scene
     from test_shadow_lists_cpu import adversarial_scene
@@ -50,8 +52,12 @@ def test_scene_staging(san, scenes):
         path = str(san.dir / (name + ".pod"))
         sc.write_pod(path)
         files.append(path)
-    out = san("stage", *files)
-    assert out.count(": ok") == 2 * len(files)
+    return files
+
+
+def test_scene_staging(san, stage_pods):
+    out = san("stage", *stage_pods)
+    assert out.count(": ok") == 2 * len(stage_pods)
 
 
 def test_scene_loader(san):
@@ -129,3 +135,76 @@ def test_tile_slots(san, w, h, tile, owners):
     out = san("tiles", w, h, tile[0], tile[1], owners)
     from kajo_amd.tiles import TileLayout
     assert "%d slots per owner" % TileLayout(w, h, owners, tile).slots_per_owner in out
+
+
+def test_lds_plan(san, stage_pods):
+    """launch_plan.h kajoLdsPlan on the staged scenes, per staging and numerics build, against the plans kajo_hip_create made before the
+    decision moved out of it (tests/golden/lds_plan.json)."""
+    import json
+    out = san("plan", "lds", *stage_pods)
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "lds_plan.json")))
+    got = {}
+    for line in out.splitlines():
+        head, fields = line.split(": ", 1)
+        path, staging, numerics = head.split()
+        got["%s %s %s" % (os.path.basename(path)[:-4], staging, numerics)] = {k: int(v) for k, v in (kv.split("=") for kv in fields.split())}
+    assert got.keys() == want.keys()
+    for key in want:
+        assert got[key] == want[key], key
+
+
+def model_shape(pixel_blocks, now, n, cold_in_lds, no_split, mailbox, per_wave, passes_done, grouped, order_valid, n_parted):
+    """launch_plan.h kajoLaunchShape restated: -> (startsInside, endsInside, launchGroups, split, chunks, parted)"""
+    starts = grouped and passes_done % 4 != 0
+    ends = grouped and (passes_done + now) % 4 != 0
+    groups = now // 4 if not starts and not ends else 0
+    small = cold_in_lds and not no_split
+    split = 1
+    if small:
+        while pixel_blocks < 3 * 4096 and split < 16 and now % (split * 2) == 0 and pixel_blocks * split * 2 <= 8 * 4096:
+            split *= 2
+    while split > 1 and mailbox + now * 1024 + split * per_wave > 48 * 1024:
+        split //= 2
+    chunks = 1
+    if small and pixel_blocks < 3 * 4096:
+        nn = n * n
+        for q in range(2, nn + 1):
+            if now * q > 16:
+                break
+            if nn % q == 0 and pixel_blocks * now * q <= 8 * 4096 and mailbox + now * nn * 1024 + now * q * per_wave <= 48 * 1024:
+                chunks = q
+                if pixel_blocks * now * q >= 4096:
+                    break
+        if now * chunks <= split:
+            chunks = 1
+    parted = chunks == 1 and split == 1 and grouped and order_valid and n_parted > 0 and 2 <= groups <= 8
+    return int(starts), int(ends), groups, split, chunks, int(parted)
+
+
+def test_launch_shape(san):
+    """launch_plan.h kajoLaunchShape against its restatement over frame sizes, pass counts and sample counts; with the cases its comments
+    document."""
+    import itertools
+    frames = [(64, 64), (200, 70), (256, 144), (256, 256), (512, 512), (640, 360), (960, 540), (1280, 720), (1920, 1080), (3840, 2160)]
+    # (small scene FAST / EXACT: spheres.json's plan; small scene STRICT: stress120's; large scene with lists: stress1000's)
+    handles = [(1, 2112, 0, 1), (1, 22528, 0, 0), (0, 27184, 512, 0)]
+    cases = []
+    for (w, h), now, n, no_split, (cold, mailbox, per_wave, grouped), done, n_parted in itertools.product(
+            frames, range(1, 33), (1, 3, 4, 5), (0, 1), handles, (0, 2, 16), (0, 512)):
+        pixel_blocks = -(-w // 64) * -(-h // 16) * 16  # 64x16 tiles of sixteen 8x8 blocks
+        cases.append((pixel_blocks, now, n, cold, no_split, mailbox, per_wave, done, grouped, 1, n_parted))
+    src, dst = str(san.dir / "shape_in.bin"), str(san.dir / "shape_out.bin")
+    np.array(cases, np.uint32).tofile(src)
+    san("plan", "shape", src, dst)
+    got = np.fromfile(dst, np.uint32).reshape(-1, 6)
+    assert len(got) == len(cases)
+    for c, g in zip(cases, got):
+        assert tuple(g) == model_shape(*c), c
+    shape = {c: tuple(g) for c, g in zip(cases, got)}
+    # BASELINE configs[0]: one pass of 16 samples on 1024 pixel blocks -> four sample chunks per pass
+    assert shape[(1024, 1, 4, 1, 0, 2112, 0, 0, 1, 1, 0)][3:5] == (1, 4)
+    # 1920x1080 (32640 pixel blocks) at 16 passes: unsplit, four whole groups, the tail parted once the order is known
+    assert shape[(32640, 16, 5, 1, 0, 2112, 0, 0, 1, 1, 512)] == (0, 0, 4, 1, 1, 1)
+    assert shape[(32640, 16, 5, 1, 1, 2112, 0, 16, 1, 1, 512)] == (0, 0, 4, 1, 1, 1)
+    # a launch that ends inside a group of four passes hands it over and is not parted
+    assert shape[(32640, 2, 5, 1, 0, 2112, 0, 16, 1, 1, 512)] == (0, 1, 0, 1, 1, 0)

@@ -4,6 +4,9 @@
 //   host_san parse  aspect a.json ...    kajo_amd/host/scene/SceneLoader.cpp on scene files (and on every prefix of each: truncated input)
 //   host_san order  in.bin out.bin       kajo_amd/csrc/launch_order.h: cost order + parted tail from a trip table; side-buffer slots checked
 //   host_san tiles  W H tileW tileH owners   render_args.h kajoTileSlot over a whole frame: every slot in range, none taken twice
+//   host_san plan lds a.pod ...          kajo_amd/csrc/launch_plan.h kajoLdsPlan: a scene's LDS plan per staging (plain, no grid, no
+//                                        visibility lists) and numerics build
+//   host_san plan shape in.bin out.bin   launch_plan.h kajoLaunchShape over a table of launches
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -12,25 +15,41 @@
 
 #include "kajo_scene.h"
 #include "launch_order.h"
+#include "launch_plan.h"
 #include "render_args.h"
 #include "scene/Scene.h"
 #include "stage.h"
 
-static int stage(int argc, char** argv)
+// a scene written by kajo_amd/scene.py Scene.write_pod; 0 or the error code
+struct Pod
 {
-    for (int a = 0; a < argc; a++) {
-        FILE* f = fopen(argv[a], "rb");
+    KajoScene sc{};
+    std::vector<KajoSphere> sp;
+    std::vector<KajoPlane> pl;
+    int read(const char* path)
+    {
+        FILE* f = fopen(path, "rb");
         if (!f) return 2;
         int32_t n[2];
         if (fread(n, 4, 2, f) != 2) return 3;
-        KajoScene sc{};
-        std::vector<KajoSphere> sp(n[0]);
-        std::vector<KajoPlane> pl(n[1]);
+        sp.resize(n[0]);
+        pl.resize(n[1]);
         if (fread(sc.backgroundColor, 4, 4, f) != 4 || fread(&sc.camera, 4, 32, f) != 32) return 4;
         if (n[0] && fread(sp.data(), sizeof(KajoSphere), n[0], f) != (size_t)n[0]) return 5;
         if (n[1] && fread(pl.data(), sizeof(KajoPlane), n[1], f) != (size_t)n[1]) return 6;
         fclose(f);
         sc.nSpheres = n[0]; sc.nPlanes = n[1]; sc.spheres = sp.data(); sc.planes = pl.data();
+        return 0;
+    }
+};
+
+static int stage(int argc, char** argv)
+{
+    for (int a = 0; a < argc; a++) {
+        Pod pod;
+        if (int rc = pod.read(argv[a])) return rc;
+        const KajoScene& sc = pod.sc;
+        const int n[2] = {sc.nSpheres, sc.nPlanes};
         float lo, hi;
         kajo::coordinateRange(sc, &lo, &hi);
         for (int lists = 0; lists < 2; lists++) {
@@ -139,6 +158,66 @@ static int tiles(int argc, char** argv)
     return 0;
 }
 
+// LDS plan of each scene file: one line per staging and numerics build, "<file> <staging> <numerics>: field=value ..."
+static int planLds(int argc, char** argv)
+{
+    for (int a = 0; a < argc; a++) {
+        Pod pod;
+        if (int rc = pod.read(argv[a])) return rc;
+        for (const char* staging : {"plain", "no_grid", "no_shadow_lists"}) {
+            const bool grid = strcmp(staging, "no_grid") != 0, lists = strcmp(staging, "no_shadow_lists") != 0;
+            kajo::StagedScene st;
+            kajo::stageScene(pod.sc, st, grid ? 48 : 0, lists); // (as kajo_hip_create stages with KAJO_FLAG_NO_GRID / NO_SHADOW_LISTS)
+            const KajoSceneLds b = kajoSceneLds(st);
+            for (Numerics k : {Numerics::Fast, Numerics::Strict, Numerics::Exact}) {
+                const KajoLdsPlan p = kajoLdsPlan(b.hotBytes, b.coldBytes, b.gridHeaderBytes, b.gridBytes, st.gridEnabled, st.shadowEnabled,
+                                                  (int)st.light.size(), k);
+                printf("%s %s %s: big=%d coldInLds=%d gridInLds=%d stealWindow=%d helpBytes=%d accBytes=%d thrL=%d holdTrips=%d hotBytes=%zu "
+                       "ldsBytes=%zu wavesPerBlock=%u fits=%d\n",
+                       argv[a], staging, k == Numerics::Fast ? "fast" : k == Numerics::Strict ? "strict" : "exact", p.big, p.coldInLds, p.gridInLds,
+                       p.stealWindow, p.helpBytes, p.accBytes, p.thrL, p.holdTrips, p.hotBytes, p.ldsBytes, p.wavesPerBlock, p.fits);
+            }
+        }
+    }
+    return 0;
+}
+
+// Launch shapes: in.bin holds records of 11 uint32 (pixelBlocks, now, n, coldInLds, noSplit, mailboxOffset, perWaveBytes, passesDone,
+// grouped, orderValid, nParted); out.bin gets 6 per record (startsInside, endsInside, launchGroups, split, chunks, parted).
+static int planShape(int argc, char** argv)
+{
+    if (argc != 2) return 2;
+    FILE* f = fopen(argv[0], "rb");
+    if (!f) return 3;
+    std::vector<uint32_t> in;
+    uint32_t r[11];
+    while (fread(r, 4, 11, f) == 11)
+        in.insert(in.end(), r, r + 11);
+    fclose(f);
+    std::vector<uint32_t> out;
+    for (size_t i = 0; i < in.size(); i += 11) {
+        const uint32_t* c = &in[i];
+        const KajoLaunchShape s = kajoLaunchShape(c[0], (int)c[1], (int)c[2], c[3] != 0, c[4] != 0, c[5], c[6], (int)c[7], c[8] != 0, c[9] != 0, c[10]);
+        const uint32_t o[6] = {s.startsInside, s.endsInside, (uint32_t)s.launchGroups, s.split, s.chunks, s.parted};
+        out.insert(out.end(), o, o + 6);
+    }
+    f = fopen(argv[1], "wb");
+    if (!f) return 4;
+    if (!out.empty())
+        fwrite(out.data(), 4, out.size(), f);
+    fclose(f);
+    return 0;
+}
+
+static int plan(int argc, char** argv)
+{
+    if (argc < 1) return 2;
+    const std::string what = argv[0];
+    if (what == "lds") return planLds(argc - 1, argv + 1);
+    if (what == "shape") return planShape(argc - 1, argv + 1);
+    return 2;
+}
+
 int main(int argc, char** argv)
 {
     if (argc < 2) return 1;
@@ -147,5 +226,6 @@ int main(int argc, char** argv)
     if (mode == "parse") return parse(argc - 2, argv + 2);
     if (mode == "order") return order(argc - 2, argv + 2);
     if (mode == "tiles") return tiles(argc - 2, argv + 2);
+    if (mode == "plan") return plan(argc - 2, argv + 2);
     return 1;
 }
