@@ -874,6 +874,24 @@ uint32_t resolvePixel(const float* a, int pass)
     return ((uint32_t)al << 24) | ((uint32_t)r << 16) | ((uint32_t)g << 8) | (uint32_t)b;
 }
 
+// The camera ray of one path (Renderer.cpp:51-64 under the stream protocol): the direction, and in rng the generator
+// after its jitter draw. The origin is o.origin.
+V3 cameraRay(const Oracle& o, const Oracle::FrameConsts& c, uint64_t seed, int pass, int x, int y, int sample, Rng& rng)
+{
+    uint64_t st[2];
+    kajo_stream_state(seed, (uint32_t)pass, (uint32_t)sample, (uint32_t)(y * c.W + x), st);
+    rng.lo = st[0];
+    rng.hi = st[1];
+    float g[4];
+    rng.generate(g);
+    const int sampleX = sample % c.n, sampleY = sample / c.n;
+    float offX = g[0] * .5f + .5f;
+    float offY = g[1] * .5f + .5f;
+    float sx = x * c.pixelWidth + sampleX * c.sampleWidth + offX * c.sampleWidth;
+    float sy = (c.H - y) * c.pixelHeight + sampleY * c.sampleHeight + offY * c.sampleHeight;
+    return normalize(o.p1 + (o.p2 - o.p1) * sx + (o.p3 - o.p1) * sy - o.origin);
+}
+
 } // namespace
 
 extern "C" {
@@ -1140,26 +1158,71 @@ int koracle_camera_ray(void* hh, int W, int Hh, int S, int pass, uint64_t seed, 
                        uint64_t* state2)
 {
     Handle* H = static_cast<Handle*>(hh);
-    const Oracle& o = *H->o;
     Oracle::FrameConsts c = Oracle::frameConsts(W, Hh, S);
     Rng rng;
-    uint64_t st[2];
-    kajo_stream_state(seed, (uint32_t)pass, (uint32_t)sample, (uint32_t)(y * W + x), st);
-    rng.lo = st[0];
-    rng.hi = st[1];
-    float g[4];
-    rng.generate(g);
-    const int sampleX = sample % c.n, sampleY = sample / c.n;
-    float offX = g[0] * .5f + .5f;
-    float offY = g[1] * .5f + .5f;
-    float sx = x * c.pixelWidth + sampleX * c.sampleWidth + offX * c.sampleWidth;
-    float sy = (c.H - y) * c.pixelHeight + sampleY * c.sampleHeight + offY * c.sampleHeight;
-    V3 direction = normalize(o.p1 + (o.p2 - o.p1) * sx + (o.p3 - o.p1) * sy - o.origin);
-    st3(ray6, 0, o.origin);
+    V3 direction = cameraRay(*H->o, c, seed, pass, x, y, sample, rng);
+    st3(ray6, 0, H->o->origin);
     st3(ray6, 1, direction);
     state2[0] = rng.lo;
     state2[1] = rng.hi;
     return 0;
+}
+
+// First-hit AOVs (include/kajo_hip.h kajo_hip_read_aov) of the rectangle (x0, y0, w, hgt) of a W x Hh frame, passes firstPass ..
+// firstPass + nPasses - 1: A (albedo.rgb, hits) and B (normal.xyz, depth) are w * hgt float4s, row 0 = the rectangle's top row, and are
+// ADDED to. Per pixel one float32 addition per word and sample, in pass order, then stratum sampleY * n + sampleX: the header's order.
+// Per sample the camera ray of koracle_camera_ray and its closest hit; a hit adds clamp((diffuse + specular) + transparency, 0, 1) of
+// its material, 1, its normal and its t; a miss adds the background colour and zeros. Rows are dealt round-robin to nThreads host
+// threads (the sums do not depend on the split).
+void koracle_aov(void* hh, int W, int Hh, int S, int firstPass, int nPasses, uint64_t seed, int x0, int y0, int w, int hgt, float* A,
+                 float* B, int nThreads)
+{
+    Handle* H = static_cast<Handle*>(hh);
+    const Oracle& o = *H->o;
+    Oracle::FrameConsts c = Oracle::frameConsts(W, Hh, S);
+    const int np = (int)o.planes.size();
+    if (nThreads < 1)
+        nThreads = 1;
+    std::vector<std::thread> pool;
+    for (int t = 0; t < nThreads; t++) {
+        pool.emplace_back([&, t] {
+            for (int ry = t; ry < hgt; ry += nThreads) {
+                for (int rx = 0; rx < w; rx++) {
+                    const int x = x0 + rx, y = y0 + ry;
+                    float* a = A + 4 * ((size_t)ry * w + rx);
+                    float* b = B + 4 * ((size_t)ry * w + rx);
+                    for (int pass = firstPass; pass < firstPass + nPasses; pass++) {
+                        for (int sample = 0; sample < c.n * c.n; sample++) {
+                            Rng rng;
+                            const V3 d = cameraRay(o, c, seed, pass, x, y, sample, rng);
+                            const Hit h = o.trace(o.origin, d, nullptr);
+                            V3 albedo = o.background, N = v3(0, 0, 0);
+                            float depth = 0.0f, hit = 0.0f;
+                            if (h.id != 0) {
+                                const Mat& m = h.id <= np ? o.planes[h.id - 1].mat : o.spheres[h.id - 1 - np].mat;
+                                const V3 l = (m.diffuse + m.specular) + m.transparency;
+                                albedo = v3(std::min(std::max(l.x, 0.0f), 1.0f), std::min(std::max(l.y, 0.0f), 1.0f),
+                                            std::min(std::max(l.z, 0.0f), 1.0f));
+                                N = h.normal;
+                                depth = h.t;
+                                hit = 1.0f;
+                            }
+                            a[0] += albedo.x;
+                            a[1] += albedo.y;
+                            a[2] += albedo.z;
+                            a[3] += hit;
+                            b[0] += N.x;
+                            b[1] += N.y;
+                            b[2] += N.z;
+                            b[3] += depth;
+                        }
+                    }
+                }
+            }
+        });
+    }
+    for (auto& th : pool)
+        th.join();
 }
 
 // Event log of ONE camera path (pixel x,y; sample index; pass): records of 4 floats

@@ -203,6 +203,20 @@ class Handle:
                                       C.c_int(h), _p(accum), C.c_int(threads), _p(ctr) if counters else None)
         return (accum, ctr) if counters else accum
 
+    def aov(self, W, H, S=32, passes=1, seed=236367, first_pass=1, rect=None, sums=None, threads=None):
+        """Oracle only: first-hit AOV sums (A, B) of include/kajo_hip.h over the rectangle (x0, y0, w, h) of the frame (default: all of
+        it) for passes first_pass .. first_pass + passes - 1, summed in the header's order -> two (h, w, 4) float32 arrays. `sums`: an
+        (A, B) pair to continue (added to in place)."""
+        assert not self.L.is_ref
+        x0, y0, w, h = rect if rect else (0, 0, W, H)
+        A, B = sums if sums is not None else (np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32))
+        assert A.shape == B.shape == (h, w, 4) and A.dtype == B.dtype == np.float32 and A.flags.c_contiguous and B.flags.c_contiguous
+        if threads is None:
+            threads = min(8, os.cpu_count() or 1)
+        self.L.lib.koracle_aov(self.h, C.c_int(W), C.c_int(H), C.c_int(S), C.c_int(first_pass), C.c_int(passes), C.c_uint64(seed),
+                               C.c_int(x0), C.c_int(y0), C.c_int(w), C.c_int(h), _p(A), _p(B), C.c_int(threads))
+        return A, B
+
     def render_native(self, W, H, passes, threads, depth_limit=8):
         """The reference's own stream discipline + threading; returns (seconds, image)."""
         if self.L.is_ref:

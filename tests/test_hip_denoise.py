@@ -29,12 +29,14 @@ def _shift(X, ox, oy):
     return Y, m
 
 
-def restate(acc, A, B, passes, samples, K, sl=4.0, sn=128.0, sd=1.0, demodulate=True):
-    """include/kajo_hip.h kajo_hip_denoise in float64: (H, W, 4) sums over passes."""
+def restate(acc, A, B, passes, samples, K, sl=4.0, sn=128.0, sd=1.0, demodulate=True, extent=None):
+    """include/kajo_hip.h kajo_hip_denoise in float64: (H, W, 4) sums over passes. extent: max(W, H) of the whole frame when the arrays
+    are a window of it (the depth scale is relative to the frame's larger side); the window's own by default."""
     acc, A, B = (np.asarray(x, np.float64) for x in (acc, A, B))
     if K == 0:
         return acc.copy()
     h, w = acc.shape[:2]
+    extent = extent or max(w, h)
     a = np.maximum(A[..., :3] / samples, 1e-3)
     nrm = np.sqrt((B[..., :3] ** 2).sum(-1, keepdims=True))
     N = np.where(nrm > 0, B[..., :3] / np.where(nrm > 0, nrm, 1), 0.0)
@@ -85,7 +87,7 @@ def restate(acc, A, B, passes, samples, K, sl=4.0, sn=128.0, sd=1.0, demodulate=
                     wt = np.full((h, w), H5[dx + 2] * H5[dy + 2])
                     if dx or dy:
                         num = np.abs(z - zq)
-                        den = sd * np.maximum(np.maximum(z, zq), 1e-4) * np.hypot(dx, dy) * d / max(w, h)
+                        den = sd * np.maximum(np.maximum(z, zq), 1e-4) * np.hypot(dx, dy) * d / extent
                         wt *= np.where(num == 0, 1.0, np.exp(-num / den))
                     dot = np.maximum((N * Nq).sum(-1), 0.0)
                     wt *= np.where(hasN & (Nq != 0).any(-1), dot ** sn, 1.0)
@@ -149,8 +151,10 @@ def _parity(r, K, demodulate, **sigmas):
 
 
 # measured on one MI355X (EXACT; spheres.json 4:3 at 100x75, 4 passes of S = 4, K = 1..5 with and without demodulation; the 1000-sphere
-# scene at 160x90): mean relative difference from the float64 restatement <= 6e-7, largest single channel 3e-5
-MEAN_TOL, MAX_TOL = 2e-3, 1e-3
+# scene at 160x90): mean relative difference from the float64 restatement <= 6e-7, largest single channel 3e-5. Over the shapes, builds
+# and sigma sets of test_shapes_builds_and_zero_sigmas_match_the_restatement (K = 1..8) and the 1080p windows: mean <= 1.1e-6 (65x5),
+# largest 3.6e-5 (45x160 FAST). MEAN_TOL is about nine times the largest mean; MAX_TOL bounds single channels.
+MEAN_TOL, MAX_TOL = 1e-5, 1e-3
 
 
 @pytest.mark.parametrize("demodulate", [True, False])
@@ -283,3 +287,57 @@ def test_refusals_on_a_device(scenes):
             r.denoise(iterations=9)
         assert e.value.code == capi.KAJO_E_INVALID
         assert np.isfinite(r.denoise(iterations=8)["radiance"][..., :3]).all()
+
+
+# 1x1 .. 65x5: frames narrower or shorter than the 5x5 footprint and the 64x4 workgroup, single rows and columns, ragged workgroups; 1x97
+# and 45x160 are taller than wide (the depth scale is relative to max(W, H)).
+SHAPES = [(1, 1), (1, 97), (97, 1), (3, 2), (65, 5), (45, 160)]
+# every sigma at 0 in turn, and all three: sigma_depth = 0 keeps only equal depths (exp(-d / 0)), sigma_luminance = 0 leaves a scale of
+# 1e-6, sigma_normal = 0 makes every normal weight pow(c, 0) = 1 (c = 0 included)
+ZERO_SIGMAS = [dict(sigma_luminance=0.0), dict(sigma_normal=0.0), dict(sigma_depth=0.0),
+               dict(sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0)]
+
+
+@pytest.mark.parametrize("build", sorted(BUILDS))
+@pytest.mark.parametrize("shape", SHAPES, ids=["%dx%d" % s for s in SHAPES])
+def test_shapes_builds_and_zero_sigmas_match_the_restatement(scenes, shape, build):
+    """K = 1..8 with the default sigmas (demodulated and not), and K = 1, 3, 8 with each zero-sigma set, in each numerics build (the
+    kernels are shared; their inputs are not)."""
+    W, H = shape
+    worst = [0.0, 0.0]
+    with HipRenderer(scenes["spheres_a43"], W, H, spp=4, aov=True, **BUILDS[build]) as r:
+        r.render(3)
+        runs = [(K, dm, {}) for K in range(1, 9) for dm in (True, False)] + [(K, True, z) for z in ZERO_SIGMAS for K in (1, 3, 8)]
+        for K, dm, sig in runs:
+            got, want = _parity(r, K, dm, **sig)
+            mean, mx, same = compare(got["radiance"], want, r.passes)
+            worst = [max(worst[0], mean), max(worst[1], mx)]
+            assert same, (K, dm, sig)
+            assert mean <= MEAN_TOL and mx <= MAX_TOL, (K, dm, sig, mean, mx)
+            assert np.isfinite(want[..., :3]).any(), (K, dm, sig)
+    print("%dx%d %s: mean rel <= %.2e, max rel <= %.2e" % (W, H, build, worst[0], worst[1]))
+
+
+def test_full_hd_windows_match_the_restatement(scenes):
+    """1920x1080, K = 5, EXACT: restated over 128x128 windows at the four corners and the centre, each padded by the filter's dependency
+    radius 1 + 2 (2^K - 1) = 63 where the frame goes on; only the window itself is compared (its padding sees a false edge)."""
+    W, H, K, win = 1920, 1080, 5, 128
+    pad = 1 + 2 * (2 ** K - 1)
+    with HipRenderer(scenes["spheres_a169"], W, H, spp=4, exact=True, aov=True) as r:
+        r.render(2)
+        acc = r.radiance()
+        aov = r.aov()
+        A, B = aov["raw"]
+        got = r.denoise(iterations=K)["radiance"]
+        passes = r.passes
+    worst = [0.0, 0.0]
+    for x0, y0 in ((0, 0), (W - win, 0), (0, H - win), (W - win, H - win), ((W - win) // 2, (H - win) // 2)):
+        px0, py0 = max(0, x0 - pad), max(0, y0 - pad)
+        px1, py1 = min(W, x0 + win + pad), min(H, y0 + win + pad)
+        cut = np.s_[py0:py1, px0:px1]
+        want = restate(acc[cut], A[cut], B[cut], passes, aov["samples"], K, extent=max(W, H))
+        inner = np.s_[y0 - py0:y0 - py0 + win, x0 - px0:x0 - px0 + win]
+        mean, mx, same = compare(got[y0:y0 + win, x0:x0 + win], want[inner], passes)
+        worst = [max(worst[0], mean), max(worst[1], mx)]
+        assert same and mean <= MEAN_TOL and mx <= MAX_TOL, ((x0, y0), mean, mx)
+    print("1080p windows: mean rel <= %.2e, max rel <= %.2e" % tuple(worst))
