@@ -102,6 +102,12 @@ extern "C" {
                                    (2 x W x H x 16 bytes) and every kajo_hip_render enqueues one more kernel per render launch, on the handle's
                                    stream, over the same passes' camera samples. Whole frame on one handle only: with tileCount != 1 create()
                                    refuses the flag (KAJO_E_INVALID). Without it nothing is allocated or launched. */
+#define KAJO_FLAG_AOV_SPECULAR 2048u /* with KAJO_FLAG_AOV only (alone: KAJO_E_INVALID at create, before a device is looked for): the AOVs are
+                                   taken at the first NON-DELTA hit -- camera rays are followed through ideal mirrors and glass by the
+                                   deterministic chain defined at kajo_hip_read_aov, so that the guides show what the mirror shows. The
+                                   same buffers and entry points; another kernel instance (kajo_hip_aov_kernel: ..._spec...). Handles
+                                   without the flag launch what they launched before. */
+#define KAJO_AOV_MAX_FOLLOW 8     /* the chain's longest: delta surfaces followed per camera sample */
 
 typedef struct KajoParams {
     int32_t samplesPerPass; /* S: nominal samples per pixel per pass (reference: 32, Renderer.cpp:21);
@@ -203,6 +209,32 @@ int kajo_hip_resolve_gathered_argb8_device(kajo_hip_t h, const void* gathered, v
    n^2 x the passes rendered into the buffers since create() or kajo_hip_reset() (mean albedo = A.rgb / samples, mean normal =
    B.xyz / samples, mean depth of the hits = B.w / A.w). Waits for outstanding work. KAJO_E_STATE on a handle created without the flag. */
 int kajo_hip_read_aov(kajo_hip_t h, float* albedoHits, float* normalDepth, int64_t* samples);
+/* With KAJO_FLAG_AOV_SPECULAR a sample's contribution is taken at the end of a deterministic chain instead of at the first hit: same
+   camera ray, same stream key (no random number is drawn), same order of summation, one float32 addition per word and sample.
+     T = (1, 1, 1);  D = 0;  ray = the camera ray;  h = the closest-hit walk of ray
+     at most KAJO_AOV_MAX_FOLLOW times, while h is a hit, with m = the hit object's material:
+         tD, tS, tT = x + y + z of m.diffuse, m.specular, m.transparency       (Shader.cpp:130-132)
+         pT = tT / (tD + tS + tT);  pD = tD / (tD + tS)                         (Shader.cpp:133,153: the integrator's own coins)
+         if      pT >= 0.5:                              d' = the ideal-transmission direction (BSDF.cpp:105-124 with glm::refract,
+                                                              ior = m.refractiveIndex, its total-internal-reflection branch included)
+         else if m.specularExponent == 0 and pD < 0.5:   d' = reflect(view, normal)   (BSDF.cpp:82-85)
+         else stop                   (comparisons with NaN are false: a material with no lobe at all stops the chain)
+         if d' == (0, 0, 0): stop
+         T = T * min(max(m.specular.rgb, 0), 1)          (both delta lobes carry the SPECULAR colour, Shader.cpp:137-139)
+         D = D + h.t
+         ray = (h.position + d' * 1e-3, d')              (the integrator's extension ray, Shader.cpp:23,197-198)
+         h = the closest-hit walk of ray
+     the final h is a hit:   albedo = T * (the albedo above of its material), normal = the world-space normal of the FINAL hit (not
+                             flipped), depth = D + h.t (the length of the whole chain), hit = 1
+     the final h is a miss:  albedo = T * backgroundColor.rgb, normal = 0, depth = 0, hit = 0
+   A chain still on a followed surface after KAJO_AOV_MAX_FOLLOW follows ends there: that surface is the final hit. view, normal and
+   position are what the integrator's vertex code forms for the same hit (view = the ray's direction, position = origin + direction * t);
+   STRICT and EXACT handles use STRICT's arithmetic for every step, FAST handles FAST's. A scene without such materials gives the
+   first-hit buffers bit for bit (T = 1 multiplies exactly, D = 0 adds exactly). In spheres.json the rule picks the mirror wall and the
+   glass sphere and nothing else.
+   kajo_hip_denoise and kajo_hip_tonemap_argb8(..., denoise) read A and B as before: nothing in the filter's definition changes; its
+   albedo, normal and depth edges and its demodulation are then those of what is seen in the mirror or through the glass, the albedo
+   tinted by the surfaces looked through and the depth measured along the whole chain. */
 /* Name of the AOV kernel instance the handle launches (one per scene class, as the render kernels: the whole scene in LDS; the grid's cell
    lists in LDS or in global memory; with or without visibility lists), or NULL without KAJO_FLAG_AOV. For tests and profiles. */
 const char* kajo_hip_aov_kernel(kajo_hip_t h);

@@ -8,6 +8,14 @@
 // Per sample: hit = id != 0; albedo = clamp((diffuse + specular) + transparency, 0, 1) of the hit object's material (the three lobe colours
 // of Shader.cpp:129-131), the background colour on a miss (Shader.cpp:116-117); the world normal hitNormal gives (no flip), 0 on a miss;
 // depth = the ray's maxDistance, 0 on a miss.
+//
+// FOLLOW (KAJO_FLAG_AOV_SPECULAR, the _spec instances): the sample is taken at the first NON-DELTA hit instead. While the hit's material
+// would send the beauty path through a delta lobe more likely than not -- ideal transmission (pT >= 0.5) or the ideal reflector
+// (exponent 0, pD < 0.5) -- the ray is continued in that lobe's one direction, exactly as the integrator forms its extension ray
+// (transmissionDirection / reflect on the integrator's own hit point and normal, origin moved kEps along the new direction), at most
+// KAJO_AOV_MAX_FOLLOW times. T, the product of the followed surfaces' clamped specular colours, scales the final albedo (or the
+// background); the depth is the length of the whole chain. The definition is in include/kajo_hip.h; no random number is drawn.
+#define KAJO_AOV_MAX_FOLLOW 8
 #define KAJO_AOV_CAT2(a, b) a##b
 #define KAJO_AOV_CAT(a, b) KAJO_AOV_CAT2(a, b)
 
@@ -39,8 +47,61 @@ KDEV void aovCameraRay(const AovArgs& args, const LdsScene& lds, int spx, int sp
     d = normalize(f3(c0.x, c0.y, c0.z) + f3(c1.x, c1.y, c1.z) * sx + f3(c2.x, c2.y, c2.z) * sy - O);
 }
 
-// COLD_LDS, LISTS, GHOME: as renderBody's (the instance of the scene class; capi.cpp picks it at create)
-template <bool COLD_LDS, bool LISTS = false, int GHOME = 0>
+// One step of a camera sample's chain: if the hit's material is one the rule follows, moves the ray (O, d) on to the extension ray of
+// its delta lobe, takes the surface's colour into T and its distance into D, and returns true. Per step one material is read: the
+// coins and the exponent, and for a followed hit the specular colour + ior.
+template <bool LISTS>
+KDEV bool aovFollowStep(const DSceneView& sc, const LdsScene& lds, const Hit& h, F3& O, F3& d, F3& T, float& D)
+{
+    if (h.id == 0)
+        return false;
+    const DFloat4* mq = reinterpret_cast<const DFloat4*>(lds.material + (h.id - 1));
+    const float pT = mq[0].y, pD = mq[0].z, exponent = mq[3].w;
+    // (comparisons with a NaN coin are false: a material with no lobe at all is not followed)
+    const bool transmit = pT >= 0.5f;
+    if (!(transmit || (exponent == 0.0f && pD < 0.5f)))
+        return false;
+    const DFloat4 m2 = mq[2];
+    const F3 N = hitNormal<LISTS>(sc, lds, h, O, d);
+    const F3 nd = transmit ? transmissionDirection(d, N, m2.w) : reflect(d, N);
+    if (nd.x == 0.0f && nd.y == 0.0f && nd.z == 0.0f)
+        return false;
+    // both delta lobes carry the SPECULAR colour (Shader.cpp:137-139)
+    T = T * f3(fminf(fmaxf(m2.x, 0.0f), 1.0f), fminf(fmaxf(m2.y, 0.0f), 1.0f), fminf(fmaxf(m2.z, 0.0f), 1.0f));
+    D = D + h.t;
+    O = (O + d * h.t) + nd * kEps; // the hit point of Raytracer.cpp:134-135, the extension ray of Shader.cpp:197-198
+    d = nd;
+    return true;
+}
+
+// The chain behind the camera ray's hit `h`: returns the hit the sample is taken at and leaves the ray that found it in (O, d), the
+// followed surfaces' colour in T and their distances in D. A wave's lanes run chains of different lengths, so this is ONE loop around
+// ONE trace call: every lane still in a chain takes part in the trip, the others pass hasRay = false as lanes outside the frame do, and
+// the wave leaves when no lane has a ray -- a wave that sees no mirror and no glass never enters it. The camera ray's own walk stays
+// the caller's, in the first-hit kernels' form: FAST's contracted arithmetic depends on what the compiler knows about the ray (the
+// camera origin is the same for every lane), and a scene without delta materials has to give the first-hit buffers bit for bit.
+// The _biglist walks carry no general sphere record and no far-origin fallback because stage.cpp only builds visibility lists for a
+// closed room of (centre, radius) spheres: a chain ray starts on a surface inside that room, like every extension ray of the integrator,
+// so that guarantee covers it (tests/test_hip_aov_specular.py: the grid scenes with glass and mirror balls).
+template <bool COLD_LDS, bool LISTS, int GHOME>
+KDEV Hit aovFollow(const DSceneView& sc, const LdsScene& lds, Hit h, F3& O, F3& d, bool hasRay, F3& T, float& D)
+{
+    int follows = 0;
+    bool chain = hasRay && aovFollowStep<LISTS>(sc, lds, h, O, d, T, D);
+    while (__ballot(chain) != 0ull) { // (wave-uniform trip count: the longest chain among the wave's lanes)
+        const Hit next = trace<!COLD_LDS, GHOME, LISTS>(sc, lds, O, d, chain);
+        if (chain) {
+            h = next;
+            follows++;
+            chain = follows < KAJO_AOV_MAX_FOLLOW && aovFollowStep<LISTS>(sc, lds, h, O, d, T, D);
+        }
+    }
+    return h;
+}
+
+// COLD_LDS, LISTS, GHOME: as renderBody's (the instance of the scene class; capi.cpp picks it at create). FOLLOW: the sample is taken at
+// the end of aovFollow's chain instead of at the first hit.
+template <bool COLD_LDS, bool LISTS = false, int GHOME = 0, bool FOLLOW = false>
 KDEV void aovBody(const AovArgs& args, unsigned char* ldsRaw)
 {
     const DSceneView& sc = args.scene;
@@ -67,8 +128,12 @@ KDEV void aovBody(const AovArgs& args, unsigned char* ldsRaw)
             for (int sampleX = 0; sampleX < n; sampleX++) {
                 F3 O, d;
                 aovCameraRay(args, lds, px, py, sampleX, sampleY, pass, O, d);
+                F3 T = f3(1.0f, 1.0f, 1.0f);
+                float D = 0.0f;
                 // (lanes outside the frame trace nothing through the grid; their sums are never written)
-                const Hit h = trace<!COLD_LDS, GHOME, LISTS>(sc, lds, O, d, inImage);
+                Hit h = trace<!COLD_LDS, GHOME, LISTS>(sc, lds, O, d, inImage);
+                if (FOLLOW)
+                    h = aovFollow<COLD_LDS, LISTS, GHOME>(sc, lds, h, O, d, inImage, T, D);
                 F3 albedo = bg, N = f3(0.0f, 0.0f, 0.0f);
                 float depth = 0.0f, hit = 0.0f;
                 if (h.id != 0) {
@@ -80,6 +145,10 @@ KDEV void aovBody(const AovArgs& args, unsigned char* ldsRaw)
                     N = hitNormal<LISTS>(sc, lds, h, O, d);
                     depth = h.t;
                     hit = 1.0f;
+                }
+                if (FOLLOW) { // (without a follow T = 1 and D = 0: the same bits as the first-hit sample)
+                    albedo = T * albedo;
+                    depth = h.id != 0 ? D + depth : 0.0f;
                 }
                 // (a miss adds zeros: every sample is one addition per word, as the definition sums them)
                 A.x += albedo.x;
@@ -134,6 +203,19 @@ extern "C" __global__ void __launch_bounds__(256) KAJO_AOV_CAT(KAJO_AOV_NAME, _b
     aovBody<false, true, 1>(args, ldsRaw);
 }
 
+// The same five with the chain of KAJO_FLAG_AOV_SPECULAR
+#define KAJO_AOV_SPEC_KERNEL(suffix, ...)                                                                              \
+    extern "C" __global__ void __launch_bounds__(256) KAJO_AOV_CAT(KAJO_AOV_NAME, suffix)(const AovArgs args)           \
+    {                                                                                                                  \
+        extern __shared__ __attribute__((aligned(16))) unsigned char ldsRaw[];                                         \
+        aovBody<__VA_ARGS__, true>(args, ldsRaw);                                                                      \
+    }
+KAJO_AOV_SPEC_KERNEL(_spec, true, false, 0)
+KAJO_AOV_SPEC_KERNEL(_spec_big, false, false, 2)
+KAJO_AOV_SPEC_KERNEL(_spec_big_lg, false, false, 1)
+KAJO_AOV_SPEC_KERNEL(_spec_biglist, false, true, 2)
+KAJO_AOV_SPEC_KERNEL(_spec_biglist_lg, false, true, 1)
+
 namespace
 {
 const void* aovKernel(int instance)
@@ -143,6 +225,11 @@ const void* aovKernel(int instance)
     case KAJO_AOV_BIG_LG: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, _big_lg));
     case KAJO_AOV_BIGLIST: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, _biglist));
     case KAJO_AOV_BIGLIST_LG: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, _biglist_lg));
+    case KAJO_AOV_SPEC_SMALL: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec));
+    case KAJO_AOV_SPEC_BIG: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec_big));
+    case KAJO_AOV_SPEC_BIG_LG: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec_big_lg));
+    case KAJO_AOV_SPEC_BIGLIST: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec_biglist));
+    case KAJO_AOV_SPEC_BIGLIST_LG: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec_biglist_lg));
     default: return reinterpret_cast<const void*>(KAJO_AOV_NAME);
     }
 }
@@ -157,6 +244,11 @@ extern "C" int KAJO_AOV_CAT(KAJO_AOV_NAME, _launch)(const AovArgs* args, int ins
     case KAJO_AOV_BIG_LG: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, _big_lg), dim3(grid), dim3(256), ldsBytes, st, *args); break;
     case KAJO_AOV_BIGLIST: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, _biglist), dim3(grid), dim3(256), ldsBytes, st, *args); break;
     case KAJO_AOV_BIGLIST_LG: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, _biglist_lg), dim3(grid), dim3(256), ldsBytes, st, *args); break;
+    case KAJO_AOV_SPEC_SMALL: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec), dim3(grid), dim3(256), ldsBytes, st, *args); break;
+    case KAJO_AOV_SPEC_BIG: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec_big), dim3(grid), dim3(256), ldsBytes, st, *args); break;
+    case KAJO_AOV_SPEC_BIG_LG: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec_big_lg), dim3(grid), dim3(256), ldsBytes, st, *args); break;
+    case KAJO_AOV_SPEC_BIGLIST: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec_biglist), dim3(grid), dim3(256), ldsBytes, st, *args); break;
+    case KAJO_AOV_SPEC_BIGLIST_LG: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec_biglist_lg), dim3(grid), dim3(256), ldsBytes, st, *args); break;
     default: hipLaunchKernelGGL(KAJO_AOV_NAME, dim3(grid), dim3(256), ldsBytes, st, *args); break;
     }
     return (int)hipGetLastError();

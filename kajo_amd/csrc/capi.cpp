@@ -79,17 +79,20 @@ struct KernelSet
 static const KernelSet kFastKernels = {kajo_render_fast_launch, kajo_render_fast_split_launch, kajo_render_fast_set_lds, kajo_resolve_fast_launch,
                                        kajo_resolve_tiles_fast_launch, kajo_tone_fast_launch, kajo_aov_fast_launch, kajo_aov_fast_set_lds,
                                        kajo_kat_trace_fast_launch, kajo_kat_shade_fast_launch,
-                                       {"kajo_aov_fast", "kajo_aov_fast_big", "kajo_aov_fast_big_lg", "kajo_aov_fast_biglist", "kajo_aov_fast_biglist_lg"}};
+                                       {"kajo_aov_fast", "kajo_aov_fast_big", "kajo_aov_fast_big_lg", "kajo_aov_fast_biglist", "kajo_aov_fast_biglist_lg",
+                                       "kajo_aov_fast_spec", "kajo_aov_fast_spec_big", "kajo_aov_fast_spec_big_lg", "kajo_aov_fast_spec_biglist", "kajo_aov_fast_spec_biglist_lg"}};
 static const KernelSet kStrictKernels = {kajo_render_strict_launch, kajo_render_strict_split_launch, kajo_render_strict_set_lds, kajo_resolve_strict_launch,
                                          kajo_resolve_tiles_strict_launch, kajo_tone_strict_launch, kajo_aov_strict_launch, kajo_aov_strict_set_lds,
                                          kajo_kat_trace_strict_launch, kajo_kat_shade_strict_launch,
-                                         {"kajo_aov_strict", "kajo_aov_strict_big", "kajo_aov_strict_big_lg", "kajo_aov_strict_biglist", "kajo_aov_strict_biglist_lg"}};
+                                         {"kajo_aov_strict", "kajo_aov_strict_big", "kajo_aov_strict_big_lg", "kajo_aov_strict_biglist", "kajo_aov_strict_biglist_lg",
+                                         "kajo_aov_strict_spec", "kajo_aov_strict_spec_big", "kajo_aov_strict_spec_big_lg", "kajo_aov_strict_spec_biglist", "kajo_aov_strict_spec_biglist_lg"}};
 // The oracle's arithmetic in everything that decides (STRICT and EXACT): which walk, which hold policy, whose resolve. EXACT has render
 // and shading kernels of its own; the STRICT instances serve it for the rest (EXACT's camera rays, walk and normals are STRICT's arithmetic).
 static const KernelSet kExactKernels = {kajo_render_exact_launch, kajo_render_exact_split_launch, kajo_render_exact_set_lds, kajo_resolve_strict_launch,
                                         kajo_resolve_tiles_strict_launch, kajo_tone_strict_launch, kajo_aov_strict_launch, kajo_aov_strict_set_lds,
                                         kajo_kat_trace_strict_launch, kajo_kat_shade_exact_launch,
-                                        {"kajo_aov_strict", "kajo_aov_strict_big", "kajo_aov_strict_big_lg", "kajo_aov_strict_biglist", "kajo_aov_strict_biglist_lg"}};
+                                        {"kajo_aov_strict", "kajo_aov_strict_big", "kajo_aov_strict_big_lg", "kajo_aov_strict_biglist", "kajo_aov_strict_biglist_lg",
+                                         "kajo_aov_strict_spec", "kajo_aov_strict_spec_big", "kajo_aov_strict_spec_big_lg", "kajo_aov_strict_spec_biglist", "kajo_aov_strict_spec_biglist_lg"}};
 
 namespace
 {
@@ -552,6 +555,8 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
         return fail(KAJO_E_INVALID, "tileIndex/tileCount out of range");
     if ((p.flags & KAJO_FLAG_AOV) && p.tileCount != 1)
         return fail(KAJO_E_INVALID, "first-hit AOVs need the whole frame on one handle (tileCount 1)");
+    if ((p.flags & KAJO_FLAG_AOV_SPECULAR) && !(p.flags & KAJO_FLAG_AOV))
+        return fail(KAJO_E_INVALID, "the first-non-delta-hit flag changes what the AOV flag's buffers hold: set the AOV flag with it");
 
     if (p.flags & (KAJO_FLAG_STRICT | KAJO_FLAG_EXACT)) {
         // integrator.inc.hip kdiv / ksqrt: the IEEE quotient and root without the compiler's range scaling are exact while operands stay
@@ -695,6 +700,8 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
             h->aovInstance = v.grid.inLds ? KAJO_AOV_BIGLIST_LG : KAJO_AOV_BIGLIST;
         else
             h->aovInstance = v.grid.inLds ? KAJO_AOV_BIG_LG : KAJO_AOV_BIG;
+        if (p.flags & KAJO_FLAG_AOV_SPECULAR) // the same scene class, with the chain to the first non-delta hit
+            h->aovInstance += KAJO_AOV_SPEC_SMALL;
         h->aovLds = h->lds.coldInLds ? h->lds.ldsBytes : h->lds.hotBytes;
         if (h->aovLds > 48 * 1024)
             CREATE_TRY((hipError_t)h->k->aovSetLds(h->aovInstance, h->aovLds));

@@ -93,7 +93,13 @@ enum KajoAovInstance
     KAJO_AOV_BIG_LG = 2,     // ... the cell lists in LDS
     KAJO_AOV_BIGLIST = 3,    // scenes with visibility lists (closed room, (centre, radius) spheres only): lists global
     KAJO_AOV_BIGLIST_LG = 4, // ... in LDS
-    KAJO_AOV_INSTANCES = 5
+    // the same five with the chain of KAJO_FLAG_AOV_SPECULAR (first non-delta hit): instance of the scene class + KAJO_AOV_SPEC_SMALL
+    KAJO_AOV_SPEC_SMALL = 5,
+    KAJO_AOV_SPEC_BIG = 6,
+    KAJO_AOV_SPEC_BIG_LG = 7,
+    KAJO_AOV_SPEC_BIGLIST = 8,
+    KAJO_AOV_SPEC_BIGLIST_LG = 9,
+    KAJO_AOV_INSTANCES = 10
 };
 
 // tile-buffer slot of pixel (x, y): tiles are dealt round-robin to `tileCount` owners; inside a

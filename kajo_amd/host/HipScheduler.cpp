@@ -157,7 +157,7 @@ struct Scheduler::Impl
             p.depthLimit = opt.depthLimit;
             p.seed = opt.seed;
             p.flags = (numerics == Options::Strict ? KAJO_FLAG_STRICT : numerics == Options::Exact ? KAJO_FLAG_EXACT : 0u) | (opt.counters ? KAJO_FLAG_COUNTERS : 0u) |
-                      (opt.aov ? KAJO_FLAG_AOV : 0u);
+                      (opt.aov ? KAJO_FLAG_AOV | (opt.aovSpecular ? KAJO_FLAG_AOV_SPECULAR : 0u) : 0u);
             p.device = opt.sameDevice ? 0 : g;
             p.tileIndex = g;
             p.tileCount = opt.gpus;

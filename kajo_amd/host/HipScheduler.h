@@ -58,6 +58,7 @@ struct Options
     bool forceGather = false;     // run the gather + compose step with ONE owner too (a one-rank communicator whose
                                   // rank sends its tile buffer to itself): the multi-GPU call sequence on a one-GPU box
     bool aov = false;             // also accumulate the first-hit albedo / normal / depth (KAJO_FLAG_AOV; readAov): one GPU only
+    bool aovSpecular = false;     // ... at the first non-delta hit, through ideal mirrors and glass (KAJO_FLAG_AOV_SPECULAR); read only with aov
     // Exposure, tone curve and automatic exposure of the image run() writes (include/kajo_hip.h kajo_hip_tonemap_argb8; with one owner
     // or after the gather). The default is the identity: every frame then takes the plain resolve, exactly as without this field.
     KajoToneParams tone = {KAJO_TONE_CLAMP, 0u, 0.0f, 0.0f, 0.18f, {0.0f, 0.0f, 0.0f}};

@@ -45,7 +45,7 @@ int main(int argc, char** argv)
     opt.passes = 16;
     opt.gpus = 1;
     std::string podPath;
-    bool verbose = false, json = false, threeArg = false;
+    bool verbose = false, json = false, threeArg = false, aovSpecular = false;
     int closeAtEvent = 0;
     bool noPreview = false;
     for (size_t i = 1; i < args.size(); i++) {
@@ -87,6 +87,8 @@ int main(int argc, char** argv)
                         "    --aov PREFIX    also write the first-hit AOVs a denoiser takes, averaged over the render's camera samples:\n"
                         "                    PREFIX_albedo.pfm, PREFIX_normal.pfm (3 channels), PREFIX_depth.pfm (1; mean over the hits)\n"
                         "                    (one GPU only)\n"
+                        "    --aov-specular  with --aov or --denoise: take the AOVs at the first non-delta hit, through ideal mirrors and glass\n"
+                        "                    (include/kajo_hip.h KAJO_FLAG_AOV_SPECULAR), so that the guides show what a mirror shows\n"
                         "    --denoise FILE  also write the frame denoised with those AOVs as guides, as a PNG (edge-aware A-trous filter,\n"
                         "                    include/kajo_hip.h kajo_hip_denoise; collects the AOVs; one GPU only)\n"
                         "    --denoise-iterations K  the filter's iterations, 0..8 (5)\n"
@@ -122,6 +124,7 @@ int main(int argc, char** argv)
         else if (a == "--auto-exposure") { toneAuto = true; toneGiven = true; }
         else if (a == "--key" && more) { toneKey = args[++i]; toneGiven = true; }
         else if (a == "--aov" && more) aovPrefix = args[++i];
+        else if (a == "--aov-specular") aovSpecular = true;
         else if (a == "--denoise" && more) denoiseOut = args[++i];
         else if (a == "--denoise-iterations" && more) denoiseIterations = std::atoi(args[++i].c_str());
         else if (a == "--json") json = true;
@@ -159,6 +162,11 @@ int main(int argc, char** argv)
         }
         opt.tone.flags = toneAuto ? KAJO_TONE_AUTO_EXPOSURE : 0u;
     }
+    if (aovSpecular && aovPrefix.empty() && denoiseOut.empty()) {
+        std::cerr << "kajo_render: --aov-specular changes the AOVs that --aov writes and --denoise is guided by: give it with --aov or --denoise" << std::endl;
+        return 1;
+    }
+    opt.aovSpecular = aovSpecular;
     if (!aovPrefix.empty()) {
         // (before any device is opened: the AOV buffers are whole-frame buffers of ONE handle, include/kajo_hip.h KAJO_FLAG_AOV)
         if (opt.gpus != 1 || threeArg) {

@@ -18,7 +18,7 @@ class HipRenderer:
     def __init__(self, scene: Scene, width: int, height: int, spp: int = 32, depth_limit: int = 8,
                  seed: int = 0o715517, strict: bool = False, exact: bool = False, counters: bool = False, device: int = 0,
                  tile=(64, 16), tile_index: int = 0, tile_count: int = 1, passes_per_launch: int = 0, flags: int = 0,
-                 aov: bool = False):
+                 aov: bool = False, aov_specular: bool = False):
         L = capi.lib()
         self._L = L
         self.scene = scene
@@ -31,6 +31,7 @@ class HipRenderer:
         p.seed = seed
         p.flags = (capi.KAJO_FLAG_STRICT if strict else 0) | (capi.KAJO_FLAG_EXACT if exact else 0) | (capi.KAJO_FLAG_COUNTERS if counters else 0) | int(flags)
         p.flags |= capi.KAJO_FLAG_AOV if aov else 0
+        p.flags |= capi.KAJO_FLAG_AOV_SPECULAR if aov_specular else 0  # (without aov the library refuses it)
         p.device = device
         p.tileW, p.tileH = tile
         p.tileIndex, p.tileCount = tile_index, tile_count

@@ -7,7 +7,9 @@ pixel and a frame of 4, both with the AOVs. For every (sigmaLuminance, sigmaNorm
 RMSE in clamped display range [0, 1] over the pixels finite in the reference and the raw frame. Prints one line per setting, best ratio
 first among those whose move stays within 0.25.
 
-    python tools/denoise_sweep.py [--out FILE]
+    python tools/denoise_sweep.py [--aov-specular] [--out FILE]
+
+--aov-specular: both handles take their AOVs at the first non-delta hit (KAJO_FLAG_AOV_SPECULAR).
 """
 import argparse
 import itertools
@@ -34,14 +36,15 @@ def rmse(img, ref, mask):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--aov-specular", action="store_true")
     args = ap.parse_args()
     z = np.load(os.path.join(ROOT, "tests", "golden", "scenes.npz"))
     sc = Scene.from_npz(z, "spheres_a169/", "spheres_a169")
     W, H = 320, 180
-    ref = HipRenderer(sc, W, H, spp=64, exact=True, aov=True, seed=12345)
+    ref = HipRenderer(sc, W, H, spp=64, exact=True, aov=True, aov_specular=args.aov_specular, seed=12345)
     ref.render(40)
     truth = ref.radiance()[..., :3] / ref.passes
-    r = HipRenderer(sc, W, H, spp=4, exact=True, aov=True)
+    r = HipRenderer(sc, W, H, spp=4, exact=True, aov=True, aov_specular=args.aov_specular)
     r.render(1)
     raw = r.radiance()[..., :3] / r.passes
     mask = np.isfinite(truth).all(-1) & np.isfinite(raw).all(-1)
@@ -52,10 +55,11 @@ def main():
         dn = r.denoise(**kw)["radiance"][..., :3] / r.passes
         mv = ref.denoise(**kw)["radiance"][..., :3] / ref.passes
         rows.append((rmse(dn, truth, mask) / e_raw, rmse(mv, truth, mask) / e_raw, demod, sl, sn, sd))
+    guides = r.aov_kernel()
     ref.close()
     r.close()
     rows.sort(key=lambda t: (t[1] > 0.25, t[0]))
-    lines = ["raw 4-spp RMSE %.4f (clamped, %d pixels); K = 5" % (e_raw, int(mask.sum())),
+    lines = ["raw 4-spp RMSE %.4f (clamped, %d pixels); K = 5; guides: %s" % (e_raw, int(mask.sum()), guides),
              "%-7s %-7s %-11s %-8s %-8s %-8s" % ("ratio", "move", "demodulate", "sigmaL", "sigmaN", "sigmaD")]
     lines += ["%-7.3f %-7.3f %-11s %-8g %-8g %-8g" % row for row in rows]
     text = "\n".join(lines) + "\n"
