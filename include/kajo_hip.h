@@ -29,6 +29,9 @@
  *   kajo_hip_tonemap_argb8   Image::linearToSRGB / colorToRGBA8 (renderer/Image.cpp:14-27) with an exposure, a tone curve and automatic
  *                            exposure in front of the clamp; kajo_hip_tonemap_gathered_argb8_device is its twin over gathered tile
  *                            buffers, kajo_hip_tone_scale reports the scale applied, kajo_hip_default_tone_params gives the defaults
+ *   kajo_hip_glare           (no counterpart: the reference has no glare) a bloom pyramid between the frame and the tone curves;
+ *                            kajo_hip_display_argb8 and kajo_hip_display_gathered_argb8_device run denoise -> glare -> tone mapping,
+ *                            kajo_hip_default_glare_params gives the defaults
  *   kajo_hip_destroy         the unique_ptr members of cpu::Scheduler (cpu/Scheduler.h:29-31)
  *
  * Pixels are dealt to GPUs as fixed-size tiles: a handle created with
@@ -329,6 +332,58 @@ int kajo_hip_tonemap_argb8(kajo_hip_t h, const KajoToneParams* p, const KajoDeno
 int kajo_hip_tonemap_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoToneParams* p, void* dst);
 /* The s of the handle's most recent tone mapping; waits for it. KAJO_E_STATE before the first one. */
 int kajo_hip_tone_scale(kajo_hip_t h, float* scale);
+
+/* Glare (bloom): a small share of every pixel's energy spread over its neighbourhood, between the frame and the tone curves, so that
+   a light far brighter than 1 gets a halo for the curve to roll off instead of a flat disc. A post-process over the handle's whole
+   frame, in kernels of its own (kajo_amd/csrc/glare.hip) on the handle's stream, in float32 IEEE arithmetic without contraction in
+   every numerics build: only its inputs depend on FAST / EXACT / STRICT. Frame in, frame out, in the units of kajo_hip_read_radiance,
+   where the denoiser sits. Definition -- P = the handle's pass count, F = the source frame in sums over passes (the accumulation, or
+   the frame kajo_hip_denoise gives), W x H, row 0 at the top; per pixel:
+     m  = F.rgb / P                      (float32 division)
+     the pixel COUNTS where all three channels of m are finite
+     x  = max(m, 0);  l = 0.2126 x.r + 0.7152 x.g + 0.0722 x.b
+     B0 = x * k,  k = 1 if threshold == 0 else max(l - threshold, 0) / max(l, 1e-6);   B0 = 0 where the pixel does not count
+   reduce, level k -> k+1, size (w+1)/2 x (h+1)/2 (integer division):
+     B_{k+1}(X, Y) = sum g_i g_j B_k(2X+i, 2Y+j) / sum g_i g_j,   i, j in {-1, 0, 1, 2},  g = [1, 3, 3, 1] / 8,
+     over the taps that lie inside level k (no edge clamping: the weights are renormalised over the taps that remain)
+   n = min(levels, the number of reductions after which the level is 1 x 1)
+   expand, level k+1 -> k: up(U)(x, y) = per axis the tap at (x >> 1) with weight 3/4 and its neighbour
+     (x >> 1) + (x & 1 ? +1 : -1) with weight 1/4; taps outside level k+1 are skipped and the weights renormalised
+     U_n = B_n;   U_k = (B_k + (n - k) * up(U_{k+1})) / (n - k + 1)   for k = n-1 .. 1;   G = up(U_1)
+     (G is the mean of the n reduced levels, each brought back to full size)
+   out.rgb = (m + strength * (G - B0)) * P   where the pixel counts;   F.rgb unchanged where it does not;   out.w = F.w
+   With threshold 0 this is a lerp between the frame and its wide blur; with a threshold it removes `strength` of the bright part and
+   adds it back spread out: energy is kept either way, up to the renormalisation at the edges (which is what keeps a constant frame
+   constant). With strength == 0, levels == 0 or n == 0 (a 1 x 1 frame) the output is F itself, so its ARGB8 is that of the plain
+   resolve / tone mapping bit for bit. A NaN or Inf pixel contributes nothing to any level and comes out with the bits it went in
+   with: glare never spreads such a pixel. Sums have a fixed order and there are no atomics: the same bits from run to run and for any
+   number of tile owners. The accumulation, the AOV buffers, the pass count and the counters (kernelMs included) are not touched.
+   Scratch (the pyramid, about 2 x 4/3 float4 frames, and the output frame) is allocated on first use and freed by kajo_hip_destroy.
+   Refusals (KAJO_E_INVALID, before any device work and before the handle is looked at): levels outside 0..12; any flag bit; a strength
+   that is not finite or outside 0..1; a threshold that is negative or not finite; non-zero reserved words. Then the tone and the denoise
+   parameters' own refusals, then the handle's (KAJO_E_STATE with no pass rendered; the denoiser's state rules with `denoise`). */
+typedef struct KajoGlareParams {
+    int32_t levels;     /* 0..12 (default 6) */
+    uint32_t flags;     /* 0: no flag defined yet; any bit is refused */
+    float strength;     /* 0..1 (default 0.1) */
+    float threshold;    /* >= 0, finite (default 0: every pixel glares in proportion) */
+    float reserved[4];  /* 0 */
+} KajoGlareParams;      /* 32 bytes */
+void kajo_hip_default_glare_params(KajoGlareParams* p); /* NULL is accepted */
+/* The frame after glare: radiance = HOST pointer to width*height*4 floats (row 0 = top), sums over passes. denoise == NULL: glare over
+   the accumulation (tileCount 1, or a composed handle, as kajo_hip_read_radiance); otherwise over the frame kajo_hip_denoise with those
+   parameters produces, formed on the device. g == NULL is refused (KAJO_E_INVALID). Waits. */
+int kajo_hip_glare(kajo_hip_t h, const KajoGlareParams* g, const KajoDenoiseParams* denoise, float* radiance);
+/* The display chain: denoise (optional, NULL = the accumulation) -> glare (optional, NULL = none) -> tone mapping, which takes the
+   glared frame as it takes the denoised one: automatic exposure is measured on the frame after glare. With g == NULL exactly
+   kajo_hip_tonemap_argb8. argb8: HOST pointer to width*height words; *scale: the s applied; either may be NULL. Waits. */
+int kajo_hip_display_argb8(kajo_hip_t h, const KajoDenoiseParams* denoise, const KajoGlareParams* g, const KajoToneParams* tone,
+                           uint32_t* argb8, float* scale);
+/* The multi-GPU twin, as kajo_hip_tonemap_gathered_argb8_device is kajo_hip_tonemap_argb8's: gathered tile buffers (NULL = the handle's
+   own when tileCount == 1) -> glare (NULL = none) -> tone mapping, into DEVICE memory, asynchronous on the handle's stream, no host
+   synchronisation. */
+int kajo_hip_display_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoGlareParams* g, const KajoToneParams* tone,
+                                           void* dst);
 
 /* Use an existing HIP stream (hipStream_t passed as void*) instead of the handle's own. */
 int kajo_hip_set_stream(kajo_hip_t h, void* stream);

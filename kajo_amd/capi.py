@@ -48,6 +48,7 @@ EXPORTS = [
     "kajo_hip_kat_strictmath", "kajo_hip_stage_shadow_lists", "kajo_hip_resolve_gathered_argb8_device", "kajo_hip_stage_info",
     "kajo_hip_launch_order", "kajo_hip_read_aov", "kajo_hip_aov_kernel", "kajo_hip_default_denoise_params", "kajo_hip_denoise",
     "kajo_hip_default_tone_params", "kajo_hip_tonemap_argb8", "kajo_hip_tonemap_gathered_argb8_device", "kajo_hip_tone_scale",
+    "kajo_hip_default_glare_params", "kajo_hip_glare", "kajo_hip_display_argb8", "kajo_hip_display_gathered_argb8_device",
 ]
 
 
@@ -64,6 +65,10 @@ class KajoDenoiseParams(C.Structure):
 class KajoToneParams(C.Structure):
     _fields_ = [("curve", C.c_int32), ("flags", C.c_uint32), ("exposure", C.c_float), ("white", C.c_float), ("key", C.c_float),
                 ("reserved", C.c_float * 3)]
+
+
+class KajoGlareParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("flags", C.c_uint32), ("strength", C.c_float), ("threshold", C.c_float), ("reserved", C.c_float * 4)]
 
 
 class KajoParams(C.Structure):
@@ -147,6 +152,14 @@ def lib():
                                                  C.POINTER(C.c_float)]
             L.kajo_hip_tonemap_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoToneParams), C.c_void_p]
             L.kajo_hip_tone_scale.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        if hasattr(L, "kajo_hip_glare"):  # (nor the glare)
+            L.kajo_hip_default_glare_params.argtypes = [C.POINTER(KajoGlareParams)]
+            L.kajo_hip_default_glare_params.restype = None
+            L.kajo_hip_glare.argtypes = [C.c_void_p, C.POINTER(KajoGlareParams), C.POINTER(KajoDenoiseParams), C.c_void_p]
+            L.kajo_hip_display_argb8.argtypes = [C.c_void_p, C.POINTER(KajoDenoiseParams), C.POINTER(KajoGlareParams), C.POINTER(KajoToneParams),
+                                                 C.c_void_p, C.POINTER(C.c_float)]
+            L.kajo_hip_display_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoGlareParams), C.POINTER(KajoToneParams),
+                                                                 C.c_void_p]
         L.kajo_hip_kat_trace.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
         L.kajo_hip_kat_shade.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.kajo_hip_kat_strictmath.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -53,6 +53,9 @@ int kajo_aov_strict_set_lds(int instance, size_t lds);
 int kajo_denoise_launch(const void* tiles, const TileMap* map, const void* albedoHits, const void* normalDepth, float passes, float samples,
                         int iterations, int demodulate, float sigmaLuminance, float sigmaNormal, float sigmaDepth, void* scratch, void** result,
                         void* stream);
+int kajo_glare_plan(int W, int H, int levels, size_t* pixels);
+int kajo_glare_launch(const void* src, const TileMap* map, int fromTiles, float passes, int n, float strength, float threshold, void* scratch,
+                      void* out, void* stream);
 int kajo_tone_fast_launch(const void* src, const TileMap* map, int fromTiles, float passes, const ToneArgs* t, void* scratch, void* dst, void* stream);
 int kajo_tone_strict_launch(const void* src, const TileMap* map, int fromTiles, float passes, const ToneArgs* t, void* scratch, void* dst, void* stream);
 }
@@ -211,6 +214,9 @@ struct KajoHip
     DeviceBuffer denoise;
     // tone mapping (tonemap.inc.hip; kajo_hip_tonemap_*), on its first call: the scale word + the logavg partials (toneLaunch)
     DeviceBuffer tone;
+    // glare (glare.hip; kajo_hip_glare, kajo_hip_display_*), on its first call: the pyramid of kajo_glare_plan at the most levels, then
+    // the output frame float4 [W * H]
+    DeviceBuffer glare;
     int toneScaleState = 0; // the s of the most recent tone mapping: 0 none yet, 1 toneScale, 2 the scale word (auto exposure)
     float toneScale = 1.0f;
 };
@@ -1125,6 +1131,49 @@ int toneLaunch(KajoHip* h, Image img, const ToneArgs& t, void* dst)
     return KAJO_OK;
 }
 
+constexpr int kGlareMaxLevels = 12;
+
+// The refusals of KajoGlareParams (KAJO_E_INVALID), before any device work and before the handle is looked at
+int checkGlare(const KajoGlareParams* g)
+{
+    if (!g)
+        return fail(KAJO_E_INVALID, "null glare parameters");
+    if (g->levels < 0 || g->levels > kGlareMaxLevels)
+        return fail(KAJO_E_INVALID, "glare levels must be in [0, 12]");
+    if (g->flags)
+        return fail(KAJO_E_INVALID, "unknown glare flag");
+    if (!std::isfinite(g->strength) || g->strength < 0.0f || g->strength > 1.0f)
+        return fail(KAJO_E_INVALID, "glare strength must be finite and in [0, 1]");
+    if (!std::isfinite(g->threshold) || g->threshold < 0.0f)
+        return fail(KAJO_E_INVALID, "glare threshold must be finite and not negative");
+    for (float r : g->reserved)
+        if (r != 0.0f)
+            return fail(KAJO_E_INVALID, "glare reserved fields must be 0");
+    return KAJO_OK;
+}
+
+// Enqueue the glare of an image (tiles through h->map's geometry, or a row-major frame): *out = the row-major frame in the glare scratch
+// that holds the result -- or the image itself where the definition makes the output a copy (strength 0, no level). Checked by checkGlare,
+// device bound.
+int glareImage(KajoHip* h, const KajoGlareParams* g, Image img, Image* out)
+{
+    const int n = kajo_glare_plan(h->W, h->H, g->levels, nullptr);
+    if (n == 0 || g->strength == 0.0f) {
+        *out = img;
+        return KAJO_OK;
+    }
+    size_t pyramid = 0;
+    (void)kajo_glare_plan(h->W, h->H, kGlareMaxLevels, &pyramid);
+    HIP_TRY(h->glare.ensure((pyramid + (size_t)h->W * h->H) * 16));
+    void* frame = h->glare.as<char>() + pyramid * 16;
+    hipError_t le = (hipError_t)kajo_glare_launch(img.src, &h->map, img.fromTiles ? 1 : 0, (float)h->passesDone, n, g->strength, g->threshold,
+                                                  h->glare.p, frame, h->stream);
+    if (le != hipSuccess)
+        return failHip(le, "glare kernel launch");
+    *out = Image{frame, false};
+    return KAJO_OK;
+}
+
 // the rays of the known-answer entry points as the kernels read them: float [n][6], origin then direction
 std::vector<float> packRays(int n, const float* origins, const float* dirs)
 {
@@ -1216,6 +1265,103 @@ int kajo_hip_tonemap_gathered_argb8_device(kajo_hip_t h, const void* gathered, c
         return fail(KAJO_E_INVALID, "null argument");
     Image img;
     return (rc = imageOf(h, true, gathered, &img)) ? rc : toneLaunch(h, img, t, dst);
+}
+
+void kajo_hip_default_glare_params(KajoGlareParams* p)
+{
+    if (!p)
+        return;
+    std::memset(p, 0, sizeof *p);
+    p->levels = 6;
+    p->flags = 0;
+    p->strength = 0.1f;
+    p->threshold = 0.0f;
+}
+
+int kajo_hip_glare(kajo_hip_t h, const KajoGlareParams* g, const KajoDenoiseParams* denoise, float* radiance)
+{
+    // (every refusal before any device work: the parameters, the denoiser's, then the handle)
+    int rc = checkGlare(g);
+    if (rc)
+        return rc;
+    if (denoise) {
+        if ((rc = checkDenoise(h, denoise)))
+            return rc;
+    } else if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    Image img;
+    if ((rc = imageOf(h, false, nullptr, &img)))
+        return rc;
+    if (denoise) {
+        void* out = nullptr;
+        if ((rc = denoiseFrame(h, denoise, &out)))
+            return rc;
+        img = Image{out, false};
+    }
+    if ((rc = glareImage(h, g, img, &img)))
+        return rc;
+    if (img.fromTiles) {
+        // (a copy of the accumulation: the composed frame, as kajo_hip_read_radiance)
+        if ((rc = composeOwn(h)))
+            return rc;
+        img = Image{h->frame.p, false};
+    }
+    if (radiance)
+        HIP_TRY(hipMemcpyAsync(radiance, img.src, (size_t)h->W * h->H * 16, hipMemcpyDeviceToHost, h->stream));
+    return kajo_hip_wait(h);
+}
+
+int kajo_hip_display_argb8(kajo_hip_t h, const KajoDenoiseParams* denoise, const KajoGlareParams* g, const KajoToneParams* tone, uint32_t* argb8,
+                           float* scale)
+{
+    // (every refusal before any device work: the glare parameters, the tone parameters, the denoiser's, then the handle)
+    int rc;
+    if (g && (rc = checkGlare(g)))
+        return rc;
+    ToneArgs t{};
+    if ((rc = toneArgsOf(tone, &t)))
+        return rc;
+    if (denoise) {
+        if ((rc = checkDenoise(h, denoise)))
+            return rc;
+    } else if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    Image img;
+    if ((rc = imageOf(h, false, nullptr, &img)))
+        return rc;
+    const size_t count = (size_t)h->W * h->H;
+    HIP_TRY(h->argb.ensure(count * 4));
+    if (denoise) {
+        void* out = nullptr;
+        if ((rc = denoiseFrame(h, denoise, &out)))
+            return rc;
+        img = Image{out, false};
+    }
+    if (g && (rc = glareImage(h, g, img, &img)))
+        return rc;
+    if ((rc = toneLaunch(h, img, t, h->argb.p)))
+        return rc;
+    if (argb8)
+        HIP_TRY(hipMemcpyAsync(argb8, h->argb.p, count * 4, hipMemcpyDeviceToHost, h->stream));
+    return scale ? kajo_hip_tone_scale(h, scale) : kajo_hip_wait(h);
+}
+
+int kajo_hip_display_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoGlareParams* g, const KajoToneParams* tone, void* dst)
+{
+    int rc;
+    if (g && (rc = checkGlare(g)))
+        return rc;
+    ToneArgs t{};
+    if ((rc = toneArgsOf(tone, &t)))
+        return rc;
+    if (!h || !dst)
+        return fail(KAJO_E_INVALID, "null argument");
+    Image img;
+    if ((rc = imageOf(h, true, gathered, &img)))
+        return rc;
+    if (g && (rc = glareImage(h, g, img, &img)))
+        return rc;
+    return toneLaunch(h, img, t, dst);
 }
 
 int kajo_hip_tone_scale(kajo_hip_t h, float* scale)

@@ -78,6 +78,9 @@ struct Scheduler::Impl
     // Options::tone is the identity (include/kajo_hip.h: s = 1 and the clamp, whatever white and key say): the plain resolve
     bool toneIsIdentity() const { return opt.tone.curve == KAJO_TONE_CLAMP && opt.tone.flags == 0 && opt.tone.exposure == 0.0f; }
 
+    // Options::glare changes the frame (include/kajo_hip.h: with strength 0 or no level the output is the input)
+    bool glareOn() const { return opt.glare.strength > 0.0f && opt.glare.levels > 0; }
+
     ~Impl()
     {
         for (kajo_hip_t h : handles)
@@ -194,7 +197,9 @@ struct Scheduler::Impl
     {
         if (opt.gpus == 1 && !opt.forceGather) {
             // single owner: the library resolves from its own tile buffer
-            if (toneIsIdentity())
+            if (glareOn())
+                check(kajo_hip_display_argb8(handles[0], nullptr, &opt.glare, &opt.tone, image->pixels.get(), &toneScale), "kajo_hip_display_argb8");
+            else if (toneIsIdentity())
                 check(kajo_hip_resolve_argb8(handles[0], image->pixels.get()), "kajo_hip_resolve_argb8");
             else
                 check(kajo_hip_tonemap_argb8(handles[0], &opt.tone, nullptr, image->pixels.get(), &toneScale), "kajo_hip_tonemap_argb8");
@@ -224,7 +229,9 @@ struct Scheduler::Impl
             }
         }
         composed = false;
-        if (toneIsIdentity())
+        if (glareOn())
+            check(kajo_hip_display_gathered_argb8_device(handles[0], gathered, &opt.glare, &opt.tone, argbDevice), "kajo_hip_display_gathered_argb8_device");
+        else if (toneIsIdentity())
             check(kajo_hip_resolve_gathered_argb8_device(handles[0], gathered, argbDevice), "kajo_hip_resolve_gathered_argb8_device");
         else
             check(kajo_hip_tonemap_gathered_argb8_device(handles[0], gathered, &opt.tone, argbDevice), "kajo_hip_tonemap_gathered_argb8_device");
@@ -232,7 +239,7 @@ struct Scheduler::Impl
         checkHip(hipMemcpyAsync(image->pixels.get(), argbDevice, (size_t)image->width * image->height * 4, hipMemcpyDeviceToHost, streams[0]),
                  "hipMemcpyAsync(image)");
         checkHip(hipStreamSynchronize(streams[0]), "hipStreamSynchronize");
-        if (!toneIsIdentity())
+        if (glareOn() || !toneIsIdentity())
             check(kajo_hip_tone_scale(handles[0], &toneScale), "kajo_hip_tone_scale"); // (the stream is drained: no wait left)
     }
     bool composed = false;
@@ -300,6 +307,16 @@ void Scheduler::readDenoisedTonemapped(const KajoDenoiseParams* params, const Ka
     KajoDenoiseParams p;
     kajo_hip_default_denoise_params(&p);
     check(kajo_hip_tonemap_argb8(d.handles[0], tone ? tone : &d.opt.tone, params ? params : &p, argb8, scale), "kajo_hip_tonemap_argb8");
+}
+
+void Scheduler::readDisplayed(const KajoDenoiseParams* denoise, const KajoGlareParams* glare, const KajoToneParams* tone, uint32_t* argb8, float* scale)
+{
+    Impl& d = *m_impl;
+    if (d.gathered && !d.composed) { // several owners (or the forced gather): the whole float frame from the last gather, as readRadiance
+        check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
+        d.composed = true;
+    }
+    check(kajo_hip_display_argb8(d.handles[0], denoise, glare ? glare : &d.opt.glare, tone ? tone : &d.opt.tone, argb8, scale), "kajo_hip_display_argb8");
 }
 
 void Scheduler::run()

@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "Scheduler.h"
-#include "kajo_hip.h" // KajoToneParams (Options::tone)
+#include "kajo_hip.h" // KajoToneParams (Options::tone), KajoGlareParams (Options::glare)
 
 class Image;
 class Preview;
@@ -62,6 +62,9 @@ struct Options
     // Exposure, tone curve and automatic exposure of the image run() writes (include/kajo_hip.h kajo_hip_tonemap_argb8; with one owner
     // or after the gather). The default is the identity: every frame then takes the plain resolve, exactly as without this field.
     KajoToneParams tone = {KAJO_TONE_CLAMP, 0u, 0.0f, 0.0f, 0.18f, {0.0f, 0.0f, 0.0f}};
+    // Glare (bloom) in front of the tone mapping of the image run() writes (include/kajo_hip.h kajo_hip_display_argb8; with one owner or
+    // after the gather). Off by default (strength 0): every frame then takes exactly the calls it takes without this field.
+    KajoGlareParams glare = {6, 0u, 0.0f, 0.0f, {0.0f, 0.0f, 0.0f, 0.0f}};
 };
 
 struct Statistics
@@ -99,6 +102,9 @@ public:
     // the same frame tone-mapped (include/kajo_hip.h kajo_hip_tonemap_argb8 with denoise = params): W*H ARGB8 words; tone null = Options::tone;
     // *scale (may be null) = the s applied
     void readDenoisedTonemapped(const KajoDenoiseParams* params, const KajoToneParams* tone, uint32_t* argb8, float* scale);
+    // the whole display chain after run() (include/kajo_hip.h kajo_hip_display_argb8 on the first handle: one GPU, or a composed frame):
+    // denoise (null = the accumulation; otherwise Options::aov) -> glare (null = Options::glare) -> tone (null = Options::tone)
+    void readDisplayed(const KajoDenoiseParams* denoise, const KajoGlareParams* glare, const KajoToneParams* tone, uint32_t* argb8, float* scale);
 
 private:
     struct Impl;

@@ -39,6 +39,8 @@ int main(int argc, char** argv)
     // tone options (include/kajo_hip.h KajoToneParams): the raw text, checked after the loop; toneGiven = any of them was given
     std::string toneCurve, toneExposure, toneWhite, toneKey;
     bool toneAuto = false, toneGiven = false;
+    // glare options (include/kajo_hip.h KajoGlareParams): the raw text, checked after the loop
+    std::string glareStrength, glareLevels, glareThreshold;
     int width = 640, height = 480;
     int denoiseIterations = 5;
     hip::Options opt;
@@ -84,6 +86,10 @@ int main(int argc, char** argv)
                         "    --white W       reinhard: the exposed luminance mapped to white, >= 0 (0 = none: L / (1 + L))\n"
                         "    --auto-exposure scale the frame's log-average luminance to --key (on top of --exposure)\n"
                         "    --key K         --auto-exposure: the grey the log-average is mapped to, > 0 (0.18)\n"
+                        "    --glare STRENGTH  glare (bloom) in front of the tone curve (-o and --denoise; include/kajo_hip.h kajo_hip_glare): the share\n"
+                        "                    of every pixel's energy, 0..1, spread over its neighbourhood (0 = none, the default; --hdr stays without)\n"
+                        "    --glare-levels N  --glare: levels of the pyramid, 0..12 (6): the halo's reach doubles with each\n"
+                        "    --glare-threshold T  --glare: only luminance above T glares, >= 0 (0: every pixel in proportion)\n"
                         "    --aov PREFIX    also write the first-hit AOVs a denoiser takes, averaged over the render's camera samples:\n"
                         "                    PREFIX_albedo.pfm, PREFIX_normal.pfm (3 channels), PREFIX_depth.pfm (1; mean over the hits)\n"
                         "                    (one GPU only)\n"
@@ -123,6 +129,9 @@ int main(int argc, char** argv)
         else if (a == "--white" && more) { toneWhite = args[++i]; toneGiven = true; }
         else if (a == "--auto-exposure") { toneAuto = true; toneGiven = true; }
         else if (a == "--key" && more) { toneKey = args[++i]; toneGiven = true; }
+        else if (a == "--glare" && more) glareStrength = args[++i];
+        else if (a == "--glare-levels" && more) glareLevels = args[++i];
+        else if (a == "--glare-threshold" && more) glareThreshold = args[++i];
         else if (a == "--aov" && more) aovPrefix = args[++i];
         else if (a == "--aov-specular") aovSpecular = true;
         else if (a == "--denoise" && more) denoiseOut = args[++i];
@@ -162,6 +171,35 @@ int main(int argc, char** argv)
         }
         opt.tone.flags = toneAuto ? KAJO_TONE_AUTO_EXPOSURE : 0u;
     }
+    if (glareStrength.empty() && (!glareLevels.empty() || !glareThreshold.empty())) {
+        std::cerr << "kajo_render: --glare-levels and --glare-threshold shape the glare that --glare STRENGTH turns on: give them with --glare" << std::endl;
+        return 1;
+    }
+    if (!glareStrength.empty()) {
+        // (before any device is opened: the refusals of kajo_hip_glare, with the option's name)
+        if (threeArg) {
+            std::cerr << "kajo_render: the glare options need the backend's options (without --three-arg)" << std::endl;
+            return 1;
+        }
+        if (!parseFloat(glareStrength, &opt.glare.strength) || opt.glare.strength < 0.0f || opt.glare.strength > 1.0f) {
+            std::cerr << "kajo_render: --glare must be a number in 0..1" << std::endl;
+            return 1;
+        }
+        if (!glareLevels.empty()) {
+            char* end = nullptr;
+            const long n = std::strtol(glareLevels.c_str(), &end, 10);
+            if (*end != '\0' || n < 0 || n > 12) {
+                std::cerr << "kajo_render: --glare-levels must be in 0..12" << std::endl;
+                return 1;
+            }
+            opt.glare.levels = (int32_t)n;
+        }
+        if (!glareThreshold.empty() && (!parseFloat(glareThreshold, &opt.glare.threshold) || opt.glare.threshold < 0.0f)) {
+            std::cerr << "kajo_render: --glare-threshold must be a finite number >= 0" << std::endl;
+            return 1;
+        }
+    }
+    const bool glareGiven = opt.glare.strength > 0.0f && opt.glare.levels > 0;
     if (aovSpecular && aovPrefix.empty() && denoiseOut.empty()) {
         std::cerr << "kajo_render: --aov-specular changes the AOVs that --aov writes and --denoise is guided by: give it with --aov or --denoise" << std::endl;
         return 1;
@@ -276,7 +314,9 @@ int main(int argc, char** argv)
             kajo_hip_default_denoise_params(&p);
             p.iterations = denoiseIterations;
             Image denoised(width, height);
-            if (toneGiven)
+            if (glareGiven)
+                hipScheduler->readDisplayed(&p, nullptr, nullptr, denoised.pixels.get(), nullptr);
+            else if (toneGiven)
                 hipScheduler->readDenoisedTonemapped(&p, nullptr, denoised.pixels.get(), nullptr);
             else
                 hipScheduler->readDenoised(&p, nullptr, denoised.pixels.get());

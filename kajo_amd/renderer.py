@@ -143,6 +143,17 @@ class HipRenderer:
         = (H, W) uint32 as argb8(), scale = the linear factor s applied to the mean radiance. curve: "clamp" | "reinhard" | "aces".
         denoise: None maps the accumulation; a dict of denoise()'s keyword arguments maps the frame denoise() would give (aov=True). The
         defaults are argb8() bit for bit. The accumulation, the AOVs and the counters are not touched."""
+        p = self._tone_params(curve, exposure, white, auto_exposure, key)
+        d = None
+        if denoise is not None:
+            d = self._denoise_params(**denoise)
+        argb8 = np.empty((self.height, self.width), np.uint32)
+        scale = C.c_float()
+        capi.check(self._L.kajo_hip_tonemap_argb8(self._h, C.byref(p), None if d is None else C.byref(d), argb8.ctypes.data_as(C.c_void_p),
+                                                  C.byref(scale)))
+        return argb8, scale.value
+
+    def _tone_params(self, curve: str = "clamp", exposure: float = 0.0, white: float = 0.0, auto_exposure: bool = False, key: float = 0.18):
         curves = {"clamp": capi.KAJO_TONE_CLAMP, "reinhard": capi.KAJO_TONE_REINHARD, "aces": capi.KAJO_TONE_ACES}
         if curve not in curves:
             raise ValueError("curve must be one of %s" % ", ".join(curves))
@@ -151,13 +162,41 @@ class HipRenderer:
         p.curve = curves[curve]
         p.flags = capi.KAJO_TONE_AUTO_EXPOSURE if auto_exposure else 0
         p.exposure, p.white, p.key = float(exposure), float(white), float(key)
-        d = None
-        if denoise is not None:
-            d = self._denoise_params(**denoise)
+        return p
+
+    def _glare_params(self, levels: int = None, strength: float = None, threshold: float = None):
+        p = capi.KajoGlareParams()
+        self._L.kajo_hip_default_glare_params(C.byref(p))
+        if levels is not None:
+            p.levels = int(levels)
+        if strength is not None:
+            p.strength = float(strength)
+        if threshold is not None:
+            p.threshold = float(threshold)
+        return p
+
+    def glare(self, levels: int = None, strength: float = None, threshold: float = None, denoise: dict = None) -> np.ndarray:
+        """The frame after the glare (bloom) pyramid (include/kajo_hip.h kajo_hip_glare): (H, W, 4) float32 sums over passes, as
+        radiance(). Arguments left None take kajo_hip_default_glare_params' values (6 levels, strength 0.1, threshold 0). denoise: None
+        glares the accumulation; a dict of denoise()'s keyword arguments glares the frame denoise() would give (aov=True). The
+        accumulation, the AOVs and the counters are not touched."""
+        g = self._glare_params(levels, strength, threshold)
+        d = None if denoise is None else self._denoise_params(**denoise)
+        out = np.empty((self.height, self.width, 4), np.float32)
+        capi.check(self._L.kajo_hip_glare(self._h, C.byref(g), None if d is None else C.byref(d), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def display(self, denoise: dict = None, glare: dict = None, **tone):
+        """The display chain (include/kajo_hip.h kajo_hip_display_argb8): denoise (optional) -> glare (optional) -> tone mapping ->
+        (argb8, scale) as tonemap(). denoise: a dict of denoise()'s keyword arguments; glare: a dict of glare()'s levels / strength /
+        threshold; tone: tonemap()'s curve, exposure, white, auto_exposure, key. With glare None it is tonemap(denoise=denoise, **tone)."""
+        t = self._tone_params(**tone)
+        d = None if denoise is None else self._denoise_params(**denoise)
+        g = None if glare is None else self._glare_params(**glare)
         argb8 = np.empty((self.height, self.width), np.uint32)
         scale = C.c_float()
-        capi.check(self._L.kajo_hip_tonemap_argb8(self._h, C.byref(p), None if d is None else C.byref(d), argb8.ctypes.data_as(C.c_void_p),
-                                                  C.byref(scale)))
+        capi.check(self._L.kajo_hip_display_argb8(self._h, None if d is None else C.byref(d), None if g is None else C.byref(g), C.byref(t),
+                                                  argb8.ctypes.data_as(C.c_void_p), C.byref(scale)))
         return argb8, scale.value
 
     def tone_scale(self) -> float:
