@@ -385,6 +385,67 @@ int kajo_hip_display_argb8(kajo_hip_t h, const KajoDenoiseParams* denoise, const
 int kajo_hip_display_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoGlareParams* g, const KajoToneParams* tone,
                                            void* dst);
 
+/* Despeckle: repair the pixels that are not a number and bound the single-pixel outliers (fireflies), in front of the display chain.
+   The integrator leaves both (the reference's own arithmetic produces NaN samples, Light.cpp:43-46; a firefly is one path that found
+   the light through an unlikely chain); the resolve, the tone curves and the glare map a NaN pixel to a black dot, the glare spreads
+   a firefly into a halo, and the denoiser lets it through into its neighbours. A post-process over the handle's whole frame, in
+   kernels of its own (kajo_amd/csrc/despeckle.hip) on the handle's stream, in float32 IEEE arithmetic without contraction in every
+   numerics build and in one fixed order: only its inputs depend on FAST / EXACT / STRICT. Frame in, frame out, in the units of
+   kajo_hip_read_radiance. Definition -- P = the handle's pass count, F = the source frame in sums over passes, W x H, row 0 at the top;
+   per pixel:
+     m = F.rgb / P                       (float32 division)
+     the pixel COUNTS where all three channels of m are finite
+     l = (0.2126 max(m.r, 0) + 0.7152 max(m.g, 0)) + 0.0722 max(m.b, 0)
+   Step 1, clamp (F -> C). N1(p) = the 8 neighbours of p that lie inside the image and count. Where p counts and |N1(p)| >= 3:
+     L_(r) = the r-th largest l over N1(p), r = min(rank, |N1(p)|)
+     b = factor * max(L_(r), floor)
+     if l > b:  C.rgb = (m * (b / l)) * P      (the hue is kept: all three channels are scaled, negative ones included)
+   Everywhere else C = F with the bits it had; C.w = F.w. factor == 0 switches the clamp off (C = F).
+   Step 2, repair (C -> out). A pixel of C counts where C.rgb / P is finite (the clamp only scales a counting pixel down: these are
+   the pixels of F that count). A pixel that counts: out = C. One that does not:
+     out.rgb = (sum of C.rgb / P over the counting pixels of N1(p), in row-major order) / |N1(p)| * P
+     where N1(p) is empty, the same mean over the counting pixels among the other 24 of the 5 x 5 window around p, in row-major order
+     where that is empty too, out = F with the bits it had;   out.w = F.w
+   Repair reads the CLAMPED frame, so a firefly beside a NaN pixel is not averaged in at its full height. The counts: pixels clamped
+   (C differs from F by the rule above) and pixels repaired (given a mean; a pixel left with its input bits is not counted).
+   Properties. A constant frame is unchanged. A k x k block of equal bright pixels, k >= 2, is unchanged at rank 1..3 (every pixel
+   of it has three neighbours as bright): lights keep their discs. A light that covers one pixel -- at rank 2 and above, one or two
+   -- IS dimmed, to `factor` times its surroundings: the rule cannot tell it from a firefly. The defaults (16, 1, 0.2) are the
+   gentlest setting of DESIGN.md section 6f's sweep that still bounds a pixel far above everything around it: at low sample counts
+   most pixels several times their neighbours are signal, which the denoiser needs. The output at a pixel depends on the input
+   frame only, through image coordinates: no atomics, no order between workgroups, so the frame and the counts are the same bits
+   for any number of tile owners, on a second call and on a twin handle. The clamp is biased (it removes energy) and is a display
+   decision: kajo_hip_read_radiance and every other existing entry point stay as they are. The accumulation, the AOV buffers, the
+   pass count and the counters (kernelMs included) are not touched. Scratch (two float4 frames, one word per workgroup and pass,
+   the two counts) is allocated on first use and freed by kajo_hip_destroy.
+   Refusals (KAJO_E_INVALID, before any device work and before the handle is looked at): NULL params; a factor that is not finite,
+   negative or inside (0, 1); a rank outside 1..4; a floor that is negative or not finite; any flag bit; non-zero reserved words. */
+typedef struct KajoDespeckleParams {
+    float factor;       /* 0 (no clamp, repair only) or >= 1, finite (default 16) */
+    int32_t rank;       /* 1..4 (default 1): the neighbour a pixel is measured against, the rank-th brightest */
+    float floor;        /* >= 0, finite (default 0.2): the least luminance the bound is formed from, so that a dim pixel on black stays */
+    uint32_t flags;     /* 0: no flag defined yet; any bit is refused */
+    float reserved[4];  /* 0 */
+} KajoDespeckleParams;  /* 32 bytes */
+void kajo_hip_default_despeckle_params(KajoDespeckleParams* p); /* NULL is accepted */
+/* The frame after the stage: radiance = HOST pointer to width*height*4 floats (row 0 = top), sums over passes; counts[0] = pixels
+   clamped, counts[1] = pixels repaired; either may be NULL. Valid where kajo_hip_read_radiance is (tileCount 1, or a composed handle);
+   KAJO_E_STATE with no pass rendered. Waits. */
+int kajo_hip_despeckle(kajo_hip_t h, const KajoDespeckleParams* p, float* radiance, int64_t counts[2]);
+/* The display chain with the stage in front: despeckle -> denoise -> glare -> tone mapping, every stage but the last optional (NULL).
+   With despeckle == NULL exactly kajo_hip_display_argb8's calls. Otherwise the denoiser filters the despeckled frame as if it were
+   the accumulation (the stage writes it in the handle's tile layout; no kernel of the denoiser changes), and automatic exposure is
+   measured at the end of the chain, as before. Refusals in the order despeckle, glare, tone, denoise, handle. Waits. */
+int kajo_hip_present_argb8(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* g,
+                           const KajoToneParams* tone, uint32_t* argb8, float* scale);
+/* The multi-GPU twin, as kajo_hip_display_gathered_argb8_device is kajo_hip_display_argb8's: gathered tile buffers (NULL = the handle's
+   own when tileCount == 1) -> despeckle (NULL = none) -> glare (NULL = none) -> tone mapping, into DEVICE memory, asynchronous on the
+   handle's stream, no host synchronisation: the counts stay on the device. The stage needs no AOVs, so it serves any number of owners. */
+int kajo_hip_present_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle, const KajoGlareParams* g,
+                                           const KajoToneParams* tone, void* dst);
+/* The two counts of the handle's most recent despeckle; waits for it. KAJO_E_STATE before the first one. */
+int kajo_hip_despeckle_counts(kajo_hip_t h, int64_t counts[2]);
+
 /* Use an existing HIP stream (hipStream_t passed as void*) instead of the handle's own. */
 int kajo_hip_set_stream(kajo_hip_t h, void* stream);
 

@@ -49,6 +49,8 @@ EXPORTS = [
     "kajo_hip_launch_order", "kajo_hip_read_aov", "kajo_hip_aov_kernel", "kajo_hip_default_denoise_params", "kajo_hip_denoise",
     "kajo_hip_default_tone_params", "kajo_hip_tonemap_argb8", "kajo_hip_tonemap_gathered_argb8_device", "kajo_hip_tone_scale",
     "kajo_hip_default_glare_params", "kajo_hip_glare", "kajo_hip_display_argb8", "kajo_hip_display_gathered_argb8_device",
+    "kajo_hip_default_despeckle_params", "kajo_hip_despeckle", "kajo_hip_present_argb8", "kajo_hip_present_gathered_argb8_device",
+    "kajo_hip_despeckle_counts",
 ]
 
 
@@ -69,6 +71,10 @@ class KajoToneParams(C.Structure):
 
 class KajoGlareParams(C.Structure):
     _fields_ = [("levels", C.c_int32), ("flags", C.c_uint32), ("strength", C.c_float), ("threshold", C.c_float), ("reserved", C.c_float * 4)]
+
+
+class KajoDespeckleParams(C.Structure):
+    _fields_ = [("factor", C.c_float), ("rank", C.c_int32), ("floor", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_float * 4)]
 
 
 class KajoParams(C.Structure):
@@ -160,6 +166,15 @@ def lib():
                                                  C.c_void_p, C.POINTER(C.c_float)]
             L.kajo_hip_display_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoGlareParams), C.POINTER(KajoToneParams),
                                                                  C.c_void_p]
+        if hasattr(L, "kajo_hip_despeckle"):  # (nor the despeckle)
+            L.kajo_hip_default_despeckle_params.argtypes = [C.POINTER(KajoDespeckleParams)]
+            L.kajo_hip_default_despeckle_params.restype = None
+            L.kajo_hip_despeckle.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.c_void_p, C.POINTER(C.c_int64)]
+            L.kajo_hip_despeckle_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+            L.kajo_hip_present_argb8.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams), C.POINTER(KajoGlareParams),
+                                                 C.POINTER(KajoToneParams), C.c_void_p, C.POINTER(C.c_float)]
+            L.kajo_hip_present_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoGlareParams),
+                                                                 C.POINTER(KajoToneParams), C.c_void_p]
         L.kajo_hip_kat_trace.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
         L.kajo_hip_kat_shade.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.kajo_hip_kat_strictmath.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

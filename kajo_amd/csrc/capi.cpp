@@ -56,6 +56,9 @@ int kajo_denoise_launch(const void* tiles, const TileMap* map, const void* albed
 int kajo_glare_plan(int W, int H, int levels, size_t* pixels);
 int kajo_glare_launch(const void* src, const TileMap* map, int fromTiles, float passes, int n, float strength, float threshold, void* scratch,
                       void* out, void* stream);
+int kajo_despeckle_groups(int W, int H);
+int kajo_despeckle_launch(const void* src, const TileMap* map, int fromTiles, float passes, float factor, int rank, float floorL, void* clamped,
+                          void* out, int toTiles, void* partials, void* counts, void* stream);
 int kajo_tone_fast_launch(const void* src, const TileMap* map, int fromTiles, float passes, const ToneArgs* t, void* scratch, void* dst, void* stream);
 int kajo_tone_strict_launch(const void* src, const TileMap* map, int fromTiles, float passes, const ToneArgs* t, void* scratch, void* dst, void* stream);
 }
@@ -217,6 +220,10 @@ struct KajoHip
     // glare (glare.hip; kajo_hip_glare, kajo_hip_display_*), on its first call: the pyramid of kajo_glare_plan at the most levels, then
     // the output frame float4 [W * H]
     DeviceBuffer glare;
+    // despeckle (despeckle.hip; kajo_hip_despeckle, kajo_hip_present_*), on its first call: the two counts (int64 [2]), the workgroups'
+    // partial counts (despeckleImage), the clamped frame float4 [W * H] and the output frame float4 [max(W * H, slotsPerOwner)]
+    DeviceBuffer despeckle;
+    bool despeckled = false; // the counts are those of a despeckle (kajo_hip_despeckle_counts)
     int toneScaleState = 0; // the s of the most recent tone mapping: 0 none yet, 1 toneScale, 2 the scale word (auto exposure)
     float toneScale = 1.0f;
 };
@@ -1070,19 +1077,22 @@ int checkDenoise(kajo_hip_t h, const KajoDenoiseParams* p)
 }
 
 // The denoised frame (sums over passes, row-major) on the handle's stream, in the denoiser's scratch: *out points into it. Checked by
-// checkDenoise, device bound.
-int denoiseFrame(KajoHip* h, const KajoDenoiseParams* p, void** out)
+// checkDenoise, device bound. tiles: the frame to filter in the handle's tile layout -- null = the accumulation, or what despeckleImage
+// wrote in its place.
+int denoiseFrame(KajoHip* h, const KajoDenoiseParams* p, void** out, const void* tiles = nullptr)
 {
+    if (!tiles)
+        tiles = h->tiles.p;
     const size_t count = (size_t)h->W * h->H;
     HIP_TRY(h->denoise.ensure(count * (3 * 16 + 4)));
     char* scratch = h->denoise.as<char>();
     *out = scratch + count * 16;
     if (p->iterations == 0) {
         // the accumulation itself (one owner: tileCount is 1 with the AOV flag)
-        HIP_TRY((hipError_t)kajo_compose_launch(h->tiles.p, &h->map, *out, h->stream));
+        HIP_TRY((hipError_t)kajo_compose_launch(tiles, &h->map, *out, h->stream));
     } else {
         const long long samples = std::max(aovSamples(h), 1LL);
-        hipError_t le = (hipError_t)kajo_denoise_launch(h->tiles.p, &h->map, h->aov.p, h->aov.as<char>() + count * 16, (float)h->passesDone,
+        hipError_t le = (hipError_t)kajo_denoise_launch(tiles, &h->map, h->aov.p, h->aov.as<char>() + count * 16, (float)h->passesDone,
                                                         (float)samples, p->iterations, (p->flags & KAJO_DENOISE_NO_DEMODULATE) ? 0 : 1,
                                                         p->sigmaLuminance, p->sigmaNormal, p->sigmaDepth, scratch, out, h->stream);
         if (le != hipSuccess)
@@ -1171,6 +1181,46 @@ int glareImage(KajoHip* h, const KajoGlareParams* g, Image img, Image* out)
     if (le != hipSuccess)
         return failHip(le, "glare kernel launch");
     *out = Image{frame, false};
+    return KAJO_OK;
+}
+
+// The refusals of KajoDespeckleParams (KAJO_E_INVALID), before any device work and before the handle is looked at
+int checkDespeckle(const KajoDespeckleParams* p)
+{
+    if (!p)
+        return fail(KAJO_E_INVALID, "null despeckle parameters");
+    if (!std::isfinite(p->factor) || p->factor < 0.0f || (p->factor > 0.0f && p->factor < 1.0f))
+        return fail(KAJO_E_INVALID, "despeckle factor must be 0 or a finite number >= 1");
+    if (p->rank < 1 || p->rank > 4)
+        return fail(KAJO_E_INVALID, "despeckle rank must be in [1, 4]");
+    if (!std::isfinite(p->floor) || p->floor < 0.0f)
+        return fail(KAJO_E_INVALID, "despeckle floor must be finite and not negative");
+    if (p->flags)
+        return fail(KAJO_E_INVALID, "unknown despeckle flag");
+    for (float r : p->reserved)
+        if (r != 0.0f)
+            return fail(KAJO_E_INVALID, "despeckle reserved fields must be 0");
+    return KAJO_OK;
+}
+
+// Enqueue the despeckle of an image (tiles through h->map's geometry, or a row-major frame): *out = the frame in the despeckle scratch
+// that holds the result -- row-major, or with asTiles in the handle's own tile layout (one owner), where the denoiser takes it for the
+// accumulation. The counts stay in the scratch's first two words. Checked by checkDespeckle, device bound.
+int despeckleImage(KajoHip* h, const KajoDespeckleParams* p, Image img, bool asTiles, Image* out)
+{
+    const size_t count = (size_t)h->W * h->H;
+    const size_t partials = (2 * (size_t)kajo_despeckle_groups(h->W, h->H) * 4 + 15) / 16 * 16;
+    const size_t outSlots = std::max(count, h->map.tileCount == 1 ? (size_t)h->map.slotsPerOwner : (size_t)0);
+    HIP_TRY(h->despeckle.ensure(16 + partials + (count + outSlots) * 16));
+    char* base = h->despeckle.as<char>();
+    void* clamped = base + 16 + partials;
+    void* frame = base + 16 + partials + count * 16;
+    hipError_t le = (hipError_t)kajo_despeckle_launch(img.src, &h->map, img.fromTiles ? 1 : 0, (float)h->passesDone, p->factor, p->rank, p->floor,
+                                                      clamped, frame, asTiles ? 1 : 0, base + 16, base, h->stream);
+    if (le != hipSuccess)
+        return failHip(le, "despeckle kernel launch");
+    h->despeckled = true;
+    *out = Image{frame, asTiles};
     return KAJO_OK;
 }
 
@@ -1358,6 +1408,115 @@ int kajo_hip_display_gathered_argb8_device(kajo_hip_t h, const void* gathered, c
         return fail(KAJO_E_INVALID, "null argument");
     Image img;
     if ((rc = imageOf(h, true, gathered, &img)))
+        return rc;
+    if (g && (rc = glareImage(h, g, img, &img)))
+        return rc;
+    return toneLaunch(h, img, t, dst);
+}
+
+void kajo_hip_default_despeckle_params(KajoDespeckleParams* p)
+{
+    if (!p)
+        return;
+    std::memset(p, 0, sizeof *p);
+    p->factor = 16.0f; // (the quality sweep)
+    p->rank = 1;
+    p->floor = 0.2f;
+    p->flags = 0;
+}
+
+int kajo_hip_despeckle(kajo_hip_t h, const KajoDespeckleParams* p, float* radiance, int64_t counts[2])
+{
+    int rc = checkDespeckle(p);
+    if (rc)
+        return rc;
+    if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    Image img;
+    if ((rc = imageOf(h, false, nullptr, &img)))
+        return rc;
+    if ((rc = despeckleImage(h, p, img, false, &img)))
+        return rc;
+    if (radiance)
+        HIP_TRY(hipMemcpyAsync(radiance, img.src, (size_t)h->W * h->H * 16, hipMemcpyDeviceToHost, h->stream));
+    return counts ? kajo_hip_despeckle_counts(h, counts) : kajo_hip_wait(h);
+}
+
+int kajo_hip_despeckle_counts(kajo_hip_t h, int64_t counts[2])
+{
+    if (!h || !counts)
+        return fail(KAJO_E_INVALID, "null argument");
+    if (!h->despeckled)
+        return fail(KAJO_E_STATE, "nothing despeckled yet");
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    static_assert(sizeof(long long) == sizeof(int64_t), "despeckle.hip writes the counts as long long");
+    HIP_TRY(hipMemcpyAsync(counts, h->despeckle.p, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    return kajo_hip_wait(h);
+}
+
+int kajo_hip_present_argb8(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* g,
+                           const KajoToneParams* tone, uint32_t* argb8, float* scale)
+{
+    if (!despeckle)
+        return kajo_hip_display_argb8(h, denoise, g, tone, argb8, scale);
+    // (every refusal before any device work: the despeckle parameters, the glare's, the tone's, the denoiser's, then the handle)
+    int rc = checkDespeckle(despeckle);
+    if (rc)
+        return rc;
+    if (g && (rc = checkGlare(g)))
+        return rc;
+    ToneArgs t{};
+    if ((rc = toneArgsOf(tone, &t)))
+        return rc;
+    if (denoise) {
+        if ((rc = checkDenoise(h, denoise)))
+            return rc;
+    } else if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    Image img;
+    if ((rc = imageOf(h, false, nullptr, &img)))
+        return rc;
+    const size_t count = (size_t)h->W * h->H;
+    HIP_TRY(h->argb.ensure(count * 4));
+    // (with the denoiser behind it the stage writes the handle's tile layout: with the AOV flag the handle is the frame's one owner)
+    if ((rc = despeckleImage(h, despeckle, img, denoise != nullptr, &img)))
+        return rc;
+    if (denoise) {
+        void* out = nullptr;
+        if ((rc = denoiseFrame(h, denoise, &out, img.src)))
+            return rc;
+        img = Image{out, false};
+    }
+    if (g && (rc = glareImage(h, g, img, &img)))
+        return rc;
+    if ((rc = toneLaunch(h, img, t, h->argb.p)))
+        return rc;
+    if (argb8)
+        HIP_TRY(hipMemcpyAsync(argb8, h->argb.p, count * 4, hipMemcpyDeviceToHost, h->stream));
+    return scale ? kajo_hip_tone_scale(h, scale) : kajo_hip_wait(h);
+}
+
+int kajo_hip_present_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle, const KajoGlareParams* g,
+                                           const KajoToneParams* tone, void* dst)
+{
+    if (!despeckle)
+        return kajo_hip_display_gathered_argb8_device(h, gathered, g, tone, dst);
+    int rc = checkDespeckle(despeckle);
+    if (rc)
+        return rc;
+    if (g && (rc = checkGlare(g)))
+        return rc;
+    ToneArgs t{};
+    if ((rc = toneArgsOf(tone, &t)))
+        return rc;
+    if (!h || !dst)
+        return fail(KAJO_E_INVALID, "null argument");
+    Image img;
+    if ((rc = imageOf(h, true, gathered, &img)))
+        return rc;
+    if ((rc = despeckleImage(h, despeckle, img, false, &img)))
         return rc;
     if (g && (rc = glareImage(h, g, img, &img)))
         return rc;

@@ -197,7 +197,10 @@ struct Scheduler::Impl
     {
         if (opt.gpus == 1 && !opt.forceGather) {
             // single owner: the library resolves from its own tile buffer
-            if (glareOn())
+            if (opt.despeckleOn)
+                check(kajo_hip_present_argb8(handles[0], &opt.despeckle, nullptr, glareOn() ? &opt.glare : nullptr, &opt.tone, image->pixels.get(), &toneScale),
+                      "kajo_hip_present_argb8");
+            else if (glareOn())
                 check(kajo_hip_display_argb8(handles[0], nullptr, &opt.glare, &opt.tone, image->pixels.get(), &toneScale), "kajo_hip_display_argb8");
             else if (toneIsIdentity())
                 check(kajo_hip_resolve_argb8(handles[0], image->pixels.get()), "kajo_hip_resolve_argb8");
@@ -229,7 +232,10 @@ struct Scheduler::Impl
             }
         }
         composed = false;
-        if (glareOn())
+        if (opt.despeckleOn)
+            check(kajo_hip_present_gathered_argb8_device(handles[0], gathered, &opt.despeckle, glareOn() ? &opt.glare : nullptr, &opt.tone, argbDevice),
+                  "kajo_hip_present_gathered_argb8_device");
+        else if (glareOn())
             check(kajo_hip_display_gathered_argb8_device(handles[0], gathered, &opt.glare, &opt.tone, argbDevice), "kajo_hip_display_gathered_argb8_device");
         else if (toneIsIdentity())
             check(kajo_hip_resolve_gathered_argb8_device(handles[0], gathered, argbDevice), "kajo_hip_resolve_gathered_argb8_device");
@@ -239,7 +245,7 @@ struct Scheduler::Impl
         checkHip(hipMemcpyAsync(image->pixels.get(), argbDevice, (size_t)image->width * image->height * 4, hipMemcpyDeviceToHost, streams[0]),
                  "hipMemcpyAsync(image)");
         checkHip(hipStreamSynchronize(streams[0]), "hipStreamSynchronize");
-        if (glareOn() || !toneIsIdentity())
+        if (opt.despeckleOn || glareOn() || !toneIsIdentity())
             check(kajo_hip_tone_scale(handles[0], &toneScale), "kajo_hip_tone_scale"); // (the stream is drained: no wait left)
     }
     bool composed = false;
@@ -319,6 +325,30 @@ void Scheduler::readDisplayed(const KajoDenoiseParams* denoise, const KajoGlareP
     check(kajo_hip_display_argb8(d.handles[0], denoise, glare ? glare : &d.opt.glare, tone ? tone : &d.opt.tone, argb8, scale), "kajo_hip_display_argb8");
 }
 
+void Scheduler::readPresented(const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* glare,
+                              const KajoToneParams* tone, uint32_t* argb8, float* scale, long long counts[2])
+{
+    Impl& d = *m_impl;
+    if (!despeckle && d.opt.despeckleOn)
+        despeckle = &d.opt.despeckle;
+    if (counts)
+        counts[0] = counts[1] = 0;
+    if (!despeckle)
+        return readDisplayed(denoise, glare, tone, argb8, scale);
+    if (d.gathered && !d.composed) { // (as readDisplayed)
+        check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
+        d.composed = true;
+    }
+    check(kajo_hip_present_argb8(d.handles[0], despeckle, denoise, glare ? glare : &d.opt.glare, tone ? tone : &d.opt.tone, argb8, scale),
+          "kajo_hip_present_argb8");
+    if (counts) {
+        int64_t c[2] = {0, 0};
+        check(kajo_hip_despeckle_counts(d.handles[0], c), "kajo_hip_despeckle_counts");
+        counts[0] = c[0];
+        counts[1] = c[1];
+    }
+}
+
 void Scheduler::run()
 {
     Impl& d = *m_impl;
@@ -385,6 +415,12 @@ void Scheduler::run()
     d.stats.batchMs = batchMs;
     d.stats.batchPasses = batchPasses;
     d.stats.toneScale = d.toneScale;
+    if (o.despeckleOn && done > 0) {
+        int64_t c[2] = {0, 0};
+        check(kajo_hip_despeckle_counts(d.handles[0], c), "kajo_hip_despeckle_counts");
+        d.stats.clamped = c[0];
+        d.stats.repaired = c[1];
+    }
     d.stats.wallSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     for (kajo_hip_t h : d.handles) {
         KajoCounters c;

@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "Scheduler.h"
-#include "kajo_hip.h" // KajoToneParams (Options::tone), KajoGlareParams (Options::glare)
+#include "kajo_hip.h" // KajoToneParams (Options::tone), KajoGlareParams (Options::glare), KajoDespeckleParams (Options::despeckle)
 
 class Image;
 class Preview;
@@ -65,6 +65,13 @@ struct Options
     // Glare (bloom) in front of the tone mapping of the image run() writes (include/kajo_hip.h kajo_hip_display_argb8; with one owner or
     // after the gather). Off by default (strength 0): every frame then takes exactly the calls it takes without this field.
     KajoGlareParams glare = {6, 0u, 0.0f, 0.0f, {0.0f, 0.0f, 0.0f, 0.0f}};
+    // Despeckle (NaN / Inf repair, firefly clamp) in front of the glare and the tone mapping of the image run() writes (include/kajo_hip.h
+    // kajo_hip_present_argb8; with one owner or after the gather). Off by default: every frame then takes exactly the calls it takes
+    // without these fields. A flag of its own beside the parameters, because factor 0 is a setting of the stage (repair only) and
+    // cannot also mean off. The defaults are written in one place, the library: whoever sets despeckleOn fills `despeckle` with
+    // kajo_hip_default_despeckle_params first (all zero, as here, is refused for its rank, loudly).
+    bool despeckleOn = false;
+    KajoDespeckleParams despeckle = {};
 };
 
 struct Statistics
@@ -77,6 +84,7 @@ struct Statistics
     std::vector<double> batchMs; // wall time of every refresh: render launch .. Image::pixels filled (host), in run() order
     std::vector<int> batchPasses;
     float toneScale = 1;   // the scale s the last image was tone-mapped with (Options::tone; 1 with the identity)
+    long long clamped = 0, repaired = 0; // pixels of the last image the despeckle clamped and repaired (Options::despeckleOn)
 };
 
 class Scheduler : public ::Scheduler
@@ -105,6 +113,10 @@ public:
     // the whole display chain after run() (include/kajo_hip.h kajo_hip_display_argb8 on the first handle: one GPU, or a composed frame):
     // denoise (null = the accumulation; otherwise Options::aov) -> glare (null = Options::glare) -> tone (null = Options::tone)
     void readDisplayed(const KajoDenoiseParams* denoise, const KajoGlareParams* glare, const KajoToneParams* tone, uint32_t* argb8, float* scale);
+    // the same chain with the despeckle in front (include/kajo_hip.h kajo_hip_present_argb8): despeckle null = Options::despeckle where
+    // Options::despeckleOn, else none (then readDisplayed); counts (may be null) = pixels clamped, pixels repaired (0, 0 without the stage)
+    void readPresented(const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* glare, const KajoToneParams* tone,
+                       uint32_t* argb8, float* scale, long long counts[2]);
 
 private:
     struct Impl;

@@ -41,6 +41,9 @@ int main(int argc, char** argv)
     bool toneAuto = false, toneGiven = false;
     // glare options (include/kajo_hip.h KajoGlareParams): the raw text, checked after the loop
     std::string glareStrength, glareLevels, glareThreshold;
+    // despeckle options (include/kajo_hip.h KajoDespeckleParams): the raw text, checked after the loop
+    std::string despeckleFactor, despeckleRank, despeckleFloor;
+    bool despeckle = false;
     int width = 640, height = 480;
     int denoiseIterations = 5;
     hip::Options opt;
@@ -90,6 +93,11 @@ int main(int argc, char** argv)
                         "                    of every pixel's energy, 0..1, spread over its neighbourhood (0 = none, the default; --hdr stays without)\n"
                         "    --glare-levels N  --glare: levels of the pyramid, 0..12 (6): the halo's reach doubles with each\n"
                         "    --glare-threshold T  --glare: only luminance above T glares, >= 0 (0: every pixel in proportion)\n"
+                        "    --despeckle     repair NaN / Inf pixels and clamp fireflies in front of the denoiser, the glare and the tone curve (-o and\n"
+                        "                    --denoise; include/kajo_hip.h kajo_hip_despeckle; any --gpus; --hdr and --raw stay without)\n"
+                        "    --despeckle-factor F  --despeckle: a pixel is bounded to F times its RANK-th brightest neighbour, F >= 1 (16; 0 = repair only)\n"
+                        "    --despeckle-rank R  --despeckle: the neighbour measured against, 1..4 (1)\n"
+                        "    --despeckle-floor X  --despeckle: the least luminance the bound is formed from, >= 0 (0.2)\n"
                         "    --aov PREFIX    also write the first-hit AOVs a denoiser takes, averaged over the render's camera samples:\n"
                         "                    PREFIX_albedo.pfm, PREFIX_normal.pfm (3 channels), PREFIX_depth.pfm (1; mean over the hits)\n"
                         "                    (one GPU only)\n"
@@ -132,6 +140,10 @@ int main(int argc, char** argv)
         else if (a == "--glare" && more) glareStrength = args[++i];
         else if (a == "--glare-levels" && more) glareLevels = args[++i];
         else if (a == "--glare-threshold" && more) glareThreshold = args[++i];
+        else if (a == "--despeckle") despeckle = true;
+        else if (a == "--despeckle-factor" && more) despeckleFactor = args[++i];
+        else if (a == "--despeckle-rank" && more) despeckleRank = args[++i];
+        else if (a == "--despeckle-floor" && more) despeckleFloor = args[++i];
         else if (a == "--aov" && more) aovPrefix = args[++i];
         else if (a == "--aov-specular") aovSpecular = true;
         else if (a == "--denoise" && more) denoiseOut = args[++i];
@@ -200,6 +212,37 @@ int main(int argc, char** argv)
         }
     }
     const bool glareGiven = opt.glare.strength > 0.0f && opt.glare.levels > 0;
+    if (!despeckle && (!despeckleFactor.empty() || !despeckleRank.empty() || !despeckleFloor.empty())) {
+        std::cerr << "kajo_render: --despeckle-factor, --despeckle-rank and --despeckle-floor shape the stage that --despeckle turns on: give them with --despeckle" << std::endl;
+        return 1;
+    }
+    if (despeckle) {
+        // (before any device is opened: the refusals of kajo_hip_despeckle, with the option's name)
+        if (threeArg) {
+            std::cerr << "kajo_render: the despeckle options need the backend's options (without --three-arg)" << std::endl;
+            return 1;
+        }
+        opt.despeckleOn = true;
+        kajo_hip_default_despeckle_params(&opt.despeckle);
+        if (!despeckleFactor.empty() && (!parseFloat(despeckleFactor, &opt.despeckle.factor) || opt.despeckle.factor < 0.0f ||
+                                         (opt.despeckle.factor > 0.0f && opt.despeckle.factor < 1.0f))) {
+            std::cerr << "kajo_render: --despeckle-factor must be 0 or a finite number >= 1" << std::endl;
+            return 1;
+        }
+        if (!despeckleRank.empty()) {
+            char* end = nullptr;
+            const long n = std::strtol(despeckleRank.c_str(), &end, 10);
+            if (*end != '\0' || n < 1 || n > 4) {
+                std::cerr << "kajo_render: --despeckle-rank must be in 1..4" << std::endl;
+                return 1;
+            }
+            opt.despeckle.rank = (int32_t)n;
+        }
+        if (!despeckleFloor.empty() && (!parseFloat(despeckleFloor, &opt.despeckle.floor) || opt.despeckle.floor < 0.0f)) {
+            std::cerr << "kajo_render: --despeckle-floor must be a finite number >= 0" << std::endl;
+            return 1;
+        }
+    }
     if (aovSpecular && aovPrefix.empty() && denoiseOut.empty()) {
         std::cerr << "kajo_render: --aov-specular changes the AOVs that --aov writes and --denoise is guided by: give it with --aov or --denoise" << std::endl;
         return 1;
@@ -314,7 +357,9 @@ int main(int argc, char** argv)
             kajo_hip_default_denoise_params(&p);
             p.iterations = denoiseIterations;
             Image denoised(width, height);
-            if (glareGiven)
+            if (despeckle)
+                hipScheduler->readPresented(nullptr, &p, nullptr, nullptr, denoised.pixels.get(), nullptr, nullptr);
+            else if (glareGiven)
                 hipScheduler->readDisplayed(&p, nullptr, nullptr, denoised.pixels.get(), nullptr);
             else if (toneGiven)
                 hipScheduler->readDenoisedTonemapped(&p, nullptr, denoised.pixels.get(), nullptr);
@@ -351,6 +396,8 @@ int main(int argc, char** argv)
         std::printf("], \"preview_updates_on_owning_thread\": %s, \"preview_event_calls\": %d", onOwner ? "true" : "false", preview->eventCalls());
         if (toneGiven)
             std::printf(", \"tone_scale\": %.9g", (double)s.toneScale);
+        if (despeckle)
+            std::printf(", \"despeckle_clamped\": %lld, \"despeckle_repaired\": %lld", s.clamped, s.repaired);
         std::printf("}\n");
     }
     return 0;

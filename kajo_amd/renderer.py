@@ -199,6 +199,48 @@ class HipRenderer:
                                                   argb8.ctypes.data_as(C.c_void_p), C.byref(scale)))
         return argb8, scale.value
 
+    def _despeckle_params(self, factor: float = None, rank: int = None, floor: float = None):
+        p = capi.KajoDespeckleParams()
+        self._L.kajo_hip_default_despeckle_params(C.byref(p))
+        if factor is not None:
+            p.factor = float(factor)
+        if rank is not None:
+            p.rank = int(rank)
+        if floor is not None:
+            p.floor = float(floor)
+        return p
+
+    def despeckle(self, factor: float = None, rank: int = None, floor: float = None) -> dict:
+        """The frame with its NaN / Inf pixels repaired and its fireflies clamped (include/kajo_hip.h kajo_hip_despeckle): radiance =
+        (H, W, 4) float32 sums over passes, as radiance(); clamped, repaired = the numbers of pixels the two steps changed. Arguments left
+        None take kajo_hip_default_despeckle_params' values (factor 16, rank 1, floor 0.2); factor 0 repairs only. The accumulation, the
+        AOVs and the counters are not touched."""
+        p = self._despeckle_params(factor, rank, floor)
+        out = np.empty((self.height, self.width, 4), np.float32)
+        counts = (C.c_int64 * 2)()
+        capi.check(self._L.kajo_hip_despeckle(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p), counts))
+        return dict(radiance=out, clamped=int(counts[0]), repaired=int(counts[1]))
+
+    def despeckle_counts(self):
+        """(clamped, repaired) of the handle's most recent despeckle (include/kajo_hip.h kajo_hip_despeckle_counts)."""
+        counts = (C.c_int64 * 2)()
+        capi.check(self._L.kajo_hip_despeckle_counts(self._h, counts))
+        return int(counts[0]), int(counts[1])
+
+    def present(self, despeckle: dict = None, denoise: dict = None, glare: dict = None, **tone):
+        """The display chain with the despeckle in front (include/kajo_hip.h kajo_hip_present_argb8): despeckle -> denoise -> glare ->
+        tone mapping -> (argb8, scale) as tonemap(), every stage but the last optional. despeckle: a dict of despeckle()'s factor / rank /
+        floor; the rest as display(). With despeckle None it is display(denoise, glare, **tone)."""
+        t = self._tone_params(**tone)
+        s = None if despeckle is None else self._despeckle_params(**despeckle)
+        d = None if denoise is None else self._denoise_params(**denoise)
+        g = None if glare is None else self._glare_params(**glare)
+        argb8 = np.empty((self.height, self.width), np.uint32)
+        scale = C.c_float()
+        ref = lambda p: None if p is None else C.byref(p)
+        capi.check(self._L.kajo_hip_present_argb8(self._h, ref(s), ref(d), ref(g), C.byref(t), argb8.ctypes.data_as(C.c_void_p), C.byref(scale)))
+        return argb8, scale.value
+
     def tone_scale(self) -> float:
         """The scale s of the most recent tone mapping (include/kajo_hip.h kajo_hip_tone_scale)."""
         scale = C.c_float()
