@@ -111,6 +111,13 @@ extern "C" {
                                    same buffers and entry points; another kernel instance (kajo_hip_aov_kernel: ..._spec...). Handles
                                    without the flag launch what they launched before. */
 #define KAJO_AOV_MAX_FOLLOW 8     /* the chain's longest: delta surfaces followed per camera sample */
+#define KAJO_FLAG_AOV_MATTE 4096u /* with KAJO_FLAG_AOV only (alone: KAJO_E_INVALID at create, before a device is looked for): object-coverage
+                                   mattes beside the AOVs -- per pixel a table of KAJO_MATTE_SLOTS (object id, sample count) pairs over the
+                                   AOVs' own samples (kajo_hip_read_matte, kajo_hip_matte_mask). create() allocates and empties the tables
+                                   (W x H x 64 bytes); the handle launches another instance of the AOV kernel (kajo_hip_aov_kernel:
+                                   ..._matte...), still one per render launch and one scene walk per sample. Handles without the flag
+                                   launch what they launched before. */
+#define KAJO_MATTE_SLOTS 8        /* (id, count) pairs per pixel */
 
 typedef struct KajoParams {
     int32_t samplesPerPass; /* S: nominal samples per pixel per pass (reference: 32, Renderer.cpp:21);
@@ -160,7 +167,8 @@ int kajo_hip_destroy(kajo_hip_t h); /* NULL is accepted */
    (1-4, 5-8, ...): a group is summed from zero in pass order, then added to the total; a group in progress is added last. */
 int kajo_hip_render(kajo_hip_t h, int passes);
 int kajo_hip_wait(kajo_hip_t h);
-/* Zero the accumulation (and the AOV buffers and their sample count) and restart the pass numbering at 1. */
+/* Zero the accumulation (and the AOV buffers, their sample count and the coverage tables of KAJO_FLAG_AOV_MATTE) and restart the pass
+   numbering at 1. */
 int kajo_hip_reset(kajo_hip_t h);
 /* Continue a progressive session from pass `passesDone`: the next pass rendered is passesDone + 1 (the reference's loop
    `for (pass = 1;; pass++)`, Renderer.cpp:44, has no end). The call does not touch the accumulation buffer and DECLARES
@@ -168,7 +176,7 @@ int kajo_hip_reset(kajo_hip_t h);
    it, so the caller restores the buffer of the session being continued through kajo_hip_tile_buffer() first (or calls
    kajo_hip_reset() and set_pass_count(0)). FAST / EXACT: a passesDone inside a group of four continues from the buffer as
    one sum (the passes of the group so far are not known apart). Pass numbers run to 2^31 - 2. The AOV buffers of KAJO_FLAG_AOV are not
-   touched: later passes are traced with their own pass numbers' streams and added to them. */
+   touched: later passes are traced with their own pass numbers' streams and added to them; nor are the tables of KAJO_FLAG_AOV_MATTE. */
 int kajo_hip_set_pass_count(kajo_hip_t h, int passesDone);
 
 /* Whole-frame outputs; valid when tileCount == 1, or on a handle that has been composed.
@@ -241,6 +249,30 @@ int kajo_hip_read_aov(kajo_hip_t h, float* albedoHits, float* normalDepth, int64
 /* Name of the AOV kernel instance the handle launches (one per scene class, as the render kernels: the whole scene in LDS; the grid's cell
    lists in LDS or in global memory; with or without visibility lists), or NULL without KAJO_FLAG_AOV. For tests and profiles. */
 const char* kajo_hip_aov_kernel(kajo_hip_t h);
+
+/* Object-coverage mattes (KAJO_FLAG_AOV_MATTE with KAJO_FLAG_AOV): which object is in a pixel, and how much of the pixel it covers.
+     object id  the one kajo_hip_kat_trace reports: 0 for a miss, 1..nPlanes the planes, then the spheres
+     samples    the AOVs' samples and no others: every pass, every stratum, the same camera ray, in pass order and then stratum order
+                sy * n + sx. A sample's id is that of the h its albedo is taken from: the first hit, or with KAJO_FLAG_AOV_SPECULAR the
+                FINAL hit of the chain above (the object seen in the mirror or through the glass)
+     table      per pixel KAJO_MATTE_SLOTS slots (id, count), counts uint32; every slot is empty after create() and kajo_hip_reset()
+     per sample if a slot holds the sample's id (0 included), its count grows by 1; otherwise the first empty slot takes the id with
+                count 1; otherwise -- eight other ids came first -- the sample is dropped. So dropped(p) = samples - sum of counts(p)
+   The table is a function of (scene, parameters, passes rendered), not of how the passes were cut into render() calls or launches: it
+   lives in the buffer between launches, as A and B do. kajo_hip_set_pass_count leaves it alone. STRICT and EXACT handles take the ids
+   from STRICT's walk, FAST handles from FAST's; everything after the walk is integer arithmetic, the same in every build.
+   kajo_hip_read_matte: the tables RANKED -- per pixel the slots by count descending, ties by id ascending, empty slots last as
+   (id -1, count 0). ids, counts: HOST pointers to width*height*KAJO_MATTE_SLOTS words (row 0 = top, a pixel's slots consecutive);
+   *samples: kajo_hip_read_aov's. Any of the three may be NULL. Waits for outstanding work.
+   kajo_hip_matte_mask: mask(p) = float32(sum of the counts of p's slots whose id is among objects[0 .. n)) / float32(samples), one
+   division, 0 with no pass rendered; dominant(p) = the id kajo_hip_read_matte puts first, as float32 (-1 for an empty table). objects:
+   ids in 0 .. nPlanes + nSpheres, repeats allowed (an id counts once), n == 0 (objects may then be NULL) gives a mask of zeros; mask,
+   dominant: HOST pointers to width*height floats, either may be NULL. Waits.
+   Both: KAJO_E_INVALID on a NULL handle (kajo_hip_matte_mask also: n < 0, NULL objects with n > 0, an id out of range); KAJO_E_STATE on a
+   handle created without the flag. The tables are only read by kernels of their own (kajo_amd/csrc/matte.hip) into scratch allocated on
+   the first call; the accumulation, the AOV buffers, the pass count and the counters (kernelMs included) are not touched. */
+int kajo_hip_read_matte(kajo_hip_t h, int32_t* ids, uint32_t* counts, int64_t* samples);
+int kajo_hip_matte_mask(kajo_hip_t h, const int32_t* objects, int n, float* mask, float* dominant);
 
 /* Edge-aware A-trous denoiser (Dammertz et al. 2010) guided by the first-hit AOVs, its luminance weight scaled by a spatial variance
    estimate (the spatial part of SVGF, Schied et al. 2017). A post-process over the handle's whole frame, in kernels of its own

@@ -35,6 +35,8 @@ KAJO_FLAG_NO_ONE_LIGHT = 256  # every numerics build: the any-number-of-lights i
 KAJO_FLAG_EXACT = 512  # decision-exact numerics: STRICT's decisions, FAST's radiance arithmetic
 KAJO_FLAG_AOV = 1024  # first-hit albedo / normal / depth buffers over the beauty render's camera samples (kajo_hip_read_aov)
 KAJO_FLAG_AOV_SPECULAR = 2048  # with KAJO_FLAG_AOV: the buffers are taken at the first non-delta hit, through ideal mirrors and glass
+KAJO_FLAG_AOV_MATTE = 4096  # with KAJO_FLAG_AOV: per-pixel (object id, sample count) tables over the AOVs' samples (kajo_hip_read_matte)
+KAJO_MATTE_SLOTS = 8
 KAJO_DENOISE_NO_DEMODULATE = 1  # KajoDenoiseParams.flags: filter the mean radiance itself, not radiance / albedo
 KAJO_TONE_CLAMP, KAJO_TONE_REINHARD, KAJO_TONE_ACES = 0, 1, 2  # KajoToneParams.curve
 KAJO_TONE_AUTO_EXPOSURE = 1  # KajoToneParams.flags: scale the frame's log-average luminance to `key`
@@ -50,7 +52,7 @@ EXPORTS = [
     "kajo_hip_default_tone_params", "kajo_hip_tonemap_argb8", "kajo_hip_tonemap_gathered_argb8_device", "kajo_hip_tone_scale",
     "kajo_hip_default_glare_params", "kajo_hip_glare", "kajo_hip_display_argb8", "kajo_hip_display_gathered_argb8_device",
     "kajo_hip_default_despeckle_params", "kajo_hip_despeckle", "kajo_hip_present_argb8", "kajo_hip_present_gathered_argb8_device",
-    "kajo_hip_despeckle_counts",
+    "kajo_hip_despeckle_counts", "kajo_hip_read_matte", "kajo_hip_matte_mask",
 ]
 
 
@@ -175,6 +177,9 @@ def lib():
                                                  C.POINTER(KajoToneParams), C.c_void_p, C.POINTER(C.c_float)]
             L.kajo_hip_present_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoGlareParams),
                                                                  C.POINTER(KajoToneParams), C.c_void_p]
+        if hasattr(L, "kajo_hip_read_matte"):  # (nor the mattes)
+            L.kajo_hip_read_matte.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+            L.kajo_hip_matte_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.kajo_hip_kat_trace.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
         L.kajo_hip_kat_shade.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.kajo_hip_kat_strictmath.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

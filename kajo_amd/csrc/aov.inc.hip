@@ -15,6 +15,11 @@
 // (transmissionDirection / reflect on the integrator's own hit point and normal, origin moved kEps along the new direction), at most
 // KAJO_AOV_MAX_FOLLOW times. T, the product of the followed surfaces' clamped specular colours, scales the final albedo (or the
 // background); the depth is the length of the whole chain. The definition is in include/kajo_hip.h; no random number is drawn.
+//
+// MATTE (KAJO_FLAG_AOV_MATTE, the _matte instances): beside the two sums a lane keeps its pixel's coverage table -- eight slots (id, count)
+// in registers, read before the sample loop and written after it as A and B are -- and counts the id of the hit the sample is taken at
+// (the final hit of the chain with FOLLOW) by the first-come rule of include/kajo_hip.h. Integers only: the same table in every build that
+// walks to the same hits.
 #define KAJO_AOV_MAX_FOLLOW 8
 #define KAJO_AOV_CAT2(a, b) a##b
 #define KAJO_AOV_CAT(a, b) KAJO_AOV_CAT2(a, b)
@@ -99,9 +104,33 @@ KDEV Hit aovFollow(const DSceneView& sc, const LdsScene& lds, Hit h, F3& O, F3& 
     return h;
 }
 
+// One sample into a pixel's table: the slot that holds `id` counts it, else the first empty slot takes it with count 1, else it is
+// dropped. Slots are only ever taken in order, so the filled ones are a prefix and one pass over the eight decides: a compare / select
+// chain on named registers (an indexed array would live in scratch).
+KDEV void matteSlot(uint32_t& slotId, uint32_t& slotCount, uint32_t id, bool& done)
+{
+    const bool take = !done && (slotCount == 0u || slotId == id);
+    slotId = take ? id : slotId;
+    slotCount += take ? 1u : 0u;
+    done = done || take;
+}
+
+KDEV void matteAdd(uint4& i0, uint4& i1, uint4& c0, uint4& c1, uint32_t id)
+{
+    bool done = false;
+    matteSlot(i0.x, c0.x, id, done);
+    matteSlot(i0.y, c0.y, id, done);
+    matteSlot(i0.z, c0.z, id, done);
+    matteSlot(i0.w, c0.w, id, done);
+    matteSlot(i1.x, c1.x, id, done);
+    matteSlot(i1.y, c1.y, id, done);
+    matteSlot(i1.z, c1.z, id, done);
+    matteSlot(i1.w, c1.w, id, done);
+}
+
 // COLD_LDS, LISTS, GHOME: as renderBody's (the instance of the scene class; capi.cpp picks it at create). FOLLOW: the sample is taken at
-// the end of aovFollow's chain instead of at the first hit.
-template <bool COLD_LDS, bool LISTS = false, int GHOME = 0, bool FOLLOW = false>
+// the end of aovFollow's chain instead of at the first hit. MATTE: the pixel's coverage table is kept beside the sums.
+template <bool COLD_LDS, bool LISTS = false, int GHOME = 0, bool FOLLOW = false, bool MATTE = false>
 KDEV void aovBody(const AovArgs& args, unsigned char* ldsRaw)
 {
     const DSceneView& sc = args.scene;
@@ -120,6 +149,15 @@ KDEV void aovBody(const AovArgs& args, unsigned char* ldsRaw)
     if (inImage) {
         A = albedoHits[at];
         B = normalDepth[at];
+    }
+    uint4* const matteIds = static_cast<uint4*>(args.matteIds);
+    uint4* const matteCounts = static_cast<uint4*>(args.matteCounts);
+    uint4 i0 = make_uint4(0u, 0u, 0u, 0u), i1 = i0, c0 = i0, c1 = i0;
+    if (MATTE && inImage) {
+        i0 = matteIds[2 * at];
+        i1 = matteIds[2 * at + 1];
+        c0 = matteCounts[2 * at];
+        c1 = matteCounts[2 * at + 1];
     }
     const F3 bg = f3(sc.background[0], sc.background[1], sc.background[2]);
     const int n = args.n, endPass = args.firstPass + args.nPasses;
@@ -159,12 +197,20 @@ KDEV void aovBody(const AovArgs& args, unsigned char* ldsRaw)
                 B.y += N.y;
                 B.z += N.z;
                 B.w += depth;
+                if (MATTE)
+                    matteAdd(i0, i1, c0, c1, (uint32_t)h.id);
             }
         }
     }
     if (inImage) {
         albedoHits[at] = A;
         normalDepth[at] = B;
+    }
+    if (MATTE && inImage) {
+        matteIds[2 * at] = i0;
+        matteIds[2 * at + 1] = i1;
+        matteCounts[2 * at] = c0;
+        matteCounts[2 * at + 1] = c1;
     }
 }
 
@@ -216,6 +262,37 @@ KAJO_AOV_SPEC_KERNEL(_spec_big_lg, false, false, 1)
 KAJO_AOV_SPEC_KERNEL(_spec_biglist, false, true, 2)
 KAJO_AOV_SPEC_KERNEL(_spec_biglist_lg, false, true, 1)
 
+// The ten again with the coverage tables of KAJO_FLAG_AOV_MATTE (COLD_LDS, LISTS, GHOME, FOLLOW as above)
+#define KAJO_AOV_MATTE_KERNEL(suffix, ...)                                                                             \
+    extern "C" __global__ void __launch_bounds__(256) KAJO_AOV_CAT(KAJO_AOV_NAME, suffix)(const AovArgs args)           \
+    {                                                                                                                  \
+        extern __shared__ __attribute__((aligned(16))) unsigned char ldsRaw[];                                         \
+        aovBody<__VA_ARGS__, true>(args, ldsRaw);                                                                      \
+    }
+KAJO_AOV_MATTE_KERNEL(_matte, true, false, 0, false)
+KAJO_AOV_MATTE_KERNEL(_matte_big, false, false, 2, false)
+KAJO_AOV_MATTE_KERNEL(_matte_big_lg, false, false, 1, false)
+KAJO_AOV_MATTE_KERNEL(_matte_biglist, false, true, 2, false)
+KAJO_AOV_MATTE_KERNEL(_matte_biglist_lg, false, true, 1, false)
+KAJO_AOV_MATTE_KERNEL(_spec_matte, true, false, 0, true)
+KAJO_AOV_MATTE_KERNEL(_spec_matte_big, false, false, 2, true)
+KAJO_AOV_MATTE_KERNEL(_spec_matte_big_lg, false, false, 1, true)
+KAJO_AOV_MATTE_KERNEL(_spec_matte_biglist, false, true, 2, true)
+KAJO_AOV_MATTE_KERNEL(_spec_matte_biglist_lg, false, true, 1, true)
+
+// (instance, kernel suffix) of the matte instances, in KajoAovInstance's order
+#define KAJO_AOV_MATTE_INSTANCES(X)                                                                                    \
+    X(KAJO_AOV_MATTE_SMALL + KAJO_AOV_SMALL, _matte)                                                                   \
+    X(KAJO_AOV_MATTE_SMALL + KAJO_AOV_BIG, _matte_big)                                                                 \
+    X(KAJO_AOV_MATTE_SMALL + KAJO_AOV_BIG_LG, _matte_big_lg)                                                           \
+    X(KAJO_AOV_MATTE_SMALL + KAJO_AOV_BIGLIST, _matte_biglist)                                                         \
+    X(KAJO_AOV_MATTE_SMALL + KAJO_AOV_BIGLIST_LG, _matte_biglist_lg)                                                   \
+    X(KAJO_AOV_MATTE_SMALL + KAJO_AOV_SPEC_SMALL, _spec_matte)                                                         \
+    X(KAJO_AOV_MATTE_SMALL + KAJO_AOV_SPEC_BIG, _spec_matte_big)                                                       \
+    X(KAJO_AOV_MATTE_SMALL + KAJO_AOV_SPEC_BIG_LG, _spec_matte_big_lg)                                                 \
+    X(KAJO_AOV_MATTE_SMALL + KAJO_AOV_SPEC_BIGLIST, _spec_matte_biglist)                                               \
+    X(KAJO_AOV_MATTE_SMALL + KAJO_AOV_SPEC_BIGLIST_LG, _spec_matte_biglist_lg)
+
 namespace
 {
 const void* aovKernel(int instance)
@@ -230,6 +307,9 @@ const void* aovKernel(int instance)
     case KAJO_AOV_SPEC_BIG_LG: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec_big_lg));
     case KAJO_AOV_SPEC_BIGLIST: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec_biglist));
     case KAJO_AOV_SPEC_BIGLIST_LG: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec_biglist_lg));
+#define KAJO_AOV_MATTE_CASE(instance, suffix) case instance: return reinterpret_cast<const void*>(KAJO_AOV_CAT(KAJO_AOV_NAME, suffix));
+    KAJO_AOV_MATTE_INSTANCES(KAJO_AOV_MATTE_CASE)
+#undef KAJO_AOV_MATTE_CASE
     default: return reinterpret_cast<const void*>(KAJO_AOV_NAME);
     }
 }
@@ -249,6 +329,9 @@ extern "C" int KAJO_AOV_CAT(KAJO_AOV_NAME, _launch)(const AovArgs* args, int ins
     case KAJO_AOV_SPEC_BIG_LG: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec_big_lg), dim3(grid), dim3(256), ldsBytes, st, *args); break;
     case KAJO_AOV_SPEC_BIGLIST: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec_biglist), dim3(grid), dim3(256), ldsBytes, st, *args); break;
     case KAJO_AOV_SPEC_BIGLIST_LG: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, _spec_biglist_lg), dim3(grid), dim3(256), ldsBytes, st, *args); break;
+#define KAJO_AOV_MATTE_CASE(instance, suffix) case instance: hipLaunchKernelGGL(KAJO_AOV_CAT(KAJO_AOV_NAME, suffix), dim3(grid), dim3(256), ldsBytes, st, *args); break;
+    KAJO_AOV_MATTE_INSTANCES(KAJO_AOV_MATTE_CASE)
+#undef KAJO_AOV_MATTE_CASE
     default: hipLaunchKernelGGL(KAJO_AOV_NAME, dim3(grid), dim3(256), ldsBytes, st, *args); break;
     }
     return (int)hipGetLastError();

@@ -59,6 +59,9 @@ int kajo_glare_launch(const void* src, const TileMap* map, int fromTiles, float 
 int kajo_despeckle_groups(int W, int H);
 int kajo_despeckle_launch(const void* src, const TileMap* map, int fromTiles, float passes, float factor, int rank, float floorL, void* clamped,
                           void* out, int toTiles, void* partials, void* counts, void* stream);
+int kajo_matte_rank_launch(const void* ids, const void* counts, int W, int H, void* rankedIds, void* rankedCounts, void* stream);
+int kajo_matte_mask_launch(const void* ids, const void* counts, int W, int H, const void* selected, unsigned nObjects, float samples, void* mask,
+                           void* dominant, void* stream);
 int kajo_tone_fast_launch(const void* src, const TileMap* map, int fromTiles, float passes, const ToneArgs* t, void* scratch, void* dst, void* stream);
 int kajo_tone_strict_launch(const void* src, const TileMap* map, int fromTiles, float passes, const ToneArgs* t, void* scratch, void* dst, void* stream);
 }
@@ -79,26 +82,35 @@ struct KernelSet
     int (*aovSetLds)(int instance, size_t lds);
     int (*katTrace)(const KatTraceArgs*, unsigned grid, size_t lds, void* stream);
     int (*katShade)(const RenderArgs*, unsigned grid, size_t lds, void* stream);
-    const char* aovNames[KAJO_AOV_INSTANCES]; // kajo_hip_aov_kernel
+    const char* aovNames[KAJO_AOV_INSTANCES]; // kajo_hip_aov_kernel: the five scene classes, with _spec, with _matte, with both
 };
 
 static const KernelSet kFastKernels = {kajo_render_fast_launch, kajo_render_fast_split_launch, kajo_render_fast_set_lds, kajo_resolve_fast_launch,
                                        kajo_resolve_tiles_fast_launch, kajo_tone_fast_launch, kajo_aov_fast_launch, kajo_aov_fast_set_lds,
                                        kajo_kat_trace_fast_launch, kajo_kat_shade_fast_launch,
                                        {"kajo_aov_fast", "kajo_aov_fast_big", "kajo_aov_fast_big_lg", "kajo_aov_fast_biglist", "kajo_aov_fast_biglist_lg",
-                                       "kajo_aov_fast_spec", "kajo_aov_fast_spec_big", "kajo_aov_fast_spec_big_lg", "kajo_aov_fast_spec_biglist", "kajo_aov_fast_spec_biglist_lg"}};
+                                       "kajo_aov_fast_spec", "kajo_aov_fast_spec_big", "kajo_aov_fast_spec_big_lg", "kajo_aov_fast_spec_biglist", "kajo_aov_fast_spec_biglist_lg",
+                                       "kajo_aov_fast_matte", "kajo_aov_fast_matte_big", "kajo_aov_fast_matte_big_lg", "kajo_aov_fast_matte_biglist", "kajo_aov_fast_matte_biglist_lg",
+                                       "kajo_aov_fast_spec_matte", "kajo_aov_fast_spec_matte_big", "kajo_aov_fast_spec_matte_big_lg", "kajo_aov_fast_spec_matte_biglist",
+                                       "kajo_aov_fast_spec_matte_biglist_lg"}};
 static const KernelSet kStrictKernels = {kajo_render_strict_launch, kajo_render_strict_split_launch, kajo_render_strict_set_lds, kajo_resolve_strict_launch,
                                          kajo_resolve_tiles_strict_launch, kajo_tone_strict_launch, kajo_aov_strict_launch, kajo_aov_strict_set_lds,
                                          kajo_kat_trace_strict_launch, kajo_kat_shade_strict_launch,
                                          {"kajo_aov_strict", "kajo_aov_strict_big", "kajo_aov_strict_big_lg", "kajo_aov_strict_biglist", "kajo_aov_strict_biglist_lg",
-                                         "kajo_aov_strict_spec", "kajo_aov_strict_spec_big", "kajo_aov_strict_spec_big_lg", "kajo_aov_strict_spec_biglist", "kajo_aov_strict_spec_biglist_lg"}};
+                                         "kajo_aov_strict_spec", "kajo_aov_strict_spec_big", "kajo_aov_strict_spec_big_lg", "kajo_aov_strict_spec_biglist", "kajo_aov_strict_spec_biglist_lg",
+                                         "kajo_aov_strict_matte", "kajo_aov_strict_matte_big", "kajo_aov_strict_matte_big_lg", "kajo_aov_strict_matte_biglist", "kajo_aov_strict_matte_biglist_lg",
+                                         "kajo_aov_strict_spec_matte", "kajo_aov_strict_spec_matte_big", "kajo_aov_strict_spec_matte_big_lg", "kajo_aov_strict_spec_matte_biglist",
+                                         "kajo_aov_strict_spec_matte_biglist_lg"}};
 // The oracle's arithmetic in everything that decides (STRICT and EXACT): which walk, which hold policy, whose resolve. EXACT has render
 // and shading kernels of its own; the STRICT instances serve it for the rest (EXACT's camera rays, walk and normals are STRICT's arithmetic).
 static const KernelSet kExactKernels = {kajo_render_exact_launch, kajo_render_exact_split_launch, kajo_render_exact_set_lds, kajo_resolve_strict_launch,
                                         kajo_resolve_tiles_strict_launch, kajo_tone_strict_launch, kajo_aov_strict_launch, kajo_aov_strict_set_lds,
                                         kajo_kat_trace_strict_launch, kajo_kat_shade_exact_launch,
                                         {"kajo_aov_strict", "kajo_aov_strict_big", "kajo_aov_strict_big_lg", "kajo_aov_strict_biglist", "kajo_aov_strict_biglist_lg",
-                                         "kajo_aov_strict_spec", "kajo_aov_strict_spec_big", "kajo_aov_strict_spec_big_lg", "kajo_aov_strict_spec_biglist", "kajo_aov_strict_spec_biglist_lg"}};
+                                         "kajo_aov_strict_spec", "kajo_aov_strict_spec_big", "kajo_aov_strict_spec_big_lg", "kajo_aov_strict_spec_biglist", "kajo_aov_strict_spec_biglist_lg",
+                                         "kajo_aov_strict_matte", "kajo_aov_strict_matte_big", "kajo_aov_strict_matte_big_lg", "kajo_aov_strict_matte_biglist", "kajo_aov_strict_matte_biglist_lg",
+                                         "kajo_aov_strict_spec_matte", "kajo_aov_strict_spec_matte_big", "kajo_aov_strict_spec_matte_big_lg", "kajo_aov_strict_spec_matte_biglist",
+                                         "kajo_aov_strict_spec_matte_biglist_lg"}};
 
 namespace
 {
@@ -213,6 +225,12 @@ struct KajoHip
     int aovInstance = KAJO_AOV_SMALL; // render_args.h KajoAovInstance: the scene class, as the render kernel is chosen
     size_t aovLds = 0;                // the instance's scene copy
     long long aovPasses = 0;
+    // object-coverage mattes (KAJO_FLAG_AOV_MATTE; aov.inc.hip MATTE): uint4 [W * H][2] ids, then uint4 [W * H][2] counts, row-major; a slot with
+    // count 0 is empty. Filled over the AOVs' samples (aovPasses counts them too)
+    DeviceBuffer matte;
+    // the matte readers' scratch (matte.hip; kajo_hip_read_matte, kajo_hip_matte_mask), on the first call: the ranked tables int32 [W * H][8]
+    // + uint32 [W * H][8], the mask and the dominant id float [2][W * H], the bitset of selected ids
+    DeviceBuffer matteScratch;
     // the denoiser's scratch (denoise.hip; kajo_hip_denoise), on its first call: float4 [3][W * H] (guide, two colour frames) + uint32 [W * H]
     DeviceBuffer denoise;
     // tone mapping (tonemap.inc.hip; kajo_hip_tonemap_*), on its first call: the scale word + the logavg partials (toneLaunch)
@@ -371,6 +389,25 @@ long long aovSamples(const KajoHip* h)
     return n * n * h->aovPasses;
 }
 
+// the coverage tables of a handle: ids and counts, a word each per slot
+size_t matteTableBytes(const KajoHip* h)
+{
+    return (size_t)h->W * h->H * KAJO_MATTE_SLOTS * 8;
+}
+
+// words of the bitset of selected object ids kajo_hip_matte_mask uploads: one bit per id 0 .. nPlanes + nSpheres
+size_t matteBitsetWords(const KajoHip* h)
+{
+    return ((size_t)h->staged.nPlanes + h->staged.nSpheres + 1 + 31) / 32;
+}
+
+// the matte readers' scratch: the ranked tables (ids, counts), the mask, the dominant id, the bitset
+size_t matteScratchBytes(const KajoHip* h)
+{
+    const size_t count = (size_t)h->W * h->H;
+    return matteTableBytes(h) + 2 * count * sizeof(float) + matteBitsetWords(h) * sizeof(uint32_t);
+}
+
 // An image to resolve or tone-map: a tile buffer through h->map's geometry, or the row-major frame
 struct Image
 {
@@ -425,7 +462,7 @@ const char* kajo_hip_last_error(void)
 
 const char* kajo_hip_version(void)
 {
-    return "kajo-hip 0.1 (gfx950)";
+    return "kajo-hip 0.1 (gfx950; aov-matte)";
 }
 
 void kajo_hip_default_params(KajoParams* p)
@@ -570,6 +607,8 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
         return fail(KAJO_E_INVALID, "first-hit AOVs need the whole frame on one handle (tileCount 1)");
     if ((p.flags & KAJO_FLAG_AOV_SPECULAR) && !(p.flags & KAJO_FLAG_AOV))
         return fail(KAJO_E_INVALID, "the first-non-delta-hit flag changes what the AOV flag's buffers hold: set the AOV flag with it");
+    if ((p.flags & KAJO_FLAG_AOV_MATTE) && !(p.flags & KAJO_FLAG_AOV))
+        return fail(KAJO_E_INVALID, "the matte flag keeps its coverage tables over the AOV flag's samples: set the AOV flag with it");
 
     if (p.flags & (KAJO_FLAG_STRICT | KAJO_FLAG_EXACT)) {
         // integrator.inc.hip kdiv / ksqrt: the IEEE quotient and root without the compiler's range scaling are exact while operands stay
@@ -715,12 +754,19 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
             h->aovInstance = v.grid.inLds ? KAJO_AOV_BIG_LG : KAJO_AOV_BIG;
         if (p.flags & KAJO_FLAG_AOV_SPECULAR) // the same scene class, with the chain to the first non-delta hit
             h->aovInstance += KAJO_AOV_SPEC_SMALL;
+        if (p.flags & KAJO_FLAG_AOV_MATTE) // ... with the coverage tables beside the sums
+            h->aovInstance += KAJO_AOV_MATTE_SMALL;
         h->aovLds = h->lds.coldInLds ? h->lds.ldsBytes : h->lds.hotBytes;
         if (h->aovLds > 48 * 1024)
             CREATE_TRY((hipError_t)h->k->aovSetLds(h->aovInstance, h->aovLds));
         const size_t bytes = 2 * (size_t)width * height * 16;
         CREATE_TRY(h->aov.alloc(bytes));
         CREATE_TRY(hipMemsetAsync(h->aov.p, 0, bytes, h->stream));
+        if (p.flags & KAJO_FLAG_AOV_MATTE) {
+            const size_t tables = matteTableBytes(h);
+            CREATE_TRY(h->matte.alloc(tables));
+            CREATE_TRY(hipMemsetAsync(h->matte.p, 0, tables, h->stream));
+        }
     }
     CREATE_TRY(hipStreamSynchronize(h->stream));
 #undef CREATE_TRY
@@ -879,6 +925,10 @@ int kajo_hip_render(kajo_hip_t h, int passes)
             g.firstPass = a.firstPass;
             g.nPasses = now;
             g.seed = a.seed;
+            if (h->matte) {
+                g.matteIds = h->matte.p;
+                g.matteCounts = h->matte.as<char>() + (size_t)h->W * h->H * KAJO_MATTE_SLOTS * 4;
+            }
             const unsigned long long blocks = (unsigned long long)((h->W + 7) / 8) * ((h->H + 7) / 8);
             HIP_TRY((hipError_t)h->k->aov(&g, h->aovInstance, (unsigned)((blocks + 3) / 4), h->aovLds, h->stream));
             h->aovPasses += now;
@@ -921,6 +971,8 @@ int kajo_hip_reset(kajo_hip_t h)
         HIP_TRY(hipMemsetAsync(h->counters.p, 0, 32 * sizeof(unsigned long long), h->stream));
     if (h->aov)
         HIP_TRY(hipMemsetAsync(h->aov.p, 0, 2 * (size_t)h->W * h->H * 16, h->stream));
+    if (h->matte)
+        HIP_TRY(hipMemsetAsync(h->matte.p, 0, matteTableBytes(h), h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->aovPasses = 0;
     h->passesDone = 0;
@@ -1038,6 +1090,74 @@ const char* kajo_hip_aov_kernel(kajo_hip_t h)
     if (!h || !h->aov)
         return nullptr;
     return h->k->aovNames[h->aovInstance];
+}
+
+int kajo_hip_read_matte(kajo_hip_t h, int32_t* ids, uint32_t* counts, int64_t* samples)
+{
+    if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    if (!h->matte)
+        return fail(KAJO_E_STATE, "the handle was created without the matte flag: no coverage tables to read");
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    const size_t count = (size_t)h->W * h->H, words = count * KAJO_MATTE_SLOTS * 4;
+    if (ids || counts) {
+        HIP_TRY(h->matteScratch.ensure(matteScratchBytes(h)));
+        char* ranked = h->matteScratch.as<char>();
+        hipError_t le = (hipError_t)kajo_matte_rank_launch(h->matte.p, h->matte.as<char>() + words, h->W, h->H, ranked, ranked + words, h->stream);
+        if (le != hipSuccess)
+            return failHip(le, "matte rank kernel launch");
+        if (ids)
+            HIP_TRY(hipMemcpyAsync(ids, ranked, words, hipMemcpyDeviceToHost, h->stream));
+        if (counts)
+            HIP_TRY(hipMemcpyAsync(counts, ranked + words, words, hipMemcpyDeviceToHost, h->stream));
+    }
+    if ((rc = kajo_hip_wait(h)))
+        return rc;
+    if (samples)
+        *samples = (int64_t)aovSamples(h);
+    return KAJO_OK;
+}
+
+int kajo_hip_matte_mask(kajo_hip_t h, const int32_t* objects, int n, float* mask, float* dominant)
+{
+    if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    if (n < 0 || (n > 0 && !objects))
+        return fail(KAJO_E_INVALID, "invalid object list");
+    if (!h->matte)
+        return fail(KAJO_E_STATE, "the handle was created without the matte flag: no coverage tables to read");
+    const int nObjects = h->staged.nPlanes + h->staged.nSpheres;
+    std::vector<uint32_t> selected(matteBitsetWords(h), 0u);
+    for (int i = 0; i < n; i++) {
+        if (objects[i] < 0 || objects[i] > nObjects)
+            return fail(KAJO_E_INVALID, "object id out of range: 0 (the background) .. the number of planes and spheres");
+        selected[(size_t)objects[i] >> 5] |= 1u << (objects[i] & 31);
+    }
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (mask || dominant) {
+        const size_t count = (size_t)h->W * h->H, words = count * KAJO_MATTE_SLOTS * 4;
+        HIP_TRY(h->matteScratch.ensure(matteScratchBytes(h)));
+        char* scratch = h->matteScratch.as<char>();
+        float* maskDevice = reinterpret_cast<float*>(scratch + 2 * words);
+        float* dominantDevice = maskDevice + count;
+        void* bits = dominantDevice + count;
+        // (pageable host memory: the copy has left `selected` when the call returns)
+        HIP_TRY(hipMemcpyAsync(bits, selected.data(), selected.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        hipError_t le = (hipError_t)kajo_matte_mask_launch(h->matte.p, h->matte.as<char>() + words, h->W, h->H, bits, (unsigned)nObjects,
+                                                           (float)aovSamples(h), mask ? maskDevice : nullptr, dominant ? dominantDevice : nullptr,
+                                                           h->stream);
+        if (le != hipSuccess)
+            return failHip(le, "matte mask kernel launch");
+        if (mask)
+            HIP_TRY(hipMemcpyAsync(mask, maskDevice, count * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        if (dominant)
+            HIP_TRY(hipMemcpyAsync(dominant, dominantDevice, count * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    }
+    return kajo_hip_wait(h);
 }
 
 void kajo_hip_default_denoise_params(KajoDenoiseParams* p)

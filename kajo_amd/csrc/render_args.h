@@ -83,6 +83,10 @@ struct AovArgs
     float pixelWidth, pixelHeight, sampleWidth, sampleHeight; // Renderer.cpp:39-42, as RenderArgs
     int32_t firstPass, nPasses;
     uint64_t seed;
+    // object-coverage mattes (KAJO_FLAG_AOV_MATTE; the _matte instances only, null otherwise): per pixel KAJO_MATTE_SLOTS slots (id, count),
+    // a slot with count 0 is empty; the filled slots are a prefix
+    void* matteIds;      // uint4 [W * H][2]
+    void* matteCounts;   // uint4 [W * H][2]
 };
 
 // AOV kernel instances (aov.inc.hip), one per scene class the render kernels tell apart (capi.cpp picks one at create)
@@ -99,7 +103,9 @@ enum KajoAovInstance
     KAJO_AOV_SPEC_BIG_LG = 7,
     KAJO_AOV_SPEC_BIGLIST = 8,
     KAJO_AOV_SPEC_BIGLIST_LG = 9,
-    KAJO_AOV_INSTANCES = 10
+    // the same ten with the per-pixel coverage tables of KAJO_FLAG_AOV_MATTE: instance + KAJO_AOV_MATTE_SMALL
+    KAJO_AOV_MATTE_SMALL = 10,
+    KAJO_AOV_INSTANCES = 20
 };
 
 // tile-buffer slot of pixel (x, y): tiles are dealt round-robin to `tileCount` owners; inside a

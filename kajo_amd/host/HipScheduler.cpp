@@ -160,7 +160,7 @@ struct Scheduler::Impl
             p.depthLimit = opt.depthLimit;
             p.seed = opt.seed;
             p.flags = (numerics == Options::Strict ? KAJO_FLAG_STRICT : numerics == Options::Exact ? KAJO_FLAG_EXACT : 0u) | (opt.counters ? KAJO_FLAG_COUNTERS : 0u) |
-                      (opt.aov ? KAJO_FLAG_AOV | (opt.aovSpecular ? KAJO_FLAG_AOV_SPECULAR : 0u) : 0u);
+                      (opt.aov ? KAJO_FLAG_AOV | (opt.aovSpecular ? KAJO_FLAG_AOV_SPECULAR : 0u) | (opt.matte ? KAJO_FLAG_AOV_MATTE : 0u) : 0u);
             p.device = opt.sameDevice ? 0 : g;
             p.tileIndex = g;
             p.tileCount = opt.gpus;
@@ -297,6 +297,21 @@ void Scheduler::readAov(float* albedoHits, float* normalDepth, long long* sample
     check(kajo_hip_read_aov(d.handles[0], albedoHits, normalDepth, &n), "kajo_hip_read_aov");
     if (samples)
         *samples = (long long)n;
+}
+
+void Scheduler::readMatte(int32_t* ids, uint32_t* counts, long long* samples)
+{
+    Impl& d = *m_impl;
+    int64_t n = 0;
+    check(kajo_hip_read_matte(d.handles[0], ids, counts, &n), "kajo_hip_read_matte");
+    if (samples)
+        *samples = (long long)n;
+}
+
+void Scheduler::readMatteMask(const int32_t* objects, int n, float* mask, float* dominant)
+{
+    Impl& d = *m_impl;
+    check(kajo_hip_matte_mask(d.handles[0], objects, n, mask, dominant), "kajo_hip_matte_mask");
 }
 
 void Scheduler::readDenoised(const KajoDenoiseParams* params, float* radiance, uint32_t* argb8)

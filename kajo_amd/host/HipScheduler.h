@@ -59,6 +59,8 @@ struct Options
                                   // rank sends its tile buffer to itself): the multi-GPU call sequence on a one-GPU box
     bool aov = false;             // also accumulate the first-hit albedo / normal / depth (KAJO_FLAG_AOV; readAov): one GPU only
     bool aovSpecular = false;     // ... at the first non-delta hit, through ideal mirrors and glass (KAJO_FLAG_AOV_SPECULAR); read only with aov
+    bool matte = false;           // ... with the per-pixel object-coverage tables beside them (KAJO_FLAG_AOV_MATTE; readMatte, readMatteMask); read
+                                  // only with aov. Off by default: every frame then takes exactly the calls it took without this field
     // Exposure, tone curve and automatic exposure of the image run() writes (include/kajo_hip.h kajo_hip_tonemap_argb8; with one owner
     // or after the gather). The default is the identity: every frame then takes the plain resolve, exactly as without this field.
     KajoToneParams tone = {KAJO_TONE_CLAMP, 0u, 0.0f, 0.0f, 0.18f, {0.0f, 0.0f, 0.0f}};
@@ -104,6 +106,11 @@ public:
     void readRadiance(float* dst);
     // first-hit AOV sums after run() (Options::aov; include/kajo_hip.h kajo_hip_read_aov): W*H*4 floats each, either may be null
     void readAov(float* albedoHits, float* normalDepth, long long* samples);
+    // the object-coverage tables after run() (Options::aov and Options::matte; include/kajo_hip.h kajo_hip_read_matte): W*H*8 ranked ids and
+    // counts, any of the three may be null
+    void readMatte(int32_t* ids, uint32_t* counts, long long* samples);
+    // the coverage of the objects[0 .. n) and the dominant id per pixel (include/kajo_hip.h kajo_hip_matte_mask): W*H floats each, either may be null
+    void readMatteMask(const int32_t* objects, int n, float* mask, float* dominant);
     // the frame denoised with the AOVs as guides after run() (Options::aov; include/kajo_hip.h kajo_hip_denoise): W*H*4 float sums and
     // W*H ARGB8 words, either may be null; params null = kajo_hip_default_denoise_params
     void readDenoised(const KajoDenoiseParams* params, float* radiance, uint32_t* argb8);

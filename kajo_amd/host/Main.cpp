@@ -30,12 +30,35 @@ bool parseFloat(const std::string& text, float* out)
     return true;
 }
 
+// a comma-separated list of object ids (whole numbers >= 0, at least one), or false
+bool parseObjects(const std::string& text, std::vector<int32_t>* out)
+{
+    out->clear();
+    size_t at = 0;
+    while (true) {
+        const size_t comma = text.find(',', at);
+        const std::string item = text.substr(at, comma == std::string::npos ? std::string::npos : comma - at);
+        char* end = nullptr;
+        const long v = std::strtol(item.c_str(), &end, 10);
+        if (item.empty() || item.size() > 9 || *end != '\0' || item[0] < '0' || item[0] > '9')
+            return false;
+        out->push_back((int32_t)v);
+        if (comma == std::string::npos)
+            return true;
+        at = comma + 1;
+    }
+}
+
 } // namespace
 
 int main(int argc, char** argv)
 {
     std::vector<std::string> args(argv, argv + argc);
     std::string rendererName = "hip", out = "out.png", rawOut, aovPrefix, denoiseOut, hdrOut, scenePath;
+    // matte options (include/kajo_hip.h kajo_hip_matte_mask): the list's raw text, checked after the loop
+    std::string matteMaskOut, matteIdsOut, matteObjectsText;
+    bool matteObjectsGiven = false;
+    std::vector<int32_t> matteObjects;
     // tone options (include/kajo_hip.h KajoToneParams): the raw text, checked after the loop; toneGiven = any of them was given
     std::string toneCurve, toneExposure, toneWhite, toneKey;
     bool toneAuto = false, toneGiven = false;
@@ -103,10 +126,16 @@ int main(int argc, char** argv)
                         "                    (one GPU only)\n"
                         "    --aov-specular  with --aov or --denoise: take the AOVs at the first non-delta hit, through ideal mirrors and glass\n"
                         "                    (include/kajo_hip.h KAJO_FLAG_AOV_SPECULAR), so that the guides show what a mirror shows\n"
+                        "    --matte-mask FILE  also write the coverage of the objects of --matte-objects as a 1-channel PFM: per pixel the share of\n"
+                        "                    the camera samples that saw one of them (include/kajo_hip.h kajo_hip_matte_mask; collects the AOVs and\n"
+                        "                    honours --aov-specular: the object seen in the mirror; one GPU only)\n"
+                        "    --matte-objects LIST  --matte-mask: object ids, comma-separated (0 the background, 1.. the planes, then the spheres)\n"
+                        "    --matte-ids FILE  also write the id of the object that covers most of each pixel as a 1-channel PFM (likewise)\n"
                         "    --denoise FILE  also write the frame denoised with those AOVs as guides, as a PNG (edge-aware A-trous filter,\n"
                         "                    include/kajo_hip.h kajo_hip_denoise; collects the AOVs; one GPU only)\n"
                         "    --denoise-iterations K  the filter's iterations, 0..8 (5)\n"
-                        "    --json          print run statistics as one JSON line (with a tone option: the scale applied, tone_scale)\n"
+                        "    --json          print run statistics as one JSON line (with a tone option: the scale applied, tone_scale; with a\n"
+                        "                    matte option: matte_samples per pixel and matte_dropped_pixels, the pixels whose table was full)\n"
                         "    -v              progress on stderr\n",
                         args[0].c_str());
             return 1;
@@ -146,6 +175,9 @@ int main(int argc, char** argv)
         else if (a == "--despeckle-floor" && more) despeckleFloor = args[++i];
         else if (a == "--aov" && more) aovPrefix = args[++i];
         else if (a == "--aov-specular") aovSpecular = true;
+        else if (a == "--matte-mask" && more) matteMaskOut = args[++i];
+        else if (a == "--matte-objects" && more) { matteObjectsText = args[++i]; matteObjectsGiven = true; }
+        else if (a == "--matte-ids" && more) matteIdsOut = args[++i];
         else if (a == "--denoise" && more) denoiseOut = args[++i];
         else if (a == "--denoise-iterations" && more) denoiseIterations = std::atoi(args[++i].c_str());
         else if (a == "--json") json = true;
@@ -243,7 +275,8 @@ int main(int argc, char** argv)
             return 1;
         }
     }
-    if (aovSpecular && aovPrefix.empty() && denoiseOut.empty()) {
+    const bool matteGiven = !matteMaskOut.empty() || !matteIdsOut.empty();
+    if (aovSpecular && aovPrefix.empty() && denoiseOut.empty() && !matteGiven) {
         std::cerr << "kajo_render: --aov-specular changes the AOVs that --aov writes and --denoise is guided by: give it with --aov or --denoise" << std::endl;
         return 1;
     }
@@ -255,6 +288,24 @@ int main(int argc, char** argv)
             return 1;
         }
         opt.aov = true;
+    }
+    if (matteObjectsGiven != !matteMaskOut.empty()) {
+        std::cerr << "kajo_render: --matte-mask FILE writes the coverage of the objects --matte-objects LIST names: give the two together" << std::endl;
+        return 1;
+    }
+    if (matteGiven) {
+        // (the coverage tables are kept beside the AOV buffers of the one handle: the same condition as --aov, checked before any device is opened)
+        if (opt.gpus != 1 || threeArg) {
+            std::cerr << "kajo_render: " << (matteMaskOut.empty() ? "--matte-ids" : "--matte-mask")
+                      << " needs the whole frame on one GPU (--gpus 1, without --three-arg)" << std::endl;
+            return 1;
+        }
+        if (matteObjectsGiven && !parseObjects(matteObjectsText, &matteObjects)) {
+            std::cerr << "kajo_render: --matte-objects must be a comma-separated list of object ids (whole numbers >= 0)" << std::endl;
+            return 1;
+        }
+        opt.aov = true;
+        opt.matte = true;
     }
     if (!denoiseOut.empty()) {
         // (the denoiser reads the AOV buffers of the one handle: the same condition as --aov, checked before any device is opened)
@@ -305,6 +356,7 @@ int main(int argc, char** argv)
     std::unique_ptr<Scheduler> scheduler;
     hip::Scheduler* hipScheduler = nullptr;
     opt.counters = json;
+    long long matteSamples = 0, matteDroppedPixels = 0; // --json with a matte option
     try {
         if (rendererName == "hip") {
             // (--three-arg: the statement integration/apply_to_kajo.sh adds to renderer/Main.cpp:135-142, word for word)
@@ -352,6 +404,26 @@ int main(int argc, char** argv)
                 !writePfm(aovPrefix + "_depth.pfm", width, height, 1, depth.data()))
                 return 3;
         }
+        if (matteGiven) {
+            const size_t count = (size_t)width * height;
+            std::vector<float> mask(matteMaskOut.empty() ? 0 : count), dominant(matteIdsOut.empty() ? 0 : count);
+            hipScheduler->readMatteMask(matteObjects.data(), (int)matteObjects.size(), matteMaskOut.empty() ? nullptr : mask.data(),
+                                        matteIdsOut.empty() ? nullptr : dominant.data());
+            if ((!matteMaskOut.empty() && !writePfm(matteMaskOut, width, height, 1, mask.data())) ||
+                (!matteIdsOut.empty() && !writePfm(matteIdsOut, width, height, 1, dominant.data())))
+                return 3;
+            if (json) {
+                // the samples a pixel's table could not hold: samples - the sum of its counts
+                std::vector<uint32_t> counts(count * KAJO_MATTE_SLOTS);
+                hipScheduler->readMatte(nullptr, counts.data(), &matteSamples);
+                for (size_t i = 0; i < count; i++) {
+                    long long held = 0;
+                    for (int k = 0; k < KAJO_MATTE_SLOTS; k++)
+                        held += counts[i * KAJO_MATTE_SLOTS + k];
+                    matteDroppedPixels += held < matteSamples ? 1 : 0;
+                }
+            }
+        }
         if (!denoiseOut.empty()) {
             KajoDenoiseParams p;
             kajo_hip_default_denoise_params(&p);
@@ -398,6 +470,8 @@ int main(int argc, char** argv)
             std::printf(", \"tone_scale\": %.9g", (double)s.toneScale);
         if (despeckle)
             std::printf(", \"despeckle_clamped\": %lld, \"despeckle_repaired\": %lld", s.clamped, s.repaired);
+        if (matteGiven)
+            std::printf(", \"matte_samples\": %lld, \"matte_dropped_pixels\": %lld", matteSamples, matteDroppedPixels);
         std::printf("}\n");
     }
     return 0;

@@ -18,7 +18,7 @@ class HipRenderer:
     def __init__(self, scene: Scene, width: int, height: int, spp: int = 32, depth_limit: int = 8,
                  seed: int = 0o715517, strict: bool = False, exact: bool = False, counters: bool = False, device: int = 0,
                  tile=(64, 16), tile_index: int = 0, tile_count: int = 1, passes_per_launch: int = 0, flags: int = 0,
-                 aov: bool = False, aov_specular: bool = False):
+                 aov: bool = False, aov_specular: bool = False, matte: bool = False):
         L = capi.lib()
         self._L = L
         self.scene = scene
@@ -32,6 +32,7 @@ class HipRenderer:
         p.flags = (capi.KAJO_FLAG_STRICT if strict else 0) | (capi.KAJO_FLAG_EXACT if exact else 0) | (capi.KAJO_FLAG_COUNTERS if counters else 0) | int(flags)
         p.flags |= capi.KAJO_FLAG_AOV if aov else 0
         p.flags |= capi.KAJO_FLAG_AOV_SPECULAR if aov_specular else 0  # (without aov the library refuses it)
+        p.flags |= capi.KAJO_FLAG_AOV_MATTE if matte else 0  # (likewise)
         p.device = device
         p.tileW, p.tileH = tile
         p.tileIndex, p.tileCount = tile_index, tile_count
@@ -114,6 +115,27 @@ class HipRenderer:
         depth = np.zeros_like(hits)
         np.divide(B[..., 3], hits, out=depth, where=hits > 0)
         return dict(raw=(A, B), samples=samples.value, albedo=A[..., :3] / s, normal=B[..., :3] / s, depth=depth, hits=hits)
+
+    def matte(self) -> dict:
+        """Object-coverage mattes (include/kajo_hip.h kajo_hip_read_matte; the handle needs aov=True, matte=True): ids (H, W, 8) int32 and
+        counts (H, W, 8) uint32, a pixel's slots ranked by count (ties by id; empty slots last as id -1, count 0); samples = the AOVs';
+        dropped (H, W) int64 = samples - the counts' sum: the samples that met a full table."""
+        ids = np.empty((self.height, self.width, capi.KAJO_MATTE_SLOTS), np.int32)
+        counts = np.empty((self.height, self.width, capi.KAJO_MATTE_SLOTS), np.uint32)
+        samples = C.c_int64()
+        capi.check(self._L.kajo_hip_read_matte(self._h, ids.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p), C.byref(samples)))
+        return dict(ids=ids, counts=counts, samples=samples.value, dropped=samples.value - counts.sum(-1, dtype=np.int64))
+
+    def matte_mask(self, objects):
+        """(mask, dominant), both (H, W) float32 (include/kajo_hip.h kajo_hip_matte_mask): the share of the pixel's samples that saw one of
+        `objects` (ids as kat_trace reports them: 0 the background, then the planes, then the spheres), and the id that covers most of
+        the pixel (-1 before the first pass)."""
+        objects = np.ascontiguousarray(objects, np.int32).reshape(-1)
+        mask = np.empty((self.height, self.width), np.float32)
+        dominant = np.empty((self.height, self.width), np.float32)
+        capi.check(self._L.kajo_hip_matte_mask(self._h, objects.ctypes.data_as(C.c_void_p) if objects.size else None, int(objects.size),
+                                               mask.ctypes.data_as(C.c_void_p), dominant.ctypes.data_as(C.c_void_p)))
+        return mask, dominant
 
     def _denoise_params(self, iterations: int = 5, sigma_luminance: float = None, sigma_normal: float = None, sigma_depth: float = None,
                         demodulate: bool = True):
