@@ -342,7 +342,12 @@ int partTheTail(KajoHip* h)
     HIP_TRY(h->partedBlocks.alloc((size_t)nParted * sizeof(uint32_t)));
     HIP_TRY(hipMemcpy(h->partedBlocks.p, h->hostOrder.data() + (n - nParted), (size_t)nParted * sizeof(uint32_t), hipMemcpyHostToDevice));
     // the later parts' group sums of one launch: compact, a workgroup's worth of slots per parted block and part (18 MB at 1920x1080)
-    HIP_TRY(h->side.alloc((size_t)(kMaxParts - 1) * nParted * block * 16));
+    // Cleared once, in front of the launches that use them on the handle's stream: a later part writes the slots of its lanes inside the
+    // image only and the fold kernel adds every slot, so a slot outside the image must hold zero for the tile buffer's to stay zero. Which
+    // lane of which parted block lies outside does not change while the order stands, so no launch has to clear anything again.
+    const size_t sideBytes = (size_t)(kMaxParts - 1) * nParted * block * 16;
+    HIP_TRY(h->side.alloc(sideBytes));
+    HIP_TRY(hipMemsetAsync(h->side.p, 0, sideBytes, h->stream));
     h->nParted = nParted;
     return KAJO_OK;
 }

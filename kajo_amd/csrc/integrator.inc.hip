@@ -1504,7 +1504,8 @@ KDEV void renderBody(const RenderArgs& args, unsigned char* ldsRaw)
 
     const F3 origin = ld3(sc.origin); // (initial values only: the loop reads the camera from lds.camera)
     // accumulated radiance of the pixel (Renderer.cpp:70-71), continued across launches
-    // (the handle zeroes the buffer when it is created or reset)
+    // (the handle zeroes the buffer when it is created or reset; a slot outside the image is never written and stays zero -- the fold
+    // kernel of a parted launch adds to it side-buffer slots that capi.cpp partTheTail cleared and no lane writes)
     F3 total = f3(0.0f, 0.0f, 0.0f);
     float totalW = 0.0f;
     // (LISTS_RMW: the large-scene list kernels of rounds 3-4 -- 128 VGPRs and spilling -- did not carry the pixel's total through the loop:

@@ -136,8 +136,9 @@ def check_against(got, F, passes, **params):
     return ratio, int(differ.sum())
 
 
-def _upload(r, frame, passes):
-    """Write `frame` (H, W, 4) float32 into the handle's accumulation through its tile buffer and declare it the sum of `passes`."""
+def _upload(r, frame, passes, tile=(64, 16)):
+    """Write `frame` (H, W, 4) float32 into the handle's accumulation through its tile buffer and declare it the sum of `passes`;
+    tile = the tile shape the handle was created with."""
     import torch
     from bench import DevicePtr
     H, W = frame.shape[:2]
@@ -145,7 +146,7 @@ def _upload(r, frame, passes):
     ptr, nbytes = r.tile_buffer()
     buf = torch.as_tensor(DevicePtr(ptr, nbytes // 4), device="cuda").view(-1, 4)
     ys, xs = np.mgrid[0:H, 0:W]
-    _, slots = TileLayout(W, H, 1).owner_and_slot(xs, ys)
+    _, slots = TileLayout(W, H, 1, tile).owner_and_slot(xs, ys)
     buf[torch.as_tensor(slots.reshape(-1).astype(np.int64), device="cuda")] = torch.as_tensor(frame.reshape(-1, 4), device="cuda")
     torch.cuda.synchronize()
     r.set_pass_count(passes)
