@@ -32,6 +32,9 @@
  *   kajo_hip_glare           (no counterpart: the reference has no glare) a bloom pyramid between the frame and the tone curves;
  *                            kajo_hip_display_argb8 and kajo_hip_display_gathered_argb8_device run denoise -> glare -> tone mapping,
  *                            kajo_hip_default_glare_params gives the defaults
+ *   kajo_hip_meter           (no counterpart: the reference has no metering) a luminance histogram of the frame in front of the tone
+ *                            curves: percentile automatic exposure, automatic white point and the range the frame spans;
+ *                            kajo_hip_present_metered_argb8 and its gathered twin put it into the display chain
  *   kajo_hip_destroy         the unique_ptr members of cpu::Scheduler (cpu/Scheduler.h:29-31)
  *
  * Pixels are dealt to GPUs as fixed-size tiles: a handle created with
@@ -477,6 +480,88 @@ int kajo_hip_present_gathered_argb8_device(kajo_hip_t h, const void* gathered, c
                                            const KajoToneParams* tone, void* dst);
 /* The two counts of the handle's most recent despeckle; waits for it. KAJO_E_STATE before the first one. */
 int kajo_hip_despeckle_counts(kajo_hip_t h, int64_t counts[2]);
+
+/* Histogram metering: percentile automatic exposure and automatic white point. The log-average of KAJO_TONE_AUTO_EXPOSURE is one number
+   that unlit background drags down and a light drags up; a luminance histogram gives the exposure that puts a chosen PERCENTILE of the
+   lit pixels at the key, the luminance below which a chosen share of them lies (Reinhard's white), and the range the frame spans. A
+   measurement at the end of the display chain, over the frame the tone kernels are handed, in kernels of its own
+   (kajo_amd/csrc/meter.hip) on the handle's stream, in float32 IEEE arithmetic without contraction in every numerics build: only its
+   inputs depend on FAST / EXACT / STRICT. Definition -- P = the handle's pass count, F = the source frame in sums over passes (after
+   whichever of despeckle, denoise and glare are asked for), W x H; per pixel:
+     m = F.rgb / P                       (float32 division)
+     the pixel COUNTS where all three channels of m are finite
+     l = (0.2126 max(m.r, 0) + 0.7152 max(m.g, 0)) + 0.0722 max(m.b, 0)      (despeckle's expression and order)
+     u = bits(l) & 0x7fffffff            (max(-0, 0) may leave -0: the sign is masked)
+     k = u >> 19                         (the exponent and four bits of the mantissa: 16 bins per stop, linear inside a sixteenth
+                                          of a stop; no logarithm is taken)
+     base = (127 - 16) << 4
+     bin = 0 if k < base (l < 2^-16, zero and denormals included), else min(k - base + 1, 513)
+   Bins 1..512 cover 2^-16 .. 2^16; bin 513 is everything from 2^16 up, +Inf included (an l of finite channels can overflow). The lower
+   edge of inner bin b is the float with the bits (b - 1 + base) << 19, its centre the mean of its edge and the next (exact in float32);
+   the centre of bin 513 is 2^16. The counts are uint32 and exact: integer addition commutes, so the histogram is the same words from
+   run to run, for any number of workgroups and for any number of tile owners, with no float sum to order.
+     nonfinite = the pixels that do not count       under = bin 0        over = bin 513
+     metered n = the sum of bins 1..513 (black does not meter);   nonfinite + the sum of all bins = W * H
+   Evaluation, on the host in binary64, pure (kajo_hip_meter_evaluate):
+     value(q), q in (0, 1]: rank r = min(n, max(1, ceil((double)q * n))); the bin is the smallest b >= 1 whose cumulative count over
+                            bins 1..b reaches r; the value is that bin's centre
+     anchorL = value(percentile);  exposure = log2(key / anchorL);  whiteL = value(whitePercentile)
+     minBin, maxBin = the first and the last non-empty bin among 1..513
+     with n = 0: anchorL 0, exposure 0, whiteL 0, minBin = maxBin = 0
+   Refusals (KAJO_E_INVALID, before any device work and before the handle is looked at): NULL params; a percentile or whitePercentile
+   that is not finite or outside (0, 1]; a key that is not finite or not above 0; an unknown flag bit; non-zero reserved words. Where
+   other stages' parameters are present too, the order is despeckle, glare, meter, tone, denoise, handle. The accumulation, the AOV
+   buffers, the matte buffers, the pass count and the counters (kernelMs included) are not touched; scratch (the workgroups' partial
+   histograms, under 1 MB at any frame size, and the 514 + 1 words of the result) is allocated on first use and freed by
+   kajo_hip_destroy. */
+#define KAJO_METER_BINS 514
+#define KAJO_METER_AUTO_WHITE 1u       /* KajoMeterParams.flags: kajo_hip_meter_tone also sets Reinhard's white from whiteL */
+typedef struct KajoMeterParams {
+    float percentile;       /* in (0, 1] (default 0.5: the median of the metered pixels) */
+    float key;              /* > 0, finite (default 0.18): the grey the anchor luminance is mapped to */
+    float whitePercentile;  /* in (0, 1] (default 0.995) */
+    uint32_t flags;         /* KAJO_METER_* (default 0) */
+    float reserved[4];      /* 0 */
+} KajoMeterParams;          /* 32 bytes */
+typedef struct KajoMeterResult {
+    int64_t pixels;         /* W * H */
+    int64_t nonfinite;      /* pixels that do not count */
+    int64_t under;          /* bin 0: below 2^-16, black included */
+    int64_t over;           /* bin 513: 2^16 and above */
+    int64_t metered;        /* n: the sum of bins 1..513 */
+    float anchorL;          /* the luminance at `percentile` */
+    float whiteL;           /* the luminance at `whitePercentile` */
+    float exposure;         /* log2(key / anchorL), in stops */
+    int32_t minBin, maxBin; /* the frame spans (maxBin - minBin + 1) / 16 stops */
+    int32_t reserved;       /* 0 */
+} KajoMeterResult;          /* 64 bytes */
+void kajo_hip_default_meter_params(KajoMeterParams* p); /* NULL is accepted */
+/* Pure host, no device and no handle: the fields of *result from a histogram, except pixels and nonfinite, which are left as the
+   caller set them. KAJO_E_INVALID: NULL hist or result, or the params' refusals above. */
+int kajo_hip_meter_evaluate(const uint32_t hist[KAJO_METER_BINS], const KajoMeterParams* p, KajoMeterResult* result);
+/* Pure host: the tone parameters a metered frame is mapped with. *out = *in with exposure = min(max(in.exposure + result.exposure,
+   -32), 32) -- the caller's EV is a compensation on top of the metered one, as on a camera -- and, with KAJO_METER_AUTO_WHITE, white =
+   whiteL * 2^out.exposure (white is in exposed units; a whiteL of 0 gives 0, i.e. no white point). KAJO_E_INVALID: a NULL argument,
+   the params' refusals, or `in` with KAJO_TONE_AUTO_EXPOSURE: that would be two automatic exposures. in and out may be one struct. */
+int kajo_hip_meter_tone(const KajoMeterResult* result, const KajoMeterParams* p, const KajoToneParams* in, KajoToneParams* out);
+/* Measures the frame kajo_hip_present_argb8 with the same first three stages would hand the tone kernels (NULL = the stage is off; with
+   all three NULL the accumulation). hist: HOST pointer to KAJO_METER_BINS words; either of hist and result may be NULL. Valid where
+   kajo_hip_read_radiance is (tileCount 1, or a composed handle); KAJO_E_STATE with no pass rendered. Waits. */
+int kajo_hip_meter(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* g,
+                   const KajoMeterParams* meter, uint32_t* hist, KajoMeterResult* result);
+/* kajo_hip_present_argb8 with the metering between the chain and the tone curves: the chain is formed once, its last frame is metered,
+   the 2 KB histogram is read back and evaluated, kajo_hip_meter_tone patches `tone`, and the tone kernels map that same frame with the
+   patched parameters. *result (may be NULL): the measurement. With meter == NULL exactly kajo_hip_present_argb8 (result is not
+   written). Refusals in the order despeckle, glare, meter, tone (KAJO_TONE_AUTO_EXPOSURE among them), denoise, handle. Waits. */
+int kajo_hip_present_metered_argb8(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* g,
+                                   const KajoMeterParams* meter, const KajoToneParams* tone, uint32_t* argb8, KajoMeterResult* result);
+/* The multi-GPU twin over gathered tile buffers (NULL = the handle's own when tileCount == 1), into DEVICE memory. This one call is NOT
+   asynchronous end to end: it waits once, for the histogram, then enqueues the tone mapping on the handle's stream and returns. The
+   tone kernels take exposure and white BY VALUE from the host, and they are not to change for this: the metered scale has to reach
+   the host before they can be launched. With meter == NULL exactly kajo_hip_present_gathered_argb8_device, asynchronous as before. */
+int kajo_hip_present_metered_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle,
+                                                   const KajoGlareParams* g, const KajoMeterParams* meter, const KajoToneParams* tone, void* dst,
+                                                   KajoMeterResult* result);
 
 /* Use an existing HIP stream (hipStream_t passed as void*) instead of the handle's own. */
 int kajo_hip_set_stream(kajo_hip_t h, void* stream);

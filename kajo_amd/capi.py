@@ -40,6 +40,8 @@ KAJO_MATTE_SLOTS = 8
 KAJO_DENOISE_NO_DEMODULATE = 1  # KajoDenoiseParams.flags: filter the mean radiance itself, not radiance / albedo
 KAJO_TONE_CLAMP, KAJO_TONE_REINHARD, KAJO_TONE_ACES = 0, 1, 2  # KajoToneParams.curve
 KAJO_TONE_AUTO_EXPOSURE = 1  # KajoToneParams.flags: scale the frame's log-average luminance to `key`
+KAJO_METER_BINS = 514  # words of a luminance histogram (kajo_hip_meter): bin 0 below 2^-16, 1..512 sixteen per stop, 513 from 2^16 up
+KAJO_METER_AUTO_WHITE = 1  # KajoMeterParams.flags: kajo_hip_meter_tone also sets Reinhard's white from whiteL
 
 # every symbol include/kajo_hip.h declares
 EXPORTS = [
@@ -53,6 +55,8 @@ EXPORTS = [
     "kajo_hip_default_glare_params", "kajo_hip_glare", "kajo_hip_display_argb8", "kajo_hip_display_gathered_argb8_device",
     "kajo_hip_default_despeckle_params", "kajo_hip_despeckle", "kajo_hip_present_argb8", "kajo_hip_present_gathered_argb8_device",
     "kajo_hip_despeckle_counts", "kajo_hip_read_matte", "kajo_hip_matte_mask",
+    "kajo_hip_default_meter_params", "kajo_hip_meter_evaluate", "kajo_hip_meter_tone", "kajo_hip_meter", "kajo_hip_present_metered_argb8",
+    "kajo_hip_present_metered_gathered_argb8_device",
 ]
 
 
@@ -77,6 +81,16 @@ class KajoGlareParams(C.Structure):
 
 class KajoDespeckleParams(C.Structure):
     _fields_ = [("factor", C.c_float), ("rank", C.c_int32), ("floor", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_float * 4)]
+
+
+class KajoMeterParams(C.Structure):
+    _fields_ = [("percentile", C.c_float), ("key", C.c_float), ("whitePercentile", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_float * 4)]
+
+
+class KajoMeterResult(C.Structure):
+    _fields_ = [("pixels", C.c_int64), ("nonfinite", C.c_int64), ("under", C.c_int64), ("over", C.c_int64), ("metered", C.c_int64),
+                ("anchorL", C.c_float), ("whiteL", C.c_float), ("exposure", C.c_float), ("minBin", C.c_int32), ("maxBin", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class KajoParams(C.Structure):
@@ -177,6 +191,21 @@ def lib():
                                                  C.POINTER(KajoToneParams), C.c_void_p, C.POINTER(C.c_float)]
             L.kajo_hip_present_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoGlareParams),
                                                                  C.POINTER(KajoToneParams), C.c_void_p]
+        if hasattr(L, "kajo_hip_meter"):  # (nor the metering)
+            L.kajo_hip_default_meter_params.argtypes = [C.POINTER(KajoMeterParams)]
+            L.kajo_hip_default_meter_params.restype = None
+            L.kajo_hip_meter_evaluate.argtypes = [C.c_void_p, C.POINTER(KajoMeterParams), C.POINTER(KajoMeterResult)]
+            L.kajo_hip_meter_tone.argtypes = [C.POINTER(KajoMeterResult), C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams),
+                                              C.POINTER(KajoToneParams)]
+            L.kajo_hip_meter.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams), C.POINTER(KajoGlareParams),
+                                         C.POINTER(KajoMeterParams), C.c_void_p, C.POINTER(KajoMeterResult)]
+            L.kajo_hip_present_metered_argb8.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams),
+                                                         C.POINTER(KajoGlareParams), C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams),
+                                                         C.c_void_p, C.POINTER(KajoMeterResult)]
+            L.kajo_hip_present_metered_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams),
+                                                                         C.POINTER(KajoGlareParams), C.POINTER(KajoMeterParams),
+                                                                         C.POINTER(KajoToneParams), C.c_void_p, C.POINTER(KajoMeterResult)]
+            L.kajo_meter_groups.argtypes = [C.c_int, C.c_int]
         if hasattr(L, "kajo_hip_read_matte"):  # (nor the mattes)
             L.kajo_hip_read_matte.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
             L.kajo_hip_matte_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

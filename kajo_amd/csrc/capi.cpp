@@ -59,6 +59,8 @@ int kajo_glare_launch(const void* src, const TileMap* map, int fromTiles, float 
 int kajo_despeckle_groups(int W, int H);
 int kajo_despeckle_launch(const void* src, const TileMap* map, int fromTiles, float passes, float factor, int rank, float floorL, void* clamped,
                           void* out, int toTiles, void* partials, void* counts, void* stream);
+int kajo_meter_groups(int W, int H);
+int kajo_meter_launch(const void* src, const TileMap* map, int fromTiles, float passes, void* partials, void* result, void* stream);
 int kajo_matte_rank_launch(const void* ids, const void* counts, int W, int H, void* rankedIds, void* rankedCounts, void* stream);
 int kajo_matte_mask_launch(const void* ids, const void* counts, int W, int H, const void* selected, unsigned nObjects, float samples, void* mask,
                            void* dominant, void* stream);
@@ -242,6 +244,9 @@ struct KajoHip
     // partial counts (despeckleImage), the clamped frame float4 [W * H] and the output frame float4 [max(W * H, slotsPerOwner)]
     DeviceBuffer despeckle;
     bool despeckled = false; // the counts are those of a despeckle (kajo_hip_despeckle_counts)
+    // metering (meter.hip; kajo_hip_meter, kajo_hip_present_metered_*), on its first call: the result (the 514 bins and the count of pixels
+    // that do not count, uint32 [kMeterRow], padded to 16 bytes), then the workgroups' partial histograms (meterImage)
+    DeviceBuffer meter;
     int toneScaleState = 0; // the s of the most recent tone mapping: 0 none yet, 1 toneScale, 2 the scale word (auto exposure)
     float toneScale = 1.0f;
 };
@@ -1644,6 +1649,286 @@ int kajo_hip_present_gathered_argb8_device(kajo_hip_t h, const void* gathered, c
     if ((rc = despeckleImage(h, despeckle, img, false, &img)))
         return rc;
     if (g && (rc = glareImage(h, g, img, &img)))
+        return rc;
+    return toneLaunch(h, img, t, dst);
+}
+
+} // extern "C"
+
+namespace
+{
+
+constexpr int kMeterRow = KAJO_METER_BINS + 1; // meter.hip: a row of counts is the bins, then the pixels that do not count
+
+// The refusals of KajoMeterParams (KAJO_E_INVALID), before any device work and before the handle is looked at
+int checkMeter(const KajoMeterParams* p)
+{
+    if (!p)
+        return fail(KAJO_E_INVALID, "null meter parameters");
+    if (!(std::isfinite(p->percentile) && p->percentile > 0.0f && p->percentile <= 1.0f))
+        return fail(KAJO_E_INVALID, "meter percentile must be finite and in (0, 1]");
+    if (!(std::isfinite(p->key) && p->key > 0.0f))
+        return fail(KAJO_E_INVALID, "meter key must be finite and positive");
+    if (!(std::isfinite(p->whitePercentile) && p->whitePercentile > 0.0f && p->whitePercentile <= 1.0f))
+        return fail(KAJO_E_INVALID, "meter white percentile must be finite and in (0, 1]");
+    if (p->flags & ~KAJO_METER_AUTO_WHITE)
+        return fail(KAJO_E_INVALID, "unknown meter flag");
+    for (float r : p->reserved)
+        if (r != 0.0f)
+            return fail(KAJO_E_INVALID, "meter reserved fields must be 0");
+    return KAJO_OK;
+}
+
+// the float with the bits (b - 1 + base) << 19: the lower edge of inner bin b, b = 1 .. 513 (include/kajo_hip.h)
+double meterEdge(int b)
+{
+    const uint32_t bits = (uint32_t)(b - 1 + ((127 - 16) << 4)) << 19;
+    float f;
+    std::memcpy(&f, &bits, sizeof f);
+    return (double)f;
+}
+
+double meterCentre(int b)
+{
+    return b >= KAJO_METER_BINS - 1 ? meterEdge(KAJO_METER_BINS - 1) : 0.5 * (meterEdge(b) + meterEdge(b + 1));
+}
+
+// the centre of the smallest bin b >= 1 whose cumulative count over bins 1..b reaches the rank of q among n > 0 metered pixels
+double meterValue(const uint32_t* hist, int64_t n, float q)
+{
+    const int64_t rank = std::min(n, std::max((int64_t)1, (int64_t)std::ceil((double)q * (double)n)));
+    int64_t seen = 0;
+    for (int b = 1; b < KAJO_METER_BINS; b++)
+        if ((seen += hist[b]) >= rank)
+            return meterCentre(b);
+    return meterCentre(KAJO_METER_BINS - 1);
+}
+
+// Enqueue the metering of an image (tiles through h->map's geometry, or a row-major frame), read the counts back and wait: counts = the
+// 514 bins, then the pixels that do not count. Device bound.
+int meterImage(KajoHip* h, Image img, uint32_t counts[kMeterRow])
+{
+    const size_t head = ((size_t)kMeterRow * 4 + 15) / 16 * 16;
+    HIP_TRY(h->meter.ensure(head + (size_t)kajo_meter_groups(h->W, h->H) * kMeterRow * 4));
+    hipError_t le = (hipError_t)kajo_meter_launch(img.src, &h->map, img.fromTiles ? 1 : 0, (float)h->passesDone, h->meter.as<char>() + head,
+                                                  h->meter.p, h->stream);
+    if (le != hipSuccess)
+        return failHip(le, "meter kernel launch");
+    HIP_TRY(hipMemcpyAsync(counts, h->meter.p, (size_t)kMeterRow * 4, hipMemcpyDeviceToHost, h->stream));
+    return kajo_hip_wait(h);
+}
+
+// counts (meterImage) -> the caller's histogram and the whole result
+int meterResult(KajoHip* h, const uint32_t counts[kMeterRow], const KajoMeterParams* p, uint32_t* hist, KajoMeterResult* result)
+{
+    if (hist)
+        std::memcpy(hist, counts, (size_t)KAJO_METER_BINS * 4);
+    if (!result)
+        return KAJO_OK;
+    std::memset(result, 0, sizeof *result);
+    result->pixels = (int64_t)h->W * h->H;
+    result->nonfinite = counts[KAJO_METER_BINS];
+    return kajo_hip_meter_evaluate(counts, p, result);
+}
+
+// The chain in front of the tone curves on the handle's stream: despeckle -> denoise -> glare, each optional, *img the frame it starts
+// from and then the one it ends with. Checked by the stages' checks, device bound.
+int chainImage(KajoHip* h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* g, Image* img)
+{
+    int rc;
+    // (with the denoiser behind it the despeckle writes the handle's tile layout: with the AOV flag the handle is the frame's one owner)
+    if (despeckle && (rc = despeckleImage(h, despeckle, *img, denoise != nullptr, img)))
+        return rc;
+    if (denoise) {
+        void* out = nullptr;
+        if ((rc = denoiseFrame(h, denoise, &out, despeckle ? img->src : nullptr)))
+            return rc;
+        *img = Image{out, false};
+    }
+    if (g && (rc = glareImage(h, g, *img, img)))
+        return rc;
+    return KAJO_OK;
+}
+
+// the refusals of the two metered chain calls in front of the handle's: despeckle, glare, meter, tone (-> *t is not formed here: the
+// metering patches the parameters first)
+int checkMeteredChain(const KajoDespeckleParams* despeckle, const KajoGlareParams* g, const KajoMeterParams* meter, const KajoToneParams* tone)
+{
+    int rc;
+    if (despeckle && (rc = checkDespeckle(despeckle)))
+        return rc;
+    if (g && (rc = checkGlare(g)))
+        return rc;
+    if ((rc = checkMeter(meter)))
+        return rc;
+    ToneArgs t{};
+    if ((rc = toneArgsOf(tone, &t)))
+        return rc;
+    if (tone->flags & KAJO_TONE_AUTO_EXPOSURE)
+        return fail(KAJO_E_INVALID, "metered exposure and the tone parameters' automatic exposure are two automatic exposures: give one");
+    return KAJO_OK;
+}
+
+// meter *img, evaluate, patch the tone parameters: *t = the kernels' arguments of the metered mapping
+int meterAndPatch(KajoHip* h, Image img, const KajoMeterParams* meter, const KajoToneParams* tone, KajoMeterResult* result, ToneArgs* t)
+{
+    uint32_t counts[kMeterRow];
+    int rc = meterImage(h, img, counts);
+    if (rc)
+        return rc;
+    KajoMeterResult measured;
+    if ((rc = meterResult(h, counts, meter, nullptr, &measured)))
+        return rc;
+    KajoToneParams patched;
+    if ((rc = kajo_hip_meter_tone(&measured, meter, tone, &patched)))
+        return rc;
+    if ((rc = toneArgsOf(&patched, t)))
+        return rc;
+    if (result)
+        *result = measured;
+    return KAJO_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void kajo_hip_default_meter_params(KajoMeterParams* p)
+{
+    if (!p)
+        return;
+    std::memset(p, 0, sizeof *p);
+    p->percentile = 0.5f;
+    p->key = 0.18f;
+    p->whitePercentile = 0.995f;
+    p->flags = 0;
+}
+
+int kajo_hip_meter_evaluate(const uint32_t hist[KAJO_METER_BINS], const KajoMeterParams* p, KajoMeterResult* result)
+{
+    int rc = checkMeter(p);
+    if (rc)
+        return rc;
+    if (!hist || !result)
+        return fail(KAJO_E_INVALID, "null argument");
+    int64_t n = 0;
+    int first = 0, last = 0;
+    for (int b = 1; b < KAJO_METER_BINS; b++) {
+        n += hist[b];
+        if (hist[b]) {
+            first = first ? first : b;
+            last = b;
+        }
+    }
+    result->under = hist[0];
+    result->over = hist[KAJO_METER_BINS - 1];
+    result->metered = n;
+    result->minBin = first;
+    result->maxBin = last;
+    result->reserved = 0;
+    result->anchorL = result->whiteL = result->exposure = 0.0f;
+    if (n > 0) {
+        const double anchor = meterValue(hist, n, p->percentile);
+        result->anchorL = (float)anchor; // (exact: a bin's centre is a float)
+        result->whiteL = (float)meterValue(hist, n, p->whitePercentile);
+        result->exposure = (float)std::log2((double)p->key / anchor);
+    }
+    return KAJO_OK;
+}
+
+int kajo_hip_meter_tone(const KajoMeterResult* result, const KajoMeterParams* p, const KajoToneParams* in, KajoToneParams* out)
+{
+    int rc = checkMeter(p);
+    if (rc)
+        return rc;
+    if (!result || !in || !out)
+        return fail(KAJO_E_INVALID, "null argument");
+    if (in->flags & KAJO_TONE_AUTO_EXPOSURE)
+        return fail(KAJO_E_INVALID, "metered exposure and the tone parameters' automatic exposure are two automatic exposures: give one");
+    KajoToneParams t = *in;
+    t.exposure = std::min(std::max(in->exposure + result->exposure, -32.0f), 32.0f);
+    if (p->flags & KAJO_METER_AUTO_WHITE)
+        t.white = (float)((double)result->whiteL * std::exp2((double)t.exposure));
+    *out = t;
+    return KAJO_OK;
+}
+
+int kajo_hip_meter(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* g,
+                   const KajoMeterParams* meter, uint32_t* hist, KajoMeterResult* result)
+{
+    // (every refusal before any device work: the despeckle parameters, the glare's, the meter's, the denoiser's, then the handle)
+    int rc;
+    if (despeckle && (rc = checkDespeckle(despeckle)))
+        return rc;
+    if (g && (rc = checkGlare(g)))
+        return rc;
+    if ((rc = checkMeter(meter)))
+        return rc;
+    if (denoise) {
+        if ((rc = checkDenoise(h, denoise)))
+            return rc;
+    } else if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    Image img;
+    if ((rc = imageOf(h, false, nullptr, &img)))
+        return rc;
+    if ((rc = chainImage(h, despeckle, denoise, g, &img)))
+        return rc;
+    uint32_t counts[kMeterRow];
+    if ((rc = meterImage(h, img, counts)))
+        return rc;
+    return meterResult(h, counts, meter, hist, result);
+}
+
+int kajo_hip_present_metered_argb8(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* g,
+                                   const KajoMeterParams* meter, const KajoToneParams* tone, uint32_t* argb8, KajoMeterResult* result)
+{
+    if (!meter)
+        return kajo_hip_present_argb8(h, despeckle, denoise, g, tone, argb8, nullptr);
+    int rc = checkMeteredChain(despeckle, g, meter, tone);
+    if (rc)
+        return rc;
+    if (denoise) {
+        if ((rc = checkDenoise(h, denoise)))
+            return rc;
+    } else if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    Image img;
+    if ((rc = imageOf(h, false, nullptr, &img)))
+        return rc;
+    const size_t count = (size_t)h->W * h->H;
+    HIP_TRY(h->argb.ensure(count * 4));
+    if ((rc = chainImage(h, despeckle, denoise, g, &img)))
+        return rc;
+    ToneArgs t{};
+    if ((rc = meterAndPatch(h, img, meter, tone, result, &t)))
+        return rc;
+    // (the frame the histogram was taken of is still where the chain left it: the same frame is mapped)
+    if ((rc = toneLaunch(h, img, t, h->argb.p)))
+        return rc;
+    if (argb8)
+        HIP_TRY(hipMemcpyAsync(argb8, h->argb.p, count * 4, hipMemcpyDeviceToHost, h->stream));
+    return kajo_hip_wait(h);
+}
+
+int kajo_hip_present_metered_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle,
+                                                   const KajoGlareParams* g, const KajoMeterParams* meter, const KajoToneParams* tone, void* dst,
+                                                   KajoMeterResult* result)
+{
+    if (!meter)
+        return kajo_hip_present_gathered_argb8_device(h, gathered, despeckle, g, tone, dst);
+    int rc = checkMeteredChain(despeckle, g, meter, tone);
+    if (rc)
+        return rc;
+    if (!h || !dst)
+        return fail(KAJO_E_INVALID, "null argument");
+    Image img;
+    if ((rc = imageOf(h, true, gathered, &img)))
+        return rc;
+    if ((rc = chainImage(h, despeckle, nullptr, g, &img)))
+        return rc;
+    ToneArgs t{};
+    if ((rc = meterAndPatch(h, img, meter, tone, result, &t))) // (the one wait: include/kajo_hip.h)
         return rc;
     return toneLaunch(h, img, t, dst);
 }

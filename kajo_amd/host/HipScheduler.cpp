@@ -74,6 +74,7 @@ struct Scheduler::Impl
     size_t tileBytes = 0;
     Statistics stats;
     float toneScale = 1; // Statistics::toneScale of the last image
+    KajoMeterResult metered = {}; // lastMeter()
 
     // Options::tone is the identity (include/kajo_hip.h: s = 1 and the clamp, whatever white and key say): the plain resolve
     bool toneIsIdentity() const { return opt.tone.curve == KAJO_TONE_CLAMP && opt.tone.flags == 0 && opt.tone.exposure == 0.0f; }
@@ -197,7 +198,12 @@ struct Scheduler::Impl
     {
         if (opt.gpus == 1 && !opt.forceGather) {
             // single owner: the library resolves from its own tile buffer
-            if (opt.despeckleOn)
+            if (opt.meterOn) {
+                check(kajo_hip_present_metered_argb8(handles[0], opt.despeckleOn ? &opt.despeckle : nullptr, nullptr, glareOn() ? &opt.glare : nullptr,
+                                                     &opt.meter, &opt.tone, image->pixels.get(), &metered),
+                      "kajo_hip_present_metered_argb8");
+                check(kajo_hip_tone_scale(handles[0], &toneScale), "kajo_hip_tone_scale");
+            } else if (opt.despeckleOn)
                 check(kajo_hip_present_argb8(handles[0], &opt.despeckle, nullptr, glareOn() ? &opt.glare : nullptr, &opt.tone, image->pixels.get(), &toneScale),
                       "kajo_hip_present_argb8");
             else if (glareOn())
@@ -232,7 +238,11 @@ struct Scheduler::Impl
             }
         }
         composed = false;
-        if (opt.despeckleOn)
+        if (opt.meterOn)
+            check(kajo_hip_present_metered_gathered_argb8_device(handles[0], gathered, opt.despeckleOn ? &opt.despeckle : nullptr,
+                                                                 glareOn() ? &opt.glare : nullptr, &opt.meter, &opt.tone, argbDevice, &metered),
+                  "kajo_hip_present_metered_gathered_argb8_device");
+        else if (opt.despeckleOn)
             check(kajo_hip_present_gathered_argb8_device(handles[0], gathered, &opt.despeckle, glareOn() ? &opt.glare : nullptr, &opt.tone, argbDevice),
                   "kajo_hip_present_gathered_argb8_device");
         else if (glareOn())
@@ -245,7 +255,7 @@ struct Scheduler::Impl
         checkHip(hipMemcpyAsync(image->pixels.get(), argbDevice, (size_t)image->width * image->height * 4, hipMemcpyDeviceToHost, streams[0]),
                  "hipMemcpyAsync(image)");
         checkHip(hipStreamSynchronize(streams[0]), "hipStreamSynchronize");
-        if (opt.despeckleOn || glareOn() || !toneIsIdentity())
+        if (opt.meterOn || opt.despeckleOn || glareOn() || !toneIsIdentity())
             check(kajo_hip_tone_scale(handles[0], &toneScale), "kajo_hip_tone_scale"); // (the stream is drained: no wait left)
     }
     bool composed = false;
@@ -278,6 +288,11 @@ Scheduler::~Scheduler() {}
 const Statistics& Scheduler::statistics() const
 {
     return m_impl->stats;
+}
+
+const KajoMeterResult& Scheduler::lastMeter() const
+{
+    return m_impl->metered;
 }
 
 void Scheduler::readRadiance(float* dst)
@@ -348,14 +363,23 @@ void Scheduler::readPresented(const KajoDespeckleParams* despeckle, const KajoDe
         despeckle = &d.opt.despeckle;
     if (counts)
         counts[0] = counts[1] = 0;
-    if (!despeckle)
+    if (!despeckle && !d.opt.meterOn)
         return readDisplayed(denoise, glare, tone, argb8, scale);
     if (d.gathered && !d.composed) { // (as readDisplayed)
         check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
         d.composed = true;
     }
-    check(kajo_hip_present_argb8(d.handles[0], despeckle, denoise, glare ? glare : &d.opt.glare, tone ? tone : &d.opt.tone, argb8, scale),
-          "kajo_hip_present_argb8");
+    if (d.opt.meterOn) {
+        check(kajo_hip_present_metered_argb8(d.handles[0], despeckle, denoise, glare ? glare : &d.opt.glare, &d.opt.meter, tone ? tone : &d.opt.tone,
+                                             argb8, &d.metered),
+              "kajo_hip_present_metered_argb8");
+        if (scale)
+            check(kajo_hip_tone_scale(d.handles[0], scale), "kajo_hip_tone_scale");
+    } else
+        check(kajo_hip_present_argb8(d.handles[0], despeckle, denoise, glare ? glare : &d.opt.glare, tone ? tone : &d.opt.tone, argb8, scale),
+              "kajo_hip_present_argb8");
+    if (!despeckle)
+        return;
     if (counts) {
         int64_t c[2] = {0, 0};
         check(kajo_hip_despeckle_counts(d.handles[0], c), "kajo_hip_despeckle_counts");

@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "Scheduler.h"
-#include "kajo_hip.h" // KajoToneParams (Options::tone), KajoGlareParams (Options::glare), KajoDespeckleParams (Options::despeckle)
+#include "kajo_hip.h" // KajoToneParams (Options::tone), KajoGlareParams (Options::glare), KajoDespeckleParams (Options::despeckle), KajoMeterParams
 
 class Image;
 class Preview;
@@ -74,6 +74,13 @@ struct Options
     // kajo_hip_default_despeckle_params first (all zero, as here, is refused for its rank, loudly).
     bool despeckleOn = false;
     KajoDespeckleParams despeckle = {};
+    // Histogram metering between the chain and the tone curve of the image run() writes (include/kajo_hip.h
+    // kajo_hip_present_metered_argb8; with one owner or after the gather): the exposure that puts `meter.percentile` of the lit pixels
+    // at `meter.key`, Options::tone's exposure a compensation on top, and with KAJO_METER_AUTO_WHITE Reinhard's white. Off by default:
+    // every frame then takes exactly the calls it takes without these fields. A flag beside the parameters, as for the despeckle:
+    // whoever sets meterOn fills `meter` with kajo_hip_default_meter_params first (all zero, as here, is refused, loudly).
+    bool meterOn = false;
+    KajoMeterParams meter = {};
 };
 
 struct Statistics
@@ -121,9 +128,13 @@ public:
     // denoise (null = the accumulation; otherwise Options::aov) -> glare (null = Options::glare) -> tone (null = Options::tone)
     void readDisplayed(const KajoDenoiseParams* denoise, const KajoGlareParams* glare, const KajoToneParams* tone, uint32_t* argb8, float* scale);
     // the same chain with the despeckle in front (include/kajo_hip.h kajo_hip_present_argb8): despeckle null = Options::despeckle where
-    // Options::despeckleOn, else none (then readDisplayed); counts (may be null) = pixels clamped, pixels repaired (0, 0 without the stage)
+    // Options::despeckleOn, else none (then readDisplayed); counts (may be null) = pixels clamped, pixels repaired (0, 0 without the stage).
+    // With Options::meterOn the chain ends in the metered call (kajo_hip_present_metered_argb8) and lastMeter() is its measurement
     void readPresented(const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* glare, const KajoToneParams* tone,
                        uint32_t* argb8, float* scale, long long counts[2]);
+
+    // the measurement of the most recent metered image (Options::meterOn: run()'s last refresh, or readPresented); all zero before it
+    const KajoMeterResult& lastMeter() const;
 
 private:
     struct Impl;

@@ -67,6 +67,8 @@ int main(int argc, char** argv)
     // despeckle options (include/kajo_hip.h KajoDespeckleParams): the raw text, checked after the loop
     std::string despeckleFactor, despeckleRank, despeckleFloor;
     bool despeckle = false;
+    // meter options (include/kajo_hip.h KajoMeterParams): the raw text, checked after the loop
+    std::string meterExposure, meterWhite;
     int width = 640, height = 480;
     int denoiseIterations = 5;
     hip::Options opt;
@@ -121,6 +123,10 @@ int main(int argc, char** argv)
                         "    --despeckle-factor F  --despeckle: a pixel is bounded to F times its RANK-th brightest neighbour, F >= 1 (16; 0 = repair only)\n"
                         "    --despeckle-rank R  --despeckle: the neighbour measured against, 1..4 (1)\n"
                         "    --despeckle-floor X  --despeckle: the least luminance the bound is formed from, >= 0 (0.2)\n"
+                        "    --meter-exposure Q  meter the frame with a luminance histogram (-o and --denoise; include/kajo_hip.h kajo_hip_meter; any\n"
+                        "                    --gpus): the exposure that puts the Q-th percentile, 0 < Q <= 1, of the lit pixels at --key; --exposure EV\n"
+                        "                    is a compensation on top. Not with --auto-exposure (--hdr and --raw stay the raw mean)\n"
+                        "    --meter-white Q  --tonemap reinhard: the white point from the histogram's Q-th percentile (implies --meter-exposure 0.5)\n"
                         "    --aov PREFIX    also write the first-hit AOVs a denoiser takes, averaged over the render's camera samples:\n"
                         "                    PREFIX_albedo.pfm, PREFIX_normal.pfm (3 channels), PREFIX_depth.pfm (1; mean over the hits)\n"
                         "                    (one GPU only)\n"
@@ -135,7 +141,8 @@ int main(int argc, char** argv)
                         "                    include/kajo_hip.h kajo_hip_denoise; collects the AOVs; one GPU only)\n"
                         "    --denoise-iterations K  the filter's iterations, 0..8 (5)\n"
                         "    --json          print run statistics as one JSON line (with a tone option: the scale applied, tone_scale; with a\n"
-                        "                    matte option: matte_samples per pixel and matte_dropped_pixels, the pixels whose table was full)\n"
+                        "                    matte option: matte_samples per pixel and matte_dropped_pixels, the pixels whose table was full; with a\n"
+                        "                    meter option: meter_exposure, meter_white, meter_anchor, meter_metered, meter_under, meter_over, meter_stops)\n"
                         "    -v              progress on stderr\n",
                         args[0].c_str());
             return 1;
@@ -173,6 +180,8 @@ int main(int argc, char** argv)
         else if (a == "--despeckle-factor" && more) despeckleFactor = args[++i];
         else if (a == "--despeckle-rank" && more) despeckleRank = args[++i];
         else if (a == "--despeckle-floor" && more) despeckleFloor = args[++i];
+        else if (a == "--meter-exposure" && more) meterExposure = args[++i];
+        else if (a == "--meter-white" && more) meterWhite = args[++i];
         else if (a == "--aov" && more) aovPrefix = args[++i];
         else if (a == "--aov-specular") aovSpecular = true;
         else if (a == "--matte-mask" && more) matteMaskOut = args[++i];
@@ -275,6 +284,36 @@ int main(int argc, char** argv)
             return 1;
         }
     }
+    const bool meterGiven = !meterExposure.empty() || !meterWhite.empty();
+    if (meterGiven) {
+        // (before any device is opened: the refusals of kajo_hip_meter and of kajo_hip_meter_tone, with the option's name)
+        if (threeArg) {
+            std::cerr << "kajo_render: the meter options need the backend's options (without --three-arg)" << std::endl;
+            return 1;
+        }
+        if (toneAuto) {
+            std::cerr << "kajo_render: --meter-exposure and --auto-exposure are two automatic exposures: give one" << std::endl;
+            return 1;
+        }
+        if (!meterWhite.empty() && opt.tone.curve != KAJO_TONE_REINHARD) {
+            std::cerr << "kajo_render: --meter-white sets the white point of --tonemap reinhard: give the two together" << std::endl;
+            return 1;
+        }
+        opt.meterOn = true;
+        kajo_hip_default_meter_params(&opt.meter);
+        if (!meterExposure.empty() && (!parseFloat(meterExposure, &opt.meter.percentile) || opt.meter.percentile <= 0.0f || opt.meter.percentile > 1.0f)) {
+            std::cerr << "kajo_render: --meter-exposure must be a percentile in (0, 1]" << std::endl;
+            return 1;
+        }
+        if (!meterWhite.empty()) {
+            if (!parseFloat(meterWhite, &opt.meter.whitePercentile) || opt.meter.whitePercentile <= 0.0f || opt.meter.whitePercentile > 1.0f) {
+                std::cerr << "kajo_render: --meter-white must be a percentile in (0, 1]" << std::endl;
+                return 1;
+            }
+            opt.meter.flags |= KAJO_METER_AUTO_WHITE;
+        }
+        opt.meter.key = opt.tone.key; // (--key, checked above; 0.18 without)
+    }
     const bool matteGiven = !matteMaskOut.empty() || !matteIdsOut.empty();
     if (aovSpecular && aovPrefix.empty() && denoiseOut.empty() && !matteGiven) {
         std::cerr << "kajo_render: --aov-specular changes the AOVs that --aov writes and --denoise is guided by: give it with --aov or --denoise" << std::endl;
@@ -357,6 +396,7 @@ int main(int argc, char** argv)
     hip::Scheduler* hipScheduler = nullptr;
     opt.counters = json;
     long long matteSamples = 0, matteDroppedPixels = 0; // --json with a matte option
+    KajoMeterResult metered = {};                       // --json with a meter option: of the image run() wrote
     try {
         if (rendererName == "hip") {
             // (--three-arg: the statement integration/apply_to_kajo.sh adds to renderer/Main.cpp:135-142, word for word)
@@ -368,6 +408,8 @@ int main(int argc, char** argv)
             return 1;
         }
         scheduler->run();
+        if (hipScheduler && meterGiven)
+            metered = hipScheduler->lastMeter();
         if (!rawOut.empty()) {
             std::vector<float> acc((size_t)width * height * 4);
             hipScheduler->readRadiance(acc.data());
@@ -429,7 +471,7 @@ int main(int argc, char** argv)
             kajo_hip_default_denoise_params(&p);
             p.iterations = denoiseIterations;
             Image denoised(width, height);
-            if (despeckle)
+            if (despeckle || meterGiven)
                 hipScheduler->readPresented(nullptr, &p, nullptr, nullptr, denoised.pixels.get(), nullptr, nullptr);
             else if (glareGiven)
                 hipScheduler->readDisplayed(&p, nullptr, nullptr, denoised.pixels.get(), nullptr);
@@ -470,6 +512,13 @@ int main(int argc, char** argv)
             std::printf(", \"tone_scale\": %.9g", (double)s.toneScale);
         if (despeckle)
             std::printf(", \"despeckle_clamped\": %lld, \"despeckle_repaired\": %lld", s.clamped, s.repaired);
+        if (meterGiven) {
+            // (of the image -o holds: run()'s last refresh -- taken before --denoise metered its own frame)
+            std::printf(", \"meter_exposure\": %.9g, \"meter_white\": %.9g, \"meter_anchor\": %.9g, \"meter_metered\": %lld, \"meter_under\": %lld, "
+                        "\"meter_over\": %lld, \"meter_stops\": %.9g",
+                        (double)metered.exposure, (double)metered.whiteL, (double)metered.anchorL, (long long)metered.metered, (long long)metered.under,
+                        (long long)metered.over, metered.metered > 0 ? (metered.maxBin - metered.minBin + 1) / 16.0 : 0.0);
+        }
         if (matteGiven)
             std::printf(", \"matte_samples\": %lld, \"matte_dropped_pixels\": %lld", matteSamples, matteDroppedPixels);
         std::printf("}\n");

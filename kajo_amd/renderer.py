@@ -249,10 +249,44 @@ class HipRenderer:
         capi.check(self._L.kajo_hip_despeckle_counts(self._h, counts))
         return int(counts[0]), int(counts[1])
 
-    def present(self, despeckle: dict = None, denoise: dict = None, glare: dict = None, **tone):
+    def _meter_params(self, percentile: float = None, key: float = None, white_percentile: float = None, auto_white: bool = False):
+        p = capi.KajoMeterParams()
+        self._L.kajo_hip_default_meter_params(C.byref(p))
+        if percentile is not None:
+            p.percentile = float(percentile)
+        if key is not None:
+            p.key = float(key)
+        if white_percentile is not None:
+            p.whitePercentile = float(white_percentile)
+        p.flags = capi.KAJO_METER_AUTO_WHITE if auto_white else 0
+        return p
+
+    @staticmethod
+    def _meter_result(r) -> dict:
+        return {k: getattr(r, k) for k, _ in capi.KajoMeterResult._fields_ if k != "reserved"}
+
+    def meter(self, despeckle: dict = None, denoise: dict = None, glare: dict = None, **params):
+        """The luminance histogram of the frame present() with the same three stages would tone-map, and what it says (include/kajo_hip.h
+        kajo_hip_meter): -> (hist, result), hist = (514,) uint32 -- bin 0 below 2^-16, bins 1..512 sixteen per stop up to 2^16, bin 513
+        above -- and result = a dict of KajoMeterResult's fields (pixels, nonfinite, under, over, metered, anchorL, whiteL, exposure in
+        stops, minBin, maxBin). params: percentile (0.5), key (0.18), white_percentile (0.995), auto_white. The accumulation, the AOVs
+        and the counters are not touched."""
+        m = self._meter_params(**params)
+        s = None if despeckle is None else self._despeckle_params(**despeckle)
+        d = None if denoise is None else self._denoise_params(**denoise)
+        g = None if glare is None else self._glare_params(**glare)
+        hist = np.empty(capi.KAJO_METER_BINS, np.uint32)
+        result = capi.KajoMeterResult()
+        ref = lambda p: None if p is None else C.byref(p)
+        capi.check(self._L.kajo_hip_meter(self._h, ref(s), ref(d), ref(g), C.byref(m), hist.ctypes.data_as(C.c_void_p), C.byref(result)))
+        return hist, self._meter_result(result)
+
+    def present(self, despeckle: dict = None, denoise: dict = None, glare: dict = None, meter: dict = None, **tone):
         """The display chain with the despeckle in front (include/kajo_hip.h kajo_hip_present_argb8): despeckle -> denoise -> glare ->
         tone mapping -> (argb8, scale) as tonemap(), every stage but the last optional. despeckle: a dict of despeckle()'s factor / rank /
-        floor; the rest as display(). With despeckle None it is display(denoise, glare, **tone)."""
+        floor; the rest as display(). With despeckle None it is display(denoise, glare, **tone). meter: a dict of meter()'s params puts
+        the metering in front of the tone curves (kajo_hip_present_metered_argb8: exposure becomes a compensation on top of the metered
+        one, auto_white sets Reinhard's white) and makes the second value the result dict of meter() instead of the scale."""
         t = self._tone_params(**tone)
         s = None if despeckle is None else self._despeckle_params(**despeckle)
         d = None if denoise is None else self._denoise_params(**denoise)
@@ -260,6 +294,12 @@ class HipRenderer:
         argb8 = np.empty((self.height, self.width), np.uint32)
         scale = C.c_float()
         ref = lambda p: None if p is None else C.byref(p)
+        if meter is not None:
+            m = self._meter_params(**meter)
+            result = capi.KajoMeterResult()
+            capi.check(self._L.kajo_hip_present_metered_argb8(self._h, ref(s), ref(d), ref(g), C.byref(m), C.byref(t),
+                                                              argb8.ctypes.data_as(C.c_void_p), C.byref(result)))
+            return argb8, self._meter_result(result)
         capi.check(self._L.kajo_hip_present_argb8(self._h, ref(s), ref(d), ref(g), C.byref(t), argb8.ctypes.data_as(C.c_void_p), C.byref(scale)))
         return argb8, scale.value
 
