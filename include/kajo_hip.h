@@ -35,6 +35,9 @@
  *   kajo_hip_meter           (no counterpart: the reference has no metering) a luminance histogram of the frame in front of the tone
  *                            curves: percentile automatic exposure, automatic white point and the range the frame spans;
  *                            kajo_hip_present_metered_argb8 and its gathered twin put it into the display chain
+ *   kajo_hip_local           (no counterpart: the reference has no local operator) an edge-aware base / detail compression of log
+ *                            luminance between the glare and the meter; kajo_hip_present_local_argb8 and its gathered twin put it into
+ *                            the display chain, kajo_hip_local_pivot reports the pivot used
  *   kajo_hip_destroy         the unique_ptr members of cpu::Scheduler (cpu/Scheduler.h:29-31)
  *
  * Pixels are dealt to GPUs as fixed-size tiles: a handle created with
@@ -562,6 +565,81 @@ int kajo_hip_present_metered_argb8(kajo_hip_t h, const KajoDespeckleParams* desp
 int kajo_hip_present_metered_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle,
                                                    const KajoGlareParams* g, const KajoMeterParams* meter, const KajoToneParams* tone, void* dst,
                                                    KajoMeterResult* result);
+
+/* Local tone mapping: an edge-aware base / detail range compression. Every other stage that maps radiance to the display is global:
+   one exposure and one curve for the whole frame, so a light of emission 445 in a room whose corners sit near 2^-8 either burns out
+   or flattens the floor. This stage compresses the range locally: it splits log luminance into a base layer (an edge-avoiding A-trous
+   filter, Dammertz et al. 2010, used as Durand & Dorsey 2002 use the bilateral) and a detail layer, shrinks the base layer's distance
+   from a pivot and keeps the detail. A post-process over the handle's whole frame, between the glare and the meter, in kernels of its
+   own (kajo_amd/csrc/local.hip) on the handle's stream, in float32 IEEE arithmetic without contraction in every numerics build and in
+   one fixed order: only its inputs depend on FAST / EXACT / STRICT. Frame in, frame out, in the units of kajo_hip_read_radiance.
+   Definition -- P = the handle's pass count, F = the source frame in sums over passes (after whichever of despeckle, denoise and glare
+   are asked for), W x H, row 0 at the top; per pixel:
+     m = F.rgb / P                        (float32 division)
+     the pixel COUNTS where all three channels of m are finite
+     l = (0.2126 max(m.r, 0) + 0.7152 max(m.g, 0)) + 0.0722 max(m.b, 0)      (despeckle's / the meter's expression and order)
+     L = log2(min(max(l, 2^-16), 2^16))   (the meter's range; zero, denormals and an overflowed l are clamped, not dropped)
+   B_0 = L. Iteration i = 0 .. K-1, step d = 2^i, taps q = p + d (dx, dy), dx, dy in -2..2, h = [1/16, 1/4, 3/8, 1/4, 1/16]:
+     w   = (h[dx] h[dy]) w_r,   t = (B_i(p) - B_i(q)) / sigmaRange,   w_r = exp2(-(t t)),  exactly 1 at the centre tap
+     B_{i+1}(p) = sum(w B_i(q)) / sum(w)  over the taps inside the image that count, both sums in row-major tap order (dy outer, dx
+                  inner); no edge clamping, the weights are renormalised over the taps that remain (the centre tap always remains
+                  for a counting p, so sum(w) >= 9/64)
+   then
+     L' = (pivot + compression (B_K - pivot)) + detail (L - B_K)
+     g  = exp2(L' - L)
+     out.rgb = (m g) P  where the pixel counts;   F.rgb with the bits it had where it does not;   out.w = F.w
+   A pixel that does not count is never a tap and comes out with the bits it went in with: the stage never spreads a NaN or Inf. With
+   compression == 1 and detail == 1 the output is F itself and the stage does no device work (as glare does none at strength 0), so
+   every ARGB8 is then the existing call's bit for bit. K = 0 gives B = L: a pure power curve on luminance about the pivot, with no
+   neighbourhood. No atomics and no order between workgroups: the output at a pixel depends on the input frame only, through image
+   coordinates, so the frame is the same bits for any number of tile owners, on a second call and on a twin handle. The accumulation,
+   the AOV buffers, the matte tables, the pass count and the counters (kernelMs included) are not touched. Scratch (three float planes
+   -- L and the two of the ping-pong -- and the output frame) is allocated on first use and freed by kajo_hip_destroy.
+   The pivot is a log2 luminance. With KAJO_LOCAL_PIVOT_METERED the stage takes the meter's histogram (kajo_hip_meter's kernels and
+   definition) of its own input frame, reads it back and uses pivot = log2(value(pivotPercentile)), value(q) as
+   kajo_hip_meter_evaluate defines it, formed on the host in binary64 and rounded to float; with no metered pixel it falls back to the
+   `pivot` field. The range is then compressed about the frame's own median instead of a guess.
+   Refusals (KAJO_E_INVALID, before any device work and before the handle is looked at): NULL params; iterations outside 0..8; an
+   unknown flag bit; a compression that is not finite or outside (0, 1]; a detail that is not finite or outside 0..4; a sigmaRange that
+   is not finite or not above 0; a pivot that is not finite or outside -16..16; a pivotPercentile that is not finite or outside
+   (0, 1] (checked with or without the flag); a non-zero reserved word. Where other stages' parameters are present too, the order
+   is despeckle, glare, local, meter, tone, denoise, handle; then the handle's own state rules (KAJO_E_STATE with no pass rendered,
+   the denoiser's rules with `denoise`). */
+#define KAJO_LOCAL_PIVOT_METERED 1u    /* KajoLocalParams.flags: the pivot is the frame's own pivotPercentile-th luminance */
+typedef struct KajoLocalParams {
+    int32_t iterations;     /* K, 0..8 (default 5) */
+    uint32_t flags;         /* KAJO_LOCAL_* (default 0) */
+    float compression;      /* (0, 1], finite (default 0.6): the factor on the base layer's distance from the pivot, in stops */
+    float detail;           /* 0..4, finite (default 1): the factor on the detail layer */
+    float sigmaRange;       /* > 0, finite, in stops (default 2) */
+    float pivot;            /* finite, -16..16 (default log2(0.18)) */
+    float pivotPercentile;  /* (0, 1] (default 0.5); read only with PIVOT_METERED */
+    float reserved;         /* 0 */
+} KajoLocalParams;          /* 32 bytes */
+void kajo_hip_default_local_params(KajoLocalParams* p); /* NULL is accepted */
+/* The frame after the stage: radiance = HOST pointer to width*height*4 floats (row 0 = top), sums over passes; may be NULL. The frame
+   kajo_hip_present_argb8 with the same first three stages would hand the tone kernels (NULL = the stage is off; with all three NULL
+   the accumulation), then this stage. local == NULL is refused (KAJO_E_INVALID). Valid where kajo_hip_read_radiance is (tileCount 1,
+   or a composed handle). Waits. */
+int kajo_hip_local(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* g,
+                   const KajoLocalParams* local, float* radiance);
+/* kajo_hip_present_metered_argb8 with the stage between the glare and the meter: despeckle -> denoise -> glare -> local -> meter ->
+   tone mapping, every stage but the last optional (NULL). The meter of the chain measures the frame AFTER the stage, so it still
+   sees what the tone kernels are handed; *result (may be NULL) is that measurement, written only with meter != NULL. With local ==
+   NULL exactly kajo_hip_present_metered_argb8: the stage is not run. Waits. */
+int kajo_hip_present_local_argb8(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* g,
+                                 const KajoLocalParams* local, const KajoMeterParams* meter, const KajoToneParams* tone, uint32_t* argb8,
+                                 KajoMeterResult* result);
+/* The multi-GPU twin over gathered tile buffers (NULL = the handle's own when tileCount == 1), into DEVICE memory; the stage needs no
+   AOVs, so it serves any number of owners. Asynchronous on the handle's stream, except that it waits once for the histogram with
+   KAJO_LOCAL_PIVOT_METERED, and once more with `meter`, as kajo_hip_present_metered_gathered_argb8_device already does. With local ==
+   NULL exactly that call. */
+int kajo_hip_present_local_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle, const KajoGlareParams* g,
+                                                 const KajoLocalParams* local, const KajoMeterParams* meter, const KajoToneParams* tone, void* dst,
+                                                 KajoMeterResult* result);
+/* The pivot of the handle's most recent run of the stage (the `pivot` field, or the metered one). KAJO_E_STATE before the first one; a
+   call in which the stage did no device work (compression == 1 and detail == 1) is not a run. */
+int kajo_hip_local_pivot(kajo_hip_t h, float* pivot);
 
 /* Use an existing HIP stream (hipStream_t passed as void*) instead of the handle's own. */
 int kajo_hip_set_stream(kajo_hip_t h, void* stream);

@@ -42,6 +42,7 @@ KAJO_TONE_CLAMP, KAJO_TONE_REINHARD, KAJO_TONE_ACES = 0, 1, 2  # KajoToneParams.
 KAJO_TONE_AUTO_EXPOSURE = 1  # KajoToneParams.flags: scale the frame's log-average luminance to `key`
 KAJO_METER_BINS = 514  # words of a luminance histogram (kajo_hip_meter): bin 0 below 2^-16, 1..512 sixteen per stop, 513 from 2^16 up
 KAJO_METER_AUTO_WHITE = 1  # KajoMeterParams.flags: kajo_hip_meter_tone also sets Reinhard's white from whiteL
+KAJO_LOCAL_PIVOT_METERED = 1  # KajoLocalParams.flags: the pivot is the frame's own pivotPercentile-th luminance
 
 # every symbol include/kajo_hip.h declares
 EXPORTS = [
@@ -57,6 +58,8 @@ EXPORTS = [
     "kajo_hip_despeckle_counts", "kajo_hip_read_matte", "kajo_hip_matte_mask",
     "kajo_hip_default_meter_params", "kajo_hip_meter_evaluate", "kajo_hip_meter_tone", "kajo_hip_meter", "kajo_hip_present_metered_argb8",
     "kajo_hip_present_metered_gathered_argb8_device",
+    "kajo_hip_default_local_params", "kajo_hip_local", "kajo_hip_present_local_argb8", "kajo_hip_present_local_gathered_argb8_device",
+    "kajo_hip_local_pivot",
 ]
 
 
@@ -91,6 +94,11 @@ class KajoMeterResult(C.Structure):
     _fields_ = [("pixels", C.c_int64), ("nonfinite", C.c_int64), ("under", C.c_int64), ("over", C.c_int64), ("metered", C.c_int64),
                 ("anchorL", C.c_float), ("whiteL", C.c_float), ("exposure", C.c_float), ("minBin", C.c_int32), ("maxBin", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class KajoLocalParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("flags", C.c_uint32), ("compression", C.c_float), ("detail", C.c_float), ("sigmaRange", C.c_float),
+                ("pivot", C.c_float), ("pivotPercentile", C.c_float), ("reserved", C.c_float)]
 
 
 class KajoParams(C.Structure):
@@ -206,6 +214,19 @@ def lib():
                                                                          C.POINTER(KajoGlareParams), C.POINTER(KajoMeterParams),
                                                                          C.POINTER(KajoToneParams), C.c_void_p, C.POINTER(KajoMeterResult)]
             L.kajo_meter_groups.argtypes = [C.c_int, C.c_int]
+        if hasattr(L, "kajo_hip_local"):  # (nor the local tone mapping)
+            L.kajo_hip_default_local_params.argtypes = [C.POINTER(KajoLocalParams)]
+            L.kajo_hip_default_local_params.restype = None
+            L.kajo_hip_local.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams), C.POINTER(KajoGlareParams),
+                                         C.POINTER(KajoLocalParams), C.c_void_p]
+            L.kajo_hip_present_local_argb8.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams),
+                                                       C.POINTER(KajoGlareParams), C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams),
+                                                       C.POINTER(KajoToneParams), C.c_void_p, C.POINTER(KajoMeterResult)]
+            L.kajo_hip_present_local_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams),
+                                                                       C.POINTER(KajoGlareParams), C.POINTER(KajoLocalParams),
+                                                                       C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams), C.c_void_p,
+                                                                       C.POINTER(KajoMeterResult)]
+            L.kajo_hip_local_pivot.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         if hasattr(L, "kajo_hip_read_matte"):  # (nor the mattes)
             L.kajo_hip_read_matte.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
             L.kajo_hip_matte_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

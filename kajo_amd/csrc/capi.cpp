@@ -61,6 +61,9 @@ int kajo_despeckle_launch(const void* src, const TileMap* map, int fromTiles, fl
                           void* out, int toTiles, void* partials, void* counts, void* stream);
 int kajo_meter_groups(int W, int H);
 int kajo_meter_launch(const void* src, const TileMap* map, int fromTiles, float passes, void* partials, void* result, void* stream);
+size_t kajo_local_plane(int W, int H);
+int kajo_local_launch(const void* src, const TileMap* map, int fromTiles, float passes, int iterations, float compression, float detail,
+                      float sigmaRange, float pivot, void* planes, void* out, void* stream);
 int kajo_matte_rank_launch(const void* ids, const void* counts, int W, int H, void* rankedIds, void* rankedCounts, void* stream);
 int kajo_matte_mask_launch(const void* ids, const void* counts, int W, int H, const void* selected, unsigned nObjects, float samples, void* mask,
                            void* dominant, void* stream);
@@ -247,6 +250,11 @@ struct KajoHip
     // metering (meter.hip; kajo_hip_meter, kajo_hip_present_metered_*), on its first call: the result (the 514 bins and the count of pixels
     // that do not count, uint32 [kMeterRow], padded to 16 bytes), then the workgroups' partial histograms (meterImage)
     DeviceBuffer meter;
+    // local tone mapping (local.hip; kajo_hip_local, kajo_hip_present_local_*), on its first call: three float planes of kajo_local_plane
+    // (log2 luminance, the two of the ping-pong), then the output frame float4 [W * H]
+    DeviceBuffer local;
+    bool localRun = false; // localPivot is that of a run of the stage (kajo_hip_local_pivot)
+    float localPivot = 0.0f;
     int toneScaleState = 0; // the s of the most recent tone mapping: 0 none yet, 1 toneScale, 2 the scale word (auto exposure)
     float toneScale = 1.0f;
 };
@@ -472,7 +480,7 @@ const char* kajo_hip_last_error(void)
 
 const char* kajo_hip_version(void)
 {
-    return "kajo-hip 0.1 (gfx950; aov-matte)";
+    return "kajo-hip 0.1 (gfx950; aov-matte; local)";
 }
 
 void kajo_hip_default_params(KajoParams* p)
@@ -1931,6 +1939,212 @@ int kajo_hip_present_metered_gathered_argb8_device(kajo_hip_t h, const void* gat
     if ((rc = meterAndPatch(h, img, meter, tone, result, &t))) // (the one wait: include/kajo_hip.h)
         return rc;
     return toneLaunch(h, img, t, dst);
+}
+
+} // extern "C"
+
+namespace
+{
+
+// The refusals of KajoLocalParams (KAJO_E_INVALID), before any device work and before the handle is looked at
+int checkLocal(const KajoLocalParams* p)
+{
+    if (!p)
+        return fail(KAJO_E_INVALID, "null local parameters");
+    if (p->iterations < 0 || p->iterations > 8)
+        return fail(KAJO_E_INVALID, "local iterations must be in [0, 8]");
+    if (p->flags & ~KAJO_LOCAL_PIVOT_METERED)
+        return fail(KAJO_E_INVALID, "unknown local flag");
+    if (!(std::isfinite(p->compression) && p->compression > 0.0f && p->compression <= 1.0f))
+        return fail(KAJO_E_INVALID, "local compression must be finite and in (0, 1]");
+    if (!(std::isfinite(p->detail) && p->detail >= 0.0f && p->detail <= 4.0f))
+        return fail(KAJO_E_INVALID, "local detail must be finite and in [0, 4]");
+    if (!(std::isfinite(p->sigmaRange) && p->sigmaRange > 0.0f))
+        return fail(KAJO_E_INVALID, "local range sigma must be finite and positive");
+    if (!(std::isfinite(p->pivot) && p->pivot >= -16.0f && p->pivot <= 16.0f))
+        return fail(KAJO_E_INVALID, "local pivot must be finite and in [-16, 16]");
+    if (!(std::isfinite(p->pivotPercentile) && p->pivotPercentile > 0.0f && p->pivotPercentile <= 1.0f))
+        return fail(KAJO_E_INVALID, "local pivot percentile must be finite and in (0, 1]");
+    if (p->reserved != 0.0f)
+        return fail(KAJO_E_INVALID, "local reserved fields must be 0");
+    return KAJO_OK;
+}
+
+// Enqueue the local tone mapping of an image (tiles through h->map's geometry, or a row-major frame): *out = the row-major frame in the
+// stage's scratch that holds the result -- or the image itself where the definition makes the output a copy (compression 1 and detail 1).
+// With KAJO_LOCAL_PIVOT_METERED the image is metered first and the histogram waited for. Checked by checkLocal, device bound.
+int localImage(KajoHip* h, const KajoLocalParams* p, Image img, Image* out)
+{
+    if (p->compression == 1.0f && p->detail == 1.0f) {
+        *out = img;
+        return KAJO_OK;
+    }
+    float pivot = p->pivot;
+    if (p->flags & KAJO_LOCAL_PIVOT_METERED) {
+        uint32_t counts[kMeterRow];
+        int rc = meterImage(h, img, counts);
+        if (rc)
+            return rc;
+        KajoMeterParams m;
+        kajo_hip_default_meter_params(&m);
+        m.percentile = p->pivotPercentile;
+        KajoMeterResult r{};
+        if ((rc = kajo_hip_meter_evaluate(counts, &m, &r)))
+            return rc;
+        if (r.metered > 0)
+            pivot = (float)std::log2((double)r.anchorL); // (anchorL = value(pivotPercentile): a bin's centre, exact in float)
+    }
+    const size_t plane = kajo_local_plane(h->W, h->H);
+    HIP_TRY(h->local.ensure(3 * plane * 4 + (size_t)h->W * h->H * 16));
+    void* frame = h->local.as<char>() + 3 * plane * 4;
+    hipError_t le = (hipError_t)kajo_local_launch(img.src, &h->map, img.fromTiles ? 1 : 0, (float)h->passesDone, p->iterations, p->compression,
+                                                  p->detail, p->sigmaRange, pivot, h->local.p, frame, h->stream);
+    if (le != hipSuccess)
+        return failHip(le, "local tone mapping kernel launch");
+    h->localRun = true;
+    h->localPivot = pivot;
+    *out = Image{frame, false};
+    return KAJO_OK;
+}
+
+// the refusals of the local chain calls in front of the handle's: despeckle, glare, local, meter, tone
+int checkLocalChain(const KajoDespeckleParams* despeckle, const KajoGlareParams* g, const KajoLocalParams* local, const KajoMeterParams* meter,
+                    const KajoToneParams* tone, ToneArgs* t)
+{
+    int rc;
+    if (despeckle && (rc = checkDespeckle(despeckle)))
+        return rc;
+    if (g && (rc = checkGlare(g)))
+        return rc;
+    if ((rc = checkLocal(local)))
+        return rc;
+    if (meter && (rc = checkMeter(meter)))
+        return rc;
+    if ((rc = toneArgsOf(tone, t)))
+        return rc;
+    if (meter && (tone->flags & KAJO_TONE_AUTO_EXPOSURE))
+        return fail(KAJO_E_INVALID, "metered exposure and the tone parameters' automatic exposure are two automatic exposures: give one");
+    return KAJO_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void kajo_hip_default_local_params(KajoLocalParams* p)
+{
+    if (!p)
+        return;
+    std::memset(p, 0, sizeof *p);
+    p->iterations = 5;
+    p->flags = 0;
+    p->compression = 0.6f;
+    p->detail = 1.0f;
+    p->sigmaRange = 2.0f;
+    p->pivot = (float)std::log2(0.18);
+    p->pivotPercentile = 0.5f;
+}
+
+int kajo_hip_local(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* g,
+                   const KajoLocalParams* local, float* radiance)
+{
+    // (every refusal before any device work: the despeckle parameters, the glare's, the stage's own, the denoiser's, then the handle)
+    int rc;
+    if (despeckle && (rc = checkDespeckle(despeckle)))
+        return rc;
+    if (g && (rc = checkGlare(g)))
+        return rc;
+    if ((rc = checkLocal(local)))
+        return rc;
+    if (denoise) {
+        if ((rc = checkDenoise(h, denoise)))
+            return rc;
+    } else if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    Image img;
+    if ((rc = imageOf(h, false, nullptr, &img)))
+        return rc;
+    if ((rc = chainImage(h, despeckle, denoise, g, &img)))
+        return rc;
+    if ((rc = localImage(h, local, img, &img)))
+        return rc;
+    if (img.fromTiles) {
+        // (a copy of the accumulation: the composed frame, as kajo_hip_read_radiance)
+        if ((rc = composeOwn(h)))
+            return rc;
+        img = Image{h->frame.p, false};
+    }
+    if (radiance)
+        HIP_TRY(hipMemcpyAsync(radiance, img.src, (size_t)h->W * h->H * 16, hipMemcpyDeviceToHost, h->stream));
+    return kajo_hip_wait(h);
+}
+
+int kajo_hip_present_local_argb8(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* g,
+                                 const KajoLocalParams* local, const KajoMeterParams* meter, const KajoToneParams* tone, uint32_t* argb8,
+                                 KajoMeterResult* result)
+{
+    if (!local)
+        return kajo_hip_present_metered_argb8(h, despeckle, denoise, g, meter, tone, argb8, result);
+    ToneArgs t{};
+    int rc = checkLocalChain(despeckle, g, local, meter, tone, &t);
+    if (rc)
+        return rc;
+    if (denoise) {
+        if ((rc = checkDenoise(h, denoise)))
+            return rc;
+    } else if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    Image img;
+    if ((rc = imageOf(h, false, nullptr, &img)))
+        return rc;
+    const size_t count = (size_t)h->W * h->H;
+    HIP_TRY(h->argb.ensure(count * 4));
+    if ((rc = chainImage(h, despeckle, denoise, g, &img)))
+        return rc;
+    if ((rc = localImage(h, local, img, &img)))
+        return rc;
+    // (the meter measures the frame after the stage: what the tone kernels are handed)
+    if (meter && (rc = meterAndPatch(h, img, meter, tone, result, &t)))
+        return rc;
+    if ((rc = toneLaunch(h, img, t, h->argb.p)))
+        return rc;
+    if (argb8)
+        HIP_TRY(hipMemcpyAsync(argb8, h->argb.p, count * 4, hipMemcpyDeviceToHost, h->stream));
+    return kajo_hip_wait(h);
+}
+
+int kajo_hip_present_local_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle, const KajoGlareParams* g,
+                                                 const KajoLocalParams* local, const KajoMeterParams* meter, const KajoToneParams* tone, void* dst,
+                                                 KajoMeterResult* result)
+{
+    if (!local)
+        return kajo_hip_present_metered_gathered_argb8_device(h, gathered, despeckle, g, meter, tone, dst, result);
+    ToneArgs t{};
+    int rc = checkLocalChain(despeckle, g, local, meter, tone, &t);
+    if (rc)
+        return rc;
+    if (!h || !dst)
+        return fail(KAJO_E_INVALID, "null argument");
+    Image img;
+    if ((rc = imageOf(h, true, gathered, &img)))
+        return rc;
+    if ((rc = chainImage(h, despeckle, nullptr, g, &img)))
+        return rc;
+    if ((rc = localImage(h, local, img, &img))) // (one wait with KAJO_LOCAL_PIVOT_METERED: include/kajo_hip.h)
+        return rc;
+    if (meter && (rc = meterAndPatch(h, img, meter, tone, result, &t))) // (and one more)
+        return rc;
+    return toneLaunch(h, img, t, dst);
+}
+
+int kajo_hip_local_pivot(kajo_hip_t h, float* pivot)
+{
+    if (!h || !pivot)
+        return fail(KAJO_E_INVALID, "null argument");
+    if (!h->localRun)
+        return fail(KAJO_E_STATE, "no local tone mapping yet");
+    *pivot = h->localPivot; // (formed on the host before the launch: nothing to wait for)
+    return KAJO_OK;
 }
 
 int kajo_hip_tone_scale(kajo_hip_t h, float* scale)

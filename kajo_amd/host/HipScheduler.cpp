@@ -82,6 +82,16 @@ struct Scheduler::Impl
     // Options::glare changes the frame (include/kajo_hip.h: with strength 0 or no level the output is the input)
     bool glareOn() const { return opt.glare.strength > 0.0f && opt.glare.levels > 0; }
 
+    // Options::local changes the frame (include/kajo_hip.h: with compression 1 and detail 1 the output is the input)
+    bool localActive() const { return opt.localOn && !(opt.local.compression == 1.0f && opt.local.detail == 1.0f); }
+    bool localRan = false; // lastLocalPivot()
+    float localPivot = 0;
+    void notePivot()
+    {
+        check(kajo_hip_local_pivot(handles[0], &localPivot), "kajo_hip_local_pivot");
+        localRan = true;
+    }
+
     ~Impl()
     {
         for (kajo_hip_t h : handles)
@@ -198,7 +208,13 @@ struct Scheduler::Impl
     {
         if (opt.gpus == 1 && !opt.forceGather) {
             // single owner: the library resolves from its own tile buffer
-            if (opt.meterOn) {
+            if (localActive()) {
+                check(kajo_hip_present_local_argb8(handles[0], opt.despeckleOn ? &opt.despeckle : nullptr, nullptr, glareOn() ? &opt.glare : nullptr,
+                                                   &opt.local, opt.meterOn ? &opt.meter : nullptr, &opt.tone, image->pixels.get(), &metered),
+                      "kajo_hip_present_local_argb8");
+                check(kajo_hip_tone_scale(handles[0], &toneScale), "kajo_hip_tone_scale");
+                notePivot();
+            } else if (opt.meterOn) {
                 check(kajo_hip_present_metered_argb8(handles[0], opt.despeckleOn ? &opt.despeckle : nullptr, nullptr, glareOn() ? &opt.glare : nullptr,
                                                      &opt.meter, &opt.tone, image->pixels.get(), &metered),
                       "kajo_hip_present_metered_argb8");
@@ -238,7 +254,13 @@ struct Scheduler::Impl
             }
         }
         composed = false;
-        if (opt.meterOn)
+        if (localActive()) {
+            check(kajo_hip_present_local_gathered_argb8_device(handles[0], gathered, opt.despeckleOn ? &opt.despeckle : nullptr,
+                                                               glareOn() ? &opt.glare : nullptr, &opt.local, opt.meterOn ? &opt.meter : nullptr,
+                                                               &opt.tone, argbDevice, &metered),
+                  "kajo_hip_present_local_gathered_argb8_device");
+            notePivot();
+        } else if (opt.meterOn)
             check(kajo_hip_present_metered_gathered_argb8_device(handles[0], gathered, opt.despeckleOn ? &opt.despeckle : nullptr,
                                                                  glareOn() ? &opt.glare : nullptr, &opt.meter, &opt.tone, argbDevice, &metered),
                   "kajo_hip_present_metered_gathered_argb8_device");
@@ -255,7 +277,7 @@ struct Scheduler::Impl
         checkHip(hipMemcpyAsync(image->pixels.get(), argbDevice, (size_t)image->width * image->height * 4, hipMemcpyDeviceToHost, streams[0]),
                  "hipMemcpyAsync(image)");
         checkHip(hipStreamSynchronize(streams[0]), "hipStreamSynchronize");
-        if (opt.meterOn || opt.despeckleOn || glareOn() || !toneIsIdentity())
+        if (localActive() || opt.meterOn || opt.despeckleOn || glareOn() || !toneIsIdentity())
             check(kajo_hip_tone_scale(handles[0], &toneScale), "kajo_hip_tone_scale"); // (the stream is drained: no wait left)
     }
     bool composed = false;
@@ -293,6 +315,13 @@ const Statistics& Scheduler::statistics() const
 const KajoMeterResult& Scheduler::lastMeter() const
 {
     return m_impl->metered;
+}
+
+bool Scheduler::lastLocalPivot(float* pivot) const
+{
+    if (m_impl->localRan && pivot)
+        *pivot = m_impl->localPivot;
+    return m_impl->localRan;
 }
 
 void Scheduler::readRadiance(float* dst)
@@ -363,13 +392,20 @@ void Scheduler::readPresented(const KajoDespeckleParams* despeckle, const KajoDe
         despeckle = &d.opt.despeckle;
     if (counts)
         counts[0] = counts[1] = 0;
-    if (!despeckle && !d.opt.meterOn)
+    if (!despeckle && !d.opt.meterOn && !d.localActive())
         return readDisplayed(denoise, glare, tone, argb8, scale);
     if (d.gathered && !d.composed) { // (as readDisplayed)
         check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
         d.composed = true;
     }
-    if (d.opt.meterOn) {
+    if (d.localActive()) {
+        check(kajo_hip_present_local_argb8(d.handles[0], despeckle, denoise, glare ? glare : &d.opt.glare, &d.opt.local,
+                                           d.opt.meterOn ? &d.opt.meter : nullptr, tone ? tone : &d.opt.tone, argb8, &d.metered),
+              "kajo_hip_present_local_argb8");
+        d.notePivot();
+        if (scale)
+            check(kajo_hip_tone_scale(d.handles[0], scale), "kajo_hip_tone_scale");
+    } else if (d.opt.meterOn) {
         check(kajo_hip_present_metered_argb8(d.handles[0], despeckle, denoise, glare ? glare : &d.opt.glare, &d.opt.meter, tone ? tone : &d.opt.tone,
                                              argb8, &d.metered),
               "kajo_hip_present_metered_argb8");

@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "Scheduler.h"
-#include "kajo_hip.h" // KajoToneParams (Options::tone), KajoGlareParams (Options::glare), KajoDespeckleParams (Options::despeckle), KajoMeterParams
+#include "kajo_hip.h" // KajoToneParams (Options::tone), KajoGlareParams (Options::glare), KajoDespeckleParams (Options::despeckle), KajoMeterParams, KajoLocalParams
 
 class Image;
 class Preview;
@@ -81,6 +81,13 @@ struct Options
     // whoever sets meterOn fills `meter` with kajo_hip_default_meter_params first (all zero, as here, is refused, loudly).
     bool meterOn = false;
     KajoMeterParams meter = {};
+    // Local tone mapping between the glare and the meter of the image run() writes (include/kajo_hip.h kajo_hip_present_local_argb8; with
+    // one owner or after the gather): the base layer of log luminance is compressed about `local.pivot`, the detail kept. Off by default:
+    // every frame then takes exactly the calls it takes without these fields; so does one with compression 1 and detail 1, which the
+    // definition makes a copy. A flag beside the parameters, as for the despeckle: whoever sets localOn fills `local` with
+    // kajo_hip_default_local_params first (all zero, as here, is refused, loudly).
+    bool localOn = false;
+    KajoLocalParams local = {};
 };
 
 struct Statistics
@@ -129,12 +136,16 @@ public:
     void readDisplayed(const KajoDenoiseParams* denoise, const KajoGlareParams* glare, const KajoToneParams* tone, uint32_t* argb8, float* scale);
     // the same chain with the despeckle in front (include/kajo_hip.h kajo_hip_present_argb8): despeckle null = Options::despeckle where
     // Options::despeckleOn, else none (then readDisplayed); counts (may be null) = pixels clamped, pixels repaired (0, 0 without the stage).
-    // With Options::meterOn the chain ends in the metered call (kajo_hip_present_metered_argb8) and lastMeter() is its measurement
+    // With Options::meterOn the chain ends in the metered call (kajo_hip_present_metered_argb8) and lastMeter() is its measurement; with
+    // Options::localOn the local tone mapping sits between the glare and the meter (kajo_hip_present_local_argb8)
     void readPresented(const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* glare, const KajoToneParams* tone,
                        uint32_t* argb8, float* scale, long long counts[2]);
 
     // the measurement of the most recent metered image (Options::meterOn: run()'s last refresh, or readPresented); all zero before it
     const KajoMeterResult& lastMeter() const;
+    // the pivot of the most recent local tone mapping (Options::localOn: run()'s last refresh, or readPresented); false where the stage has
+    // not run (off, or a copy by its parameters)
+    bool lastLocalPivot(float* pivot) const;
 
 private:
     struct Impl;

@@ -69,6 +69,8 @@ int main(int argc, char** argv)
     bool despeckle = false;
     // meter options (include/kajo_hip.h KajoMeterParams): the raw text, checked after the loop
     std::string meterExposure, meterWhite;
+    // local tone mapping options (include/kajo_hip.h KajoLocalParams): the raw text, checked after the loop
+    std::string localContrast, localDetail, localRange, localIterations, localPivot;
     int width = 640, height = 480;
     int denoiseIterations = 5;
     hip::Options opt;
@@ -143,7 +145,15 @@ int main(int argc, char** argv)
                         "    --json          print run statistics as one JSON line (with a tone option: the scale applied, tone_scale; with a\n"
                         "                    matte option: matte_samples per pixel and matte_dropped_pixels, the pixels whose table was full; with a\n"
                         "                    meter option: meter_exposure, meter_white, meter_anchor, meter_metered, meter_under, meter_over, meter_stops)\n"
-                        "    -v              progress on stderr\n",
+                        "    -v              progress on stderr\n"
+                        "    --local-contrast C  local tone mapping between the glare and the meter (-o and --denoise; include/kajo_hip.h kajo_hip_local;\n"
+                        "                    any --gpus): the large-scale differences in log luminance are scaled by C, 0 < C <= 1, about the pivot,\n"
+                        "                    the small-scale ones kept (1 = none, the default; --hdr and --raw stay the raw mean)\n"
+                        "    --local-detail D  --local-contrast: the factor on the small-scale differences, 0..4 (1)\n"
+                        "    --local-range STOPS  --local-contrast: differences beyond about this many stops are edges the base layer keeps, > 0 (2)\n"
+                        "    --local-iterations K  --local-contrast: iterations of the edge-aware filter, 0..8 (5): its reach doubles with each\n"
+                        "    --local-pivot STOPS|metered[:Q]  --local-contrast: the log2 luminance that stays put, -16..16 (log2(0.18)), or the frame's own\n"
+                        "                    Q-th percentile, 0 < Q <= 1 (0.5), from the meter's histogram (--json: local_pivot and the parameters used)\n",
                         args[0].c_str());
             return 1;
         } else if (a == "-w" && more) width = std::atoi(args[++i].c_str());
@@ -182,6 +192,11 @@ int main(int argc, char** argv)
         else if (a == "--despeckle-floor" && more) despeckleFloor = args[++i];
         else if (a == "--meter-exposure" && more) meterExposure = args[++i];
         else if (a == "--meter-white" && more) meterWhite = args[++i];
+        else if (a == "--local-contrast" && more) localContrast = args[++i];
+        else if (a == "--local-detail" && more) localDetail = args[++i];
+        else if (a == "--local-range" && more) localRange = args[++i];
+        else if (a == "--local-iterations" && more) localIterations = args[++i];
+        else if (a == "--local-pivot" && more) localPivot = args[++i];
         else if (a == "--aov" && more) aovPrefix = args[++i];
         else if (a == "--aov-specular") aovSpecular = true;
         else if (a == "--matte-mask" && more) matteMaskOut = args[++i];
@@ -314,6 +329,52 @@ int main(int argc, char** argv)
         }
         opt.meter.key = opt.tone.key; // (--key, checked above; 0.18 without)
     }
+    if (localContrast.empty() && (!localDetail.empty() || !localRange.empty() || !localIterations.empty() || !localPivot.empty())) {
+        std::cerr << "kajo_render: --local-detail, --local-range, --local-iterations and --local-pivot shape the stage that --local-contrast turns on: give them with --local-contrast" << std::endl;
+        return 1;
+    }
+    const bool localGiven = !localContrast.empty();
+    if (localGiven) {
+        // (before any device is opened: the refusals of kajo_hip_local, with the option's name)
+        if (threeArg) {
+            std::cerr << "kajo_render: the local tone mapping options need the backend's options (without --three-arg)" << std::endl;
+            return 1;
+        }
+        opt.localOn = true;
+        kajo_hip_default_local_params(&opt.local);
+        if (!parseFloat(localContrast, &opt.local.compression) || opt.local.compression <= 0.0f || opt.local.compression > 1.0f) {
+            std::cerr << "kajo_render: --local-contrast: local compression must be finite and in (0, 1]" << std::endl;
+            return 1;
+        }
+        if (!localDetail.empty() && (!parseFloat(localDetail, &opt.local.detail) || opt.local.detail < 0.0f || opt.local.detail > 4.0f)) {
+            std::cerr << "kajo_render: --local-detail: local detail must be finite and in [0, 4]" << std::endl;
+            return 1;
+        }
+        if (!localRange.empty() && (!parseFloat(localRange, &opt.local.sigmaRange) || opt.local.sigmaRange <= 0.0f)) {
+            std::cerr << "kajo_render: --local-range: local range sigma must be finite and positive" << std::endl;
+            return 1;
+        }
+        if (!localIterations.empty()) {
+            char* end = nullptr;
+            const long n = std::strtol(localIterations.c_str(), &end, 10);
+            if (*end != '\0' || n < 0 || n > 8) {
+                std::cerr << "kajo_render: --local-iterations: local iterations must be in [0, 8]" << std::endl;
+                return 1;
+            }
+            opt.local.iterations = (int32_t)n;
+        }
+        if (localPivot.compare(0, 7, "metered") == 0 && (localPivot.size() == 7 || localPivot[7] == ':')) {
+            opt.local.flags |= KAJO_LOCAL_PIVOT_METERED;
+            if (localPivot.size() > 7 && (!parseFloat(localPivot.substr(8), &opt.local.pivotPercentile) || opt.local.pivotPercentile <= 0.0f ||
+                                          opt.local.pivotPercentile > 1.0f)) {
+                std::cerr << "kajo_render: --local-pivot metered:Q: local pivot percentile must be finite and in (0, 1]" << std::endl;
+                return 1;
+            }
+        } else if (!localPivot.empty() && (!parseFloat(localPivot, &opt.local.pivot) || opt.local.pivot < -16.0f || opt.local.pivot > 16.0f)) {
+            std::cerr << "kajo_render: --local-pivot: local pivot must be finite and in [-16, 16], or metered[:Q]" << std::endl;
+            return 1;
+        }
+    }
     const bool matteGiven = !matteMaskOut.empty() || !matteIdsOut.empty();
     if (aovSpecular && aovPrefix.empty() && denoiseOut.empty() && !matteGiven) {
         std::cerr << "kajo_render: --aov-specular changes the AOVs that --aov writes and --denoise is guided by: give it with --aov or --denoise" << std::endl;
@@ -397,6 +458,8 @@ int main(int argc, char** argv)
     opt.counters = json;
     long long matteSamples = 0, matteDroppedPixels = 0; // --json with a matte option
     KajoMeterResult metered = {};                       // --json with a meter option: of the image run() wrote
+    float localPivotUsed = 0;                           // --json with --local-contrast: of the image run() wrote
+    bool localRan = false;
     try {
         if (rendererName == "hip") {
             // (--three-arg: the statement integration/apply_to_kajo.sh adds to renderer/Main.cpp:135-142, word for word)
@@ -410,6 +473,8 @@ int main(int argc, char** argv)
         scheduler->run();
         if (hipScheduler && meterGiven)
             metered = hipScheduler->lastMeter();
+        if (hipScheduler && localGiven)
+            localRan = hipScheduler->lastLocalPivot(&localPivotUsed);
         if (!rawOut.empty()) {
             std::vector<float> acc((size_t)width * height * 4);
             hipScheduler->readRadiance(acc.data());
@@ -471,7 +536,7 @@ int main(int argc, char** argv)
             kajo_hip_default_denoise_params(&p);
             p.iterations = denoiseIterations;
             Image denoised(width, height);
-            if (despeckle || meterGiven)
+            if (despeckle || meterGiven || localGiven)
                 hipScheduler->readPresented(nullptr, &p, nullptr, nullptr, denoised.pixels.get(), nullptr, nullptr);
             else if (glareGiven)
                 hipScheduler->readDisplayed(&p, nullptr, nullptr, denoised.pixels.get(), nullptr);
@@ -518,6 +583,17 @@ int main(int argc, char** argv)
                         "\"meter_over\": %lld, \"meter_stops\": %.9g",
                         (double)metered.exposure, (double)metered.whiteL, (double)metered.anchorL, (long long)metered.metered, (long long)metered.under,
                         (long long)metered.over, metered.metered > 0 ? (metered.maxBin - metered.minBin + 1) / 16.0 : 0.0);
+        }
+        if (localGiven) {
+            // (local_pivot: of the image -o holds; null where the parameters make the stage a copy and it did not run)
+            std::printf(", \"local_compression\": %.9g, \"local_detail\": %.9g, \"local_range\": %.9g, \"local_iterations\": %d, "
+                        "\"local_pivot_metered\": %s, \"local_pivot_percentile\": %.9g, \"local_pivot\": ",
+                        (double)opt.local.compression, (double)opt.local.detail, (double)opt.local.sigmaRange, (int)opt.local.iterations,
+                        (opt.local.flags & KAJO_LOCAL_PIVOT_METERED) ? "true" : "false", (double)opt.local.pivotPercentile);
+            if (localRan)
+                std::printf("%.9g", (double)localPivotUsed);
+            else
+                std::printf("null");
         }
         if (matteGiven)
             std::printf(", \"matte_samples\": %lld, \"matte_dropped_pixels\": %lld", matteSamples, matteDroppedPixels);

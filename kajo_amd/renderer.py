@@ -281,12 +281,47 @@ class HipRenderer:
         capi.check(self._L.kajo_hip_meter(self._h, ref(s), ref(d), ref(g), C.byref(m), hist.ctypes.data_as(C.c_void_p), C.byref(result)))
         return hist, self._meter_result(result)
 
-    def present(self, despeckle: dict = None, denoise: dict = None, glare: dict = None, meter: dict = None, **tone):
+    def _local_params(self, compression: float = None, detail: float = None, sigma_range: float = None, iterations: int = None,
+                      pivot: float = None, metered: bool = False, pivot_percentile: float = None):
+        p = capi.KajoLocalParams()
+        self._L.kajo_hip_default_local_params(C.byref(p))
+        for field, value in (("compression", compression), ("detail", detail), ("sigmaRange", sigma_range), ("pivot", pivot),
+                             ("pivotPercentile", pivot_percentile)):
+            if value is not None:
+                setattr(p, field, float(value))
+        if iterations is not None:
+            p.iterations = int(iterations)
+        p.flags = capi.KAJO_LOCAL_PIVOT_METERED if metered else 0
+        return p
+
+    def local(self, despeckle: dict = None, denoise: dict = None, glare: dict = None, **params) -> np.ndarray:
+        """The frame after the local tone mapping (include/kajo_hip.h kajo_hip_local): (H, W, 4) float32 sums over passes, as radiance().
+        params: compression (0.6), detail (1), sigma_range (2 stops), iterations (5), pivot (log2(0.18)), metered (the pivot is the
+        frame's own pivot_percentile-th luminance, 0.5); those left out take kajo_hip_default_local_params' values. despeckle, denoise,
+        glare: the stages in front, as present(). The accumulation, the AOVs and the counters are not touched."""
+        l = self._local_params(**params)
+        s = None if despeckle is None else self._despeckle_params(**despeckle)
+        d = None if denoise is None else self._denoise_params(**denoise)
+        g = None if glare is None else self._glare_params(**glare)
+        out = np.empty((self.height, self.width, 4), np.float32)
+        ref = lambda p: None if p is None else C.byref(p)
+        capi.check(self._L.kajo_hip_local(self._h, ref(s), ref(d), ref(g), C.byref(l), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def local_pivot(self) -> float:
+        """The pivot (log2 luminance) of the most recent local tone mapping (include/kajo_hip.h kajo_hip_local_pivot)."""
+        pivot = C.c_float()
+        capi.check(self._L.kajo_hip_local_pivot(self._h, C.byref(pivot)))
+        return pivot.value
+
+    def present(self, despeckle: dict = None, denoise: dict = None, glare: dict = None, meter: dict = None, local: dict = None, **tone):
         """The display chain with the despeckle in front (include/kajo_hip.h kajo_hip_present_argb8): despeckle -> denoise -> glare ->
         tone mapping -> (argb8, scale) as tonemap(), every stage but the last optional. despeckle: a dict of despeckle()'s factor / rank /
         floor; the rest as display(). With despeckle None it is display(denoise, glare, **tone). meter: a dict of meter()'s params puts
         the metering in front of the tone curves (kajo_hip_present_metered_argb8: exposure becomes a compensation on top of the metered
-        one, auto_white sets Reinhard's white) and makes the second value the result dict of meter() instead of the scale."""
+        one, auto_white sets Reinhard's white) and makes the second value the result dict of meter() instead of the scale. local: a dict
+        of local()'s params puts the local tone mapping between the glare and the meter (kajo_hip_present_local_argb8; the call is
+        routed there only when it is given)."""
         t = self._tone_params(**tone)
         s = None if despeckle is None else self._despeckle_params(**despeckle)
         d = None if denoise is None else self._denoise_params(**denoise)
@@ -294,6 +329,13 @@ class HipRenderer:
         argb8 = np.empty((self.height, self.width), np.uint32)
         scale = C.c_float()
         ref = lambda p: None if p is None else C.byref(p)
+        if local is not None:
+            l = self._local_params(**local)
+            m = None if meter is None else self._meter_params(**meter)
+            result = capi.KajoMeterResult()
+            capi.check(self._L.kajo_hip_present_local_argb8(self._h, ref(s), ref(d), ref(g), C.byref(l), ref(m), C.byref(t),
+                                                            argb8.ctypes.data_as(C.c_void_p), C.byref(result)))
+            return argb8, (self.tone_scale() if m is None else self._meter_result(result))
         if meter is not None:
             m = self._meter_params(**meter)
             result = capi.KajoMeterResult()
