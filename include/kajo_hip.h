@@ -110,7 +110,8 @@ extern "C" {
 #define KAJO_FLAG_AOV 1024u   /* first-hit AOVs for denoisers (kajo_hip_read_aov): create() allocates and zeroes two whole-frame float4 buffers
                                    (2 x W x H x 16 bytes) and every kajo_hip_render enqueues one more kernel per render launch, on the handle's
                                    stream, over the same passes' camera samples. Whole frame on one handle only: with tileCount != 1 create()
-                                   refuses the flag (KAJO_E_INVALID). Without it nothing is allocated or launched. */
+                                   refuses the flag (KAJO_E_INVALID) unless KAJO_FLAG_AOV_TILED is set with it. Without it nothing is
+                                   allocated or launched. */
 #define KAJO_FLAG_AOV_SPECULAR 2048u /* with KAJO_FLAG_AOV only (alone: KAJO_E_INVALID at create, before a device is looked for): the AOVs are
                                    taken at the first NON-DELTA hit -- camera rays are followed through ideal mirrors and glass by the
                                    deterministic chain defined at kajo_hip_read_aov, so that the guides show what the mirror shows. The
@@ -124,6 +125,14 @@ extern "C" {
                                    ..._matte...), still one per render launch and one scene walk per sample. Handles without the flag
                                    launch what they launched before. */
 #define KAJO_MATTE_SLOTS 8        /* (id, count) pairs per pixel */
+#define KAJO_FLAG_AOV_TILED 8192u /* with KAJO_FLAG_AOV only (alone: KAJO_E_INVALID at create, before a device is looked for): tiled AOVs, for
+                                   any tileIndex / tileCount. The handle keeps the AOV sums (and with KAJO_FLAG_AOV_MATTE the coverage tables)
+                                   of its OWN tiles only, in the tile layout of the accumulation, and its AOV kernel runs over those tiles;
+                                   the whole-frame buffers every AOV reader takes are formed by kajo_hip_compose_aov from the owners'
+                                   gathered tile buffers (kajo_hip_aov_tile_buffers). Combines with KAJO_FLAG_AOV_SPECULAR and
+                                   KAJO_FLAG_AOV_MATTE; the same kernel instances (kajo_hip_aov_kernel). The frame of such a handle is
+                                   at most 524288 x 262144 pixels, a tile at most 524280 a side (KAJO_E_INVALID). Handles without the
+                                   flag allocate, launch and refuse what they did before. */
 
 typedef struct KajoParams {
     int32_t samplesPerPass; /* S: nominal samples per pixel per pass (reference: 32, Renderer.cpp:21);
@@ -279,6 +288,36 @@ const char* kajo_hip_aov_kernel(kajo_hip_t h);
    the first call; the accumulation, the AOV buffers, the pass count and the counters (kernelMs included) are not touched. */
 int kajo_hip_read_matte(kajo_hip_t h, int32_t* ids, uint32_t* counts, int64_t* samples);
 int kajo_hip_matte_mask(kajo_hip_t h, const int32_t* objects, int n, float* mask, float* dominant);
+
+/* Tiled AOVs (KAJO_FLAG_AOV_TILED with KAJO_FLAG_AOV). A pixel's AOV sums and its coverage table are formed by one lane, sample after sample in
+   pass order and then stratum order, from streams keyed by the pixel's index in the whole frame: they are the same words whoever owns the
+   pixel's tile. A tiled handle keeps them for its own tiles:
+     the AOV tile buffer    float4 A[slotsPerOwner] (albedo.rgb sums, hits) followed by float4 B[slotsPerOwner] (normal.xyz sums, depth sum)
+     the matte tile buffer  (KAJO_FLAG_AOV_MATTE) uint4 ids[slotsPerOwner][2] followed by uint4 counts[slotsPerOwner][2], first-come order
+   a pixel at the slot it has in the accumulation's tile buffer (kajo_hip_tile_buffer; slotsPerOwner = its bytes / 16). Both have the same
+   size on every owner, padding included; they are zeroed at create and by kajo_hip_reset, and the padding (slots of no pixel: tiles cut by
+   the frame's edges, owners with a tile fewer) stays zero. An owner without a tile launches no AOV kernel. kajo_hip_set_pass_count leaves
+   them alone.
+   kajo_hip_aov_tile_buffers: the DEVICE pointers and sizes, for one gather per buffer: *aovBytes = 2 * slotsPerOwner * 16, *matteBytes =
+   slotsPerOwner * 64; without the matte flag *matte = NULL and *matteBytes = 0. Any out pointer may be NULL. KAJO_E_INVALID on a NULL
+   handle, KAJO_E_STATE on a handle without KAJO_FLAG_AOV_TILED.
+   kajo_hip_compose_aov: on any handle with the flag ("the root"), scatters gathered tile buffers into whole-frame row-major buffers in the
+   one-owner handle's layout (W x H x 32 bytes of sums, W x H x 64 bytes of tables, allocated on the root at the first call), with one
+   kernel on the handle's stream; asynchronous. gatheredAov / gatheredMatte: DEVICE pointers to tileCount consecutive AOV / matte tile
+   buffers in rank order; NULL = the handle's own buffer when tileCount is 1, while with tileCount > 1 a NULL gatheredAov is KAJO_E_INVALID
+   and a NULL gatheredMatte on a matte handle composes the sums only (the matte readers then stay KAJO_E_STATE). gatheredMatte is ignored
+   without the matte flag. The call DECLARES that the gathered buffers hold the root's own AOV pass count, as kajo_hip_set_pass_count
+   declares for the accumulation: *samples of the readers is reported from that count. KAJO_E_INVALID on a NULL handle, KAJO_E_STATE on a
+   handle without the flag.
+   After it -- and after kajo_hip_compose for the float frame where the accumulation is read (tileCount > 1) -- kajo_hip_read_aov,
+   kajo_hip_read_matte, kajo_hip_matte_mask, kajo_hip_denoise and the `denoise` argument of kajo_hip_tonemap_argb8, kajo_hip_glare,
+   kajo_hip_display_argb8, kajo_hip_present_argb8, kajo_hip_meter, kajo_hip_present_metered_argb8, kajo_hip_local and
+   kajo_hip_present_local_argb8 behave on the root exactly as on a one-owner handle without the flag that rendered the same passes. On a
+   tiled handle (tileCount 1 too) they give KAJO_E_STATE before the first kajo_hip_compose_aov and again after any kajo_hip_render of at
+   least one pass or kajo_hip_reset that followed the last one. The accumulation, the tile buffers, the pass count and the counters
+   (kernelMs included) are not touched by either call; the whole-frame buffers are freed by kajo_hip_destroy. */
+int kajo_hip_aov_tile_buffers(kajo_hip_t h, void** aov, size_t* aovBytes, void** matte, size_t* matteBytes);
+int kajo_hip_compose_aov(kajo_hip_t h, const void* gatheredAov, const void* gatheredMatte);
 
 /* Edge-aware A-trous denoiser (Dammertz et al. 2010) guided by the first-hit AOVs, its luminance weight scaled by a spatial variance
    estimate (the spatial part of SVGF, Schied et al. 2017). A post-process over the handle's whole frame, in kernels of its own

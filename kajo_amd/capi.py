@@ -36,6 +36,7 @@ KAJO_FLAG_EXACT = 512  # decision-exact numerics: STRICT's decisions, FAST's rad
 KAJO_FLAG_AOV = 1024  # first-hit albedo / normal / depth buffers over the beauty render's camera samples (kajo_hip_read_aov)
 KAJO_FLAG_AOV_SPECULAR = 2048  # with KAJO_FLAG_AOV: the buffers are taken at the first non-delta hit, through ideal mirrors and glass
 KAJO_FLAG_AOV_MATTE = 4096  # with KAJO_FLAG_AOV: per-pixel (object id, sample count) tables over the AOVs' samples (kajo_hip_read_matte)
+KAJO_FLAG_AOV_TILED = 8192  # with KAJO_FLAG_AOV: the sums of the handle's own tiles, any tileIndex / tileCount (kajo_hip_compose_aov)
 KAJO_MATTE_SLOTS = 8
 KAJO_DENOISE_NO_DEMODULATE = 1  # KajoDenoiseParams.flags: filter the mean radiance itself, not radiance / albedo
 KAJO_TONE_CLAMP, KAJO_TONE_REINHARD, KAJO_TONE_ACES = 0, 1, 2  # KajoToneParams.curve
@@ -60,6 +61,7 @@ EXPORTS = [
     "kajo_hip_present_metered_gathered_argb8_device",
     "kajo_hip_default_local_params", "kajo_hip_local", "kajo_hip_present_local_argb8", "kajo_hip_present_local_gathered_argb8_device",
     "kajo_hip_local_pivot",
+    "kajo_hip_aov_tile_buffers", "kajo_hip_compose_aov",
 ]
 
 
@@ -230,6 +232,10 @@ def lib():
         if hasattr(L, "kajo_hip_read_matte"):  # (nor the mattes)
             L.kajo_hip_read_matte.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
             L.kajo_hip_matte_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        if hasattr(L, "kajo_hip_compose_aov"):  # (nor the tiled AOVs)
+            L.kajo_hip_aov_tile_buffers.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                                    C.POINTER(C.c_size_t)]
+            L.kajo_hip_compose_aov.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.kajo_hip_kat_trace.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
         L.kajo_hip_kat_shade.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.kajo_hip_kat_strictmath.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -2,7 +2,8 @@
 // kernel_fast.hip behind integrator.inc.hip: the SAME device functions (stageToLds, trace, hitNormal) on the beauty render's own camera
 // samples. The STRICT instance serves STRICT and EXACT handles: EXACT's camera rays, walk and normals are STRICT's arithmetic.
 //
-// Shape: one wave per 8x8 pixel block and one lane per pixel, as in the render kernels, so that a wave's camera rays stay coherent. A lane
+// Shape: one wave per 8x8 pixel block and one lane per pixel, as in the render kernels, so that a wave's camera rays stay coherent (the
+// blocks of the whole frame, or with AovArgs::tiledBlocks those of the handle's own tiles: aovBody). A lane
 // reads its pixel's two float4 sums, adds its samples one at a time -- pass order, then stratum sy * n + sx -- and writes them back: the
 // sequential loop is what fixes the summation order, so the buffers do not depend on how the passes were cut into launches.
 // Per sample: hit = id != 0; albedo = clamp((diffuse + specular) + transparency, 0, 1) of the hit object's material (the three lobe colours
@@ -134,24 +135,49 @@ template <bool COLD_LDS, bool LISTS = false, int GHOME = 0, bool FOLLOW = false,
 KDEV void aovBody(const AovArgs& args, unsigned char* ldsRaw)
 {
     const DSceneView& sc = args.scene;
-    const LdsScene lds = stageToLds<COLD_LDS>(sc, ldsRaw);
     const int lane = threadIdx.x & 63;
     const int block = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6))); // (wave-uniform)
+    // The wave's 8x8 pixel block and where its sums live. Whole-frame buffers: the blocks of the frame in row order, a pixel's sums at its
+    // row-major index. TILED (KAJO_FLAG_AOV_TILED): the blocks of the handle's OWN tiles in the order of the accumulation's tile buffer
+    // (integrator.inc.hip: owned tile, then wave block inside the tile), a pixel's sums at kajoTileSlot's slot = block * 64 + lane -- a wave's
+    // 64 float4 are contiguous. The arithmetic is the wave's, not the lane's: it stays in scalar registers.
+    // The tiled shape is worked out IN FRONT of the scene's staging and leaves ONE scalar register behind, `where`: the block's corner in
+    // units of 8 pixels, x | y << 16 (capi.cpp bounds the frame of a tiled handle accordingly), -1 = whole-frame buffers, -2 = a wave beyond
+    // the owner's blocks. The large-scene instances have no scalar register to spare while they stage, and none was to be added to them.
+    int where = -1;
+    if (args.tiledBlocks) {
+        where = -2;
+        if (block < args.tiledBlocks) {
+            const int wavesX = (int)(args.tileWaves & 0xffffu), wavesY = (int)(args.tileWaves >> 16), wavesPerTile = wavesX * wavesY;
+            const int tilesX = (args.W + wavesX * 8 - 1) / (wavesX * 8);
+            const int ownedTile = block / wavesPerTile, wb = block - ownedTile * wavesPerTile;
+            const int tile = args.tileIndex + ownedTile * args.tileCount;
+            const int ty = tile / tilesX, by = wb / wavesX;
+            where = ((tile - ty * tilesX) * wavesX + (wb - by * wavesX)) | ((ty * wavesY + by) << 16);
+        }
+    }
+    where = __builtin_amdgcn_readfirstlane(where);
+    const LdsScene lds = stageToLds<COLD_LDS>(sc, ldsRaw);
+    // (the grid's last workgroup may have waves beyond the blocks: they leave here, past the last barrier)
+    const bool tiled = where >= 0;
     const int blocksX = (args.W + 7) >> 3;
-    if (block >= blocksX * ((args.H + 7) >> 3)) // (the grid's last workgroup may have waves beyond the frame: past the last barrier)
+    if (tiled ? false : where == -2 || block >= blocksX * ((args.H + 7) >> 3))
         return;
-    const int px = (block % blocksX) * 8 + (lane & 7), py = (block / blocksX) * 8 + (lane >> 3);
+    const int x0 = tiled ? (where & 0xffff) * 8 : (block % blocksX) * 8;
+    const int y0 = tiled ? (where >> 16) * 8 : (block / blocksX) * 8;
+    const int px = x0 + (lane & 7), py = y0 + (lane >> 3);
     const bool inImage = px < args.W && py < args.H;
-    const size_t at = inImage ? (size_t)py * args.W + px : 0;
+    // (x0 and y0 are multiples of 8: the pixel's low bits are its lane)
+    const size_t at = !inImage ? 0 : tiled ? (size_t)block * 64 + (size_t)(((py & 7) << 3) | (px & 7)) : (size_t)py * args.W + px;
     float4* const albedoHits = static_cast<float4*>(args.albedoHits);
-    float4* const normalDepth = static_cast<float4*>(args.normalDepth);
+    float4* const normalDepth = albedoHits + args.slots;
     float4 A = make_float4(0.0f, 0.0f, 0.0f, 0.0f), B = A;
     if (inImage) {
         A = albedoHits[at];
         B = normalDepth[at];
     }
     uint4* const matteIds = static_cast<uint4*>(args.matteIds);
-    uint4* const matteCounts = static_cast<uint4*>(args.matteCounts);
+    uint4* const matteCounts = matteIds + 2 * (size_t)args.slots;
     uint4 i0 = make_uint4(0u, 0u, 0u, 0u), i1 = i0, c0 = i0, c1 = i0;
     if (MATTE && inImage) {
         i0 = matteIds[2 * at];

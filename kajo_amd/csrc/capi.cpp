@@ -50,8 +50,8 @@ int kajo_aov_fast_launch(const AovArgs*, int instance, unsigned grid, size_t lds
 int kajo_aov_strict_launch(const AovArgs*, int instance, unsigned grid, size_t lds, void* stream);
 int kajo_aov_fast_set_lds(int instance, size_t lds);
 int kajo_aov_strict_set_lds(int instance, size_t lds);
-int kajo_denoise_launch(const void* tiles, const TileMap* map, const void* albedoHits, const void* normalDepth, float passes, float samples,
-                        int iterations, int demodulate, float sigmaLuminance, float sigmaNormal, float sigmaDepth, void* scratch, void** result,
+int kajo_denoise_launch(const void* src, const TileMap* map, int fromTiles, const void* albedoHits, const void* normalDepth, float passes,
+                        float samples, int iterations, int demodulate, float sigmaLuminance, float sigmaNormal, float sigmaDepth, void* scratch, void** result,
                         void* stream);
 int kajo_glare_plan(int W, int H, int levels, size_t* pixels);
 int kajo_glare_launch(const void* src, const TileMap* map, int fromTiles, float passes, int n, float strength, float threshold, void* scratch,
@@ -64,6 +64,7 @@ int kajo_meter_launch(const void* src, const TileMap* map, int fromTiles, float 
 size_t kajo_local_plane(int W, int H);
 int kajo_local_launch(const void* src, const TileMap* map, int fromTiles, float passes, int iterations, float compression, float detail,
                       float sigmaRange, float pivot, void* planes, void* out, void* stream);
+int kajo_compose_aov_launch(const void* gatheredAov, const void* gatheredMatte, const TileMap* map, void* aov, void* matte, void* stream);
 int kajo_matte_rank_launch(const void* ids, const void* counts, int W, int H, void* rankedIds, void* rankedCounts, void* stream);
 int kajo_matte_mask_launch(const void* ids, const void* counts, int W, int H, const void* selected, unsigned nObjects, float samples, void* mask,
                            void* dominant, void* stream);
@@ -233,6 +234,12 @@ struct KajoHip
     // object-coverage mattes (KAJO_FLAG_AOV_MATTE; aov.inc.hip MATTE): uint4 [W * H][2] ids, then uint4 [W * H][2] counts, row-major; a slot with
     // count 0 is empty. Filled over the AOVs' samples (aovPasses counts them too)
     DeviceBuffer matte;
+    // tiled AOVs (KAJO_FLAG_AOV_TILED): the sums and tables of the handle's OWN tiles in the accumulation's tile layout -- float4 [2][slotsPerOwner]
+    // and uint4 [2][slotsPerOwner][2] -- are what the AOV kernel adds to; `aov` and `matte` above are then the composed whole frame, allocated
+    // by the first kajo_hip_compose_aov and valid (aovComposed, matteComposed) until the next render or reset
+    bool aovTiled = false;
+    DeviceBuffer aovTiles, matteTiles;
+    bool aovComposed = false, matteComposed = false;
     // the matte readers' scratch (matte.hip; kajo_hip_read_matte, kajo_hip_matte_mask), on the first call: the ranked tables int32 [W * H][8]
     // + uint32 [W * H][8], the mask and the dominant id float [2][W * H], the bitset of selected ids
     DeviceBuffer matteScratch;
@@ -426,6 +433,38 @@ size_t matteScratchBytes(const KajoHip* h)
     return matteTableBytes(h) + 2 * count * sizeof(float) + matteBitsetWords(h) * sizeof(uint32_t);
 }
 
+// bytes of a tiled handle's AOV tile buffer and of its matte tile buffer (the same on every owner, padding included)
+size_t aovTileBytes(const KajoHip* h)
+{
+    return 2 * (size_t)h->map.slotsPerOwner * 16;
+}
+
+size_t matteTileBytes(const KajoHip* h)
+{
+    return (size_t)h->map.slotsPerOwner * KAJO_MATTE_SLOTS * 8;
+}
+
+// The whole-frame AOV sums are at hand: the refusals of their readers, `unflagged` for a handle without the AOV flag. A tiled handle
+// (KAJO_FLAG_AOV_TILED) has them from kajo_hip_compose_aov until the next render or reset.
+int aovReady(const KajoHip* h, const char* unflagged)
+{
+    if (!(h->params.flags & KAJO_FLAG_AOV))
+        return fail(KAJO_E_STATE, unflagged);
+    if (h->aovTiled && !h->aovComposed)
+        return fail(KAJO_E_STATE, "a handle with tiled AOVs has the whole-frame AOVs only after kajo_hip_compose_aov() of the passes rendered so far");
+    return KAJO_OK;
+}
+
+// ... and the whole-frame coverage tables
+int matteReady(const KajoHip* h)
+{
+    if (!(h->params.flags & KAJO_FLAG_AOV_MATTE))
+        return fail(KAJO_E_STATE, "the handle was created without the matte flag: no coverage tables to read");
+    if (h->aovTiled && !h->matteComposed)
+        return fail(KAJO_E_STATE, "a handle with tiled AOVs has the whole-frame coverage tables only after kajo_hip_compose_aov() with the matte tile buffers");
+    return KAJO_OK;
+}
+
 // An image to resolve or tone-map: a tile buffer through h->map's geometry, or the row-major frame
 struct Image
 {
@@ -480,7 +519,7 @@ const char* kajo_hip_last_error(void)
 
 const char* kajo_hip_version(void)
 {
-    return "kajo-hip 0.1 (gfx950; aov-matte; local)";
+    return "kajo-hip 0.1 (gfx950; aov-matte; local; aov-tiled)";
 }
 
 void kajo_hip_default_params(KajoParams* p)
@@ -621,12 +660,17 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
         return fail(KAJO_E_INVALID, "tile size must be multiples of 8 with tileW*tileH a multiple of 256");
     if (p.tileCount < 1 || p.tileIndex < 0 || p.tileIndex >= p.tileCount)
         return fail(KAJO_E_INVALID, "tileIndex/tileCount out of range");
-    if ((p.flags & KAJO_FLAG_AOV) && p.tileCount != 1)
+    if ((p.flags & KAJO_FLAG_AOV) && !(p.flags & KAJO_FLAG_AOV_TILED) && p.tileCount != 1)
         return fail(KAJO_E_INVALID, "first-hit AOVs need the whole frame on one handle (tileCount 1)");
     if ((p.flags & KAJO_FLAG_AOV_SPECULAR) && !(p.flags & KAJO_FLAG_AOV))
         return fail(KAJO_E_INVALID, "the first-non-delta-hit flag changes what the AOV flag's buffers hold: set the AOV flag with it");
     if ((p.flags & KAJO_FLAG_AOV_MATTE) && !(p.flags & KAJO_FLAG_AOV))
         return fail(KAJO_E_INVALID, "the matte flag keeps its coverage tables over the AOV flag's samples: set the AOV flag with it");
+    if ((p.flags & KAJO_FLAG_AOV_TILED) && !(p.flags & KAJO_FLAG_AOV))
+        return fail(KAJO_E_INVALID, "the tiled flag changes where the AOV flag's sums are kept: set the AOV flag with it");
+    // (aov.inc.hip: a wave of the tiled launch carries its block's corner and the tile's shape in 16-bit fields, in units of 8 pixels)
+    if ((p.flags & KAJO_FLAG_AOV_TILED) && (width > 524288 || height > 262144 || p.tileW > 524280 || p.tileH > 524280))
+        return fail(KAJO_E_INVALID, "tiled AOVs: the frame must be within 524288 x 262144 and a tile within 524280 pixels a side");
 
     if (p.flags & (KAJO_FLAG_STRICT | KAJO_FLAG_EXACT)) {
         // integrator.inc.hip kdiv / ksqrt: the IEEE quotient and root without the compiler's range scaling are exact while operands stay
@@ -777,13 +821,24 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
         h->aovLds = h->lds.coldInLds ? h->lds.ldsBytes : h->lds.hotBytes;
         if (h->aovLds > 48 * 1024)
             CREATE_TRY((hipError_t)h->k->aovSetLds(h->aovInstance, h->aovLds));
-        const size_t bytes = 2 * (size_t)width * height * 16;
-        CREATE_TRY(h->aov.alloc(bytes));
-        CREATE_TRY(hipMemsetAsync(h->aov.p, 0, bytes, h->stream));
-        if (p.flags & KAJO_FLAG_AOV_MATTE) {
-            const size_t tables = matteTableBytes(h);
-            CREATE_TRY(h->matte.alloc(tables));
-            CREATE_TRY(hipMemsetAsync(h->matte.p, 0, tables, h->stream));
+        h->aovTiled = (p.flags & KAJO_FLAG_AOV_TILED) != 0;
+        if (h->aovTiled) {
+            // the sums of the handle's own tiles only (the whole-frame buffers: kajo_hip_compose_aov, on the handle it is called on)
+            CREATE_TRY(h->aovTiles.alloc(aovTileBytes(h)));
+            CREATE_TRY(hipMemsetAsync(h->aovTiles.p, 0, aovTileBytes(h), h->stream));
+            if (p.flags & KAJO_FLAG_AOV_MATTE) {
+                CREATE_TRY(h->matteTiles.alloc(matteTileBytes(h)));
+                CREATE_TRY(hipMemsetAsync(h->matteTiles.p, 0, matteTileBytes(h), h->stream));
+            }
+        } else {
+            const size_t bytes = 2 * (size_t)width * height * 16;
+            CREATE_TRY(h->aov.alloc(bytes));
+            CREATE_TRY(hipMemsetAsync(h->aov.p, 0, bytes, h->stream));
+            if (p.flags & KAJO_FLAG_AOV_MATTE) {
+                const size_t tables = matteTableBytes(h);
+                CREATE_TRY(h->matte.alloc(tables));
+                CREATE_TRY(hipMemsetAsync(h->matte.p, 0, tables, h->stream));
+            }
         }
     }
     CREATE_TRY(hipStreamSynchronize(h->stream));
@@ -824,7 +879,12 @@ int kajo_hip_render(kajo_hip_t h, int passes)
     int rc = bind(h);
     if (rc)
         return rc;
+    if (passes > 0) // (tiled AOVs: the composed whole-frame buffers are those of the passes before)
+        h->aovComposed = h->matteComposed = false;
     if (passes == 0 || h->nTilesOwned == 0) {
+        // (an owner without a tile launches nothing; its zeroed AOV tile buffers count the passes like the others')
+        if (h->aovTiled)
+            h->aovPasses += passes;
         h->passesDone += passes;
         return KAJO_OK;
     }
@@ -926,13 +986,13 @@ int kajo_hip_render(kajo_hip_t h, int passes)
         }
         HIP_TRY(hipEventRecord(e1, h->stream));
         h->pending.emplace_back(e0, e1);
-        if (h->aov) {
+        if (p.flags & KAJO_FLAG_AOV) {
             // the first-hit AOVs of the same passes, behind the render launch and outside its timing events (KajoCounters.kernelMs)
             AovArgs g;
             std::memset(&g, 0, sizeof g);
             g.scene = h->view;
-            g.albedoHits = h->aov.p;
-            g.normalDepth = h->aov.as<char>() + (size_t)h->W * h->H * 16;
+            g.albedoHits = h->aovTiled ? h->aovTiles.p : h->aov.p;
+            g.slots = h->aovTiled ? (uint32_t)h->map.slotsPerOwner : (uint32_t)(h->W * h->H);
             g.W = h->W;
             g.H = h->H;
             g.n = a.n;
@@ -943,11 +1003,17 @@ int kajo_hip_render(kajo_hip_t h, int passes)
             g.firstPass = a.firstPass;
             g.nPasses = now;
             g.seed = a.seed;
-            if (h->matte) {
-                g.matteIds = h->matte.p;
-                g.matteCounts = h->matte.as<char>() + (size_t)h->W * h->H * KAJO_MATTE_SLOTS * 4;
+            if (p.flags & KAJO_FLAG_AOV_MATTE)
+                g.matteIds = h->aovTiled ? h->matteTiles.p : h->matte.p;
+            unsigned long long blocks = (unsigned long long)((h->W + 7) / 8) * ((h->H + 7) / 8);
+            if (h->aovTiled) {
+                // one wave per 8x8 block of the handle's own tiles, in the tile buffer's order (nTilesOwned > 0 here: no empty grid)
+                blocks = (unsigned long long)h->nTilesOwned * (p.tileW / 8) * (p.tileH / 8);
+                g.tiledBlocks = (int32_t)blocks;
+                g.tileWaves = (uint32_t)(p.tileW / 8) | ((uint32_t)(p.tileH / 8) << 16);
+                g.tileIndex = p.tileIndex;
+                g.tileCount = p.tileCount;
             }
-            const unsigned long long blocks = (unsigned long long)((h->W + 7) / 8) * ((h->H + 7) / 8);
             HIP_TRY((hipError_t)h->k->aov(&g, h->aovInstance, (unsigned)((blocks + 3) / 4), h->aovLds, h->stream));
             h->aovPasses += now;
         }
@@ -991,7 +1057,12 @@ int kajo_hip_reset(kajo_hip_t h)
         HIP_TRY(hipMemsetAsync(h->aov.p, 0, 2 * (size_t)h->W * h->H * 16, h->stream));
     if (h->matte)
         HIP_TRY(hipMemsetAsync(h->matte.p, 0, matteTableBytes(h), h->stream));
+    if (h->aovTiles)
+        HIP_TRY(hipMemsetAsync(h->aovTiles.p, 0, aovTileBytes(h), h->stream));
+    if (h->matteTiles)
+        HIP_TRY(hipMemsetAsync(h->matteTiles.p, 0, matteTileBytes(h), h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    h->aovComposed = h->matteComposed = false;
     h->aovPasses = 0;
     h->passesDone = 0;
     h->carryValid = false;
@@ -1033,6 +1104,50 @@ int kajo_hip_compose(kajo_hip_t h, const void* gathered)
     HIP_TRY(h->frame.ensure((size_t)h->W * h->H * 16));
     HIP_TRY((hipError_t)kajo_compose_launch(gathered, &h->map, h->frame.p, h->stream));
     h->frameValid = true;
+    return KAJO_OK;
+}
+
+int kajo_hip_aov_tile_buffers(kajo_hip_t h, void** aov, size_t* aovBytes, void** matte, size_t* matteBytes)
+{
+    if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    if (!h->aovTiled)
+        return fail(KAJO_E_STATE, "the handle was created without the tiled AOV flag: its AOV sums are whole-frame buffers");
+    if (aov)
+        *aov = h->aovTiles.p;
+    if (aovBytes)
+        *aovBytes = aovTileBytes(h);
+    if (matte)
+        *matte = h->matteTiles.p;
+    if (matteBytes)
+        *matteBytes = h->matteTiles ? matteTileBytes(h) : 0;
+    return KAJO_OK;
+}
+
+int kajo_hip_compose_aov(kajo_hip_t h, const void* gatheredAov, const void* gatheredMatte)
+{
+    if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    if (!h->aovTiled)
+        return fail(KAJO_E_STATE, "the handle was created without the tiled AOV flag: its AOV sums are whole-frame buffers already");
+    if (h->map.tileCount == 1) {
+        if (!gatheredAov)
+            gatheredAov = h->aovTiles.p;
+        if (!gatheredMatte)
+            gatheredMatte = h->matteTiles.p;
+    } else if (!gatheredAov)
+        return fail(KAJO_E_INVALID, "a handle that owns part of the frame needs the gathered AOV tile buffers");
+    if (!(h->params.flags & KAJO_FLAG_AOV_MATTE))
+        gatheredMatte = nullptr;
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    HIP_TRY(h->aov.ensure(2 * (size_t)h->W * h->H * 16));
+    if (gatheredMatte)
+        HIP_TRY(h->matte.ensure(matteTableBytes(h)));
+    HIP_TRY((hipError_t)kajo_compose_aov_launch(gatheredAov, gatheredMatte, &h->map, h->aov.p, gatheredMatte ? h->matte.p : nullptr, h->stream));
+    h->aovComposed = true;
+    h->matteComposed = gatheredMatte != nullptr;
     return KAJO_OK;
 }
 
@@ -1086,10 +1201,10 @@ int kajo_hip_read_aov(kajo_hip_t h, float* albedoHits, float* normalDepth, int64
 {
     if (!h)
         return fail(KAJO_E_INVALID, "null handle");
-    if (!h->aov)
-        return fail(KAJO_E_STATE, "the handle was created without the AOV flag: no first-hit AOVs to read");
-    int rc = bind(h);
+    int rc = aovReady(h, "the handle was created without the AOV flag: no first-hit AOVs to read");
     if (rc)
+        return rc;
+    if ((rc = bind(h)))
         return rc;
     const size_t bytes = (size_t)h->W * h->H * 16;
     if (albedoHits)
@@ -1105,7 +1220,7 @@ int kajo_hip_read_aov(kajo_hip_t h, float* albedoHits, float* normalDepth, int64
 
 const char* kajo_hip_aov_kernel(kajo_hip_t h)
 {
-    if (!h || !h->aov)
+    if (!h || !(h->params.flags & KAJO_FLAG_AOV))
         return nullptr;
     return h->k->aovNames[h->aovInstance];
 }
@@ -1114,10 +1229,10 @@ int kajo_hip_read_matte(kajo_hip_t h, int32_t* ids, uint32_t* counts, int64_t* s
 {
     if (!h)
         return fail(KAJO_E_INVALID, "null handle");
-    if (!h->matte)
-        return fail(KAJO_E_STATE, "the handle was created without the matte flag: no coverage tables to read");
-    int rc = bind(h);
+    int rc = matteReady(h);
     if (rc)
+        return rc;
+    if ((rc = bind(h)))
         return rc;
     const size_t count = (size_t)h->W * h->H, words = count * KAJO_MATTE_SLOTS * 4;
     if (ids || counts) {
@@ -1144,8 +1259,9 @@ int kajo_hip_matte_mask(kajo_hip_t h, const int32_t* objects, int n, float* mask
         return fail(KAJO_E_INVALID, "null handle");
     if (n < 0 || (n > 0 && !objects))
         return fail(KAJO_E_INVALID, "invalid object list");
-    if (!h->matte)
-        return fail(KAJO_E_STATE, "the handle was created without the matte flag: no coverage tables to read");
+    int rc = matteReady(h);
+    if (rc)
+        return rc;
     const int nObjects = h->staged.nPlanes + h->staged.nSpheres;
     std::vector<uint32_t> selected(matteBitsetWords(h), 0u);
     for (int i = 0; i < n; i++) {
@@ -1153,8 +1269,7 @@ int kajo_hip_matte_mask(kajo_hip_t h, const int32_t* objects, int n, float* mask
             return fail(KAJO_E_INVALID, "object id out of range: 0 (the background) .. the number of planes and spheres");
         selected[(size_t)objects[i] >> 5] |= 1u << (objects[i] & 31);
     }
-    int rc = bind(h);
-    if (rc)
+    if ((rc = bind(h)))
         return rc;
     if (mask || dominant) {
         const size_t count = (size_t)h->W * h->H, words = count * KAJO_MATTE_SLOTS * 4;
@@ -1207,32 +1322,40 @@ int checkDenoise(kajo_hip_t h, const KajoDenoiseParams* p)
             return fail(KAJO_E_INVALID, "denoise sigmas must be finite and not negative");
     if (!h)
         return fail(KAJO_E_INVALID, "null handle");
-    if (!h->aov)
-        return fail(KAJO_E_STATE, "the handle was created without the AOV flag: nothing to guide the denoiser");
+    int rc = aovReady(h, "the handle was created without the AOV flag: nothing to guide the denoiser");
+    if (rc)
+        return rc;
     if (h->passesDone < 1)
         return fail(KAJO_E_STATE, "nothing rendered yet");
+    // (tiled AOVs on an owner of part of the frame: the frame to filter is the composed one)
+    if (h->map.tileCount != 1 && !h->frameValid)
+        return fail(KAJO_E_STATE, "whole-frame output needs kajo_hip_compose() when tileCount > 1");
     return KAJO_OK;
 }
 
 // The denoised frame (sums over passes, row-major) on the handle's stream, in the denoiser's scratch: *out points into it. Checked by
-// checkDenoise, device bound. tiles: the frame to filter in the handle's tile layout -- null = the accumulation, or what despeckleImage
-// wrote in its place.
-int denoiseFrame(KajoHip* h, const KajoDenoiseParams* p, void** out, const void* tiles = nullptr)
+// checkDenoise, device bound. staged: the frame to filter where a stage ran in front (what despeckleImage wrote), in the handle's tile
+// layout or row-major -- null = the accumulation: the handle's own tiles while it is the frame's one owner, else the composed frame
+// (tiled AOVs; checkDenoise has seen it valid).
+int denoiseFrame(KajoHip* h, const KajoDenoiseParams* p, void** out, const Image* staged = nullptr)
 {
-    if (!tiles)
-        tiles = h->tiles.p;
+    const Image img = staged ? *staged : h->map.tileCount == 1 ? Image{h->tiles.p, true} : Image{h->frame.p, false};
     const size_t count = (size_t)h->W * h->H;
     HIP_TRY(h->denoise.ensure(count * (3 * 16 + 4)));
     char* scratch = h->denoise.as<char>();
     *out = scratch + count * 16;
     if (p->iterations == 0) {
-        // the accumulation itself (one owner: tileCount is 1 with the AOV flag)
-        HIP_TRY((hipError_t)kajo_compose_launch(tiles, &h->map, *out, h->stream));
+        // the frame itself
+        if (img.fromTiles)
+            HIP_TRY((hipError_t)kajo_compose_launch(img.src, &h->map, *out, h->stream));
+        else
+            HIP_TRY(hipMemcpyAsync(*out, img.src, count * 16, hipMemcpyDeviceToDevice, h->stream));
     } else {
         const long long samples = std::max(aovSamples(h), 1LL);
-        hipError_t le = (hipError_t)kajo_denoise_launch(tiles, &h->map, h->aov.p, h->aov.as<char>() + count * 16, (float)h->passesDone,
-                                                        (float)samples, p->iterations, (p->flags & KAJO_DENOISE_NO_DEMODULATE) ? 0 : 1,
-                                                        p->sigmaLuminance, p->sigmaNormal, p->sigmaDepth, scratch, out, h->stream);
+        hipError_t le = (hipError_t)kajo_denoise_launch(img.src, &h->map, img.fromTiles ? 1 : 0, h->aov.p, h->aov.as<char>() + count * 16,
+                                                        (float)h->passesDone, (float)samples, p->iterations,
+                                                        (p->flags & KAJO_DENOISE_NO_DEMODULATE) ? 0 : 1, p->sigmaLuminance, p->sigmaNormal,
+                                                        p->sigmaDepth, scratch, out, h->stream);
         if (le != hipSuccess)
             return failHip(le, "denoise kernel launch");
     }
@@ -1618,12 +1741,13 @@ int kajo_hip_present_argb8(kajo_hip_t h, const KajoDespeckleParams* despeckle, c
         return rc;
     const size_t count = (size_t)h->W * h->H;
     HIP_TRY(h->argb.ensure(count * 4));
-    // (with the denoiser behind it the stage writes the handle's tile layout: with the AOV flag the handle is the frame's one owner)
-    if ((rc = despeckleImage(h, despeckle, img, denoise != nullptr, &img)))
+    // (with the denoiser behind it the stage writes the handle's tile layout where the handle is the frame's one owner, else -- tiled AOVs,
+    // the composed frame -- row-major: the denoiser reads either)
+    if ((rc = despeckleImage(h, despeckle, img, denoise != nullptr && h->map.tileCount == 1, &img)))
         return rc;
     if (denoise) {
         void* out = nullptr;
-        if ((rc = denoiseFrame(h, denoise, &out, img.src)))
+        if ((rc = denoiseFrame(h, denoise, &out, &img)))
             return rc;
         img = Image{out, false};
     }
@@ -1744,12 +1868,13 @@ int meterResult(KajoHip* h, const uint32_t counts[kMeterRow], const KajoMeterPar
 int chainImage(KajoHip* h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* g, Image* img)
 {
     int rc;
-    // (with the denoiser behind it the despeckle writes the handle's tile layout: with the AOV flag the handle is the frame's one owner)
-    if (despeckle && (rc = despeckleImage(h, despeckle, *img, denoise != nullptr, img)))
+    // (with the denoiser behind it the despeckle writes the handle's tile layout where the handle is the frame's one owner, else -- tiled
+    // AOVs, the composed frame -- row-major: the denoiser reads either)
+    if (despeckle && (rc = despeckleImage(h, despeckle, *img, denoise != nullptr && h->map.tileCount == 1, img)))
         return rc;
     if (denoise) {
         void* out = nullptr;
-        if ((rc = denoiseFrame(h, denoise, &out, despeckle ? img->src : nullptr)))
+        if ((rc = denoiseFrame(h, denoise, &out, despeckle ? img : nullptr)))
             return rc;
         *img = Image{out, false};
     }

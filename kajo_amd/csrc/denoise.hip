@@ -4,7 +4,7 @@
 // filter's arithmetic is this file's own, so only its inputs depend on FAST / EXACT / STRICT.
 //
 // One lane per pixel, workgroups of 64x4 pixels. Passes over the frame, each a kernel on the handle's stream:
-//   prepare    accumulation (tile buffer) + AOV sums -> guide (N.xyz, z) and colour (e.rgb, 0)
+//   prepare    accumulation (tile buffer, or a row-major frame: fromTiles) + AOV sums -> guide (N.xyz, z) and colour (e.rgb, 0)
 //   variance   colour -> colour' (e.rgb, v0): the 3x3 variance of the luminance
 //   atrous     one per iteration, step 2^i, colour ping-pong: (e, v) -> (e', v')
 //   remodulate colour -> sums in the accumulation's units (in place)
@@ -35,6 +35,17 @@ __device__ inline float luminance(float4 c)
     return 0.2126f * c.x + 0.7152f * c.y + 0.0722f * c.z;
 }
 
+// the frame to filter at pixel (x, y): the one owner's tile buffer through the tile map, or a row-major frame (a composed or staged one)
+__device__ inline float4 sumAt(const float4* src, const TileMap& map, int fromTiles, int x, int y)
+{
+    if (!fromTiles)
+        return src[(size_t)y * map.W + x];
+    int owner;
+    uint32_t slot;
+    kajoTileSlot(map, x, y, &owner, &slot);
+    return src[(size_t)owner * map.slotsPerOwner + slot];
+}
+
 __device__ inline float3 albedoOf(float4 A, float samples)
 {
     return make_float3(fmaxf(A.x / samples, kAlbedoFloor), fmaxf(A.y / samples, kAlbedoFloor), fmaxf(A.z / samples, kAlbedoFloor));
@@ -48,7 +59,7 @@ __device__ inline float edgeWeight(float num, float den)
 
 } // namespace
 
-extern "C" __global__ void __launch_bounds__(256) kajo_denoise_prepare(const float4* tiles, TileMap map, const float4* albedoHits,
+extern "C" __global__ void __launch_bounds__(256) kajo_denoise_prepare(const float4* src, TileMap map, int fromTiles, const float4* albedoHits,
                                                                         const float4* normalDepth, float passes, float samples,
                                                                         int demodulate, float4* guide, float4* colour)
 {
@@ -56,11 +67,8 @@ extern "C" __global__ void __launch_bounds__(256) kajo_denoise_prepare(const flo
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= map.W || y >= map.H)
         return;
-    int owner;
-    uint32_t slot;
-    kajoTileSlot(map, x, y, &owner, &slot);
     const size_t i = (size_t)y * map.W + x;
-    const float4 sum = tiles[slot];
+    const float4 sum = sumAt(src, map, fromTiles, x, y);
     const float4 A = albedoHits[i];
     const float4 B = normalDepth[i];
     float4 e = make_float4(sum.x / passes, sum.y / passes, sum.z / passes, 0.0f);
@@ -205,17 +213,14 @@ extern "C" __global__ void __launch_bounds__(256) kajo_denoise_atrous(const floa
 
 // colour (e.rgb) -> sums in the accumulation's units: e * max(a, 1e-3) * P (demodulated) or e * P; .w from the accumulation. In place
 // (colour == out): every lane reads and writes its own pixel only.
-extern "C" __global__ void __launch_bounds__(256) kajo_denoise_remodulate(const float4* colour, const float4* tiles, TileMap map,
-                                                                           const float4* albedoHits, float passes, float samples,
-                                                                           int demodulate, float4* out)
+extern "C" __global__ void __launch_bounds__(256) kajo_denoise_remodulate(const float4* colour, const float4* src, TileMap map,
+                                                                           int fromTiles, const float4* albedoHits, float passes,
+                                                                           float samples, int demodulate, float4* out)
 {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= map.W || y >= map.H)
         return;
-    int owner;
-    uint32_t slot;
-    kajoTileSlot(map, x, y, &owner, &slot);
     const size_t i = (size_t)y * map.W + x;
     float4 e = colour[i];
     if (demodulate) {
@@ -224,13 +229,14 @@ extern "C" __global__ void __launch_bounds__(256) kajo_denoise_remodulate(const 
         e.y = e.y * a.y;
         e.z = e.z * a.z;
     }
-    out[i] = make_float4(e.x * passes, e.y * passes, e.z * passes, tiles[slot].w);
+    out[i] = make_float4(e.x * passes, e.y * passes, e.z * passes, sumAt(src, map, fromTiles, x, y).w);
 }
 
 // The whole filter for iterations >= 1 on `stream`: scratch = three float4 frames (guide, and the two colour buffers the
-// iterations alternate between). *result = the frame that holds the result (scratch + 16 W H or + 32 W H).
-extern "C" int kajo_denoise_launch(const void* tiles, const TileMap* map, const void* albedoHits, const void* normalDepth, float passes,
-                                   float samples, int iterations, int demodulate, float sigmaLuminance, float sigmaNormal, float sigmaDepth,
+// iterations alternate between). *result = the frame that holds the result (scratch + 16 W H or + 32 W H). src: the frame to filter, the
+// one owner's tile buffer (fromTiles) or row-major.
+extern "C" int kajo_denoise_launch(const void* src, const TileMap* map, int fromTiles, const void* albedoHits, const void* normalDepth,
+                                   float passes, float samples, int iterations, int demodulate, float sigmaLuminance, float sigmaNormal, float sigmaDepth,
                                    void* scratch, void** result, void* stream)
 {
     const hipStream_t s = static_cast<hipStream_t>(stream);
@@ -239,7 +245,7 @@ extern "C" int kajo_denoise_launch(const void* tiles, const TileMap* map, const 
     float4* buf[2] = {guide + frame, guide + 2 * frame};
     const DenoiseFrame f = {map->W, map->H};
     const dim3 grid((map->W + 63) / 64, (map->H + 3) / 4), block(256);
-    hipLaunchKernelGGL(kajo_denoise_prepare, grid, block, 0, s, static_cast<const float4*>(tiles), *map,
+    hipLaunchKernelGGL(kajo_denoise_prepare, grid, block, 0, s, static_cast<const float4*>(src), *map, fromTiles,
                        static_cast<const float4*>(albedoHits), static_cast<const float4*>(normalDepth), passes, samples, demodulate, guide, buf[0]);
     hipLaunchKernelGGL(kajo_denoise_variance, grid, block, 0, s, buf[0], f, buf[1]);
     int cur = 1;
@@ -248,7 +254,7 @@ extern "C" int kajo_denoise_launch(const void* tiles, const TileMap* map, const 
                            buf[cur ^ 1]);
         cur ^= 1;
     }
-    hipLaunchKernelGGL(kajo_denoise_remodulate, grid, block, 0, s, buf[cur], static_cast<const float4*>(tiles), *map,
+    hipLaunchKernelGGL(kajo_denoise_remodulate, grid, block, 0, s, buf[cur], static_cast<const float4*>(src), *map, fromTiles,
                        static_cast<const float4*>(albedoHits), passes, samples, demodulate, buf[cur]);
     *result = buf[cur];
     return (int)hipGetLastError();

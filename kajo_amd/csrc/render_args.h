@@ -71,22 +71,29 @@ struct KatTraceArgs
 };
 
 // First-hit AOVs (aov.inc.hip, KAJO_FLAG_AOV): the camera samples of passes [firstPass, firstPass + nPasses) traced once more, without
-// shading. Two whole-frame buffers, row-major, row 0 = top: albedoHits (sum of albedo.rgb, number of hits) and normalDepth (sum of
+// shading. Two whole-frame buffers, row-major, row 0 = top (or the handle's own tiles: `tiledBlocks` below): albedoHits (sum of albedo.rgb, number of hits) and normalDepth (sum of
 // normal.xyz, sum of depth).
 struct AovArgs
 {
     DSceneView scene;
-    void* albedoHits;    // float4 [W * H]
-    void* normalDepth;   // float4 [W * H]
+    void* albedoHits;    // float4 [2][slots]: the albedo + hits sums, then the normal + depth sums
     int32_t W, H;
     int32_t n;           // strata per axis
     float pixelWidth, pixelHeight, sampleWidth, sampleHeight; // Renderer.cpp:39-42, as RenderArgs
     int32_t firstPass, nPasses;
+    uint32_t slots;      // elements per buffer: W * H, or with `tiledBlocks` the owner's padded slots (TileMap::slotsPerOwner)
     uint64_t seed;
     // object-coverage mattes (KAJO_FLAG_AOV_MATTE; the _matte instances only, null otherwise): per pixel KAJO_MATTE_SLOTS slots (id, count),
     // a slot with count 0 is empty; the filled slots are a prefix
-    void* matteIds;      // uint4 [W * H][2]
-    void* matteCounts;   // uint4 [W * H][2]
+    void* matteIds;      // uint4 [2][slots][2]: the ids, then the counts
+    // Tiled AOVs (KAJO_FLAG_AOV_TILED): the buffers hold the handle's OWN tiles in the accumulation's tile layout, a pixel at kajoTileSlot's
+    // slot, and the launch runs one wave per 8x8 block of those tiles: tiledBlocks = nTilesOwned * wavesPerTile of them. 0 = whole-frame
+    // row-major buffers, one wave per block of the frame (the fields behind it are not read).
+    // The block is kept as small as the kernels' scalar registers ask: every word of it is loaded in front of the scene's staging, where the
+    // large-scene instances have none to spare -- hence one base pointer per pair of buffers and the packed tile shape.
+    int32_t tiledBlocks;
+    uint32_t tileWaves;  // (tileW / 8) | (tileH / 8) << 16
+    int32_t tileIndex, tileCount;
 };
 
 // AOV kernel instances (aov.inc.hip), one per scene class the render kernels tell apart (capi.cpp picks one at create)

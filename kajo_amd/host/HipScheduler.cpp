@@ -72,6 +72,11 @@ struct Scheduler::Impl
     void* gathered = nullptr;         // on device 0: gpus consecutive tile buffers
     void* argbDevice = nullptr;       // on device 0: the resolved image of a gathered frame, before it goes to Image::pixels
     size_t tileBytes = 0;
+    // Options::aovTiled with a gather: on device 0, gpus consecutive AOV tile buffers and (Options::matte) matte tile buffers
+    void* aovGathered = nullptr;
+    void* matteGathered = nullptr;
+    size_t aovTileBytes = 0, matteTileBytes = 0;
+    bool aovComposed = false; // handle 0 holds the whole-frame AOVs of the passes rendered so far
     Statistics stats;
     float toneScale = 1; // Statistics::toneScale of the last image
     KajoMeterResult metered = {}; // lastMeter()
@@ -108,6 +113,10 @@ struct Scheduler::Impl
         }
         if (argbDevice)
             (void)hipFree(argbDevice);
+        if (aovGathered)
+            (void)hipFree(aovGathered);
+        if (matteGathered)
+            (void)hipFree(matteGathered);
     }
 
     void create(const scene::Scene& s)
@@ -148,7 +157,7 @@ struct Scheduler::Impl
         }
         if (opt.gpus < 1)
             throw std::runtime_error("hip::Scheduler: no GPU visible (this backend has no CPU path)");
-        if (opt.aov && opt.gpus != 1)
+        if (opt.aov && opt.gpus != 1 && !opt.aovTiled)
             throw std::runtime_error("hip::Scheduler: first-hit AOVs need the whole frame on one GPU (gpus = 1)");
         if (opt.sameDevice && opt.gather != Options::Copy)
             throw std::runtime_error("hip::Scheduler: sameDevice needs gather = Copy (RCCL wants one rank per device)");
@@ -171,7 +180,9 @@ struct Scheduler::Impl
             p.depthLimit = opt.depthLimit;
             p.seed = opt.seed;
             p.flags = (numerics == Options::Strict ? KAJO_FLAG_STRICT : numerics == Options::Exact ? KAJO_FLAG_EXACT : 0u) | (opt.counters ? KAJO_FLAG_COUNTERS : 0u) |
-                      (opt.aov ? KAJO_FLAG_AOV | (opt.aovSpecular ? KAJO_FLAG_AOV_SPECULAR : 0u) | (opt.matte ? KAJO_FLAG_AOV_MATTE : 0u) : 0u);
+                      (opt.aov ? KAJO_FLAG_AOV | (opt.aovSpecular ? KAJO_FLAG_AOV_SPECULAR : 0u) | (opt.matte ? KAJO_FLAG_AOV_MATTE : 0u) |
+                                 (opt.aovTiled ? KAJO_FLAG_AOV_TILED : 0u)
+                               : 0u);
             p.device = opt.sameDevice ? 0 : g;
             p.tileIndex = g;
             p.tileCount = opt.gpus;
@@ -199,7 +210,64 @@ struct Scheduler::Impl
                 comms.resize(opt.gpus);
                 checkNccl(ncclCommInitAll(comms.data(), opt.gpus, devices.data()), "ncclCommInitAll");
             }
+            if (opt.aov && opt.aovTiled) {
+                void *a = nullptr, *m = nullptr;
+                check(kajo_hip_aov_tile_buffers(handles[0], &a, &aovTileBytes, &m, &matteTileBytes), "kajo_hip_aov_tile_buffers");
+                checkHip(hipSetDevice(devices[0]), "hipSetDevice");
+                checkHip(hipMalloc(&aovGathered, aovTileBytes * opt.gpus), "hipMalloc(AOV gather buffer)");
+                if (matteTileBytes)
+                    checkHip(hipMalloc(&matteGathered, matteTileBytes * opt.gpus), "hipMalloc(matte gather buffer)");
+            }
         }
+    }
+
+    // Options::aovTiled: the whole-frame AOVs (and the float frame the denoiser filters) on handle 0, for the readers that need them. One
+    // exchange per buffer by the frame's own mechanism, then the two compose kernels; nothing where they are at hand already.
+    void composeAov()
+    {
+        if (!opt.aov || !opt.aovTiled || aovComposed)
+            return;
+        if (!gathered) { // single owner: its own tile buffers
+            check(kajo_hip_compose_aov(handles[0], nullptr, nullptr), "kajo_hip_compose_aov");
+            aovComposed = true;
+            return;
+        }
+        if (opt.gather == Options::Rccl) {
+            checkNccl(ncclGroupStart(), "ncclGroupStart");
+            for (int g = 0; g < opt.gpus; g++) {
+                void *a = nullptr, *m = nullptr;
+                check(kajo_hip_aov_tile_buffers(handles[g], &a, nullptr, &m, nullptr), "kajo_hip_aov_tile_buffers");
+                checkNccl(ncclSend(a, aovTileBytes / 4, ncclFloat, 0, comms[g], streams[g]), "ncclSend");
+                checkNccl(ncclRecv(static_cast<char*>(aovGathered) + (size_t)g * aovTileBytes, aovTileBytes / 4, ncclFloat, g, comms[0], streams[0]),
+                          "ncclRecv");
+                if (matteGathered) {
+                    checkNccl(ncclSend(m, matteTileBytes / 4, ncclUint32, 0, comms[g], streams[g]), "ncclSend");
+                    checkNccl(ncclRecv(static_cast<char*>(matteGathered) + (size_t)g * matteTileBytes, matteTileBytes / 4, ncclUint32, g, comms[0],
+                                       streams[0]),
+                              "ncclRecv");
+                }
+            }
+            checkNccl(ncclGroupEnd(), "ncclGroupEnd");
+        } else {
+            for (int g = 0; g < opt.gpus; g++) {
+                void *a = nullptr, *m = nullptr;
+                check(kajo_hip_aov_tile_buffers(handles[g], &a, nullptr, &m, nullptr), "kajo_hip_aov_tile_buffers");
+                check(kajo_hip_wait(handles[g]), "kajo_hip_wait");
+                checkHip(hipSetDevice(devices[0]), "hipSetDevice");
+                checkHip(hipMemcpyAsync(static_cast<char*>(aovGathered) + (size_t)g * aovTileBytes, a, aovTileBytes, hipMemcpyDefault, streams[0]),
+                         "hipMemcpyAsync(AOV gather)");
+                if (matteGathered)
+                    checkHip(hipMemcpyAsync(static_cast<char*>(matteGathered) + (size_t)g * matteTileBytes, m, matteTileBytes, hipMemcpyDefault,
+                                            streams[0]),
+                             "hipMemcpyAsync(matte gather)");
+            }
+        }
+        if (!composed) { // the float frame from the last gather, as readRadiance: the denoiser filters it
+            check(kajo_hip_compose(handles[0], gathered), "kajo_hip_compose");
+            composed = true;
+        }
+        check(kajo_hip_compose_aov(handles[0], aovGathered, matteGathered), "kajo_hip_compose_aov");
+        aovComposed = true;
     }
 
     // One exchange per displayed frame: every owner's tile buffer -> GPU 0; then the image straight
@@ -337,6 +405,7 @@ void Scheduler::readRadiance(float* dst)
 void Scheduler::readAov(float* albedoHits, float* normalDepth, long long* samples)
 {
     Impl& d = *m_impl;
+    d.composeAov();
     int64_t n = 0;
     check(kajo_hip_read_aov(d.handles[0], albedoHits, normalDepth, &n), "kajo_hip_read_aov");
     if (samples)
@@ -346,6 +415,7 @@ void Scheduler::readAov(float* albedoHits, float* normalDepth, long long* sample
 void Scheduler::readMatte(int32_t* ids, uint32_t* counts, long long* samples)
 {
     Impl& d = *m_impl;
+    d.composeAov();
     int64_t n = 0;
     check(kajo_hip_read_matte(d.handles[0], ids, counts, &n), "kajo_hip_read_matte");
     if (samples)
@@ -355,6 +425,7 @@ void Scheduler::readMatte(int32_t* ids, uint32_t* counts, long long* samples)
 void Scheduler::readMatteMask(const int32_t* objects, int n, float* mask, float* dominant)
 {
     Impl& d = *m_impl;
+    d.composeAov();
     check(kajo_hip_matte_mask(d.handles[0], objects, n, mask, dominant), "kajo_hip_matte_mask");
 }
 
@@ -363,6 +434,7 @@ void Scheduler::readDenoised(const KajoDenoiseParams* params, float* radiance, u
     Impl& d = *m_impl;
     KajoDenoiseParams p;
     kajo_hip_default_denoise_params(&p);
+    d.composeAov();
     check(kajo_hip_denoise(d.handles[0], params ? params : &p, radiance, argb8), "kajo_hip_denoise");
 }
 
@@ -371,6 +443,7 @@ void Scheduler::readDenoisedTonemapped(const KajoDenoiseParams* params, const Ka
     Impl& d = *m_impl;
     KajoDenoiseParams p;
     kajo_hip_default_denoise_params(&p);
+    d.composeAov();
     check(kajo_hip_tonemap_argb8(d.handles[0], tone ? tone : &d.opt.tone, params ? params : &p, argb8, scale), "kajo_hip_tonemap_argb8");
 }
 
@@ -381,6 +454,8 @@ void Scheduler::readDisplayed(const KajoDenoiseParams* denoise, const KajoGlareP
         check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
         d.composed = true;
     }
+    if (denoise)
+        d.composeAov();
     check(kajo_hip_display_argb8(d.handles[0], denoise, glare ? glare : &d.opt.glare, tone ? tone : &d.opt.tone, argb8, scale), "kajo_hip_display_argb8");
 }
 
@@ -398,6 +473,8 @@ void Scheduler::readPresented(const KajoDespeckleParams* despeckle, const KajoDe
         check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
         d.composed = true;
     }
+    if (denoise)
+        d.composeAov();
     if (d.localActive()) {
         check(kajo_hip_present_local_argb8(d.handles[0], despeckle, denoise, glare ? glare : &d.opt.glare, &d.opt.local,
                                            d.opt.meterOn ? &d.opt.meter : nullptr, tone ? tone : &d.opt.tone, argb8, &d.metered),
@@ -470,6 +547,7 @@ void Scheduler::run()
         for (kajo_hip_t h : d.handles)
             check(kajo_hip_wait(h), "kajo_hip_wait");
         done += now;
+        d.aovComposed = false;
         d.gatherAndResolve();
         const double batchWall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count();
         batchMs.push_back(batchWall);

@@ -57,10 +57,14 @@ struct Options
     bool sameDevice = false;      // all tile owners on device 0 (needs gather = Copy)
     bool forceGather = false;     // run the gather + compose step with ONE owner too (a one-rank communicator whose
                                   // rank sends its tile buffer to itself): the multi-GPU call sequence on a one-GPU box
-    bool aov = false;             // also accumulate the first-hit albedo / normal / depth (KAJO_FLAG_AOV; readAov): one GPU only
+    bool aov = false;             // also accumulate the first-hit albedo / normal / depth (KAJO_FLAG_AOV; readAov): one GPU only, unless aovTiled
     bool aovSpecular = false;     // ... at the first non-delta hit, through ideal mirrors and glass (KAJO_FLAG_AOV_SPECULAR); read only with aov
     bool matte = false;           // ... with the per-pixel object-coverage tables beside them (KAJO_FLAG_AOV_MATTE; readMatte, readMatteMask); read
                                   // only with aov. Off by default: every frame then takes exactly the calls it took without this field
+    bool aovTiled = false;        // ... every owner keeps the AOVs (and tables) of its own tiles (KAJO_FLAG_AOV_TILED): aov on any number of GPUs. The
+                                  // AOV tile buffers are gathered to GPU 0 and composed ON DEMAND, by the readers that need them (readAov, readMatte,
+                                  // readMatteMask, readDenoised*, and readDisplayed / readPresented with denoise parameters), never by a refresh of
+                                  // run(): the gather is two (with matte six) times the frame's bytes. Read only with aov
     // Exposure, tone curve and automatic exposure of the image run() writes (include/kajo_hip.h kajo_hip_tonemap_argb8; with one owner
     // or after the gather). The default is the identity: every frame then takes the plain resolve, exactly as without this field.
     KajoToneParams tone = {KAJO_TONE_CLAMP, 0u, 0.0f, 0.0f, 0.18f, {0.0f, 0.0f, 0.0f}};

@@ -77,7 +77,7 @@ int main(int argc, char** argv)
     opt.passes = 16;
     opt.gpus = 1;
     std::string podPath;
-    bool verbose = false, json = false, threeArg = false, aovSpecular = false;
+    bool verbose = false, json = false, threeArg = false, aovSpecular = false, aovTiled = false;
     int closeAtEvent = 0;
     bool noPreview = false;
     for (size_t i = 1; i < args.size(); i++) {
@@ -131,16 +131,19 @@ int main(int argc, char** argv)
                         "    --meter-white Q  --tonemap reinhard: the white point from the histogram's Q-th percentile (implies --meter-exposure 0.5)\n"
                         "    --aov PREFIX    also write the first-hit AOVs a denoiser takes, averaged over the render's camera samples:\n"
                         "                    PREFIX_albedo.pfm, PREFIX_normal.pfm (3 channels), PREFIX_depth.pfm (1; mean over the hits)\n"
-                        "                    (one GPU only)\n"
+                        "                    (one GPU only, unless --aov-tiled)\n"
                         "    --aov-specular  with --aov or --denoise: take the AOVs at the first non-delta hit, through ideal mirrors and glass\n"
                         "                    (include/kajo_hip.h KAJO_FLAG_AOV_SPECULAR), so that the guides show what a mirror shows\n"
+                        "    --aov-tiled     with --aov, --matte-mask, --matte-ids or --denoise: every GPU keeps the AOVs of its own tiles\n"
+                        "                    (include/kajo_hip.h KAJO_FLAG_AOV_TILED), so that those options take any --gpus (--same-device too); the\n"
+                        "                    tiles are gathered and composed when a file is written, not at every refresh (--json: aov_tiled)\n"
                         "    --matte-mask FILE  also write the coverage of the objects of --matte-objects as a 1-channel PFM: per pixel the share of\n"
                         "                    the camera samples that saw one of them (include/kajo_hip.h kajo_hip_matte_mask; collects the AOVs and\n"
-                        "                    honours --aov-specular: the object seen in the mirror; one GPU only)\n"
+                        "                    honours --aov-specular: the object seen in the mirror; one GPU only, unless --aov-tiled)\n"
                         "    --matte-objects LIST  --matte-mask: object ids, comma-separated (0 the background, 1.. the planes, then the spheres)\n"
                         "    --matte-ids FILE  also write the id of the object that covers most of each pixel as a 1-channel PFM (likewise)\n"
                         "    --denoise FILE  also write the frame denoised with those AOVs as guides, as a PNG (edge-aware A-trous filter,\n"
-                        "                    include/kajo_hip.h kajo_hip_denoise; collects the AOVs; one GPU only)\n"
+                        "                    include/kajo_hip.h kajo_hip_denoise; collects the AOVs; one GPU only, unless --aov-tiled)\n"
                         "    --denoise-iterations K  the filter's iterations, 0..8 (5)\n"
                         "    --json          print run statistics as one JSON line (with a tone option: the scale applied, tone_scale; with a\n"
                         "                    matte option: matte_samples per pixel and matte_dropped_pixels, the pixels whose table was full; with a\n"
@@ -199,6 +202,7 @@ int main(int argc, char** argv)
         else if (a == "--local-pivot" && more) localPivot = args[++i];
         else if (a == "--aov" && more) aovPrefix = args[++i];
         else if (a == "--aov-specular") aovSpecular = true;
+        else if (a == "--aov-tiled") aovTiled = true;
         else if (a == "--matte-mask" && more) matteMaskOut = args[++i];
         else if (a == "--matte-objects" && more) { matteObjectsText = args[++i]; matteObjectsGiven = true; }
         else if (a == "--matte-ids" && more) matteIdsOut = args[++i];
@@ -381,9 +385,15 @@ int main(int argc, char** argv)
         return 1;
     }
     opt.aovSpecular = aovSpecular;
+    if (aovTiled && aovPrefix.empty() && denoiseOut.empty() && !matteGiven) {
+        std::cerr << "kajo_render: --aov-tiled changes where the AOVs of --aov, --matte-mask, --matte-ids and --denoise are kept: give it with one of them" << std::endl;
+        return 1;
+    }
+    opt.aovTiled = aovTiled;
     if (!aovPrefix.empty()) {
-        // (before any device is opened: the AOV buffers are whole-frame buffers of ONE handle, include/kajo_hip.h KAJO_FLAG_AOV)
-        if (opt.gpus != 1 || threeArg) {
+        // (before any device is opened: the AOV buffers are whole-frame buffers of ONE handle, include/kajo_hip.h KAJO_FLAG_AOV, unless every
+        // owner keeps its own tiles', --aov-tiled)
+        if ((opt.gpus != 1 && !aovTiled) || threeArg) {
             std::cerr << "kajo_render: --aov needs the whole frame on one GPU (--gpus 1, without --three-arg)" << std::endl;
             return 1;
         }
@@ -395,7 +405,7 @@ int main(int argc, char** argv)
     }
     if (matteGiven) {
         // (the coverage tables are kept beside the AOV buffers of the one handle: the same condition as --aov, checked before any device is opened)
-        if (opt.gpus != 1 || threeArg) {
+        if ((opt.gpus != 1 && !aovTiled) || threeArg) {
             std::cerr << "kajo_render: " << (matteMaskOut.empty() ? "--matte-ids" : "--matte-mask")
                       << " needs the whole frame on one GPU (--gpus 1, without --three-arg)" << std::endl;
             return 1;
@@ -409,7 +419,7 @@ int main(int argc, char** argv)
     }
     if (!denoiseOut.empty()) {
         // (the denoiser reads the AOV buffers of the one handle: the same condition as --aov, checked before any device is opened)
-        if (opt.gpus != 1 || threeArg) {
+        if ((opt.gpus != 1 && !aovTiled) || threeArg) {
             std::cerr << "kajo_render: --denoise needs the whole frame on one GPU (--gpus 1, without --three-arg)" << std::endl;
             return 1;
         }
@@ -595,6 +605,8 @@ int main(int argc, char** argv)
             else
                 std::printf("null");
         }
+        if (aovTiled)
+            std::printf(", \"aov_tiled\": true");
         if (matteGiven)
             std::printf(", \"matte_samples\": %lld, \"matte_dropped_pixels\": %lld", matteSamples, matteDroppedPixels);
         std::printf("}\n");

@@ -18,7 +18,7 @@ class HipRenderer:
     def __init__(self, scene: Scene, width: int, height: int, spp: int = 32, depth_limit: int = 8,
                  seed: int = 0o715517, strict: bool = False, exact: bool = False, counters: bool = False, device: int = 0,
                  tile=(64, 16), tile_index: int = 0, tile_count: int = 1, passes_per_launch: int = 0, flags: int = 0,
-                 aov: bool = False, aov_specular: bool = False, matte: bool = False):
+                 aov: bool = False, aov_specular: bool = False, matte: bool = False, aov_tiled: bool = False):
         L = capi.lib()
         self._L = L
         self.scene = scene
@@ -33,6 +33,7 @@ class HipRenderer:
         p.flags |= capi.KAJO_FLAG_AOV if aov else 0
         p.flags |= capi.KAJO_FLAG_AOV_SPECULAR if aov_specular else 0  # (without aov the library refuses it)
         p.flags |= capi.KAJO_FLAG_AOV_MATTE if matte else 0  # (likewise)
+        p.flags |= capi.KAJO_FLAG_AOV_TILED if aov_tiled else 0  # (likewise; with it aov takes any tile_index / tile_count)
         p.device = device
         p.tileW, p.tileH = tile
         p.tileIndex, p.tileCount = tile_index, tile_count
@@ -387,6 +388,18 @@ class HipRenderer:
 
     def compose(self, gathered_device_ptr: int):
         capi.check(self._L.kajo_hip_compose(self._h, C.c_void_p(gathered_device_ptr)))
+
+    def aov_tile_buffers(self):
+        """(aov_ptr, aov_bytes, matte_ptr, matte_bytes) of a handle with aov_tiled=True (include/kajo_hip.h kajo_hip_aov_tile_buffers):
+        device pointers; matte_ptr is None and matte_bytes 0 without matte=True."""
+        aov, aov_bytes, matte, matte_bytes = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
+        capi.check(self._L.kajo_hip_aov_tile_buffers(self._h, C.byref(aov), C.byref(aov_bytes), C.byref(matte), C.byref(matte_bytes)))
+        return aov.value, aov_bytes.value, matte.value, matte_bytes.value
+
+    def compose_aov(self, gathered_aov_ptr=None, gathered_matte_ptr=None):
+        """The whole-frame AOVs (and coverage tables) of this handle from the owners' gathered tile buffers, device pointers in rank order
+        (include/kajo_hip.h kajo_hip_compose_aov); None = the handle's own buffer where it is the frame's one owner."""
+        capi.check(self._L.kajo_hip_compose_aov(self._h, C.c_void_p(gathered_aov_ptr), C.c_void_p(gathered_matte_ptr)))
 
 
 def stage_scene(scene: Scene):
