@@ -38,6 +38,9 @@
  *   kajo_hip_local           (no counterpart: the reference has no local operator) an edge-aware base / detail compression of log
  *                            luminance between the glare and the meter; kajo_hip_present_local_argb8 and its gathered twin put it into
  *                            the display chain, kajo_hip_local_pivot reports the pivot used
+ *   kajo_hip_lens            (no counterpart: the reference's camera is a pinhole, Renderer.cpp:29-55) depth of field as a lens blur from
+ *                            the depth AOV between the denoiser and the glare; kajo_hip_present_lens_argb8 puts it into the display
+ *                            chain, kajo_hip_lens_coc and kajo_hip_lens_depth_at report the circle of confusion and the depth it is from
  *   kajo_hip_destroy         the unique_ptr members of cpu::Scheduler (cpu/Scheduler.h:29-31)
  *
  * Pixels are dealt to GPUs as fixed-size tiles: a handle created with
@@ -679,6 +682,75 @@ int kajo_hip_present_local_gathered_argb8_device(kajo_hip_t h, const void* gathe
 /* The pivot of the handle's most recent run of the stage (the `pivot` field, or the metered one). KAJO_E_STATE before the first one; a
    call in which the stage did no device work (compression == 1 and detail == 1) is not a run. */
 int kajo_hip_local_pivot(kajo_hip_t h, float* pivot);
+
+/* Depth of field: a lens blur from the depth AOV, between the denoiser and the glare. Every image of the chain is otherwise taken
+   through a pinhole. This stage blurs each pixel by the circle of confusion (CoC) a thin lens focused at focusDistance gives its depth.
+   It is an IMAGE-SPACE APPROXIMATION: one depth per pixel -- the depth AOV, B.w / A.w, the mean hit distance over the beauty render's
+   own camera samples, with KAJO_FLAG_AOV_SPECULAR the length of the whole chain, so what is seen in a mirror or through glass is
+   defocused by its optical distance -- and nothing behind a foreground object can be revealed. A post-process over the handle's whole
+   frame in kernels of its own (kajo_amd/csrc/lens.hip) on the handle's stream, in float32 IEEE arithmetic without contraction in every
+   numerics build and in one fixed order: only its inputs depend on FAST / EXACT / STRICT. Frame in, frame out, in the units of
+   kajo_hip_read_radiance. It comes after the denoiser (whose guides are pinhole-aligned) and before the glare (which models scattering
+   behind the lens).
+   Definition -- P = the handle's pass count, F = the source frame in sums over passes (after whichever of despeckle and denoise are
+   asked for), A and B the whole-frame AOV buffers of kajo_hip_read_aov, W x H, row 0 at the top, Hf = (float)H; per pixel p:
+     m = F.rgb / P                          the pixel COUNTS where all three channels are finite
+     z = B.w / A.w  where A.w > 0 and the quotient is finite and > 0;  +inf otherwise  (a miss, or a poisoned depth: "far")
+     u = |1 - focusDistance / z|            (u = 1 for z = +inf)
+     r = min((aperture * Hf) * u, (float)maxRadius)      the CoC's radius in pixels (fminf: a NaN product gives maxRadius)
+   the thin lens's CoC with its constants folded into `aperture`: the radius at infinite depth as a fraction of the frame's height, so
+   the same parameters give the same picture at any resolution. Taps q = p + (dx, dy), |dx|, |dy| <= maxRadius; only taps inside the
+   image that count are used; d = sqrtf((float)(dx*dx + dy*dy)):
+     re = r_q               where z_q <= z_p   (q is in front of p or level with it: its disc lies over p)
+          min(r_q, r_p)     otherwise          (q is behind p: it cannot bleed over a sharper foreground)
+     c  = min(max((re + 1) - d, 0), 1)         a disc with a one-pixel soft edge; exactly 1 at the centre tap
+     w  = c / (1 + pi_f * (re * (re + 1)))     pi_f = (float)M_PI; the divisor approximates the lattice sum of c (ratio 1.000 at r = 0,
+                                               0.996 .. 1.026 for r up to 16)
+     sumW += w;  sum.rgb += w * m_q            row-major tap order (dy outer, dx inner), accumulators start at +0, no FMA
+     out.rgb = (sum.rgb / sumW) * P  where p counts;   F.rgb with the bits it had where it does not;   out.w = F.w
+   What follows from it: the centre tap always has w > 0 for a counting p, so sumW > 0. A pixel that does not count is never a tap: the
+   stage spreads no NaN and repairs none (that is the despeckle's job). A tap with c == 0 adds +-0 to sums that start at +0, so any
+   culling that skips only such taps and keeps the order of the rest gives the same bits (the kernel's per-workgroup window bound). With
+   aperture == 0 the output is F itself and the stage does no device work (as the glare at strength 0), so every image is then the
+   existing call's bit for bit. A frame whose every r is 0 comes out as (F.rgb / P) * P. A constant frame stays constant within
+   rounding under any depth field. No atomics and no order between workgroups: the output at a pixel depends on the inputs through image
+   coordinates only, so the frame is the same bits on a second call, on a twin handle and on the root of any number of tile owners. The
+   accumulation, the AOV buffers, the matte tables, the pass count and the counters (kernelMs included) are not touched. Scratch (the
+   planes r and z, the tap records and the output frame) is allocated on first use and freed by kajo_hip_destroy.
+   Refusals (KAJO_E_INVALID, before any device work and before the handle is looked at): NULL params; an aperture that is not finite or
+   outside 0..1; a focusDistance that is not finite or not above 0; a maxRadius outside 1..KAJO_LENS_MAX_RADIUS; a flag bit; a non-zero
+   reserved word. Where other stages' parameters are present too, the order is despeckle, lens, glare, local, meter, tone, denoise,
+   handle. Then the handle's state, by the denoiser's rules: KAJO_E_STATE on a handle without KAJO_FLAG_AOV, with no pass rendered, on
+   a tiled handle (KAJO_FLAG_AOV_TILED) before kajo_hip_compose_aov or after a later render or reset, and on an owner of part of the
+   frame without a composed frame. There is no gathered *_device twin: the stage needs whole-frame AOVs, as the denoiser does; several
+   owners are served through the root after kajo_hip_compose and kajo_hip_compose_aov. */
+#define KAJO_LENS_MAX_RADIUS 16
+typedef struct KajoLensParams {
+    float aperture;       /* >= 0, finite, <= 1 (default 0.01) */
+    float focusDistance;  /* > 0, finite, in the depth AOV's units (default 10) */
+    int32_t maxRadius;    /* 1..KAJO_LENS_MAX_RADIUS (default 16) */
+    uint32_t flags;       /* 0: an unknown bit is refused */
+    float reserved[4];    /* 0 */
+} KajoLensParams;         /* 32 bytes */
+void kajo_hip_default_lens_params(KajoLensParams* p); /* NULL is accepted */
+/* The frame after the stage: radiance = HOST pointer to width*height*4 floats (row 0 = top), sums over passes; may be NULL. The frame
+   kajo_hip_present_argb8 with the same first two stages would hand the glare (NULL = the stage is off; with both NULL the
+   accumulation), then this stage. lens == NULL is refused (KAJO_E_INVALID). Waits. */
+int kajo_hip_lens(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoLensParams* lens,
+                  float* radiance);
+/* The stage's decisions: the planes r (radius) and z (depth) of the definition, HOST pointers to width*height floats each (row 0 =
+   top); either may be NULL. z = +inf is reported as +inf. They do not depend on the frame. What a test holds bit for bit, and the data
+   behind a focus-peaking overlay. Waits. */
+int kajo_hip_lens_coc(kajo_hip_t h, const KajoLensParams* lens, float* radius, float* depth);
+/* The definition's z at one pixel: autofocus on what is under the cursor. +inf means "far". KAJO_E_INVALID outside the frame (after
+   the NULL checks, before the handle's state). With focusDistance set to it, r at that pixel is exactly 0. Waits. */
+int kajo_hip_lens_depth_at(kajo_hip_t h, int x, int y, float* z);
+/* kajo_hip_present_local_argb8 with the stage between the denoiser and the glare: despeckle -> denoise -> lens -> glare -> local ->
+   meter -> tone mapping, every stage but the last optional (NULL). With lens == NULL exactly kajo_hip_present_local_argb8: the stage is
+   not run and the handle needs no AOVs. *result as there. Waits. */
+int kajo_hip_present_lens_argb8(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoLensParams* lens,
+                                const KajoGlareParams* g, const KajoLocalParams* local, const KajoMeterParams* meter, const KajoToneParams* tone,
+                                uint32_t* argb8, KajoMeterResult* result);
 
 /* Use an existing HIP stream (hipStream_t passed as void*) instead of the handle's own. */
 int kajo_hip_set_stream(kajo_hip_t h, void* stream);

@@ -43,6 +43,7 @@ KAJO_TONE_CLAMP, KAJO_TONE_REINHARD, KAJO_TONE_ACES = 0, 1, 2  # KajoToneParams.
 KAJO_TONE_AUTO_EXPOSURE = 1  # KajoToneParams.flags: scale the frame's log-average luminance to `key`
 KAJO_METER_BINS = 514  # words of a luminance histogram (kajo_hip_meter): bin 0 below 2^-16, 1..512 sixteen per stop, 513 from 2^16 up
 KAJO_METER_AUTO_WHITE = 1  # KajoMeterParams.flags: kajo_hip_meter_tone also sets Reinhard's white from whiteL
+KAJO_LENS_MAX_RADIUS = 16  # KajoLensParams.maxRadius: the largest circle of confusion, in pixels
 KAJO_LOCAL_PIVOT_METERED = 1  # KajoLocalParams.flags: the pivot is the frame's own pivotPercentile-th luminance
 
 # every symbol include/kajo_hip.h declares
@@ -61,6 +62,7 @@ EXPORTS = [
     "kajo_hip_present_metered_gathered_argb8_device",
     "kajo_hip_default_local_params", "kajo_hip_local", "kajo_hip_present_local_argb8", "kajo_hip_present_local_gathered_argb8_device",
     "kajo_hip_local_pivot",
+    "kajo_hip_default_lens_params", "kajo_hip_lens", "kajo_hip_lens_coc", "kajo_hip_lens_depth_at", "kajo_hip_present_lens_argb8",
     "kajo_hip_aov_tile_buffers", "kajo_hip_compose_aov",
 ]
 
@@ -101,6 +103,11 @@ class KajoMeterResult(C.Structure):
 class KajoLocalParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("flags", C.c_uint32), ("compression", C.c_float), ("detail", C.c_float), ("sigmaRange", C.c_float),
                 ("pivot", C.c_float), ("pivotPercentile", C.c_float), ("reserved", C.c_float)]
+
+
+class KajoLensParams(C.Structure):
+    _fields_ = [("aperture", C.c_float), ("focusDistance", C.c_float), ("maxRadius", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_float * 4)]
 
 
 class KajoParams(C.Structure):
@@ -229,6 +236,17 @@ def lib():
                                                                        C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams), C.c_void_p,
                                                                        C.POINTER(KajoMeterResult)]
             L.kajo_hip_local_pivot.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        if hasattr(L, "kajo_hip_lens"):  # (nor the depth of field)
+            L.kajo_hip_default_lens_params.argtypes = [C.POINTER(KajoLensParams)]
+            L.kajo_hip_default_lens_params.restype = None
+            L.kajo_hip_lens.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams), C.POINTER(KajoLensParams),
+                                        C.c_void_p]
+            L.kajo_hip_lens_coc.argtypes = [C.c_void_p, C.POINTER(KajoLensParams), C.c_void_p, C.c_void_p]
+            L.kajo_hip_lens_depth_at.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
+            L.kajo_hip_present_lens_argb8.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams),
+                                                      C.POINTER(KajoLensParams), C.POINTER(KajoGlareParams), C.POINTER(KajoLocalParams),
+                                                      C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams), C.c_void_p,
+                                                      C.POINTER(KajoMeterResult)]
         if hasattr(L, "kajo_hip_read_matte"):  # (nor the mattes)
             L.kajo_hip_read_matte.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
             L.kajo_hip_matte_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <new>
 #include <string>
 #include <utility>
@@ -64,6 +65,11 @@ int kajo_meter_launch(const void* src, const TileMap* map, int fromTiles, float 
 size_t kajo_local_plane(int W, int H);
 int kajo_local_launch(const void* src, const TileMap* map, int fromTiles, float passes, int iterations, float compression, float detail,
                       float sigmaRange, float pivot, void* planes, void* out, void* stream);
+size_t kajo_lens_plane(int W, int H);
+int kajo_lens_coc_launch(const TileMap* map, const void* albedoHits, const void* normalDepth, float aperture, float focusDistance, int maxRadius,
+                         void* scratch, void* stream);
+int kajo_lens_launch(const void* src, const TileMap* map, int fromTiles, float passes, const void* albedoHits, const void* normalDepth,
+                     float aperture, float focusDistance, int maxRadius, void* scratch, void* out, void* stream);
 int kajo_compose_aov_launch(const void* gatheredAov, const void* gatheredMatte, const TileMap* map, void* aov, void* matte, void* stream);
 int kajo_matte_rank_launch(const void* ids, const void* counts, int W, int H, void* rankedIds, void* rankedCounts, void* stream);
 int kajo_matte_mask_launch(const void* ids, const void* counts, int W, int H, const void* selected, unsigned nObjects, float samples, void* mask,
@@ -262,6 +268,9 @@ struct KajoHip
     DeviceBuffer local;
     bool localRun = false; // localPivot is that of a run of the stage (kajo_hip_local_pivot)
     float localPivot = 0.0f;
+    // depth of field (lens.hip; kajo_hip_lens, kajo_hip_lens_coc, kajo_hip_present_lens_argb8), on its first call: two float planes of
+    // kajo_lens_plane (r, z), the tap records float4 [W * H], then the output frame float4 [W * H]
+    DeviceBuffer lens;
     int toneScaleState = 0; // the s of the most recent tone mapping: 0 none yet, 1 toneScale, 2 the scale word (auto exposure)
     float toneScale = 1.0f;
 };
@@ -519,7 +528,7 @@ const char* kajo_hip_last_error(void)
 
 const char* kajo_hip_version(void)
 {
-    return "kajo-hip 0.1 (gfx950; aov-matte; local; aov-tiled)";
+    return "kajo-hip 0.1 (gfx950; aov-matte; local; aov-tiled; lens)";
 }
 
 void kajo_hip_default_params(KajoParams* p)
@@ -2270,6 +2279,215 @@ int kajo_hip_local_pivot(kajo_hip_t h, float* pivot)
         return fail(KAJO_E_STATE, "no local tone mapping yet");
     *pivot = h->localPivot; // (formed on the host before the launch: nothing to wait for)
     return KAJO_OK;
+}
+
+} // extern "C"
+
+namespace
+{
+
+// The refusals of KajoLensParams (KAJO_E_INVALID), before any device work and before the handle is looked at
+int checkLens(const KajoLensParams* p)
+{
+    if (!p)
+        return fail(KAJO_E_INVALID, "null lens parameters");
+    if (!(std::isfinite(p->aperture) && p->aperture >= 0.0f && p->aperture <= 1.0f))
+        return fail(KAJO_E_INVALID, "lens aperture must be finite and in [0, 1]");
+    if (!(std::isfinite(p->focusDistance) && p->focusDistance > 0.0f))
+        return fail(KAJO_E_INVALID, "lens focus distance must be finite and positive");
+    if (p->maxRadius < 1 || p->maxRadius > KAJO_LENS_MAX_RADIUS)
+        return fail(KAJO_E_INVALID, "lens max radius must be in [1, 16]");
+    if (p->flags)
+        return fail(KAJO_E_INVALID, "unknown lens flag");
+    for (float r : p->reserved)
+        if (r != 0.0f)
+            return fail(KAJO_E_INVALID, "lens reserved fields must be 0");
+    return KAJO_OK;
+}
+
+// ... and of the handle (KAJO_E_STATE), by the denoiser's rules: the whole-frame AOVs at hand, something rendered, the whole frame
+int checkLensHandle(kajo_hip_t h)
+{
+    if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    int rc = aovReady(h, "the handle was created without the AOV flag: no depth to focus the lens by");
+    if (rc)
+        return rc;
+    if (h->passesDone < 1)
+        return fail(KAJO_E_STATE, "nothing rendered yet");
+    if (h->map.tileCount != 1 && !h->frameValid)
+        return fail(KAJO_E_STATE, "whole-frame output needs kajo_hip_compose() when tileCount > 1");
+    return KAJO_OK;
+}
+
+size_t lensScratchBytes(const KajoHip* h)
+{
+    return 2 * kajo_lens_plane(h->W, h->H) * 4 + 2 * (size_t)h->W * h->H * 16;
+}
+
+// Enqueue the lens blur of an image (tiles through h->map's geometry, or a row-major frame): *out = the row-major frame in the stage's
+// scratch that holds the result -- or the image itself where the definition makes the output a copy (aperture 0). Checked by checkLens
+// and checkLensHandle, device bound.
+int lensImage(KajoHip* h, const KajoLensParams* p, Image img, Image* out)
+{
+    if (p->aperture == 0.0f) {
+        *out = img;
+        return KAJO_OK;
+    }
+    const size_t count = (size_t)h->W * h->H;
+    HIP_TRY(h->lens.ensure(lensScratchBytes(h)));
+    void* frame = h->lens.as<char>() + 2 * kajo_lens_plane(h->W, h->H) * 4 + count * 16;
+    hipError_t le = (hipError_t)kajo_lens_launch(img.src, &h->map, img.fromTiles ? 1 : 0, (float)h->passesDone, h->aov.p,
+                                                 h->aov.as<char>() + count * 16, p->aperture, p->focusDistance, p->maxRadius, h->lens.p, frame,
+                                                 h->stream);
+    if (le != hipSuccess)
+        return failHip(le, "lens kernel launch");
+    *out = Image{frame, false};
+    return KAJO_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void kajo_hip_default_lens_params(KajoLensParams* p)
+{
+    if (!p)
+        return;
+    std::memset(p, 0, sizeof *p);
+    p->aperture = 0.01f;
+    p->focusDistance = 10.0f;
+    p->maxRadius = KAJO_LENS_MAX_RADIUS;
+}
+
+int kajo_hip_lens(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoLensParams* lens,
+                  float* radiance)
+{
+    // (every refusal before any device work: the despeckle parameters, the stage's own, the denoiser's, then the handle)
+    int rc;
+    if (despeckle && (rc = checkDespeckle(despeckle)))
+        return rc;
+    if ((rc = checkLens(lens)))
+        return rc;
+    if (denoise && (rc = checkDenoise(h, denoise)))
+        return rc;
+    if ((rc = checkLensHandle(h)))
+        return rc;
+    Image img;
+    if ((rc = imageOf(h, false, nullptr, &img)))
+        return rc;
+    if ((rc = chainImage(h, despeckle, denoise, nullptr, &img)))
+        return rc;
+    if ((rc = lensImage(h, lens, img, &img)))
+        return rc;
+    if (img.fromTiles) {
+        // (a copy of the accumulation: the composed frame, as kajo_hip_read_radiance)
+        if ((rc = composeOwn(h)))
+            return rc;
+        img = Image{h->frame.p, false};
+    }
+    if (radiance)
+        HIP_TRY(hipMemcpyAsync(radiance, img.src, (size_t)h->W * h->H * 16, hipMemcpyDeviceToHost, h->stream));
+    return kajo_hip_wait(h);
+}
+
+int kajo_hip_lens_coc(kajo_hip_t h, const KajoLensParams* lens, float* radius, float* depth)
+{
+    int rc = checkLens(lens);
+    if (rc)
+        return rc;
+    if ((rc = checkLensHandle(h)))
+        return rc;
+    if ((rc = bind(h)))
+        return rc;
+    const size_t count = (size_t)h->W * h->H;
+    HIP_TRY(h->lens.ensure(lensScratchBytes(h)));
+    hipError_t le = (hipError_t)kajo_lens_coc_launch(&h->map, h->aov.p, h->aov.as<char>() + count * 16, lens->aperture, lens->focusDistance,
+                                                     lens->maxRadius, h->lens.p, h->stream);
+    if (le != hipSuccess)
+        return failHip(le, "lens kernel launch");
+    if (radius)
+        HIP_TRY(hipMemcpyAsync(radius, h->lens.p, count * 4, hipMemcpyDeviceToHost, h->stream));
+    if (depth)
+        HIP_TRY(hipMemcpyAsync(depth, h->lens.as<float>() + kajo_lens_plane(h->W, h->H), count * 4, hipMemcpyDeviceToHost, h->stream));
+    return kajo_hip_wait(h);
+}
+
+int kajo_hip_lens_depth_at(kajo_hip_t h, int x, int y, float* z)
+{
+    if (!h || !z)
+        return fail(KAJO_E_INVALID, "null argument");
+    if (x < 0 || y < 0 || x >= h->W || y >= h->H)
+        return fail(KAJO_E_INVALID, "the pixel is outside the frame");
+    int rc = checkLensHandle(h);
+    if (rc)
+        return rc;
+    if ((rc = bind(h)))
+        return rc;
+    const size_t count = (size_t)h->W * h->H, at = (size_t)y * h->W + x;
+    float a = 0.0f, b = 0.0f; // A.w (hits) and B.w (depth) of the pixel
+    HIP_TRY(hipMemcpyAsync(&a, h->aov.as<float>() + at * 4 + 3, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(&b, h->aov.as<float>() + (count + at) * 4 + 3, 4, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = kajo_hip_wait(h)))
+        return rc;
+    // (one IEEE float32 division, as the kernel's)
+    *z = std::numeric_limits<float>::infinity();
+    if (a > 0.0f) {
+        const float q = b / a;
+        if (std::isfinite(q) && q > 0.0f)
+            *z = q;
+    }
+    return KAJO_OK;
+}
+
+int kajo_hip_present_lens_argb8(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoLensParams* lens,
+                                const KajoGlareParams* g, const KajoLocalParams* local, const KajoMeterParams* meter, const KajoToneParams* tone,
+                                uint32_t* argb8, KajoMeterResult* result)
+{
+    if (!lens)
+        return kajo_hip_present_local_argb8(h, despeckle, denoise, g, local, meter, tone, argb8, result);
+    // (every refusal before any device work: despeckle, lens, glare, local, meter, tone, the denoiser's, then the handle)
+    int rc;
+    if (despeckle && (rc = checkDespeckle(despeckle)))
+        return rc;
+    if ((rc = checkLens(lens)))
+        return rc;
+    if (g && (rc = checkGlare(g)))
+        return rc;
+    if (local && (rc = checkLocal(local)))
+        return rc;
+    if (meter && (rc = checkMeter(meter)))
+        return rc;
+    ToneArgs t{};
+    if ((rc = toneArgsOf(tone, &t)))
+        return rc;
+    if (meter && (tone->flags & KAJO_TONE_AUTO_EXPOSURE))
+        return fail(KAJO_E_INVALID, "metered exposure and the tone parameters' automatic exposure are two automatic exposures: give one");
+    if (denoise && (rc = checkDenoise(h, denoise)))
+        return rc;
+    if ((rc = checkLensHandle(h)))
+        return rc;
+    Image img;
+    if ((rc = imageOf(h, false, nullptr, &img)))
+        return rc;
+    const size_t count = (size_t)h->W * h->H;
+    HIP_TRY(h->argb.ensure(count * 4));
+    if ((rc = chainImage(h, despeckle, denoise, nullptr, &img)))
+        return rc;
+    if ((rc = lensImage(h, lens, img, &img)))
+        return rc;
+    if (g && (rc = glareImage(h, g, img, &img)))
+        return rc;
+    if (local && (rc = localImage(h, local, img, &img)))
+        return rc;
+    // (the meter measures the frame the tone kernels are handed)
+    if (meter && (rc = meterAndPatch(h, img, meter, tone, result, &t)))
+        return rc;
+    if ((rc = toneLaunch(h, img, t, h->argb.p)))
+        return rc;
+    if (argb8)
+        HIP_TRY(hipMemcpyAsync(argb8, h->argb.p, count * 4, hipMemcpyDeviceToHost, h->stream));
+    return kajo_hip_wait(h);
 }
 
 int kajo_hip_tone_scale(kajo_hip_t h, float* scale)

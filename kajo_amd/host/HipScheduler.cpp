@@ -3,7 +3,9 @@
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <stdexcept>
@@ -97,6 +99,10 @@ struct Scheduler::Impl
         localRan = true;
     }
 
+    bool lensRan = false; // lastLens()
+    float lensFocus = 0, lensMaxRadiusPx = 0;
+    std::vector<float> lensRadius;
+
     ~Impl()
     {
         for (kajo_hip_t h : handles)
@@ -157,6 +163,10 @@ struct Scheduler::Impl
         }
         if (opt.gpus < 1)
             throw std::runtime_error("hip::Scheduler: no GPU visible (this backend has no CPU path)");
+        if (opt.lensOn && !opt.aov)
+            throw std::runtime_error("hip::Scheduler: lensOn needs the depth AOV (aov = true)");
+        if (opt.lensOn && opt.gpus != 1 && !opt.aovTiled)
+            throw std::runtime_error("hip::Scheduler: lensOn with more than one GPU needs aovTiled");
         if (opt.aov && opt.gpus != 1 && !opt.aovTiled)
             throw std::runtime_error("hip::Scheduler: first-hit AOVs need the whole frame on one GPU (gpus = 1)");
         if (opt.sameDevice && opt.gather != Options::Copy)
@@ -392,6 +402,15 @@ bool Scheduler::lastLocalPivot(float* pivot) const
     return m_impl->localRan;
 }
 
+bool Scheduler::lastLens(float* focusDistance, float* maxRadiusPx) const
+{
+    if (m_impl->lensRan && focusDistance)
+        *focusDistance = m_impl->lensFocus;
+    if (m_impl->lensRan && maxRadiusPx)
+        *maxRadiusPx = m_impl->lensMaxRadiusPx;
+    return m_impl->lensRan;
+}
+
 void Scheduler::readRadiance(float* dst)
 {
     Impl& d = *m_impl;
@@ -467,15 +486,40 @@ void Scheduler::readPresented(const KajoDespeckleParams* despeckle, const KajoDe
         despeckle = &d.opt.despeckle;
     if (counts)
         counts[0] = counts[1] = 0;
-    if (!despeckle && !d.opt.meterOn && !d.localActive())
+    if (!despeckle && !d.opt.meterOn && !d.localActive() && !d.opt.lensOn)
         return readDisplayed(denoise, glare, tone, argb8, scale);
     if (d.gathered && !d.composed) { // (as readDisplayed)
         check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
         d.composed = true;
     }
-    if (denoise)
+    if (denoise || d.opt.lensOn)
         d.composeAov();
-    if (d.localActive()) {
+    if (d.opt.lensOn) {
+        KajoLensParams lens = d.opt.lens;
+        if (d.opt.lensFocusAt.x >= 0) {
+            float z = 0;
+            check(kajo_hip_lens_depth_at(d.handles[0], d.opt.lensFocusAt.x, d.opt.lensFocusAt.y, &z), "kajo_hip_lens_depth_at");
+            if (!std::isfinite(z))
+                throw std::runtime_error("hip::Scheduler: the pixel to focus on (" + std::to_string(d.opt.lensFocusAt.x) + ", " +
+                                         std::to_string(d.opt.lensFocusAt.y) + ") is far (a miss, or no finite depth): nothing to focus on");
+            lens.focusDistance = z;
+        }
+        check(kajo_hip_present_lens_argb8(d.handles[0], despeckle, denoise, &lens, glare ? glare : &d.opt.glare,
+                                          d.opt.localOn ? &d.opt.local : nullptr, d.opt.meterOn ? &d.opt.meter : nullptr,
+                                          tone ? tone : &d.opt.tone, argb8, &d.metered),
+              "kajo_hip_present_lens_argb8");
+        if (d.localActive())
+            d.notePivot();
+        if (scale)
+            check(kajo_hip_tone_scale(d.handles[0], scale), "kajo_hip_tone_scale");
+        d.lensRadius.resize((size_t)d.image->width * d.image->height);
+        check(kajo_hip_lens_coc(d.handles[0], &lens, d.lensRadius.data(), nullptr), "kajo_hip_lens_coc");
+        d.lensFocus = lens.focusDistance;
+        d.lensMaxRadiusPx = 0;
+        for (float r : d.lensRadius)
+            d.lensMaxRadiusPx = std::max(d.lensMaxRadiusPx, r);
+        d.lensRan = true;
+    } else if (d.localActive()) {
         check(kajo_hip_present_local_argb8(d.handles[0], despeckle, denoise, glare ? glare : &d.opt.glare, &d.opt.local,
                                            d.opt.meterOn ? &d.opt.meter : nullptr, tone ? tone : &d.opt.tone, argb8, &d.metered),
               "kajo_hip_present_local_argb8");

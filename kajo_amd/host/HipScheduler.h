@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "Scheduler.h"
-#include "kajo_hip.h" // KajoToneParams (Options::tone), KajoGlareParams (Options::glare), KajoDespeckleParams (Options::despeckle), KajoMeterParams, KajoLocalParams
+#include "kajo_hip.h" // KajoToneParams (Options::tone), KajoGlareParams (Options::glare), KajoDespeckleParams (Options::despeckle), KajoMeterParams, KajoLocalParams, KajoLensParams
 
 class Image;
 class Preview;
@@ -92,6 +92,14 @@ struct Options
     // kajo_hip_default_local_params first (all zero, as here, is refused, loudly).
     bool localOn = false;
     KajoLocalParams local = {};
+    // Depth of field between the denoiser and the glare of the images readPresented() hands out (include/kajo_hip.h
+    // kajo_hip_present_lens_argb8): a lens blur from the depth AOV, an image-space approximation. It needs `aov`, and with more than one GPU
+    // `aovTiled` (both refused at construction otherwise). Off by default: every call is then the one made without these fields. Whoever sets
+    // lensOn fills `lens` with kajo_hip_default_lens_params first. lensFocusAt: the pixel to focus on (kajo_hip_lens_depth_at; a pixel that
+    // is "far" is refused when the image is read); x = -1 means "use lens.focusDistance".
+    bool lensOn = false;
+    KajoLensParams lens = {};
+    struct { int x = -1, y = -1; } lensFocusAt;
 };
 
 struct Statistics
@@ -141,7 +149,9 @@ public:
     // the same chain with the despeckle in front (include/kajo_hip.h kajo_hip_present_argb8): despeckle null = Options::despeckle where
     // Options::despeckleOn, else none (then readDisplayed); counts (may be null) = pixels clamped, pixels repaired (0, 0 without the stage).
     // With Options::meterOn the chain ends in the metered call (kajo_hip_present_metered_argb8) and lastMeter() is its measurement; with
-    // Options::localOn the local tone mapping sits between the glare and the meter (kajo_hip_present_local_argb8)
+    // Options::localOn the local tone mapping sits between the glare and the meter (kajo_hip_present_local_argb8); with Options::lensOn the
+    // depth of field sits between the denoiser and the glare (kajo_hip_present_lens_argb8; the AOVs are gathered and composed first, as
+    // for `denoise`), and lastLens() is what it focused on
     void readPresented(const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* glare, const KajoToneParams* tone,
                        uint32_t* argb8, float* scale, long long counts[2]);
 
@@ -150,6 +160,9 @@ public:
     // the pivot of the most recent local tone mapping (Options::localOn: run()'s last refresh, or readPresented); false where the stage has
     // not run (off, or a copy by its parameters)
     bool lastLocalPivot(float* pivot) const;
+    // the focus distance of the most recent image with the depth of field (Options::lensOn: readPresented) and the largest circle of
+    // confusion in it, in pixels; false where the stage has not run
+    bool lastLens(float* focusDistance, float* maxRadiusPx) const;
 
 private:
     struct Impl;

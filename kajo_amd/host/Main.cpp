@@ -71,6 +71,8 @@ int main(int argc, char** argv)
     std::string meterExposure, meterWhite;
     // local tone mapping options (include/kajo_hip.h KajoLocalParams): the raw text, checked after the loop
     std::string localContrast, localDetail, localRange, localIterations, localPivot;
+    // depth of field options (include/kajo_hip.h KajoLensParams): the raw text, checked after the loop
+    std::string lensAperture, lensFocus, lensFocusAt, lensMaxRadius;
     int width = 640, height = 480;
     int denoiseIterations = 5;
     hip::Options opt;
@@ -156,7 +158,14 @@ int main(int argc, char** argv)
                         "    --local-range STOPS  --local-contrast: differences beyond about this many stops are edges the base layer keeps, > 0 (2)\n"
                         "    --local-iterations K  --local-contrast: iterations of the edge-aware filter, 0..8 (5): its reach doubles with each\n"
                         "    --local-pivot STOPS|metered[:Q]  --local-contrast: the log2 luminance that stays put, -16..16 (log2(0.18)), or the frame's own\n"
-                        "                    Q-th percentile, 0 < Q <= 1 (0.5), from the meter's histogram (--json: local_pivot and the parameters used)\n",
+                        "                    Q-th percentile, 0 < Q <= 1 (0.5), from the meter's histogram (--json: local_pivot and the parameters used)\n"
+                        "    --lens-aperture A  depth of field between the denoiser and the glare (-o and --denoise; include/kajo_hip.h kajo_hip_lens): a lens\n"
+                        "                    blur from the depth AOV, A = the blur radius at infinite depth as a fraction of the height, 0..1 (0 = none).\n"
+                        "                    Implies the AOVs as --denoise does (--gpus other than 1 needs --aov-tiled; honours --aov-specular); an\n"
+                        "                    image-space approximation; --hdr and --raw stay the raw mean (--json: lens_focus, lens_max_radius_px)\n"
+                        "    --lens-focus D  --lens-aperture: the distance in focus, > 0, in the depth AOV's units\n"
+                        "    --lens-focus-at X,Y  --lens-aperture: focus on what that pixel shows (the default: the frame's centre pixel)\n"
+                        "    --lens-max-radius R  --lens-aperture: the largest blur radius in pixels, 1..16 (16)\n",
                         args[0].c_str());
             return 1;
         } else if (a == "-w" && more) width = std::atoi(args[++i].c_str());
@@ -200,6 +209,10 @@ int main(int argc, char** argv)
         else if (a == "--local-range" && more) localRange = args[++i];
         else if (a == "--local-iterations" && more) localIterations = args[++i];
         else if (a == "--local-pivot" && more) localPivot = args[++i];
+        else if (a == "--lens-aperture" && more) lensAperture = args[++i];
+        else if (a == "--lens-focus" && more) lensFocus = args[++i];
+        else if (a == "--lens-focus-at" && more) lensFocusAt = args[++i];
+        else if (a == "--lens-max-radius" && more) lensMaxRadius = args[++i];
         else if (a == "--aov" && more) aovPrefix = args[++i];
         else if (a == "--aov-specular") aovSpecular = true;
         else if (a == "--aov-tiled") aovTiled = true;
@@ -379,13 +392,63 @@ int main(int argc, char** argv)
             return 1;
         }
     }
+    if (lensAperture.empty() && (!lensFocus.empty() || !lensFocusAt.empty() || !lensMaxRadius.empty())) {
+        std::cerr << "kajo_render: --lens-focus, --lens-focus-at and --lens-max-radius shape the stage that --lens-aperture turns on: give them with --lens-aperture" << std::endl;
+        return 1;
+    }
+    const bool lensGiven = !lensAperture.empty();
+    if (lensGiven) {
+        // (before any device is opened: the refusals of kajo_hip_lens, with the option's name)
+        if (!lensFocus.empty() && !lensFocusAt.empty()) {
+            std::cerr << "kajo_render: --lens-focus and --lens-focus-at are two ways to focus: give one" << std::endl;
+            return 1;
+        }
+        // (the stage reads the AOV buffers of the one handle: the same condition as --denoise)
+        if ((opt.gpus != 1 && !aovTiled) || threeArg) {
+            std::cerr << "kajo_render: --lens-aperture needs the whole frame on one GPU (--gpus 1, without --three-arg)" << std::endl;
+            return 1;
+        }
+        opt.lensOn = true;
+        kajo_hip_default_lens_params(&opt.lens);
+        if (!parseFloat(lensAperture, &opt.lens.aperture) || opt.lens.aperture < 0.0f || opt.lens.aperture > 1.0f) {
+            std::cerr << "kajo_render: --lens-aperture: lens aperture must be finite and in [0, 1]" << std::endl;
+            return 1;
+        }
+        if (!lensFocus.empty() && (!parseFloat(lensFocus, &opt.lens.focusDistance) || opt.lens.focusDistance <= 0.0f)) {
+            std::cerr << "kajo_render: --lens-focus: lens focus distance must be finite and positive" << std::endl;
+            return 1;
+        }
+        if (!lensMaxRadius.empty()) {
+            char* end = nullptr;
+            const long n = std::strtol(lensMaxRadius.c_str(), &end, 10);
+            if (end == lensMaxRadius.c_str() || *end != '\0' || n < 1 || n > KAJO_LENS_MAX_RADIUS) {
+                std::cerr << "kajo_render: --lens-max-radius: lens max radius must be in [1, 16]" << std::endl;
+                return 1;
+            }
+            opt.lens.maxRadius = (int32_t)n;
+        }
+        if (!lensFocusAt.empty()) {
+            int fx = -1, fy = -1;
+            char tail = 0;
+            if (std::sscanf(lensFocusAt.c_str(), "%d,%d%c", &fx, &fy, &tail) != 2 || fx < 0 || fy < 0 || fx >= width || fy >= height) {
+                std::cerr << "kajo_render: --lens-focus-at X,Y must be a pixel of the frame" << std::endl;
+                return 1;
+            }
+            opt.lensFocusAt.x = fx;
+            opt.lensFocusAt.y = fy;
+        } else if (lensFocus.empty()) {
+            opt.lensFocusAt.x = width / 2;
+            opt.lensFocusAt.y = height / 2;
+        }
+        opt.aov = true;
+    }
     const bool matteGiven = !matteMaskOut.empty() || !matteIdsOut.empty();
-    if (aovSpecular && aovPrefix.empty() && denoiseOut.empty() && !matteGiven) {
+    if (aovSpecular && aovPrefix.empty() && denoiseOut.empty() && !matteGiven && !lensGiven) {
         std::cerr << "kajo_render: --aov-specular changes the AOVs that --aov writes and --denoise is guided by: give it with --aov or --denoise" << std::endl;
         return 1;
     }
     opt.aovSpecular = aovSpecular;
-    if (aovTiled && aovPrefix.empty() && denoiseOut.empty() && !matteGiven) {
+    if (aovTiled && aovPrefix.empty() && denoiseOut.empty() && !matteGiven && !lensGiven) {
         std::cerr << "kajo_render: --aov-tiled changes where the AOVs of --aov, --matte-mask, --matte-ids and --denoise are kept: give it with one of them" << std::endl;
         return 1;
     }
@@ -470,6 +533,8 @@ int main(int argc, char** argv)
     KajoMeterResult metered = {};                       // --json with a meter option: of the image run() wrote
     float localPivotUsed = 0;                           // --json with --local-contrast: of the image run() wrote
     bool localRan = false;
+    float lensFocusUsed = 0, lensMaxRadiusPx = 0; // --json with --lens-aperture: of the image -o holds
+    bool lensRan = false;
     try {
         if (rendererName == "hip") {
             // (--three-arg: the statement integration/apply_to_kajo.sh adds to renderer/Main.cpp:135-142, word for word)
@@ -485,6 +550,14 @@ int main(int argc, char** argv)
             metered = hipScheduler->lastMeter();
         if (hipScheduler && localGiven)
             localRan = hipScheduler->lastLocalPivot(&localPivotUsed);
+        if (lensGiven) {
+            // (the image -o holds: the display chain with the stage in it, from the frame as run() left it; a focus pixel that is far is
+            // refused here, after the render)
+            hipScheduler->readPresented(nullptr, nullptr, nullptr, nullptr, image->pixels.get(), nullptr, nullptr);
+            lensRan = hipScheduler->lastLens(&lensFocusUsed, &lensMaxRadiusPx);
+            if (meterGiven)
+                metered = hipScheduler->lastMeter();
+        }
         if (!rawOut.empty()) {
             std::vector<float> acc((size_t)width * height * 4);
             hipScheduler->readRadiance(acc.data());
@@ -546,7 +619,7 @@ int main(int argc, char** argv)
             kajo_hip_default_denoise_params(&p);
             p.iterations = denoiseIterations;
             Image denoised(width, height);
-            if (despeckle || meterGiven || localGiven)
+            if (despeckle || meterGiven || localGiven || lensGiven)
                 hipScheduler->readPresented(nullptr, &p, nullptr, nullptr, denoised.pixels.get(), nullptr, nullptr);
             else if (glareGiven)
                 hipScheduler->readDisplayed(&p, nullptr, nullptr, denoised.pixels.get(), nullptr);
@@ -605,6 +678,8 @@ int main(int argc, char** argv)
             else
                 std::printf("null");
         }
+        if (lensGiven && lensRan)
+            std::printf(", \"lens_focus\": %.9g, \"lens_max_radius_px\": %.9g", (double)lensFocusUsed, (double)lensMaxRadiusPx);
         if (aovTiled)
             std::printf(", \"aov_tiled\": true");
         if (matteGiven)

@@ -315,14 +315,55 @@ class HipRenderer:
         capi.check(self._L.kajo_hip_local_pivot(self._h, C.byref(pivot)))
         return pivot.value
 
-    def present(self, despeckle: dict = None, denoise: dict = None, glare: dict = None, meter: dict = None, local: dict = None, **tone):
+    def _lens_params(self, aperture: float = None, focus_distance: float = None, max_radius: int = None):
+        p = capi.KajoLensParams()
+        self._L.kajo_hip_default_lens_params(C.byref(p))
+        if aperture is not None:
+            p.aperture = float(aperture)
+        if focus_distance is not None:
+            p.focusDistance = float(focus_distance)
+        if max_radius is not None:
+            p.maxRadius = int(max_radius)
+        return p
+
+    def lens(self, despeckle: dict = None, denoise: dict = None, **params) -> np.ndarray:
+        """The frame after the depth of field (include/kajo_hip.h kajo_hip_lens): (H, W, 4) float32 sums over passes, as radiance().
+        params: aperture (0.01, the circle of confusion's radius at infinite depth as a fraction of the frame's height), focus_distance
+        (10, in the depth AOV's units), max_radius (16 pixels); those left out take kajo_hip_default_lens_params' values. despeckle,
+        denoise: the stages in front, as present(). Needs aov=True. The accumulation, the AOVs and the counters are not touched."""
+        l = self._lens_params(**params)
+        s = None if despeckle is None else self._despeckle_params(**despeckle)
+        d = None if denoise is None else self._denoise_params(**denoise)
+        out = np.empty((self.height, self.width, 4), np.float32)
+        ref = lambda p: None if p is None else C.byref(p)
+        capi.check(self._L.kajo_hip_lens(self._h, ref(s), ref(d), C.byref(l), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def lens_coc(self, **params) -> dict:
+        """The depth of field's decisions (include/kajo_hip.h kajo_hip_lens_coc): dict(radius=(H, W) float32 circle of confusion in pixels,
+        depth=(H, W) float32, +inf = far). params as lens()."""
+        l = self._lens_params(**params)
+        radius = np.empty((self.height, self.width), np.float32)
+        depth = np.empty((self.height, self.width), np.float32)
+        capi.check(self._L.kajo_hip_lens_coc(self._h, C.byref(l), radius.ctypes.data_as(C.c_void_p), depth.ctypes.data_as(C.c_void_p)))
+        return dict(radius=radius, depth=depth)
+
+    def lens_depth_at(self, x: int, y: int) -> float:
+        """The depth the lens sees at one pixel (include/kajo_hip.h kajo_hip_lens_depth_at): what to focus on; inf = far."""
+        z = C.c_float()
+        capi.check(self._L.kajo_hip_lens_depth_at(self._h, int(x), int(y), C.byref(z)))
+        return z.value
+
+    def present(self, despeckle: dict = None, denoise: dict = None, glare: dict = None, meter: dict = None, local: dict = None,
+                lens: dict = None, **tone):
         """The display chain with the despeckle in front (include/kajo_hip.h kajo_hip_present_argb8): despeckle -> denoise -> glare ->
         tone mapping -> (argb8, scale) as tonemap(), every stage but the last optional. despeckle: a dict of despeckle()'s factor / rank /
         floor; the rest as display(). With despeckle None it is display(denoise, glare, **tone). meter: a dict of meter()'s params puts
         the metering in front of the tone curves (kajo_hip_present_metered_argb8: exposure becomes a compensation on top of the metered
         one, auto_white sets Reinhard's white) and makes the second value the result dict of meter() instead of the scale. local: a dict
         of local()'s params puts the local tone mapping between the glare and the meter (kajo_hip_present_local_argb8; the call is
-        routed there only when it is given)."""
+        routed there only when it is given). lens: a dict of lens()'s params puts the depth of field between the denoiser and the glare
+        (kajo_hip_present_lens_argb8; likewise routed there only when it is given)."""
         t = self._tone_params(**tone)
         s = None if despeckle is None else self._despeckle_params(**despeckle)
         d = None if denoise is None else self._denoise_params(**denoise)
@@ -330,6 +371,14 @@ class HipRenderer:
         argb8 = np.empty((self.height, self.width), np.uint32)
         scale = C.c_float()
         ref = lambda p: None if p is None else C.byref(p)
+        if lens is not None:
+            f = self._lens_params(**lens)
+            l = None if local is None else self._local_params(**local)
+            m = None if meter is None else self._meter_params(**meter)
+            result = capi.KajoMeterResult()
+            capi.check(self._L.kajo_hip_present_lens_argb8(self._h, ref(s), ref(d), C.byref(f), ref(g), ref(l), ref(m), C.byref(t),
+                                                           argb8.ctypes.data_as(C.c_void_p), C.byref(result)))
+            return argb8, (self.tone_scale() if m is None else self._meter_result(result))
         if local is not None:
             l = self._local_params(**local)
             m = None if meter is None else self._meter_params(**meter)
