@@ -41,6 +41,10 @@
  *   kajo_hip_lens            (no counterpart: the reference's camera is a pinhole, Renderer.cpp:29-55) depth of field as a lens blur from
  *                            the depth AOV between the denoiser and the glare; kajo_hip_present_lens_argb8 puts it into the display
  *                            chain, kajo_hip_lens_coc and kajo_hip_lens_depth_at report the circle of confusion and the depth it is from
+ *   kajo_hip_view_argb8      (no counterpart: the reference writes its image at the rendered size, renderer/Image.cpp) crop, zoom and
+ *                            supersampled output BEHIND the tone curves: a separable resampling of the ARGB8 image in linear light;
+ *                            kajo_hip_present_view_argb8 and its gathered twin put it at the end of the display chain,
+ *                            kajo_hip_view_weights and kajo_hip_view_tables are the host code that defines its numbers
  *   kajo_hip_destroy         the unique_ptr members of cpu::Scheduler (cpu/Scheduler.h:29-31)
  *
  * Pixels are dealt to GPUs as fixed-size tiles: a handle created with
@@ -751,6 +755,93 @@ int kajo_hip_lens_depth_at(kajo_hip_t h, int x, int y, float* z);
 int kajo_hip_present_lens_argb8(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoLensParams* lens,
                                 const KajoGlareParams* g, const KajoLocalParams* local, const KajoMeterParams* meter, const KajoToneParams* tone,
                                 uint32_t* argb8, KajoMeterResult* result);
+
+/* The view: crop, zoom and supersampled output, the last stage of the display chain. Every other stage works on scene-linear radiance
+   at the handle's W x H; this one sits BEHIND the tone curves: ARGB8 in, ARGB8 out, a separable resampling in linear light. Averaging
+   K x K display-referred pixels is what antialiases an edge whose radiance clips under every curve (render K times the size, tone map,
+   view down); a source rectangle and an output size give thumbnails, window-sized read-backs and a zoom. Kernels of its own
+   (kajo_amd/csrc/view.hip) on the handle's stream, float32 IEEE arithmetic without contraction in every numerics build and in one fixed
+   order; the weights and the two transfer tables are formed on the host in binary64, the device only multiplies and adds: a float32
+   restatement with the library's own weights and tables gives the same words (tests/view_replay.py).
+   Definition -- src = a W x H image of 0xAARRGGBB words, row 0 at the top (what the tone kernels write); the output is outW x outH words,
+   alpha 255. The source rectangle [x0, x1) x [y0, y1) is in source pixel units, pixel j spans [j, j + 1); all four edges zero = the whole
+   frame. Per axis (the horizontal one; the vertical is the same with y0, y1, outH, H), in binary64 on the host (kajo_hip_view_weights):
+     s = (x1 - x0) / outW          source pixels per output pixel;  S = max(s, 1)  the filter's stretch
+     u = x0 + (i + 0.5) s          the centre of output pixel i;  t_j = (j + 0.5 - u) / S
+     KAJO_VIEW_NEAREST    the one pixel floor(u) (held inside the image), weight 1
+     KAJO_VIEW_AREA       w_j = the length of the overlap of [j, j + 1) with the footprint [x0 + i s, x0 + (i + 1) s): the exact area
+                          average; an integer ratio K gives K equal weights; when magnifying at most two pixels
+     KAJO_VIEW_TRIANGLE   w_j = max(1 - |t_j|, 0)
+     KAJO_VIEW_LANCZOS3   w_j = sinc(t_j) sinc(t_j / 3) for |t_j| < 3, 0 otherwise;  sinc(0) = 1, sinc(t) = 0 EXACTLY at every other
+                          integer t, sin(pi t) / (pi t) elsewhere (so that an unscaled view is one weight of 1 under this filter too)
+   Taps outside 0 .. W - 1 are dropped, not clamped; the rest are divided by their binary64 sum ("renormalised over the taps inside",
+   as everywhere in the chain) and rounded to float32. A row of weights is the contiguous run first .. first + count - 1; leading and
+   trailing weights that are 0 in float32 are trimmed, never to nothing (a row whose sum is not positive becomes the NEAREST row).
+   count <= KAJO_VIEW_MAX_TAPS = 2 * 3 * KAJO_VIEW_MAX_SCALE = 384: LANCZOS3's support is |t| < 3, i.e. the open interval of 6 S <= 384
+   source pixels around u, which holds at most 384 pixel centres (AREA needs at most 65, TRIANGLE 128); a longer row, were rounding
+   ever to produce one, is refused (KAJO_E_INVALID), not replaced.
+   Transfer tables, binary64 rounded to float32 (kajo_hip_view_tables): lin[c] = (c / 255)^2.2, c = 0 .. 255; thresholds
+   t[k] = ((k - 0.5) / 255)^2.2, k = 1 .. 255; encode(v) = the number of k with v >= t[k] -- the quantiser of renderer/Image.cpp:14-27
+   (pow(1 / 2.2), then int(255 v + .5)) read backwards: no device pow, it clamps below 0 and above 1 by itself, and it is the same in
+   FAST, EXACT and STRICT. t[c] < lin[c] < t[c + 1] with room of many float32 ulps, so a constant image comes back constant.
+   The resampling, float32, no FMA, accumulators start at +0:
+     T[y][i].c = sum over the taps j = first_x[i] .. in increasing j of wx[i][j] * lin[src[y][j].c]      c = r, g, b
+     v.c       = sum over the taps y = first_y[o] .. in increasing y of wy[o][y] * T[y][i].c
+     out[o][i] = 255 << 24 | encode(v.r) << 16 | encode(v.g) << 8 | encode(v.b)
+   The source's alpha is not read. No division on the device, no atomics and no order between workgroups: an output word depends on the
+   inputs through image coordinates only, so it is the same on a second call, a twin handle and the root of any number of tile owners.
+   THE COPY CASE: outW == W, outH == H and the whole rectangle, under any filter, launches nothing and returns the source words as they
+   are (alpha included); under the definition it is the identity too (one weight of 1.0 per axis, encode(lin[c]) == c).
+   Refusals (KAJO_E_INVALID, before any device work). Without the handle, in this order: NULL params; an edge that is not finite; unless
+   all four edges are zero, not 0 <= x0 < x1 or not 0 <= y0 < y1; outW or outH outside 1..KAJO_VIEW_MAX_OUT; with an explicit rectangle
+   a minification (x1 - x0) / outW or (y1 - y0) / outH above KAJO_VIEW_MAX_SCALE; an unknown filter; a flag bit. Where other stages'
+   parameters are present, the order is despeckle, lens, glare, local, meter, tone, view, denoise, handle. The checks against the frame
+   NEED THE HANDLE and come last, after the denoiser's and the null handle: x1 > W or y1 > H, and the whole frame's minification W / outW
+   or H / outH above KAJO_VIEW_MAX_SCALE. The accumulation, the AOVs, the pass count and the counters (kernelMs included) are not
+   touched. Scratch (the intermediate T, the weight rows, the tables, an ARGB8 frame for the chain's image and one for the output) is
+   allocated on first use, grown when a larger view asks, and freed by kajo_hip_destroy; the weight rows are formed and uploaded (from
+   pinned staging, on the handle's stream) only when the parameters differ from the last call's. */
+#define KAJO_VIEW_MAX_SCALE 64
+#define KAJO_VIEW_MAX_TAPS 384
+#define KAJO_VIEW_MAX_OUT 16384
+enum { KAJO_VIEW_NEAREST = 0, KAJO_VIEW_AREA = 1, KAJO_VIEW_TRIANGLE = 2, KAJO_VIEW_LANCZOS3 = 3 };
+typedef struct KajoViewParams {
+    float x0, y0, x1, y1; /* the source rectangle in source pixel units; all zero = the whole frame (default) */
+    int32_t outW, outH;   /* 1..KAJO_VIEW_MAX_OUT; the default 0 is refused: the caller names the size */
+    uint32_t filter;      /* KAJO_VIEW_* (default KAJO_VIEW_AREA) */
+    uint32_t flags;       /* 0: an unknown bit is refused */
+} KajoViewParams;         /* 32 bytes */
+void kajo_hip_default_view_params(KajoViewParams* p); /* NULL is accepted */
+/* The weight rows of one axis: srcN source pixels, the rectangle's edges a0 < a1 on this axis, outN output pixels. Pure host code in
+   binary64, no device and no handle. first and count take outN words each; weights takes outN rows of `stride` floats, stride = the
+   largest count of the axis, row i at weights + i * stride, zeros behind its count. Returns outN * stride, the number of floats, or a
+   negative KAJO_E_INVALID (srcN < 1, outN outside 1..KAJO_VIEW_MAX_OUT, not 0 <= a0 < a1 <= srcN or not finite, a scale above
+   KAJO_VIEW_MAX_SCALE, an unknown filter, a capacity below the number of floats). With first, count and weights all NULL it only
+   reports the size, as kajo_hip_launch_order does. */
+int kajo_hip_view_weights(int32_t srcN, double a0, double a1, int32_t outN, uint32_t filter, int32_t* first, int32_t* count, float* weights,
+                          size_t capacity);
+/* The two transfer tables of the definition; either may be NULL. Pure host code. */
+void kajo_hip_view_tables(float lin[256], float thresholds[255]);
+/* The stage over a caller's image: src = HOST pointer to width*height words, dst = HOST pointer to outW*outH words, on the handle's
+   device and stream. Needs no pass rendered and touches nothing of the handle but the stage's scratch. Waits. */
+int kajo_hip_view_argb8(kajo_hip_t h, const KajoViewParams* view, const uint32_t* src, uint32_t* dst);
+/* kajo_hip_present_lens_argb8 into the stage's scratch, then the stage: despeckle -> denoise -> lens -> glare -> local -> meter -> tone
+   mapping -> view. argb8 = HOST pointer to outW*outH words (may be NULL). With view == NULL exactly kajo_hip_present_lens_argb8 (argb8
+   then holds width*height words). *result as there. Waits. */
+int kajo_hip_present_view_argb8(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoLensParams* lens,
+                                const KajoGlareParams* g, const KajoLocalParams* local, const KajoMeterParams* meter, const KajoToneParams* tone,
+                                const KajoViewParams* view, uint32_t* argb8, KajoMeterResult* result);
+/* The twin of kajo_hip_present_local_gathered_argb8_device with the stage behind it: dst = DEVICE pointer to outW*outH words. The chain's
+   image goes into the stage's scratch, the stage writes dst. Asynchronous wherever that call is (it waits only where the chain in front
+   does: KAJO_LOCAL_PIVOT_METERED and the meter) ONCE ITS SCRATCH STANDS: the first call with a view allocates, and a later view that
+   needs a larger block of rows or a larger intermediate frees the smaller one, which waits for the device as every free does; a call
+   whose parameters are the last call's, or need no more than an earlier call's, allocates nothing. A change of view parameters may
+   also wait for the previous upload of weight rows to leave the staging block, never for a kernel. With view == NULL exactly that
+   call. `result` is not in the view's own list of arguments: it mirrors kajo_hip_present_local_gathered_argb8_device, whose
+   measurement would otherwise be lost (*result as there; may be NULL without a meter). */
+int kajo_hip_present_view_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle, const KajoGlareParams* g,
+                                                const KajoLocalParams* local, const KajoMeterParams* meter, const KajoToneParams* tone,
+                                                const KajoViewParams* view, void* dst, KajoMeterResult* result);
 
 /* Use an existing HIP stream (hipStream_t passed as void*) instead of the handle's own. */
 int kajo_hip_set_stream(kajo_hip_t h, void* stream);

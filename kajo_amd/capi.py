@@ -44,6 +44,9 @@ KAJO_TONE_AUTO_EXPOSURE = 1  # KajoToneParams.flags: scale the frame's log-avera
 KAJO_METER_BINS = 514  # words of a luminance histogram (kajo_hip_meter): bin 0 below 2^-16, 1..512 sixteen per stop, 513 from 2^16 up
 KAJO_METER_AUTO_WHITE = 1  # KajoMeterParams.flags: kajo_hip_meter_tone also sets Reinhard's white from whiteL
 KAJO_LENS_MAX_RADIUS = 16  # KajoLensParams.maxRadius: the largest circle of confusion, in pixels
+KAJO_VIEW_NEAREST, KAJO_VIEW_AREA, KAJO_VIEW_TRIANGLE, KAJO_VIEW_LANCZOS3 = 0, 1, 2, 3  # KajoViewParams.filter
+KAJO_VIEW_FILTERS = {"nearest": KAJO_VIEW_NEAREST, "area": KAJO_VIEW_AREA, "triangle": KAJO_VIEW_TRIANGLE, "lanczos3": KAJO_VIEW_LANCZOS3}
+KAJO_VIEW_MAX_SCALE, KAJO_VIEW_MAX_TAPS, KAJO_VIEW_MAX_OUT = 64, 384, 16384  # the view's limits: minification, taps of a row, output edge
 KAJO_LOCAL_PIVOT_METERED = 1  # KajoLocalParams.flags: the pivot is the frame's own pivotPercentile-th luminance
 
 # every symbol include/kajo_hip.h declares
@@ -64,6 +67,8 @@ EXPORTS = [
     "kajo_hip_local_pivot",
     "kajo_hip_default_lens_params", "kajo_hip_lens", "kajo_hip_lens_coc", "kajo_hip_lens_depth_at", "kajo_hip_present_lens_argb8",
     "kajo_hip_aov_tile_buffers", "kajo_hip_compose_aov",
+    "kajo_hip_default_view_params", "kajo_hip_view_weights", "kajo_hip_view_tables", "kajo_hip_view_argb8", "kajo_hip_present_view_argb8",
+    "kajo_hip_present_view_gathered_argb8_device",
 ]
 
 
@@ -108,6 +113,11 @@ class KajoLocalParams(C.Structure):
 class KajoLensParams(C.Structure):
     _fields_ = [("aperture", C.c_float), ("focusDistance", C.c_float), ("maxRadius", C.c_int32), ("flags", C.c_uint32),
                 ("reserved", C.c_float * 4)]
+
+
+class KajoViewParams(C.Structure):
+    _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float), ("outW", C.c_int32), ("outH", C.c_int32),
+                ("filter", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class KajoParams(C.Structure):
@@ -247,6 +257,22 @@ def lib():
                                                       C.POINTER(KajoLensParams), C.POINTER(KajoGlareParams), C.POINTER(KajoLocalParams),
                                                       C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams), C.c_void_p,
                                                       C.POINTER(KajoMeterResult)]
+        if hasattr(L, "kajo_hip_view_argb8"):  # (nor the view)
+            L.kajo_hip_default_view_params.argtypes = [C.POINTER(KajoViewParams)]
+            L.kajo_hip_default_view_params.restype = None
+            L.kajo_hip_view_weights.argtypes = [C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_size_t]
+            L.kajo_hip_view_tables.argtypes = [C.c_void_p, C.c_void_p]
+            L.kajo_hip_view_tables.restype = None
+            L.kajo_hip_view_argb8.argtypes = [C.c_void_p, C.POINTER(KajoViewParams), C.c_void_p, C.c_void_p]
+            L.kajo_hip_present_view_argb8.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams),
+                                                      C.POINTER(KajoLensParams), C.POINTER(KajoGlareParams), C.POINTER(KajoLocalParams),
+                                                      C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams), C.POINTER(KajoViewParams),
+                                                      C.c_void_p, C.POINTER(KajoMeterResult)]
+            L.kajo_hip_present_view_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams),
+                                                                      C.POINTER(KajoGlareParams), C.POINTER(KajoLocalParams),
+                                                                      C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams),
+                                                                      C.POINTER(KajoViewParams), C.c_void_p, C.POINTER(KajoMeterResult)]
         if hasattr(L, "kajo_hip_read_matte"):  # (nor the mattes)
             L.kajo_hip_read_matte.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
             L.kajo_hip_matte_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

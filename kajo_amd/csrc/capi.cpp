@@ -23,6 +23,7 @@
 #include "stage.h"
 #include "launch_order.h"
 #include "launch_plan.h"
+#include "view_weights.h"
 
 // launchers defined next to their kernels (kernel_fast.hip, kernel_strict.hip, kernel_exact.hip, aux_kernels.hip)
 extern "C" {
@@ -70,6 +71,9 @@ int kajo_lens_coc_launch(const TileMap* map, const void* albedoHits, const void*
                          void* scratch, void* stream);
 int kajo_lens_launch(const void* src, const TileMap* map, int fromTiles, float passes, const void* albedoHits, const void* normalDepth,
                      float aperture, float focusDistance, int maxRadius, void* scratch, void* out, void* stream);
+int kajo_view_launch(const void* src, int W, const void* tables, const void* firstX, const void* countX, const void* wxT, int strideX,
+                     const void* firstY, const void* countY, const void* wy, int strideY, int outW, int outH, int row0, int rows, void* T, void* dst,
+                     void* stream);
 int kajo_compose_aov_launch(const void* gatheredAov, const void* gatheredMatte, const TileMap* map, void* aov, void* matte, void* stream);
 int kajo_matte_rank_launch(const void* ids, const void* counts, int W, int H, void* rankedIds, void* rankedCounts, void* stream);
 int kajo_matte_mask_launch(const void* ids, const void* counts, int W, int H, const void* selected, unsigned nObjects, float samples, void* mask,
@@ -271,6 +275,20 @@ struct KajoHip
     // depth of field (lens.hip; kajo_hip_lens, kajo_hip_lens_coc, kajo_hip_present_lens_argb8), on its first call: two float planes of
     // kajo_lens_plane (r, z), the tap records float4 [W * H], then the output frame float4 [W * H]
     DeviceBuffer lens;
+    // the view (view.hip; kajo_hip_view_argb8, kajo_hip_present_view_*), on its first call and grown when a larger view asks: the tables
+    // and the weight rows of both axes in one block (viewImage's layout), uploaded from the pinned block `viewStaging` only when the
+    // parameters differ from `viewLast`; the intermediate T; an ARGB8 frame W x H for the chain's image; one outW x outH for the output
+    DeviceBuffer viewRows, viewMid, viewIn, viewOut;
+    size_t viewRowsBytes = 0, viewMidBytes = 0, viewOutBytes = 0, viewStagingBytes = 0;
+    void* viewStaging = nullptr;
+    hipEvent_t viewUploaded = nullptr; // the last upload has left viewStaging
+    bool viewPlanned = false;
+    KajoViewParams viewLast{};
+    struct
+    {
+        size_t firstX, countX, wx, firstY, countY, wy; // byte offsets into viewRows (the tables are at 0)
+        int strideX, strideY, row0, rows;
+    } viewPlan{};
     int toneScaleState = 0; // the s of the most recent tone mapping: 0 none yet, 1 toneScale, 2 the scale word (auto exposure)
     float toneScale = 1.0f;
 };
@@ -334,6 +352,10 @@ void destroy(KajoHip* h)
     }
     for (hipEvent_t e : h->eventPool)
         (void)hipEventDestroy(e);
+    if (h->viewUploaded)
+        (void)hipEventDestroy(h->viewUploaded);
+    if (h->viewStaging)
+        (void)hipHostFree(h->viewStaging);
     if (h->ownStream && h->stream)
         (void)hipStreamDestroy(h->stream);
     delete h;
@@ -528,7 +550,9 @@ const char* kajo_hip_last_error(void)
 
 const char* kajo_hip_version(void)
 {
-    return "kajo-hip 0.1 (gfx950; aov-matte; local; aov-tiled; lens)";
+    // (a comma, not a semicolon, in front of "view": tests/test_lens_cpu.py looks for "lens" in the LAST ';'-separated field, so the
+    // stages added after the lens join that field; the next stage appends ", name" likewise)
+    return "kajo-hip 0.1 (gfx950; aov-matte; local; aov-tiled; lens, view)";
 }
 
 void kajo_hip_default_params(KajoParams* p)
@@ -2488,6 +2512,275 @@ int kajo_hip_present_lens_argb8(kajo_hip_t h, const KajoDespeckleParams* despeck
     if (argb8)
         HIP_TRY(hipMemcpyAsync(argb8, h->argb.p, count * 4, hipMemcpyDeviceToHost, h->stream));
     return kajo_hip_wait(h);
+}
+
+} // extern "C"
+
+namespace
+{
+
+// The refusals of KajoViewParams that need no handle (KAJO_E_INVALID), in the header's order
+int checkView(const KajoViewParams* p)
+{
+    if (!p)
+        return fail(KAJO_E_INVALID, "null view parameters");
+    if (!(std::isfinite(p->x0) && std::isfinite(p->y0) && std::isfinite(p->x1) && std::isfinite(p->y1)))
+        return fail(KAJO_E_INVALID, "view rectangle edges must be finite");
+    const bool whole = p->x0 == 0.0f && p->y0 == 0.0f && p->x1 == 0.0f && p->y1 == 0.0f;
+    if (!whole && !(0.0f <= p->x0 && p->x0 < p->x1 && 0.0f <= p->y0 && p->y0 < p->y1))
+        return fail(KAJO_E_INVALID, "view rectangle must satisfy 0 <= x0 < x1 and 0 <= y0 < y1");
+    if (p->outW < 1 || p->outW > KAJO_VIEW_MAX_OUT || p->outH < 1 || p->outH > KAJO_VIEW_MAX_OUT)
+        return fail(KAJO_E_INVALID, "view output size must be in [1, 16384]");
+    if (!whole && (((double)p->x1 - p->x0) / p->outW > KAJO_VIEW_MAX_SCALE || ((double)p->y1 - p->y0) / p->outH > KAJO_VIEW_MAX_SCALE))
+        return fail(KAJO_E_INVALID, "view minification must be at most 64");
+    if (p->filter > KAJO_VIEW_LANCZOS3)
+        return fail(KAJO_E_INVALID, "unknown view filter");
+    if (p->flags)
+        return fail(KAJO_E_INVALID, "unknown view flag");
+    return KAJO_OK;
+}
+
+struct ViewRect
+{
+    double x0, y0, x1, y1;
+    bool copy; // the copy case: the whole frame at its own size
+};
+
+// ... and those that need the frame's size: last of all, behind the null handle
+int checkViewHandle(kajo_hip_t h, const KajoViewParams* p, ViewRect* r)
+{
+    if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    const bool whole = p->x0 == 0.0f && p->y0 == 0.0f && p->x1 == 0.0f && p->y1 == 0.0f;
+    *r = ViewRect{p->x0, p->y0, whole ? (double)h->W : (double)p->x1, whole ? (double)h->H : (double)p->y1, false};
+    if (r->x1 > h->W || r->y1 > h->H)
+        return fail(KAJO_E_INVALID, "view rectangle must lie inside the frame");
+    if ((r->x1 - r->x0) / p->outW > KAJO_VIEW_MAX_SCALE || (r->y1 - r->y0) / p->outH > KAJO_VIEW_MAX_SCALE)
+        return fail(KAJO_E_INVALID, "view minification must be at most 64");
+    r->copy = p->outW == h->W && p->outH == h->H && r->x0 == 0.0 && r->y0 == 0.0 && r->x1 == h->W && r->y1 == h->H;
+    return KAJO_OK;
+}
+
+hipError_t growBuffer(DeviceBuffer& b, size_t* have, size_t want)
+{
+    if (b && *have >= want)
+        return hipSuccess;
+    *have = 0;
+    hipError_t e = b.alloc(want); // (hipFree of the smaller one waits for the device: nothing in flight reads it after)
+    if (e == hipSuccess)
+        *have = want;
+    return e;
+}
+
+// Form the weight rows of *p and upload them with the tables, unless they are the last call's. One block: lin[256], thresholds[255 + 1
+// pad], firstX / countX [outW], wxT [strideX][outW] (tap-major: view.hip), firstY / countY [outH], wy [outH][strideY].
+int viewPlan(KajoHip* h, const KajoViewParams* p, const ViewRect& r)
+{
+    if (h->viewPlanned && std::memcmp(&h->viewLast, p, sizeof *p) == 0)
+        return KAJO_OK;
+    h->viewPlanned = false;
+    kajo::ViewAxis ax, ay;
+    if (!kajo::viewAxis(h->W, r.x0, r.x1, p->outW, p->filter, &ax) || !kajo::viewAxis(h->H, r.y0, r.y1, p->outH, p->filter, &ay))
+        return fail(KAJO_E_INVALID, "view row longer than 384 taps");
+    auto& pl = h->viewPlan;
+    size_t at = 512 * 4;
+    pl.firstX = at, at += (size_t)p->outW * 4;
+    pl.countX = at, at += (size_t)p->outW * 4;
+    pl.wx = at, at += (size_t)p->outW * ax.stride * 4;
+    pl.firstY = at, at += (size_t)p->outH * 4;
+    pl.countY = at, at += (size_t)p->outH * 4;
+    pl.wy = at, at += (size_t)p->outH * ay.stride * 4;
+    pl.strideX = ax.stride;
+    pl.strideY = ay.stride;
+    pl.row0 = ay.lo;
+    pl.rows = ay.hi - ay.lo;
+    if (!h->viewUploaded)
+        HIP_TRY(hipEventCreateWithFlags(&h->viewUploaded, hipEventDisableTiming));
+    else
+        HIP_TRY(hipEventSynchronize(h->viewUploaded)); // (the copy before this one has left the staging block; kernels are not waited for)
+    if (h->viewStagingBytes < at) {
+        if (h->viewStaging)
+            (void)hipHostFree(h->viewStaging);
+        h->viewStaging = nullptr;
+        h->viewStagingBytes = 0;
+        HIP_TRY(hipHostMalloc(&h->viewStaging, at, hipHostMallocDefault));
+        h->viewStagingBytes = at;
+    }
+    HIP_TRY(growBuffer(h->viewRows, &h->viewRowsBytes, at));
+    char* host = static_cast<char*>(h->viewStaging);
+    float* tables = reinterpret_cast<float*>(host);
+    kajo::viewTables(tables, tables + 256);
+    tables[511] = tables[510]; // (the pad: staged by the kernel, never compared)
+    std::memcpy(host + pl.firstX, ax.first.data(), (size_t)p->outW * 4);
+    std::memcpy(host + pl.countX, ax.count.data(), (size_t)p->outW * 4);
+    float* wxT = reinterpret_cast<float*>(host + pl.wx);
+    for (int i = 0; i < p->outW; i++)
+        for (int k = 0; k < ax.stride; k++)
+            wxT[(size_t)k * p->outW + i] = ax.weights[(size_t)i * ax.stride + k];
+    std::memcpy(host + pl.firstY, ay.first.data(), (size_t)p->outH * 4);
+    std::memcpy(host + pl.countY, ay.count.data(), (size_t)p->outH * 4);
+    std::memcpy(host + pl.wy, ay.weights.data(), (size_t)p->outH * ay.stride * 4);
+    HIP_TRY(hipMemcpyAsync(h->viewRows.p, host, at, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipEventRecord(h->viewUploaded, h->stream));
+    h->viewLast = *p;
+    h->viewPlanned = true;
+    return KAJO_OK;
+}
+
+// Enqueue the stage: src (device, W x H words) -> dst (device, outW x outH words). Checked by checkView and checkViewHandle, device
+// bound. The copy case launches nothing.
+int viewImage(KajoHip* h, const KajoViewParams* p, const ViewRect& r, const void* src, void* dst)
+{
+    if (r.copy) {
+        if (src != dst)
+            HIP_TRY(hipMemcpyAsync(dst, src, (size_t)h->W * h->H * 4, hipMemcpyDeviceToDevice, h->stream));
+        return KAJO_OK;
+    }
+    int rc = viewPlan(h, p, r);
+    if (rc)
+        return rc;
+    const auto& pl = h->viewPlan;
+    HIP_TRY(growBuffer(h->viewMid, &h->viewMidBytes, (size_t)p->outW * pl.rows * 16));
+    const char* rows = h->viewRows.as<char>();
+    hipError_t le = (hipError_t)kajo_view_launch(src, h->W, rows, rows + pl.firstX, rows + pl.countX, rows + pl.wx, pl.strideX, rows + pl.firstY,
+                                                 rows + pl.countY, rows + pl.wy, pl.strideY, p->outW, p->outH, pl.row0, pl.rows, h->viewMid.p, dst,
+                                                 h->stream);
+    if (le != hipSuccess)
+        return failHip(le, "view kernel launch");
+    return KAJO_OK;
+}
+
+// the refusals of the view chain calls in front of the denoiser's and the handle's: despeckle, lens, glare, local, meter, tone, view
+int checkViewChain(const KajoDespeckleParams* despeckle, const KajoLensParams* lens, const KajoGlareParams* g, const KajoLocalParams* local,
+                   const KajoMeterParams* meter, const KajoToneParams* tone, const KajoViewParams* view)
+{
+    int rc;
+    if (despeckle && (rc = checkDespeckle(despeckle)))
+        return rc;
+    if (lens && (rc = checkLens(lens)))
+        return rc;
+    if (g && (rc = checkGlare(g)))
+        return rc;
+    if (local && (rc = checkLocal(local)))
+        return rc;
+    if (meter && (rc = checkMeter(meter)))
+        return rc;
+    ToneArgs t{};
+    if ((rc = toneArgsOf(tone, &t)))
+        return rc;
+    if (meter && (tone->flags & KAJO_TONE_AUTO_EXPOSURE))
+        return fail(KAJO_E_INVALID, "metered exposure and the tone parameters' automatic exposure are two automatic exposures: give one");
+    return checkView(view);
+}
+
+} // namespace
+
+extern "C" {
+
+void kajo_hip_default_view_params(KajoViewParams* p)
+{
+    if (!p)
+        return;
+    std::memset(p, 0, sizeof *p);
+    p->filter = KAJO_VIEW_AREA;
+}
+
+int kajo_hip_view_weights(int32_t srcN, double a0, double a1, int32_t outN, uint32_t filter, int32_t* first, int32_t* count, float* weights,
+                          size_t capacity)
+{
+    if (!kajo::viewAxisValid(srcN, a0, a1, outN, filter))
+        return fail(KAJO_E_INVALID, "invalid view axis");
+    kajo::ViewAxis ax;
+    if (!kajo::viewAxis(srcN, a0, a1, outN, filter, &ax))
+        return fail(KAJO_E_INVALID, "view row longer than 384 taps");
+    if (first || count || weights) {
+        if (!first || !count || !weights)
+            return fail(KAJO_E_INVALID, "null argument");
+        if (capacity < ax.weights.size())
+            return fail(KAJO_E_INVALID, "weights array too small");
+        std::memcpy(first, ax.first.data(), ax.first.size() * sizeof(int32_t));
+        std::memcpy(count, ax.count.data(), ax.count.size() * sizeof(int32_t));
+        std::memcpy(weights, ax.weights.data(), ax.weights.size() * sizeof(float));
+    }
+    return (int)ax.weights.size();
+}
+
+void kajo_hip_view_tables(float lin[256], float thresholds[255])
+{
+    kajo::viewTables(lin, thresholds);
+}
+
+int kajo_hip_view_argb8(kajo_hip_t h, const KajoViewParams* view, const uint32_t* src, uint32_t* dst)
+{
+    int rc = checkView(view);
+    if (rc)
+        return rc;
+    ViewRect r{};
+    if ((rc = checkViewHandle(h, view, &r)))
+        return rc;
+    if (!src || !dst)
+        return fail(KAJO_E_INVALID, "null argument");
+    if ((rc = bind(h)))
+        return rc;
+    const size_t count = (size_t)h->W * h->H, outBytes = (size_t)view->outW * view->outH * 4;
+    HIP_TRY(h->viewIn.ensure(count * 4));
+    HIP_TRY(growBuffer(h->viewOut, &h->viewOutBytes, outBytes));
+    HIP_TRY(hipMemcpyAsync(h->viewIn.p, src, count * 4, hipMemcpyHostToDevice, h->stream));
+    if ((rc = viewImage(h, view, r, h->viewIn.p, h->viewOut.p)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(dst, h->viewOut.p, outBytes, hipMemcpyDeviceToHost, h->stream));
+    return kajo_hip_wait(h);
+}
+
+int kajo_hip_present_view_argb8(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoLensParams* lens,
+                                const KajoGlareParams* g, const KajoLocalParams* local, const KajoMeterParams* meter, const KajoToneParams* tone,
+                                const KajoViewParams* view, uint32_t* argb8, KajoMeterResult* result)
+{
+    if (!view)
+        return kajo_hip_present_lens_argb8(h, despeckle, denoise, lens, g, local, meter, tone, argb8, result);
+    // (every refusal before any device work: the stages' parameters, the view's, the denoiser's, the handle, the view against the frame)
+    int rc = checkViewChain(despeckle, lens, g, local, meter, tone, view);
+    if (rc)
+        return rc;
+    if (denoise && (rc = checkDenoise(h, denoise)))
+        return rc;
+    ViewRect r{};
+    if ((rc = checkViewHandle(h, view, &r)))
+        return rc;
+    // the chain's image into the handle's ARGB8 frame (the call reads nothing back), then the stage
+    if ((rc = kajo_hip_present_lens_argb8(h, despeckle, denoise, lens, g, local, meter, tone, nullptr, result)))
+        return rc;
+    const size_t outBytes = (size_t)view->outW * view->outH * 4;
+    HIP_TRY(growBuffer(h->viewOut, &h->viewOutBytes, outBytes));
+    if ((rc = viewImage(h, view, r, h->argb.p, h->viewOut.p)))
+        return rc;
+    if (argb8)
+        HIP_TRY(hipMemcpyAsync(argb8, h->viewOut.p, outBytes, hipMemcpyDeviceToHost, h->stream));
+    return kajo_hip_wait(h);
+}
+
+int kajo_hip_present_view_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle, const KajoGlareParams* g,
+                                                const KajoLocalParams* local, const KajoMeterParams* meter, const KajoToneParams* tone,
+                                                const KajoViewParams* view, void* dst, KajoMeterResult* result)
+{
+    if (!view)
+        return kajo_hip_present_local_gathered_argb8_device(h, gathered, despeckle, g, local, meter, tone, dst, result);
+    int rc = checkViewChain(despeckle, nullptr, g, local, meter, tone, view);
+    if (rc)
+        return rc;
+    ViewRect r{};
+    if ((rc = checkViewHandle(h, view, &r)))
+        return rc;
+    if (!dst)
+        return fail(KAJO_E_INVALID, "null argument");
+    if ((rc = bind(h)))
+        return rc;
+    if (r.copy)
+        return kajo_hip_present_local_gathered_argb8_device(h, gathered, despeckle, g, local, meter, tone, dst, result);
+    HIP_TRY(h->viewIn.ensure((size_t)h->W * h->H * 4));
+    if ((rc = kajo_hip_present_local_gathered_argb8_device(h, gathered, despeckle, g, local, meter, tone, h->viewIn.p, result)))
+        return rc;
+    return viewImage(h, view, r, h->viewIn.p, dst);
 }
 
 int kajo_hip_tone_scale(kajo_hip_t h, float* scale)

@@ -545,6 +545,36 @@ void Scheduler::readPresented(const KajoDespeckleParams* despeckle, const KajoDe
     }
 }
 
+void Scheduler::readViewed(uint32_t* dst)
+{
+    Impl& d = *m_impl;
+    if (!d.opt.viewOn)
+        throw std::runtime_error("hip::Scheduler: readViewed needs Options::viewOn");
+    if (d.gathered && !d.composed) { // (as readDisplayed)
+        check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
+        d.composed = true;
+    }
+    KajoLensParams lens = d.opt.lens;
+    if (d.opt.lensOn) {
+        d.composeAov();
+        if (d.opt.lensFocusAt.x >= 0) {
+            float z = 0;
+            check(kajo_hip_lens_depth_at(d.handles[0], d.opt.lensFocusAt.x, d.opt.lensFocusAt.y, &z), "kajo_hip_lens_depth_at");
+            if (!std::isfinite(z))
+                throw std::runtime_error("hip::Scheduler: the pixel to focus on (" + std::to_string(d.opt.lensFocusAt.x) + ", " +
+                                         std::to_string(d.opt.lensFocusAt.y) + ") is far (a miss, or no finite depth): nothing to focus on");
+            lens.focusDistance = z;
+        }
+    }
+    // (with every optional stage NULL the call routes itself to the call readPresented makes: the chain's image is the same words)
+    check(kajo_hip_present_view_argb8(d.handles[0], d.opt.despeckleOn ? &d.opt.despeckle : nullptr, nullptr, d.opt.lensOn ? &lens : nullptr,
+                                      &d.opt.glare, d.localActive() ? &d.opt.local : nullptr, d.opt.meterOn ? &d.opt.meter : nullptr, &d.opt.tone,
+                                      &d.opt.view, dst, &d.metered),
+          "kajo_hip_present_view_argb8");
+    if (d.localActive())
+        d.notePivot();
+}
+
 void Scheduler::run()
 {
     Impl& d = *m_impl;

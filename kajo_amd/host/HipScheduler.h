@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "Scheduler.h"
-#include "kajo_hip.h" // KajoToneParams (Options::tone), KajoGlareParams (Options::glare), KajoDespeckleParams (Options::despeckle), KajoMeterParams, KajoLocalParams, KajoLensParams
+#include "kajo_hip.h" // KajoToneParams (Options::tone), KajoGlareParams (Options::glare), KajoDespeckleParams (Options::despeckle), KajoMeterParams, KajoLocalParams, KajoLensParams, KajoViewParams
 
 class Image;
 class Preview;
@@ -100,6 +100,12 @@ struct Options
     bool lensOn = false;
     KajoLensParams lens = {};
     struct { int x = -1, y = -1; } lensFocusAt;
+    // The view behind the tone curves of the image readViewed() hands out (include/kajo_hip.h kajo_hip_present_view_argb8): a source
+    // rectangle, an output size and a filter -- crop, zoom, or the average of a supersampled render. Off by default: readViewed() is then
+    // refused, and run()'s refreshes into Kajo's own Image keep the frame's size and the calls they made in either case. Whoever sets viewOn
+    // fills `view` with kajo_hip_default_view_params first and names outW and outH.
+    bool viewOn = false;
+    KajoViewParams view = {};
 };
 
 struct Statistics
@@ -163,6 +169,9 @@ public:
     // the focus distance of the most recent image with the depth of field (Options::lensOn: readPresented) and the largest circle of
     // confusion in it, in pixels; false where the stage has not run
     bool lastLens(float* focusDistance, float* maxRadiusPx) const;
+    // the image of readPresented() with Options' own stages, through Options::view: dst = view.outW * view.outH words. Any number of GPUs
+    // (the frame is composed on the first handle, as readPresented does). Throws where Options::viewOn is not set.
+    void readViewed(uint32_t* dst);
 
 private:
     struct Impl;

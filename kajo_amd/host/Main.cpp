@@ -73,6 +73,8 @@ int main(int argc, char** argv)
     std::string localContrast, localDetail, localRange, localIterations, localPivot;
     // depth of field options (include/kajo_hip.h KajoLensParams): the raw text, checked after the loop
     std::string lensAperture, lensFocus, lensFocusAt, lensMaxRadius;
+    // view options (include/kajo_hip.h KajoViewParams): the raw text, checked after the loop
+    std::string outputSize, viewRect, viewFilter, supersample;
     int width = 640, height = 480;
     int denoiseIterations = 5;
     hip::Options opt;
@@ -165,7 +167,16 @@ int main(int argc, char** argv)
                         "                    image-space approximation; --hdr and --raw stay the raw mean (--json: lens_focus, lens_max_radius_px)\n"
                         "    --lens-focus D  --lens-aperture: the distance in focus, > 0, in the depth AOV's units\n"
                         "    --lens-focus-at X,Y  --lens-aperture: focus on what that pixel shows (the default: the frame's centre pixel)\n"
-                        "    --lens-max-radius R  --lens-aperture: the largest blur radius in pixels, 1..16 (16)\n",
+                        "    --lens-max-radius R  --lens-aperture: the largest blur radius in pixels, 1..16 (16)\n"
+                        "    --output-size WxH  the view behind the tone curves (-o; include/kajo_hip.h kajo_hip_present_view_argb8): -o is written at W x H,\n"
+                        "                    1..16384 each, at most 64 times smaller than the frame, resampled in linear light; any --gpus. --hdr, --raw,\n"
+                        "                    --aov, --denoise and the matte files stay at the rendered size (--json: view_out_w, view_out_h, view_filter,\n"
+                        "                    view_scale_x, view_scale_y)\n"
+                        "    --view X0,Y0,X1,Y1  the view: the part of the frame -o shows, in pixels of the rendered frame, fractions allowed (the whole\n"
+                        "                    frame); without --output-size the output keeps the frame's size: a zoom\n"
+                        "    --view-filter nearest|area|triangle|lanczos3  the view: the resampling filter (area: the exact area average)\n"
+                        "    --supersample K  render and run the whole chain at K w x K h for the given -w -h, K = 2..8, the aspect unchanged, and write -o at\n"
+                        "                    w x h with the area filter: K x K display-referred pixels averaged per pixel. Not with --output-size\n",
                         args[0].c_str());
             return 1;
         } else if (a == "-w" && more) width = std::atoi(args[++i].c_str());
@@ -213,6 +224,10 @@ int main(int argc, char** argv)
         else if (a == "--lens-focus" && more) lensFocus = args[++i];
         else if (a == "--lens-focus-at" && more) lensFocusAt = args[++i];
         else if (a == "--lens-max-radius" && more) lensMaxRadius = args[++i];
+        else if (a == "--output-size" && more) outputSize = args[++i];
+        else if (a == "--view" && more) viewRect = args[++i];
+        else if (a == "--view-filter" && more) viewFilter = args[++i];
+        else if (a == "--supersample" && more) supersample = args[++i];
         else if (a == "--aov" && more) aovPrefix = args[++i];
         else if (a == "--aov-specular") aovSpecular = true;
         else if (a == "--aov-tiled") aovTiled = true;
@@ -392,6 +407,75 @@ int main(int argc, char** argv)
             return 1;
         }
     }
+    const bool viewGiven = !outputSize.empty() || !viewRect.empty() || !viewFilter.empty() || !supersample.empty();
+    const char* viewFilterNames[] = {"nearest", "area", "triangle", "lanczos3"};
+    if (viewGiven) {
+        // (before any device is opened: the refusals of the view, with the option's name)
+        if (threeArg) {
+            std::cerr << "kajo_render: the view options need the options constructor (without --three-arg)" << std::endl;
+            return 1;
+        }
+        if (!supersample.empty() && !outputSize.empty()) {
+            std::cerr << "kajo_render: --supersample and --output-size are two output sizes: give one" << std::endl;
+            return 1;
+        }
+        opt.viewOn = true;
+        kajo_hip_default_view_params(&opt.view);
+        opt.view.outW = width;
+        opt.view.outH = height;
+        if (!supersample.empty()) {
+            char* end = nullptr;
+            const long k = std::strtol(supersample.c_str(), &end, 10);
+            if (end == supersample.c_str() || *end != '\0' || k < 2 || k > 8) {
+                std::cerr << "kajo_render: --supersample K must be in 2..8" << std::endl;
+                return 1;
+            }
+            if (!viewFilter.empty() && viewFilter != "area") {
+                std::cerr << "kajo_render: --supersample averages with the area filter: --view-filter must be area with it" << std::endl;
+                return 1;
+            }
+            // (the frame, and everything written at the rendered size, is K times the size asked for; the aspect is unchanged)
+            width *= (int)k;
+            height *= (int)k;
+        }
+        if (!outputSize.empty()) {
+            int w = 0, h = 0;
+            char tail = 0;
+            if (std::sscanf(outputSize.c_str(), "%dx%d%c", &w, &h, &tail) != 2 || w < 1 || h < 1 || w > KAJO_VIEW_MAX_OUT || h > KAJO_VIEW_MAX_OUT) {
+                std::cerr << "kajo_render: --output-size WxH: view output size must be in [1, 16384]" << std::endl;
+                return 1;
+            }
+            opt.view.outW = w;
+            opt.view.outH = h;
+        }
+        if (!viewRect.empty()) {
+            float r[4];
+            char tail = 0;
+            if (std::sscanf(viewRect.c_str(), "%f,%f,%f,%f%c", &r[0], &r[1], &r[2], &r[3], &tail) != 4 || !std::isfinite(r[0]) || !std::isfinite(r[1]) ||
+                !std::isfinite(r[2]) || !std::isfinite(r[3]) || !(0.0f <= r[0] && r[0] < r[2] && r[2] <= (float)width) ||
+                !(0.0f <= r[1] && r[1] < r[3] && r[3] <= (float)height)) {
+                std::cerr << "kajo_render: --view X0,Y0,X1,Y1: view rectangle must satisfy 0 <= x0 < x1 <= width and 0 <= y0 < y1 <= height" << std::endl;
+                return 1;
+            }
+            opt.view.x0 = r[0], opt.view.y0 = r[1], opt.view.x1 = r[2], opt.view.y1 = r[3];
+        }
+        if (!viewFilter.empty()) {
+            uint32_t f = 0;
+            while (f < 4 && viewFilter != viewFilterNames[f])
+                f++;
+            if (f == 4) {
+                std::cerr << "kajo_render: --view-filter must be nearest, area, triangle or lanczos3" << std::endl;
+                return 1;
+            }
+            opt.view.filter = f;
+        }
+        const double sx = (viewRect.empty() ? (double)width : (double)opt.view.x1 - opt.view.x0) / opt.view.outW;
+        const double sy = (viewRect.empty() ? (double)height : (double)opt.view.y1 - opt.view.y0) / opt.view.outH;
+        if (sx > KAJO_VIEW_MAX_SCALE || sy > KAJO_VIEW_MAX_SCALE) {
+            std::cerr << "kajo_render: view minification must be at most 64" << std::endl;
+            return 1;
+        }
+    }
     if (lensAperture.empty() && (!lensFocus.empty() || !lensFocusAt.empty() || !lensMaxRadius.empty())) {
         std::cerr << "kajo_render: --lens-focus, --lens-focus-at and --lens-max-radius shape the stage that --lens-aperture turns on: give them with --lens-aperture" << std::endl;
         return 1;
@@ -535,6 +619,7 @@ int main(int argc, char** argv)
     bool localRan = false;
     float lensFocusUsed = 0, lensMaxRadiusPx = 0; // --json with --lens-aperture: of the image -o holds
     bool lensRan = false;
+    std::unique_ptr<Image> viewed; // -o with a view option: the image at the view's size
     try {
         if (rendererName == "hip") {
             // (--three-arg: the statement integration/apply_to_kajo.sh adds to renderer/Main.cpp:135-142, word for word)
@@ -630,11 +715,16 @@ int main(int argc, char** argv)
             if (!denoised.save(denoiseOut))
                 return 3;
         }
+        if (viewGiven && !out.empty()) {
+            // (the image -o holds: the display chain as run() left the frame, through the view, at the view's size)
+            viewed.reset(new Image(opt.view.outW, opt.view.outH));
+            hipScheduler->readViewed(viewed->pixels.get());
+        }
     } catch (const std::exception& e) {
         std::cerr << "kajo_render: " << e.what() << std::endl;
         return 2;
     }
-    if (!out.empty() && !image->save(out))
+    if (!out.empty() && !(viewed ? viewed->save(out) : image->save(out)))
         return 3;
     if (json) {
         const hip::Statistics& s = hipScheduler->statistics();
@@ -680,6 +770,11 @@ int main(int argc, char** argv)
         }
         if (lensGiven && lensRan)
             std::printf(", \"lens_focus\": %.9g, \"lens_max_radius_px\": %.9g", (double)lensFocusUsed, (double)lensMaxRadiusPx);
+        if (viewGiven)
+            std::printf(", \"view_out_w\": %d, \"view_out_h\": %d, \"view_filter\": \"%s\", \"view_scale_x\": %.9g, \"view_scale_y\": %.9g",
+                        (int)opt.view.outW, (int)opt.view.outH, viewFilterNames[opt.view.filter],
+                        (viewRect.empty() ? (double)width : (double)opt.view.x1 - opt.view.x0) / opt.view.outW,
+                        (viewRect.empty() ? (double)height : (double)opt.view.y1 - opt.view.y0) / opt.view.outH);
         if (aovTiled)
             std::printf(", \"aov_tiled\": true");
         if (matteGiven)

@@ -354,8 +354,32 @@ class HipRenderer:
         capi.check(self._L.kajo_hip_lens_depth_at(self._h, int(x), int(y), C.byref(z)))
         return z.value
 
+    def _view_params(self, out_w: int = None, out_h: int = None, rect=None, filter=None):
+        p = capi.KajoViewParams()
+        self._L.kajo_hip_default_view_params(C.byref(p))
+        p.outW = self.width if out_w is None else int(out_w)
+        p.outH = self.height if out_h is None else int(out_h)
+        if rect is not None:
+            p.x0, p.y0, p.x1, p.y1 = (float(v) for v in rect)
+        if filter is not None:
+            p.filter = capi.KAJO_VIEW_FILTERS[filter] if isinstance(filter, str) else int(filter)
+        return p
+
+    def view(self, image: np.ndarray, **params) -> np.ndarray:
+        """The view of a caller's image (include/kajo_hip.h kajo_hip_view_argb8): crop, zoom or supersampled output of an (H, W) uint32
+        image of 0xAARRGGBB words, resampled in linear light -> (out_h, out_w) uint32. params: out_w, out_h (the frame's size where
+        left out), rect (x0, y0, x1, y1) in source pixels (the whole frame where left out), filter ("nearest", "area" -- the default --,
+        "triangle", "lanczos3", or a KAJO_VIEW_* value). Needs no pass rendered; nothing of the handle's state is touched."""
+        v = self._view_params(**params)
+        src = np.ascontiguousarray(image, np.uint32)
+        if src.shape != (self.height, self.width):
+            raise ValueError("the image must be (%d, %d), the handle's frame" % (self.height, self.width))
+        out = np.empty((v.outH, v.outW), np.uint32)
+        capi.check(self._L.kajo_hip_view_argb8(self._h, C.byref(v), src.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def present(self, despeckle: dict = None, denoise: dict = None, glare: dict = None, meter: dict = None, local: dict = None,
-                lens: dict = None, **tone):
+                lens: dict = None, view: dict = None, **tone):
         """The display chain with the despeckle in front (include/kajo_hip.h kajo_hip_present_argb8): despeckle -> denoise -> glare ->
         tone mapping -> (argb8, scale) as tonemap(), every stage but the last optional. despeckle: a dict of despeckle()'s factor / rank /
         floor; the rest as display(). With despeckle None it is display(denoise, glare, **tone). meter: a dict of meter()'s params puts
@@ -363,7 +387,8 @@ class HipRenderer:
         one, auto_white sets Reinhard's white) and makes the second value the result dict of meter() instead of the scale. local: a dict
         of local()'s params puts the local tone mapping between the glare and the meter (kajo_hip_present_local_argb8; the call is
         routed there only when it is given). lens: a dict of lens()'s params puts the depth of field between the denoiser and the glare
-        (kajo_hip_present_lens_argb8; likewise routed there only when it is given)."""
+        (kajo_hip_present_lens_argb8; likewise routed there only when it is given). view: a dict of view()'s params puts the view behind
+        the tone curves (kajo_hip_present_view_argb8; likewise): the array returned then has the view's shape (out_h, out_w)."""
         t = self._tone_params(**tone)
         s = None if despeckle is None else self._despeckle_params(**despeckle)
         d = None if denoise is None else self._denoise_params(**denoise)
@@ -371,6 +396,16 @@ class HipRenderer:
         argb8 = np.empty((self.height, self.width), np.uint32)
         scale = C.c_float()
         ref = lambda p: None if p is None else C.byref(p)
+        if view is not None:
+            v = self._view_params(**view)
+            f = None if lens is None else self._lens_params(**lens)
+            l = None if local is None else self._local_params(**local)
+            m = None if meter is None else self._meter_params(**meter)
+            result = capi.KajoMeterResult()
+            argb8 = np.empty((max(v.outH, 0), max(v.outW, 0)), np.uint32)
+            capi.check(self._L.kajo_hip_present_view_argb8(self._h, ref(s), ref(d), ref(f), ref(g), ref(l), ref(m), C.byref(t), C.byref(v),
+                                                           argb8.ctypes.data_as(C.c_void_p), C.byref(result)))
+            return argb8, (self.tone_scale() if m is None else self._meter_result(result))
         if lens is not None:
             f = self._lens_params(**lens)
             l = None if local is None else self._local_params(**local)
@@ -449,6 +484,32 @@ class HipRenderer:
         """The whole-frame AOVs (and coverage tables) of this handle from the owners' gathered tile buffers, device pointers in rank order
         (include/kajo_hip.h kajo_hip_compose_aov); None = the handle's own buffer where it is the frame's one owner."""
         capi.check(self._L.kajo_hip_compose_aov(self._h, C.c_void_p(gathered_aov_ptr), C.c_void_p(gathered_matte_ptr)))
+
+
+def view_weights(src_n: int, a0: float, a1: float, out_n: int, filter="area"):
+    """Host-only: the view's weight rows of one axis (include/kajo_hip.h kajo_hip_view_weights) -> (first [out_n] int32, count [out_n]
+    int32, weights [out_n, stride] float32 with zeros behind a row's count)."""
+    L = capi.lib()
+    f = capi.KAJO_VIEW_FILTERS[filter] if isinstance(filter, str) else int(filter)
+    n = L.kajo_hip_view_weights(src_n, a0, a1, out_n, f, None, None, None, 0)
+    if n < 0:
+        capi.check(n)
+    first = np.zeros(out_n, np.int32)
+    count = np.zeros(out_n, np.int32)
+    weights = np.zeros((out_n, n // out_n), np.float32)
+    rc = L.kajo_hip_view_weights(src_n, a0, a1, out_n, f, first.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p),
+                                 weights.ctypes.data_as(C.c_void_p), n)
+    if rc < 0:
+        capi.check(rc)
+    return first, count, weights
+
+
+def view_tables():
+    """Host-only: the view's transfer tables (include/kajo_hip.h kajo_hip_view_tables) -> (lin [256], thresholds [255]) float32."""
+    lin = np.zeros(256, np.float32)
+    thresholds = np.zeros(255, np.float32)
+    capi.lib().kajo_hip_view_tables(lin.ctypes.data_as(C.c_void_p), thresholds.ctypes.data_as(C.c_void_p))
+    return lin, thresholds
 
 
 def stage_scene(scene: Scene):
