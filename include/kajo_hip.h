@@ -45,6 +45,10 @@
  *                            supersampled output BEHIND the tone curves: a separable resampling of the ARGB8 image in linear light;
  *                            kajo_hip_present_view_argb8 and its gathered twin put it at the end of the display chain,
  *                            kajo_hip_view_weights and kajo_hip_view_tables are the host code that defines its numbers
+ *   kajo_hip_grade           (no counterpart: the reference writes the colours it integrated) white balance, an ASC CDL op and per-object
+ *                            regrades weighted by the coverage mattes, between the denoiser and the lens; kajo_hip_present_grade_argb8
+ *                            and its gathered twin put it into the display chain, kajo_hip_grade_pixels, kajo_hip_grade_white_balance
+ *                            and kajo_hip_grade_neutral are the host code that defines its numbers
  *   kajo_hip_destroy         the unique_ptr members of cpu::Scheduler (cpu/Scheduler.h:29-31)
  *
  * Pixels are dealt to GPUs as fixed-size tiles: a handle created with
@@ -842,6 +846,111 @@ int kajo_hip_present_view_argb8(kajo_hip_t h, const KajoDespeckleParams* despeck
 int kajo_hip_present_view_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle, const KajoGlareParams* g,
                                                 const KajoLocalParams* local, const KajoMeterParams* meter, const KajoToneParams* tone,
                                                 const KajoViewParams* view, void* dst, KajoMeterResult* result);
+
+/* The grade: white balance, an ASC CDL op over the frame, and per-object regrades by matte. Every other stage of the chain decides how
+   bright a pixel is or where it lands; this one changes its colour, and it is what the coverage mattes are for: "regrade one ball or
+   dim the lights" without rendering again. Frame in, frame out, in scene-linear radiance (the units of kajo_hip_read_radiance), between
+   the denoiser and the lens: a regraded ball is then defocused, haloed and metered with its new colour, and a dimmed light throws a
+   dimmer glare. Kernels of its own (kajo_amd/csrc/grade.hip) on the handle's stream; the arithmetic is kajo_amd/csrc/grade_math.h,
+   compiled for the device and for kajo_hip_grade_pixels from the same lines, float32 IEEE without contraction in every numerics build
+   and in the order written: only the stage's inputs depend on FAST / EXACT / STRICT.
+   Definition -- P = the handle's pass count, F = the source frame in sums over passes (after whichever of despeckle and denoise are
+   asked for); per pixel:
+     m      = F.rgb / P                         the pixel COUNTS where all three are finite; otherwise out = F with the bits it had
+     op(v):   t.c = max(v.c * slope.c + offset.c, 0)      one product, one sum; fmaxf, with +0 for -0 (and for a NaN)
+              t.c = kajo_powf(t.c, power.c)               only where power.c != 1 (include/kajo_strictmath.h)
+              l   = (0.2126f * t.r + 0.7152f * t.g) + 0.0722f * t.b
+              t.c = l + saturation * (t.c - l)            only where saturation != 1
+     c      = global.op(m)
+     for k = 0 .. nRegions-1, in order:
+       mask_k = kajo_hip_matte_mask's mask for regions[k].objects: float32(sum of the selected slots' counts) / float32(samples)
+       a      = amount_k * mask_k
+       c.c    = c.c + a * (op_k(c).c - c.c)
+     out.rgb = c * P;   out.w = F.w
+   What follows from it: nothing is clamped above. The saturation step can go below 0 and is left so (the next op's max lifts it).
+   Each region sees the result of the regions before it. A pixel with mask_k == 0 keeps c bit for bit through region k: a == 0 adds +-0
+   to a value (a finite one: where op_k overflows, 0 * inf is a NaN as anywhere). The mattes are antialiased, so a regraded edge is. A
+   value that overflows is +inf, and inf - inf under the saturation step is a NaN whose payload is the machine's. White balance has no
+   field of its own: it is gains multiplied into the global slope, in binary64, rounded once (kajo_hip_grade_white_balance,
+   kajo_hip_grade_neutral).
+   THE IDENTITY CASE: the global op at its defaults and nRegions == 0. The stage then does no device work and the output is the source
+   image itself (a negative channel included, which the rule would lift to 0), as the lens does at aperture 0: every chain image is then
+   the existing call's bit for bit. No atomics and no cross-lane work: a pixel depends on the inputs through image coordinates only,
+   so the frame is the same bits on a second call, on a twin handle and on the root of any number of tile owners. The accumulation,
+   the AOVs, the matte tables, the pass count and the counters (kernelMs included) are not touched. Scratch (the output frame, the
+   parameter block and the regions' id bitsets, uploaded only when the parameters differ from the last call's) is allocated on first
+   use and freed by kajo_hip_destroy.
+   Refusals (KAJO_E_INVALID, before any device work and without the handle): NULL params; a slope, offset, power, saturation or amount
+   that is not finite or outside its range below; nRegions outside 0..KAJO_GRADE_MAX_REGIONS; a flag bit; a non-zero reserved word;
+   in a region in use, n outside 1..KAJO_GRADE_REGION_OBJECTS or a negative object id (regions[nRegions..] are not read). Where other
+   stages' parameters are present too, the order is despeckle, grade, lens, glare, local, meter, tone, view, denoise, handle. Then, for
+   nRegions > 0, the handle: an id above nPlanes + nSpheres (KAJO_E_INVALID; so is a scene whose nRegions bitsets of nPlanes + nSpheres + 1
+   bits, in whole words, exceed the 64 KiB the kernel stages: more than 131071 objects with four regions, 524287 with one), and the state by kajo_hip_matte_mask's rules -- KAJO_E_STATE on a handle without KAJO_FLAG_AOV_MATTE,
+   with no pass rendered, on a tiled handle (KAJO_FLAG_AOV_TILED) before kajo_hip_compose_aov with the matte tile buffers or after a
+   later render or reset, and on an owner of part of the frame without a composed frame. With nRegions == 0 the handle needs no AOVs. */
+#define KAJO_GRADE_MAX_REGIONS 4
+#define KAJO_GRADE_REGION_OBJECTS 16
+typedef struct KajoGradeOp {      /* ASC CDL order: slope, offset, power, then saturation */
+    float slope[3];               /* finite, 0 .. 2^16          (default 1) */
+    float offset[3];              /* finite, |.| <= 2^16        (default 0) */
+    float power[3];               /* finite, 1/8 .. 8           (default 1) */
+    float saturation;             /* finite, 0 .. 4             (default 1) */
+    float reserved[2];            /* 0 */
+} KajoGradeOp;                    /* 48 bytes */
+typedef struct KajoGradeRegion {
+    KajoGradeOp op;
+    int32_t objects[KAJO_GRADE_REGION_OBJECTS]; /* ids as kajo_hip_matte_mask takes them */
+    int32_t n;                    /* 1 .. KAJO_GRADE_REGION_OBJECTS */
+    float amount;                 /* finite, 0 .. 1 (default 1) */
+    uint32_t reserved[2];         /* 0 */
+} KajoGradeRegion;                /* 128 bytes */
+typedef struct KajoGradeParams {
+    KajoGradeOp global;
+    int32_t nRegions;             /* 0 .. KAJO_GRADE_MAX_REGIONS (default 0) */
+    uint32_t flags;               /* 0: an unknown bit is refused */
+    uint32_t reserved[2];         /* 0 */
+    KajoGradeRegion regions[KAJO_GRADE_MAX_REGIONS];
+} KajoGradeParams;                /* 576 bytes */
+/* The identity: every op at its defaults (the regions' too, amount 1, n 0), nRegions 0. NULL is accepted. */
+void kajo_hip_default_grade_params(KajoGradeParams* p);
+/* The rule above over n pixels of MEANS, pure host code (no handle, no device), compiled from the device's own lines: rgb = n * 3
+   floats (m of the definition), masks = n * nRegions floats (pixel-major: mask_k of pixel i at masks[i * nRegions + k]; may be NULL with
+   nRegions == 0), out = n * 3 floats (c of the definition; a pixel that does not count is copied with its bits; under the identity
+   case every pixel is). KAJO_E_INVALID for what the stage refuses without a handle, a NULL array or n < 0. */
+int kajo_hip_grade_pixels(const KajoGradeParams* p, const float* rgb, const float* masks, int64_t n, float* out);
+/* White balance for an illuminant of correlated colour temperature `kelvin` (1667 .. 25000) and a green / magenta `tint` (|tint| <= 1,
+   in stops of green gain), pure host code in binary64. The Planckian chromaticity by Kim et al. 2002, T = kelvin:
+     x = -0.2661239e9/T^3 - 0.2343589e6/T^2 + 0.8776956e3/T + 0.179910    T <= 4000
+         -3.0258469e9/T^3 + 2.1070379e6/T^2 + 0.2226347e3/T + 0.240390    above
+     y = -1.1063814 x^3 - 1.34811020 x^2 + 2.18555832 x - 0.20219683      T <= 2222
+         -0.9549476 x^3 - 1.37418593 x^2 + 2.09137015 x - 0.16748867      T <= 4000
+          3.0817580 x^3 - 5.87338670 x^2 + 3.75112997 x - 0.37001483      above
+   XYZ = (x / y, 1, (1 - x - y) / y); linear sRGB through the rows (3.2404542, -1.5371385, -0.4985314), (-0.9692660, 1.8760108,
+   0.0415560), (0.0556434, -0.2040259, 1.0572252); a channel <= 1e-3 is KAJO_E_INVALID (the illuminant is outside sRGB: below about
+   1900 K). g.c = 1 / rgb.c, g.g *= 2^tint, g /= 0.2126 g.r + 0.7152 g.g + 0.0722 g.b, rounded to float32: a surface lit by that
+   illuminant comes out grey at its own luminance. Callers multiply the gains into the global slope in binary64 and round once. */
+int kajo_hip_grade_white_balance(double kelvin, double tint, float gains[3]);
+/* The "click on what should be grey" form: g.c = Y / rgb.c with Y = 0.2126 r + 0.7152 g + 0.0722 b of the pixel, normalised the same
+   way, binary64 rounded to float32. A channel that is not finite or <= 0 is KAJO_E_INVALID. A grey pixel gives (1, 1, 1). */
+int kajo_hip_grade_neutral(const float rgb[3], float gains[3]);
+/* The frame after the stage: radiance = HOST pointer to width*height*4 floats (row 0 = top), sums over passes; may be NULL. The frame
+   kajo_hip_lens with the same first two stages would start from, then this stage. grade == NULL is refused (KAJO_E_INVALID). Waits. */
+int kajo_hip_grade(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGradeParams* grade,
+                   float* radiance);
+/* The whole chain: despeckle -> denoise -> grade -> lens -> glare -> local -> meter -> tone mapping -> view, every stage but the tone
+   mapping optional (NULL). With grade == NULL exactly kajo_hip_present_view_argb8. argb8 and *result as there. Waits. */
+int kajo_hip_present_grade_argb8(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGradeParams* grade,
+                                 const KajoLensParams* lens, const KajoGlareParams* g, const KajoLocalParams* local, const KajoMeterParams* meter,
+                                 const KajoToneParams* tone, const KajoViewParams* view, uint32_t* argb8, KajoMeterResult* result);
+/* The twin of kajo_hip_present_view_gathered_argb8_device with the stage behind the despeckle: dst = DEVICE pointer to outW*outH words
+   (width*height without a view). The global op works for any number of owners; nRegions > 0 is refused here (KAJO_E_INVALID, with the
+   stage's other refusals): regions need whole-frame tables, as the lens needs whole-frame AOVs -- several owners are served through the
+   root after kajo_hip_compose and kajo_hip_compose_aov. It adds no wait of its own once its scratch stands (a change of parameters may
+   wait for the previous upload of the parameter block to leave its staging, never for a kernel). With grade == NULL exactly that call. */
+int kajo_hip_present_grade_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle,
+                                                 const KajoGradeParams* grade, const KajoGlareParams* g, const KajoLocalParams* local,
+                                                 const KajoMeterParams* meter, const KajoToneParams* tone, const KajoViewParams* view, void* dst,
+                                                 KajoMeterResult* result);
 
 /* Use an existing HIP stream (hipStream_t passed as void*) instead of the handle's own. */
 int kajo_hip_set_stream(kajo_hip_t h, void* stream);

@@ -47,6 +47,7 @@ KAJO_LENS_MAX_RADIUS = 16  # KajoLensParams.maxRadius: the largest circle of con
 KAJO_VIEW_NEAREST, KAJO_VIEW_AREA, KAJO_VIEW_TRIANGLE, KAJO_VIEW_LANCZOS3 = 0, 1, 2, 3  # KajoViewParams.filter
 KAJO_VIEW_FILTERS = {"nearest": KAJO_VIEW_NEAREST, "area": KAJO_VIEW_AREA, "triangle": KAJO_VIEW_TRIANGLE, "lanczos3": KAJO_VIEW_LANCZOS3}
 KAJO_VIEW_MAX_SCALE, KAJO_VIEW_MAX_TAPS, KAJO_VIEW_MAX_OUT = 64, 384, 16384  # the view's limits: minification, taps of a row, output edge
+KAJO_GRADE_MAX_REGIONS, KAJO_GRADE_REGION_OBJECTS = 4, 16  # KajoGradeParams: regions of a grade, object ids of a region
 KAJO_LOCAL_PIVOT_METERED = 1  # KajoLocalParams.flags: the pivot is the frame's own pivotPercentile-th luminance
 
 # every symbol include/kajo_hip.h declares
@@ -69,6 +70,8 @@ EXPORTS = [
     "kajo_hip_aov_tile_buffers", "kajo_hip_compose_aov",
     "kajo_hip_default_view_params", "kajo_hip_view_weights", "kajo_hip_view_tables", "kajo_hip_view_argb8", "kajo_hip_present_view_argb8",
     "kajo_hip_present_view_gathered_argb8_device",
+    "kajo_hip_default_grade_params", "kajo_hip_grade_pixels", "kajo_hip_grade_white_balance", "kajo_hip_grade_neutral", "kajo_hip_grade",
+    "kajo_hip_present_grade_argb8", "kajo_hip_present_grade_gathered_argb8_device",
 ]
 
 
@@ -118,6 +121,21 @@ class KajoLensParams(C.Structure):
 class KajoViewParams(C.Structure):
     _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float), ("outW", C.c_int32), ("outH", C.c_int32),
                 ("filter", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class KajoGradeOp(C.Structure):
+    _fields_ = [("slope", C.c_float * 3), ("offset", C.c_float * 3), ("power", C.c_float * 3), ("saturation", C.c_float),
+                ("reserved", C.c_float * 2)]
+
+
+class KajoGradeRegion(C.Structure):
+    _fields_ = [("op", KajoGradeOp), ("objects", C.c_int32 * KAJO_GRADE_REGION_OBJECTS), ("n", C.c_int32), ("amount", C.c_float),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class KajoGradeParams(C.Structure):
+    _fields_ = [("global_", KajoGradeOp), ("nRegions", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2),
+                ("regions", KajoGradeRegion * KAJO_GRADE_MAX_REGIONS)]  # (global_: the header's `global`, a keyword here)
 
 
 class KajoParams(C.Structure):
@@ -273,6 +291,23 @@ def lib():
                                                                       C.POINTER(KajoGlareParams), C.POINTER(KajoLocalParams),
                                                                       C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams),
                                                                       C.POINTER(KajoViewParams), C.c_void_p, C.POINTER(KajoMeterResult)]
+        if hasattr(L, "kajo_hip_grade"):  # (nor the grade)
+            L.kajo_hip_default_grade_params.argtypes = [C.POINTER(KajoGradeParams)]
+            L.kajo_hip_default_grade_params.restype = None
+            L.kajo_hip_grade_pixels.argtypes = [C.POINTER(KajoGradeParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+            L.kajo_hip_grade_white_balance.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_float * 3)]
+            L.kajo_hip_grade_neutral.argtypes = [C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3)]
+            L.kajo_hip_grade.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams), C.POINTER(KajoGradeParams),
+                                         C.c_void_p]
+            L.kajo_hip_present_grade_argb8.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams),
+                                                       C.POINTER(KajoGradeParams), C.POINTER(KajoLensParams), C.POINTER(KajoGlareParams),
+                                                       C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams),
+                                                       C.POINTER(KajoViewParams), C.c_void_p, C.POINTER(KajoMeterResult)]
+            L.kajo_hip_present_grade_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams),
+                                                                       C.POINTER(KajoGradeParams), C.POINTER(KajoGlareParams),
+                                                                       C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams),
+                                                                       C.POINTER(KajoToneParams), C.POINTER(KajoViewParams), C.c_void_p,
+                                                                       C.POINTER(KajoMeterResult)]
         if hasattr(L, "kajo_hip_read_matte"):  # (nor the mattes)
             L.kajo_hip_read_matte.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
             L.kajo_hip_matte_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

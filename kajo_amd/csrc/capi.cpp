@@ -24,6 +24,7 @@
 #include "launch_order.h"
 #include "launch_plan.h"
 #include "view_weights.h"
+#include "grade_math.h"
 
 // launchers defined next to their kernels (kernel_fast.hip, kernel_strict.hip, kernel_exact.hip, aux_kernels.hip)
 extern "C" {
@@ -74,6 +75,9 @@ int kajo_lens_launch(const void* src, const TileMap* map, int fromTiles, float p
 int kajo_view_launch(const void* src, int W, const void* tables, const void* firstX, const void* countX, const void* wxT, int strideX,
                      const void* firstY, const void* countY, const void* wy, int strideY, int outW, int outH, int row0, int rows, void* T, void* dst,
                      void* stream);
+size_t kajo_grade_block_bytes(void);
+int kajo_grade_launch(const void* src, const TileMap* map, int fromTiles, float passes, const void* block, int nRegions, const void* ids,
+                      const void* counts, unsigned words, unsigned nObjects, float samples, void* out, void* stream);
 int kajo_compose_aov_launch(const void* gatheredAov, const void* gatheredMatte, const TileMap* map, void* aov, void* matte, void* stream);
 int kajo_matte_rank_launch(const void* ids, const void* counts, int W, int H, void* rankedIds, void* rankedCounts, void* stream);
 int kajo_matte_mask_launch(const void* ids, const void* counts, int W, int H, const void* selected, unsigned nObjects, float samples, void* mask,
@@ -289,6 +293,14 @@ struct KajoHip
         size_t firstX, countX, wx, firstY, countY, wy; // byte offsets into viewRows (the tables are at 0)
         int strideX, strideY, row0, rows;
     } viewPlan{};
+    // the grade (grade.hip; kajo_hip_grade, kajo_hip_present_grade_*), on its first call: the output frame float4 [W * H]; the parameter
+    // block (five ops and the regions' amounts) with the regions' id bitsets behind it, uploaded from the pinned block `gradeStaging`
+    // only when the parameters differ from `gradeLast`
+    DeviceBuffer grade, gradeBlock;
+    void* gradeStaging = nullptr;
+    hipEvent_t gradeUploaded = nullptr; // the last upload has left gradeStaging
+    bool gradePlanned = false;
+    KajoGradeParams gradeLast{};
     int toneScaleState = 0; // the s of the most recent tone mapping: 0 none yet, 1 toneScale, 2 the scale word (auto exposure)
     float toneScale = 1.0f;
 };
@@ -356,6 +368,10 @@ void destroy(KajoHip* h)
         (void)hipEventDestroy(h->viewUploaded);
     if (h->viewStaging)
         (void)hipHostFree(h->viewStaging);
+    if (h->gradeUploaded)
+        (void)hipEventDestroy(h->gradeUploaded);
+    if (h->gradeStaging)
+        (void)hipHostFree(h->gradeStaging);
     if (h->ownStream && h->stream)
         (void)hipStreamDestroy(h->stream);
     delete h;
@@ -552,7 +568,7 @@ const char* kajo_hip_version(void)
 {
     // (a comma, not a semicolon, in front of "view": tests/test_lens_cpu.py looks for "lens" in the LAST ';'-separated field, so the
     // stages added after the lens join that field; the next stage appends ", name" likewise)
-    return "kajo-hip 0.1 (gfx950; aov-matte; local; aov-tiled; lens, view)";
+    return "kajo-hip 0.1 (gfx950; aov-matte; local; aov-tiled; lens, view, grade)";
 }
 
 void kajo_hip_default_params(KajoParams* p)
@@ -2779,6 +2795,415 @@ int kajo_hip_present_view_gathered_argb8_device(kajo_hip_t h, const void* gather
         return kajo_hip_present_local_gathered_argb8_device(h, gathered, despeckle, g, local, meter, tone, dst, result);
     HIP_TRY(h->viewIn.ensure((size_t)h->W * h->H * 4));
     if ((rc = kajo_hip_present_local_gathered_argb8_device(h, gathered, despeckle, g, local, meter, tone, h->viewIn.p, result)))
+        return rc;
+    return viewImage(h, view, r, h->viewIn.p, dst);
+}
+
+} // extern "C"
+
+namespace
+{
+
+static_assert(sizeof(KajoGradeOp) == 48 && sizeof(KajoGradeRegion) == 128 && sizeof(KajoGradeParams) == 576, "include/kajo_hip.h states the sizes");
+
+// the parameter block grade.hip reads (its GradeBlock): the global op, then the regions', twelve floats each
+struct GradeOpWords
+{
+    float slope[3], offset[3], power[3], saturation, amount, pad;
+};
+constexpr size_t kGradeBlockBytes = (1 + KAJO_GRADE_MAX_REGIONS) * sizeof(GradeOpWords);
+constexpr size_t kGradeMaxBitsetBytes = 64 * 1024; // the regions' bitsets are staged in LDS: kajo_grade_launch
+
+int checkGradeOp(const KajoGradeOp& op)
+{
+    for (int c = 0; c < 3; c++) {
+        if (!(std::isfinite(op.slope[c]) && op.slope[c] >= 0.0f && op.slope[c] <= 65536.0f))
+            return fail(KAJO_E_INVALID, "grade slope must be finite and in [0, 65536]");
+        if (!(std::isfinite(op.offset[c]) && std::fabs(op.offset[c]) <= 65536.0f))
+            return fail(KAJO_E_INVALID, "grade offset must be finite and in [-65536, 65536]");
+        if (!(std::isfinite(op.power[c]) && op.power[c] >= 0.125f && op.power[c] <= 8.0f))
+            return fail(KAJO_E_INVALID, "grade power must be finite and in [1/8, 8]");
+    }
+    if (!(std::isfinite(op.saturation) && op.saturation >= 0.0f && op.saturation <= 4.0f))
+        return fail(KAJO_E_INVALID, "grade saturation must be finite and in [0, 4]");
+    for (float r : op.reserved)
+        if (r != 0.0f)
+            return fail(KAJO_E_INVALID, "grade reserved fields must be 0");
+    return KAJO_OK;
+}
+
+// The refusals of KajoGradeParams (KAJO_E_INVALID), before any device work and before the handle is looked at
+int checkGrade(const KajoGradeParams* p)
+{
+    if (!p)
+        return fail(KAJO_E_INVALID, "null grade parameters");
+    int rc = checkGradeOp(p->global);
+    if (rc)
+        return rc;
+    if (p->nRegions < 0 || p->nRegions > KAJO_GRADE_MAX_REGIONS)
+        return fail(KAJO_E_INVALID, "grade regions must number 0 to 4");
+    if (p->flags)
+        return fail(KAJO_E_INVALID, "unknown grade flag");
+    if (p->reserved[0] || p->reserved[1])
+        return fail(KAJO_E_INVALID, "grade reserved fields must be 0");
+    for (int k = 0; k < p->nRegions; k++) {
+        const KajoGradeRegion& r = p->regions[k];
+        if ((rc = checkGradeOp(r.op)))
+            return rc;
+        if (r.n < 1 || r.n > KAJO_GRADE_REGION_OBJECTS)
+            return fail(KAJO_E_INVALID, "a grade region selects 1 to 16 objects");
+        for (int i = 0; i < r.n; i++)
+            if (r.objects[i] < 0)
+                return fail(KAJO_E_INVALID, "object id out of range: 0 (the background) .. the number of planes and spheres");
+        if (!(std::isfinite(r.amount) && r.amount >= 0.0f && r.amount <= 1.0f))
+            return fail(KAJO_E_INVALID, "grade region amount must be finite and in [0, 1]");
+        if (r.reserved[0] || r.reserved[1])
+            return fail(KAJO_E_INVALID, "grade reserved fields must be 0");
+    }
+    return KAJO_OK;
+}
+
+bool gradeIsIdentity(const KajoGradeParams* p)
+{
+    return p->nRegions == 0 && kajo::gradeOpIsDefault(p->global);
+}
+
+// ... and of the handle. wholeFrame: the call works on the handle's own frame (not on gathered tile buffers). With regions the state
+// follows kajo_hip_matte_mask's rules; without them the handle needs no AOVs.
+int checkGradeHandle(kajo_hip_t h, const KajoGradeParams* p, bool wholeFrame)
+{
+    if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    if (p->nRegions > 0) {
+        int rc = matteReady(h);
+        if (rc)
+            return rc;
+    }
+    if (wholeFrame || p->nRegions > 0) {
+        if (h->passesDone < 1)
+            return fail(KAJO_E_STATE, "nothing rendered yet");
+        if (wholeFrame && h->map.tileCount != 1 && !h->frameValid)
+            return fail(KAJO_E_STATE, "whole-frame output needs kajo_hip_compose() when tileCount > 1");
+    }
+    if (p->nRegions > 0) {
+        const int nObjects = h->staged.nPlanes + h->staged.nSpheres;
+        for (int k = 0; k < p->nRegions; k++)
+            for (int i = 0; i < p->regions[k].n; i++)
+                if (p->regions[k].objects[i] > nObjects)
+                    return fail(KAJO_E_INVALID, "object id out of range: 0 (the background) .. the number of planes and spheres");
+        if ((size_t)p->nRegions * matteBitsetWords(h) * sizeof(uint32_t) > kGradeMaxBitsetBytes)
+            return fail(KAJO_E_INVALID, "grade regions: the scene has too many objects for " + std::to_string(p->nRegions) +
+                                            " regions (their id bitsets must fit 64 KiB: 524287 objects with one region, 131071 with four)");
+    }
+    return KAJO_OK;
+}
+
+// Form the parameter block of *p and, with regions, their bitsets, and upload them, unless they are the last call's
+// (the upload is ordered on the stream it was enqueued on, as the view's cached rows are: a caller that changes the handle's stream with
+// kajo_hip_set_stream between two calls with equal parameters orders the two streams itself, as for every other buffer of the handle)
+int gradePlan(KajoHip* h, const KajoGradeParams* p)
+{
+    if (h->gradePlanned && std::memcmp(&h->gradeLast, p, sizeof *p) == 0)
+        return KAJO_OK;
+    h->gradePlanned = false;
+    if (kajo_grade_block_bytes() != kGradeBlockBytes)
+        return fail(KAJO_E_INVALID, "grade parameter block layout mismatch");
+    const size_t words = matteBitsetWords(h);
+    const size_t bytes = kGradeBlockBytes + KAJO_GRADE_MAX_REGIONS * words * sizeof(uint32_t);
+    if (!h->gradeUploaded)
+        HIP_TRY(hipEventCreateWithFlags(&h->gradeUploaded, hipEventDisableTiming));
+    else
+        HIP_TRY(hipEventSynchronize(h->gradeUploaded)); // (the copy before this one has left the staging block; kernels are not waited for)
+    if (!h->gradeStaging)
+        HIP_TRY(hipHostMalloc(&h->gradeStaging, bytes, hipHostMallocDefault));
+    HIP_TRY(h->gradeBlock.ensure(bytes));
+    std::memset(h->gradeStaging, 0, bytes);
+    GradeOpWords* ops = static_cast<GradeOpWords*>(h->gradeStaging);
+    uint32_t* bits = reinterpret_cast<uint32_t*>(static_cast<char*>(h->gradeStaging) + kGradeBlockBytes);
+    for (int k = 0; k <= p->nRegions; k++) {
+        const KajoGradeOp& op = k == 0 ? p->global : p->regions[k - 1].op;
+        std::memcpy(ops[k].slope, op.slope, sizeof op.slope);
+        std::memcpy(ops[k].offset, op.offset, sizeof op.offset);
+        std::memcpy(ops[k].power, op.power, sizeof op.power);
+        ops[k].saturation = op.saturation;
+        ops[k].amount = k == 0 ? 1.0f : p->regions[k - 1].amount;
+        if (k > 0)
+            for (int i = 0; i < p->regions[k - 1].n; i++) {
+                const int32_t id = p->regions[k - 1].objects[i]; // (0 .. nObjects: checkGradeHandle)
+                bits[(size_t)(k - 1) * words + ((size_t)id >> 5)] |= 1u << (id & 31);
+            }
+    }
+    HIP_TRY(hipMemcpyAsync(h->gradeBlock.p, h->gradeStaging, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipEventRecord(h->gradeUploaded, h->stream));
+    h->gradeLast = *p;
+    h->gradePlanned = true;
+    return KAJO_OK;
+}
+
+// Enqueue the grade of an image (tiles through h->map's geometry, or a row-major frame): *out = the row-major frame in the stage's
+// scratch that holds the result -- or the image itself in the identity case. Checked by checkGrade and checkGradeHandle, device bound.
+int gradeImage(KajoHip* h, const KajoGradeParams* p, Image img, Image* out)
+{
+    if (gradeIsIdentity(p)) {
+        *out = img;
+        return KAJO_OK;
+    }
+    const size_t count = (size_t)h->W * h->H;
+    HIP_TRY(h->grade.ensure(count * 16));
+    int rc = gradePlan(h, p);
+    if (rc)
+        return rc;
+    const bool regions = p->nRegions > 0;
+    const size_t tableWords = count * KAJO_MATTE_SLOTS * 4;
+    hipError_t le = (hipError_t)kajo_grade_launch(img.src, &h->map, img.fromTiles ? 1 : 0, (float)h->passesDone, h->gradeBlock.p, p->nRegions,
+                                                  regions ? h->matte.p : nullptr, regions ? h->matte.as<char>() + tableWords : nullptr,
+                                                  (unsigned)matteBitsetWords(h), (unsigned)(h->staged.nPlanes + h->staged.nSpheres),
+                                                  (float)aovSamples(h), h->grade.p, h->stream);
+    if (le != hipSuccess)
+        return failHip(le, "grade kernel launch");
+    *out = Image{h->grade.p, false};
+    return KAJO_OK;
+}
+
+// the refusals of the grade chain calls in front of the denoiser's and the handle's: despeckle, grade, lens, glare, local, meter, tone,
+// view; -> *t the tone kernels' arguments
+int checkGradeChain(const KajoDespeckleParams* despeckle, const KajoGradeParams* grade, const KajoLensParams* lens, const KajoGlareParams* g,
+                    const KajoLocalParams* local, const KajoMeterParams* meter, const KajoToneParams* tone, const KajoViewParams* view, ToneArgs* t)
+{
+    int rc;
+    if (despeckle && (rc = checkDespeckle(despeckle)))
+        return rc;
+    if ((rc = checkGrade(grade)))
+        return rc;
+    if (lens && (rc = checkLens(lens)))
+        return rc;
+    if (g && (rc = checkGlare(g)))
+        return rc;
+    if (local && (rc = checkLocal(local)))
+        return rc;
+    if (meter && (rc = checkMeter(meter)))
+        return rc;
+    if ((rc = toneArgsOf(tone, t)))
+        return rc;
+    if (meter && (tone->flags & KAJO_TONE_AUTO_EXPOSURE))
+        return fail(KAJO_E_INVALID, "metered exposure and the tone parameters' automatic exposure are two automatic exposures: give one");
+    return view ? checkView(view) : KAJO_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void kajo_hip_default_grade_params(KajoGradeParams* p)
+{
+    if (!p)
+        return;
+    std::memset(p, 0, sizeof *p);
+    KajoGradeOp op{};
+    for (int c = 0; c < 3; c++)
+        op.slope[c] = op.power[c] = 1.0f;
+    op.saturation = 1.0f;
+    p->global = op;
+    for (KajoGradeRegion& r : p->regions) {
+        r.op = op;
+        r.amount = 1.0f;
+    }
+}
+
+int kajo_hip_grade_pixels(const KajoGradeParams* p, const float* rgb, const float* masks, int64_t n, float* out)
+{
+    int rc = checkGrade(p);
+    if (rc)
+        return rc;
+    if (n < 0 || (n > 0 && (!rgb || !out || (p->nRegions > 0 && !masks))))
+        return fail(KAJO_E_INVALID, "null argument");
+    const bool identity = gradeIsIdentity(p);
+    for (int64_t i = 0; i < n; i++) {
+        const float* m = rgb + 3 * i;
+        float* o = out + 3 * i;
+        if (identity || !(kajo::gradeFinite(m[0]) && kajo::gradeFinite(m[1]) && kajo::gradeFinite(m[2]))) {
+            std::memmove(o, m, 3 * sizeof(float));
+            continue;
+        }
+        float c[3];
+        kajo::gradeOp(p->global, m, c);
+        for (int k = 0; k < p->nRegions; k++)
+            kajo::gradeRegion(p->regions[k].op, p->regions[k].amount, masks[i * p->nRegions + k], c);
+        std::memcpy(o, c, sizeof c);
+    }
+    return KAJO_OK;
+}
+
+namespace
+{
+// g normalised to luminance 1, rounded to float32
+void gradeGainsOut(double r, double g, double b, float gains[3])
+{
+    const double y = 0.2126 * r + 0.7152 * g + 0.0722 * b;
+    gains[0] = (float)(r / y);
+    gains[1] = (float)(g / y);
+    gains[2] = (float)(b / y);
+}
+} // namespace
+
+int kajo_hip_grade_white_balance(double kelvin, double tint, float gains[3])
+{
+    if (!gains)
+        return fail(KAJO_E_INVALID, "null argument");
+    if (!(std::isfinite(kelvin) && kelvin >= 1667.0 && kelvin <= 25000.0))
+        return fail(KAJO_E_INVALID, "white balance temperature must be in [1667, 25000] kelvin");
+    if (!(std::isfinite(tint) && std::fabs(tint) <= 1.0))
+        return fail(KAJO_E_INVALID, "white balance tint must be in [-1, 1]");
+    const double T = kelvin, T2 = T * T, T3 = T2 * T;
+    const double x = T <= 4000.0 ? -0.2661239e9 / T3 - 0.2343589e6 / T2 + 0.8776956e3 / T + 0.179910
+                                 : -3.0258469e9 / T3 + 2.1070379e6 / T2 + 0.2226347e3 / T + 0.240390;
+    const double x2 = x * x, x3 = x2 * x;
+    const double y = T <= 2222.0   ? -1.1063814 * x3 - 1.34811020 * x2 + 2.18555832 * x - 0.20219683
+                     : T <= 4000.0 ? -0.9549476 * x3 - 1.37418593 * x2 + 2.09137015 * x - 0.16748867
+                                   : 3.0817580 * x3 - 5.87338670 * x2 + 3.75112997 * x - 0.37001483;
+    const double X = x / y, Y = 1.0, Z = (1.0 - x - y) / y;
+    const double rgb[3] = {3.2404542 * X - 1.5371385 * Y - 0.4985314 * Z, -0.9692660 * X + 1.8760108 * Y + 0.0415560 * Z,
+                           0.0556434 * X - 0.2040259 * Y + 1.0572252 * Z};
+    for (double c : rgb)
+        if (!(c > 1e-3))
+            return fail(KAJO_E_INVALID, "white balance temperature is outside sRGB");
+    gradeGainsOut(1.0 / rgb[0], (1.0 / rgb[1]) * std::exp2(tint), 1.0 / rgb[2], gains);
+    return KAJO_OK;
+}
+
+int kajo_hip_grade_neutral(const float rgb[3], float gains[3])
+{
+    if (!rgb || !gains)
+        return fail(KAJO_E_INVALID, "null argument");
+    for (int c = 0; c < 3; c++)
+        if (!(std::isfinite(rgb[c]) && rgb[c] > 0.0f))
+            return fail(KAJO_E_INVALID, "a neutral needs three finite positive channels");
+    const double r = rgb[0], g = rgb[1], b = rgb[2];
+    const double Y = 0.2126 * r + 0.7152 * g + 0.0722 * b;
+    gradeGainsOut(Y / r, Y / g, Y / b, gains);
+    return KAJO_OK;
+}
+
+int kajo_hip_grade(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGradeParams* grade,
+                   float* radiance)
+{
+    // (every refusal before any device work: the despeckle parameters, the stage's own, the denoiser's, then the handle)
+    int rc;
+    if (despeckle && (rc = checkDespeckle(despeckle)))
+        return rc;
+    if ((rc = checkGrade(grade)))
+        return rc;
+    if (denoise && (rc = checkDenoise(h, denoise)))
+        return rc;
+    if ((rc = checkGradeHandle(h, grade, true)))
+        return rc;
+    Image img;
+    if ((rc = imageOf(h, false, nullptr, &img)))
+        return rc;
+    if ((rc = chainImage(h, despeckle, denoise, nullptr, &img)))
+        return rc;
+    if ((rc = gradeImage(h, grade, img, &img)))
+        return rc;
+    if (img.fromTiles) {
+        // (a copy of the accumulation: the composed frame, as kajo_hip_read_radiance)
+        if ((rc = composeOwn(h)))
+            return rc;
+        img = Image{h->frame.p, false};
+    }
+    if (radiance)
+        HIP_TRY(hipMemcpyAsync(radiance, img.src, (size_t)h->W * h->H * 16, hipMemcpyDeviceToHost, h->stream));
+    return kajo_hip_wait(h);
+}
+
+int kajo_hip_present_grade_argb8(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGradeParams* grade,
+                                 const KajoLensParams* lens, const KajoGlareParams* g, const KajoLocalParams* local, const KajoMeterParams* meter,
+                                 const KajoToneParams* tone, const KajoViewParams* view, uint32_t* argb8, KajoMeterResult* result)
+{
+    if (!grade)
+        return kajo_hip_present_view_argb8(h, despeckle, denoise, lens, g, local, meter, tone, view, argb8, result);
+    // (every refusal before any device work: the stages' parameters, the denoiser's, the handle, the view against the frame)
+    ToneArgs t{};
+    int rc = checkGradeChain(despeckle, grade, lens, g, local, meter, tone, view, &t);
+    if (rc)
+        return rc;
+    if (denoise && (rc = checkDenoise(h, denoise)))
+        return rc;
+    if ((rc = checkGradeHandle(h, grade, true)))
+        return rc;
+    if (lens && (rc = checkLensHandle(h)))
+        return rc;
+    ViewRect r{};
+    if (view && (rc = checkViewHandle(h, view, &r)))
+        return rc;
+    Image img;
+    if ((rc = imageOf(h, false, nullptr, &img)))
+        return rc;
+    const size_t count = (size_t)h->W * h->H;
+    HIP_TRY(h->argb.ensure(count * 4));
+    if ((rc = chainImage(h, despeckle, denoise, nullptr, &img)))
+        return rc;
+    if ((rc = gradeImage(h, grade, img, &img)))
+        return rc;
+    if (lens && (rc = lensImage(h, lens, img, &img)))
+        return rc;
+    if (g && (rc = glareImage(h, g, img, &img)))
+        return rc;
+    if (local && (rc = localImage(h, local, img, &img)))
+        return rc;
+    // (the meter measures the frame the tone kernels are handed)
+    if (meter && (rc = meterAndPatch(h, img, meter, tone, result, &t)))
+        return rc;
+    if ((rc = toneLaunch(h, img, t, h->argb.p)))
+        return rc;
+    if (!view) {
+        if (argb8)
+            HIP_TRY(hipMemcpyAsync(argb8, h->argb.p, count * 4, hipMemcpyDeviceToHost, h->stream));
+        return kajo_hip_wait(h);
+    }
+    const size_t outBytes = (size_t)view->outW * view->outH * 4;
+    HIP_TRY(growBuffer(h->viewOut, &h->viewOutBytes, outBytes));
+    if ((rc = viewImage(h, view, r, h->argb.p, h->viewOut.p)))
+        return rc;
+    if (argb8)
+        HIP_TRY(hipMemcpyAsync(argb8, h->viewOut.p, outBytes, hipMemcpyDeviceToHost, h->stream));
+    return kajo_hip_wait(h);
+}
+
+int kajo_hip_present_grade_gathered_argb8_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle,
+                                                 const KajoGradeParams* grade, const KajoGlareParams* g, const KajoLocalParams* local,
+                                                 const KajoMeterParams* meter, const KajoToneParams* tone, const KajoViewParams* view, void* dst,
+                                                 KajoMeterResult* result)
+{
+    if (!grade)
+        return kajo_hip_present_view_gathered_argb8_device(h, gathered, despeckle, g, local, meter, tone, view, dst, result);
+    ToneArgs t{};
+    int rc = checkGradeChain(despeckle, grade, nullptr, g, local, meter, tone, view, &t);
+    if (rc)
+        return rc;
+    if (grade->nRegions > 0)
+        return fail(KAJO_E_INVALID, "grade regions need the whole frame's coverage tables: kajo_hip_present_grade_argb8 on the root");
+    if (!h || !dst)
+        return fail(KAJO_E_INVALID, "null argument");
+    ViewRect r{};
+    if (view && (rc = checkViewHandle(h, view, &r)))
+        return rc;
+    Image img;
+    if ((rc = imageOf(h, true, gathered, &img)))
+        return rc;
+    if ((rc = chainImage(h, despeckle, nullptr, nullptr, &img)))
+        return rc;
+    if ((rc = gradeImage(h, grade, img, &img)))
+        return rc;
+    if (g && (rc = glareImage(h, g, img, &img)))
+        return rc;
+    if (local && (rc = localImage(h, local, img, &img))) // (one wait with KAJO_LOCAL_PIVOT_METERED: include/kajo_hip.h)
+        return rc;
+    if (meter && (rc = meterAndPatch(h, img, meter, tone, result, &t))) // (and one more)
+        return rc;
+    if (!view || r.copy)
+        return toneLaunch(h, img, t, dst);
+    HIP_TRY(h->viewIn.ensure((size_t)h->W * h->H * 4));
+    if ((rc = toneLaunch(h, img, t, h->viewIn.p)))
         return rc;
     return viewImage(h, view, r, h->viewIn.p, dst);
 }

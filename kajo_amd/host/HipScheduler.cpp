@@ -102,6 +102,9 @@ struct Scheduler::Impl
     bool lensRan = false; // lastLens()
     float lensFocus = 0, lensMaxRadiusPx = 0;
     std::vector<float> lensRadius;
+    bool gradeRan = false; // lastGrade()
+    float gradeSlope[3] = {1, 1, 1};
+    std::vector<float> gradeFrame;
 
     ~Impl()
     {
@@ -167,6 +170,10 @@ struct Scheduler::Impl
             throw std::runtime_error("hip::Scheduler: lensOn needs the depth AOV (aov = true)");
         if (opt.lensOn && opt.gpus != 1 && !opt.aovTiled)
             throw std::runtime_error("hip::Scheduler: lensOn with more than one GPU needs aovTiled");
+        if (opt.gradeOn && opt.grade.nRegions > 0 && !(opt.aov && opt.matte))
+            throw std::runtime_error("hip::Scheduler: grade regions need the coverage mattes (aov = true, matte = true)");
+        if (opt.gradeOn && opt.grade.nRegions > 0 && opt.gpus != 1 && !opt.aovTiled)
+            throw std::runtime_error("hip::Scheduler: grade regions with more than one GPU need aovTiled");
         if (opt.aov && opt.gpus != 1 && !opt.aovTiled)
             throw std::runtime_error("hip::Scheduler: first-hit AOVs need the whole frame on one GPU (gpus = 1)");
         if (opt.sameDevice && opt.gather != Options::Copy)
@@ -233,6 +240,53 @@ struct Scheduler::Impl
 
     // Options::aovTiled: the whole-frame AOVs (and the float frame the denoiser filters) on handle 0, for the readers that need them. One
     // exchange per buffer by the frame's own mechanism, then the two compose kernels; nothing where they are at hand already.
+    // the grade's parameters for an image: Options::grade, with the gains of Options::gradeNeutralAt -- from the chain's frame in front of
+    // the grade (kajo_hip_grade with the identity returns it) -- multiplied into the global slope in binary64 and rounded once
+    void gradeParams(const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, KajoGradeParams* out)
+    {
+        *out = opt.grade;
+        if (opt.gradeNeutralAt.x >= 0) {
+            KajoGradeParams identity;
+            kajo_hip_default_grade_params(&identity);
+            gradeFrame.resize((size_t)image->width * image->height * 4);
+            check(kajo_hip_grade(handles[0], despeckle, denoise, &identity, gradeFrame.data()), "kajo_hip_grade");
+            const float* px = &gradeFrame[((size_t)opt.gradeNeutralAt.y * image->width + opt.gradeNeutralAt.x) * 4];
+            float gains[3];
+            if (kajo_hip_grade_neutral(px, gains) != KAJO_OK)
+                throw std::runtime_error("hip::Scheduler: the pixel that should be grey (" + std::to_string(opt.gradeNeutralAt.x) + ", " +
+                                         std::to_string(opt.gradeNeutralAt.y) + ") has a channel that is not finite and positive: no neutral there");
+            for (int c = 0; c < 3; c++)
+                out->global.slope[c] = (float)((double)out->global.slope[c] * (double)gains[c]);
+        }
+        std::memcpy(gradeSlope, out->global.slope, sizeof gradeSlope);
+        gradeRan = true;
+    }
+
+    // Options::lensFocusAt into the parameters: the depth under that pixel
+    void focusLens(KajoLensParams* lens)
+    {
+        if (opt.lensFocusAt.x < 0)
+            return;
+        float z = 0;
+        check(kajo_hip_lens_depth_at(handles[0], opt.lensFocusAt.x, opt.lensFocusAt.y, &z), "kajo_hip_lens_depth_at");
+        if (!std::isfinite(z))
+            throw std::runtime_error("hip::Scheduler: the pixel to focus on (" + std::to_string(opt.lensFocusAt.x) + ", " +
+                                     std::to_string(opt.lensFocusAt.y) + ") is far (a miss, or no finite depth): nothing to focus on");
+        lens->focusDistance = z;
+    }
+
+    // lastLens() of an image made with `lens`
+    void noteLens(const KajoLensParams& lens)
+    {
+        lensRadius.resize((size_t)image->width * image->height);
+        check(kajo_hip_lens_coc(handles[0], &lens, lensRadius.data(), nullptr), "kajo_hip_lens_coc");
+        lensFocus = lens.focusDistance;
+        lensMaxRadiusPx = 0;
+        for (float r : lensRadius)
+            lensMaxRadiusPx = std::max(lensMaxRadiusPx, r);
+        lensRan = true;
+    }
+
     void composeAov()
     {
         if (!opt.aov || !opt.aovTiled || aovComposed)
@@ -402,6 +456,13 @@ bool Scheduler::lastLocalPivot(float* pivot) const
     return m_impl->localRan;
 }
 
+bool Scheduler::lastGrade(float slope[3]) const
+{
+    if (m_impl->gradeRan && slope)
+        std::memcpy(slope, m_impl->gradeSlope, sizeof m_impl->gradeSlope);
+    return m_impl->gradeRan;
+}
+
 bool Scheduler::lastLens(float* focusDistance, float* maxRadiusPx) const
 {
     if (m_impl->lensRan && focusDistance)
@@ -486,15 +547,31 @@ void Scheduler::readPresented(const KajoDespeckleParams* despeckle, const KajoDe
         despeckle = &d.opt.despeckle;
     if (counts)
         counts[0] = counts[1] = 0;
-    if (!despeckle && !d.opt.meterOn && !d.localActive() && !d.opt.lensOn)
+    if (!despeckle && !d.opt.meterOn && !d.localActive() && !d.opt.lensOn && !d.opt.gradeOn)
         return readDisplayed(denoise, glare, tone, argb8, scale);
     if (d.gathered && !d.composed) { // (as readDisplayed)
         check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
         d.composed = true;
     }
-    if (denoise || d.opt.lensOn)
+    if (denoise || d.opt.lensOn || (d.opt.gradeOn && d.opt.grade.nRegions > 0))
         d.composeAov();
-    if (d.opt.lensOn) {
+    if (d.opt.gradeOn) {
+        KajoGradeParams grade;
+        d.gradeParams(despeckle, denoise, &grade);
+        KajoLensParams lens = d.opt.lens;
+        if (d.opt.lensOn)
+            d.focusLens(&lens);
+        check(kajo_hip_present_grade_argb8(d.handles[0], despeckle, denoise, &grade, d.opt.lensOn ? &lens : nullptr, glare ? glare : &d.opt.glare,
+                                           d.localActive() ? &d.opt.local : nullptr, d.opt.meterOn ? &d.opt.meter : nullptr,
+                                           tone ? tone : &d.opt.tone, nullptr, argb8, &d.metered),
+              "kajo_hip_present_grade_argb8");
+        if (d.localActive())
+            d.notePivot();
+        if (scale)
+            check(kajo_hip_tone_scale(d.handles[0], scale), "kajo_hip_tone_scale");
+        if (d.opt.lensOn)
+            d.noteLens(lens);
+    } else if (d.opt.lensOn) {
         KajoLensParams lens = d.opt.lens;
         if (d.opt.lensFocusAt.x >= 0) {
             float z = 0;
@@ -565,6 +642,19 @@ void Scheduler::readViewed(uint32_t* dst)
                                          std::to_string(d.opt.lensFocusAt.y) + ") is far (a miss, or no finite depth): nothing to focus on");
             lens.focusDistance = z;
         }
+    }
+    if (d.opt.gradeOn) {
+        if (d.opt.grade.nRegions > 0)
+            d.composeAov();
+        KajoGradeParams grade;
+        d.gradeParams(d.opt.despeckleOn ? &d.opt.despeckle : nullptr, nullptr, &grade);
+        check(kajo_hip_present_grade_argb8(d.handles[0], d.opt.despeckleOn ? &d.opt.despeckle : nullptr, nullptr, &grade,
+                                           d.opt.lensOn ? &lens : nullptr, &d.opt.glare, d.localActive() ? &d.opt.local : nullptr,
+                                           d.opt.meterOn ? &d.opt.meter : nullptr, &d.opt.tone, &d.opt.view, dst, &d.metered),
+              "kajo_hip_present_grade_argb8");
+        if (d.localActive())
+            d.notePivot();
+        return;
     }
     // (with every optional stage NULL the call routes itself to the call readPresented makes: the chain's image is the same words)
     check(kajo_hip_present_view_argb8(d.handles[0], d.opt.despeckleOn ? &d.opt.despeckle : nullptr, nullptr, d.opt.lensOn ? &lens : nullptr,

@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "Scheduler.h"
-#include "kajo_hip.h" // KajoToneParams (Options::tone), KajoGlareParams (Options::glare), KajoDespeckleParams (Options::despeckle), KajoMeterParams, KajoLocalParams, KajoLensParams, KajoViewParams
+#include "kajo_hip.h" // KajoToneParams (Options::tone), KajoGlareParams (Options::glare), KajoDespeckleParams (Options::despeckle), KajoMeterParams, KajoLocalParams, KajoLensParams, KajoViewParams, KajoGradeParams
 
 class Image;
 class Preview;
@@ -106,6 +106,16 @@ struct Options
     // fills `view` with kajo_hip_default_view_params first and names outW and outH.
     bool viewOn = false;
     KajoViewParams view = {};
+    // The grade between the denoiser and the lens of the images readPresented() and readViewed() hand out (include/kajo_hip.h
+    // kajo_hip_present_grade_argb8): white balance and an ASC CDL op over the frame, per-object regrades by matte. The global op works for any
+    // number of GPUs (the frame is composed on the first handle); regions need `aov` and `matte`, and with more than one GPU `aovTiled`
+    // (refused at construction otherwise). Off by default: every call is then the one made without these fields. Whoever sets gradeOn fills
+    // `grade` with kajo_hip_default_grade_params first. gradeNeutralAt: a pixel that should be grey -- its colour in the chain's frame in
+    // front of the grade gives gains (kajo_hip_grade_neutral) that are multiplied into grade.global.slope when the image is read; a pixel
+    // with a channel that is not finite and positive is refused then; x = -1 means none.
+    bool gradeOn = false;
+    KajoGradeParams grade = {};
+    struct { int x = -1, y = -1; } gradeNeutralAt;
 };
 
 struct Statistics
@@ -157,7 +167,8 @@ public:
     // With Options::meterOn the chain ends in the metered call (kajo_hip_present_metered_argb8) and lastMeter() is its measurement; with
     // Options::localOn the local tone mapping sits between the glare and the meter (kajo_hip_present_local_argb8); with Options::lensOn the
     // depth of field sits between the denoiser and the glare (kajo_hip_present_lens_argb8; the AOVs are gathered and composed first, as
-    // for `denoise`), and lastLens() is what it focused on
+    // for `denoise`), and lastLens() is what it focused on; with Options::gradeOn the grade sits between the denoiser and the lens
+    // (kajo_hip_present_grade_argb8; with regions the mattes are gathered and composed first), and lastGrade() is the slope it used
     void readPresented(const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGlareParams* glare, const KajoToneParams* tone,
                        uint32_t* argb8, float* scale, long long counts[2]);
 
@@ -169,6 +180,9 @@ public:
     // the focus distance of the most recent image with the depth of field (Options::lensOn: readPresented) and the largest circle of
     // confusion in it, in pixels; false where the stage has not run
     bool lastLens(float* focusDistance, float* maxRadiusPx) const;
+    // the global slope of the most recent image with the grade (Options::gradeOn: readPresented, readViewed), the gains of
+    // Options::gradeNeutralAt in it; false where the stage has not run
+    bool lastGrade(float slope[3]) const;
     // the image of readPresented() with Options' own stages, through Options::view: dst = view.outW * view.outH words. Any number of GPUs
     // (the frame is composed on the first handle, as readPresented does). Throws where Options::viewOn is not set.
     void readViewed(uint32_t* dst);

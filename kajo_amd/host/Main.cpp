@@ -49,6 +49,62 @@ bool parseObjects(const std::string& text, std::vector<int32_t>* out)
     }
 }
 
+// three numbers R,G,B -- or, where `orOne`, one number for all three; text that is no number becomes a NaN (the library refuses it by name)
+bool parseTriple(const std::string& text, bool orOne, float out[3])
+{
+    std::vector<std::string> items;
+    size_t at = 0;
+    while (true) {
+        const size_t comma = text.find(',', at);
+        items.push_back(text.substr(at, comma == std::string::npos ? std::string::npos : comma - at));
+        if (comma == std::string::npos)
+            break;
+        at = comma + 1;
+    }
+    if (!(items.size() == 3 || (orOne && items.size() == 1)))
+        return false;
+    for (int c = 0; c < 3; c++)
+        if (!parseFloat(items[items.size() == 1 ? 0 : c], &out[c]))
+            out[c] = NAN;
+    return true;
+}
+
+// --grade-region IDS:key=v[:key=v...] into a region that holds the defaults
+bool parseRegion(const std::string& text, KajoGradeRegion* r)
+{
+    std::vector<std::string> parts;
+    size_t at = 0;
+    while (true) {
+        const size_t colon = text.find(':', at);
+        parts.push_back(text.substr(at, colon == std::string::npos ? std::string::npos : colon - at));
+        if (colon == std::string::npos)
+            break;
+        at = colon + 1;
+    }
+    std::vector<int32_t> ids;
+    if (!parseObjects(parts[0], &ids) || ids.size() > KAJO_GRADE_REGION_OBJECTS)
+        return false;
+    r->n = (int32_t)ids.size();
+    for (size_t i = 0; i < ids.size(); i++)
+        r->objects[i] = ids[i];
+    for (size_t i = 1; i < parts.size(); i++) {
+        const size_t eq = parts[i].find('=');
+        if (eq == std::string::npos)
+            return false;
+        const std::string key = parts[i].substr(0, eq), value = parts[i].substr(eq + 1);
+        if (key == "slope" || key == "offset" || key == "power") {
+            if (!parseTriple(value, true, key == "slope" ? r->op.slope : key == "offset" ? r->op.offset : r->op.power))
+                return false;
+        } else if (key == "saturation" || key == "amount") {
+            float* field = key == "saturation" ? &r->op.saturation : &r->amount;
+            if (!parseFloat(value, field))
+                *field = NAN;
+        } else
+            return false;
+    }
+    return true;
+}
+
 } // namespace
 
 int main(int argc, char** argv)
@@ -75,6 +131,9 @@ int main(int argc, char** argv)
     std::string lensAperture, lensFocus, lensFocusAt, lensMaxRadius;
     // view options (include/kajo_hip.h KajoViewParams): the raw text, checked after the loop
     std::string outputSize, viewRect, viewFilter, supersample;
+    // grade options (include/kajo_hip.h KajoGradeParams): the raw text, checked after the loop
+    std::string gradeSlope, gradeOffset, gradePower, gradeSaturation, whiteBalance, whiteBalanceAt;
+    std::vector<std::string> gradeRegions;
     int width = 640, height = 480;
     int denoiseIterations = 5;
     hip::Options opt;
@@ -176,7 +235,20 @@ int main(int argc, char** argv)
                         "                    frame); without --output-size the output keeps the frame's size: a zoom\n"
                         "    --view-filter nearest|area|triangle|lanczos3  the view: the resampling filter (area: the exact area average)\n"
                         "    --supersample K  render and run the whole chain at K w x K h for the given -w -h, K = 2..8, the aspect unchanged, and write -o at\n"
-                        "                    w x h with the area filter: K x K display-referred pixels averaged per pixel. Not with --output-size\n",
+                        "                    w x h with the area filter: K x K display-referred pixels averaged per pixel. Not with --output-size\n"
+                        "    --grade-slope R,G,B  the grade between the denoiser and the lens (-o and --denoise; include/kajo_hip.h kajo_hip_grade): an ASC CDL\n"
+                        "                    op over the frame in scene-linear radiance, out = max(in * slope + offset, 0) ^ power, then the saturation;\n"
+                        "                    slopes in 0..65536 (1). Any --gpus. --hdr, --raw, --aov and the matte files stay ungraded (--json: grade_*)\n"
+                        "    --grade-offset R,G,B  the grade: offsets in -65536..65536 (0)\n"
+                        "    --grade-power R,G,B  the grade: powers in 1/8..8 (1)\n"
+                        "    --grade-saturation S  the grade: saturation about the Rec. 709 luminance, 0..4 (1)\n"
+                        "    --white-balance KELVIN[,TINT]  the grade: gains that make a surface lit by that colour temperature (1667..25000; the blue of\n"
+                        "                    one below about 1900 is outside sRGB) grey at its own luminance, multiplied into the slope; TINT in -1..1\n"
+                        "                    stops of green\n"
+                        "    --white-balance-at X,Y  the grade: the gains that make that pixel of the frame in front of the grade grey\n"
+                        "    --grade-region IDS:key=v[:key=v...]  the grade: regrade the objects IDS (a comma-separated list of at most 16 ids, as\n"
+                        "                    --matte-objects) by their coverage mattes; keys slope, offset, power (one number or R,G,B), saturation, amount\n"
+                        "                    (0..1, 1). Up to four times, applied in order. One GPU, or any --gpus with --aov-tiled\n",
                         args[0].c_str());
             return 1;
         } else if (a == "-w" && more) width = std::atoi(args[++i].c_str());
@@ -228,6 +300,13 @@ int main(int argc, char** argv)
         else if (a == "--view" && more) viewRect = args[++i];
         else if (a == "--view-filter" && more) viewFilter = args[++i];
         else if (a == "--supersample" && more) supersample = args[++i];
+        else if (a == "--grade-slope" && more) gradeSlope = args[++i];
+        else if (a == "--grade-offset" && more) gradeOffset = args[++i];
+        else if (a == "--grade-power" && more) gradePower = args[++i];
+        else if (a == "--grade-saturation" && more) gradeSaturation = args[++i];
+        else if (a == "--white-balance" && more) whiteBalance = args[++i];
+        else if (a == "--white-balance-at" && more) whiteBalanceAt = args[++i];
+        else if (a == "--grade-region" && more) gradeRegions.push_back(args[++i]);
         else if (a == "--aov" && more) aovPrefix = args[++i];
         else if (a == "--aov-specular") aovSpecular = true;
         else if (a == "--aov-tiled") aovTiled = true;
@@ -526,13 +605,97 @@ int main(int argc, char** argv)
         }
         opt.aov = true;
     }
+    const bool gradeGiven = !gradeSlope.empty() || !gradeOffset.empty() || !gradePower.empty() || !gradeSaturation.empty() || !whiteBalance.empty() ||
+                            !whiteBalanceAt.empty() || !gradeRegions.empty();
+    double whiteBalanceKelvin = 0, whiteBalanceTint = 0;
+    if (gradeGiven) {
+        // (before any device is opened: the refusals of kajo_hip_grade and of kajo_hip_grade_white_balance, in the library's own words -- text
+        // that is no number becomes a NaN, which they refuse)
+        if (threeArg) {
+            std::cerr << "kajo_render: the grade options need the backend's options (without --three-arg)" << std::endl;
+            return 1;
+        }
+        if (!whiteBalance.empty() && !whiteBalanceAt.empty()) {
+            std::cerr << "kajo_render: --white-balance and --white-balance-at are two white balances: give one" << std::endl;
+            return 1;
+        }
+        if (gradeRegions.size() > KAJO_GRADE_MAX_REGIONS) {
+            std::cerr << "kajo_render: --grade-region can be given four times at the most" << std::endl;
+            return 1;
+        }
+        opt.gradeOn = true;
+        kajo_hip_default_grade_params(&opt.grade);
+        if ((!gradeSlope.empty() && !parseTriple(gradeSlope, false, opt.grade.global.slope)) ||
+            (!gradeOffset.empty() && !parseTriple(gradeOffset, false, opt.grade.global.offset)) ||
+            (!gradePower.empty() && !parseTriple(gradePower, false, opt.grade.global.power))) {
+            std::cerr << "kajo_render: --grade-slope, --grade-offset and --grade-power take three numbers R,G,B" << std::endl;
+            return 1;
+        }
+        if (!gradeSaturation.empty() && !parseFloat(gradeSaturation, &opt.grade.global.saturation))
+            opt.grade.global.saturation = NAN;
+        for (const std::string& text : gradeRegions) {
+            KajoGradeRegion& r = opt.grade.regions[opt.grade.nRegions++];
+            if (!parseRegion(text, &r)) {
+                std::cerr << "kajo_render: --grade-region IDS:key=v[:key=v...] takes a comma-separated list of at most 16 object ids (whole numbers >= 0), then "
+                             "the keys slope, offset, power (one number or R,G,B), saturation and amount"
+                          << std::endl;
+                return 1;
+            }
+        }
+        if (kajo_hip_grade_pixels(&opt.grade, nullptr, nullptr, 0, nullptr) != KAJO_OK) {
+            std::cerr << "kajo_render: the grade options: " << kajo_hip_last_error() << std::endl;
+            return 1;
+        }
+        if (!whiteBalance.empty()) {
+            const size_t comma = whiteBalance.find(',');
+            float kelvin = NAN, tint = 0.0f;
+            if (!parseFloat(whiteBalance.substr(0, comma), &kelvin))
+                kelvin = NAN;
+            if (comma != std::string::npos && !parseFloat(whiteBalance.substr(comma + 1), &tint))
+                tint = NAN;
+            float gains[3];
+            if (kajo_hip_grade_white_balance(kelvin, tint, gains) != KAJO_OK) {
+                std::cerr << "kajo_render: --white-balance KELVIN[,TINT]: " << kajo_hip_last_error() << std::endl;
+                return 1;
+            }
+            whiteBalanceKelvin = kelvin;
+            whiteBalanceTint = tint;
+            // (into the slope in binary64, rounded once; the product stays inside the slope's range or the library refuses it below)
+            for (int c = 0; c < 3; c++)
+                opt.grade.global.slope[c] = (float)((double)opt.grade.global.slope[c] * (double)gains[c]);
+            if (kajo_hip_grade_pixels(&opt.grade, nullptr, nullptr, 0, nullptr) != KAJO_OK) {
+                std::cerr << "kajo_render: the grade options: " << kajo_hip_last_error() << std::endl;
+                return 1;
+            }
+        }
+        if (!whiteBalanceAt.empty()) {
+            int x = -1, y = -1;
+            char tail = 0;
+            if (std::sscanf(whiteBalanceAt.c_str(), "%d,%d%c", &x, &y, &tail) != 2 || x < 0 || y < 0 || x >= width || y >= height) {
+                std::cerr << "kajo_render: --white-balance-at X,Y must be a pixel of the frame" << std::endl;
+                return 1;
+            }
+            opt.gradeNeutralAt.x = x;
+            opt.gradeNeutralAt.y = y;
+        }
+        if (opt.grade.nRegions > 0) {
+            // (the regions read the coverage tables kept beside the AOV buffers of the one handle: the same condition as --matte-mask)
+            if (opt.gpus != 1 && !aovTiled) {
+                std::cerr << "kajo_render: --grade-region needs the whole frame's mattes: --gpus 1, or any --gpus with --aov-tiled" << std::endl;
+                return 1;
+            }
+            opt.aov = true;
+            opt.matte = true;
+        }
+    }
+    const bool gradeRegionsGiven = gradeGiven && opt.grade.nRegions > 0;
     const bool matteGiven = !matteMaskOut.empty() || !matteIdsOut.empty();
-    if (aovSpecular && aovPrefix.empty() && denoiseOut.empty() && !matteGiven && !lensGiven) {
+    if (aovSpecular && aovPrefix.empty() && denoiseOut.empty() && !matteGiven && !lensGiven && !gradeRegionsGiven) {
         std::cerr << "kajo_render: --aov-specular changes the AOVs that --aov writes and --denoise is guided by: give it with --aov or --denoise" << std::endl;
         return 1;
     }
     opt.aovSpecular = aovSpecular;
-    if (aovTiled && aovPrefix.empty() && denoiseOut.empty() && !matteGiven && !lensGiven) {
+    if (aovTiled && aovPrefix.empty() && denoiseOut.empty() && !matteGiven && !lensGiven && !gradeRegionsGiven) {
         std::cerr << "kajo_render: --aov-tiled changes where the AOVs of --aov, --matte-mask, --matte-ids and --denoise are kept: give it with one of them" << std::endl;
         return 1;
     }
@@ -619,6 +782,8 @@ int main(int argc, char** argv)
     bool localRan = false;
     float lensFocusUsed = 0, lensMaxRadiusPx = 0; // --json with --lens-aperture: of the image -o holds
     bool lensRan = false;
+    float gradeSlopeUsed[3] = {1, 1, 1}; // --json with a grade option: of the image -o holds
+    bool gradeRan = false;
     std::unique_ptr<Image> viewed; // -o with a view option: the image at the view's size
     try {
         if (rendererName == "hip") {
@@ -635,11 +800,14 @@ int main(int argc, char** argv)
             metered = hipScheduler->lastMeter();
         if (hipScheduler && localGiven)
             localRan = hipScheduler->lastLocalPivot(&localPivotUsed);
-        if (lensGiven) {
+        if (lensGiven || gradeGiven) {
             // (the image -o holds: the display chain with the stage in it, from the frame as run() left it; a focus pixel that is far is
             // refused here, after the render)
             hipScheduler->readPresented(nullptr, nullptr, nullptr, nullptr, image->pixels.get(), nullptr, nullptr);
-            lensRan = hipScheduler->lastLens(&lensFocusUsed, &lensMaxRadiusPx);
+            if (lensGiven)
+                lensRan = hipScheduler->lastLens(&lensFocusUsed, &lensMaxRadiusPx);
+            if (gradeGiven)
+                gradeRan = hipScheduler->lastGrade(gradeSlopeUsed);
             if (meterGiven)
                 metered = hipScheduler->lastMeter();
         }
@@ -704,7 +872,7 @@ int main(int argc, char** argv)
             kajo_hip_default_denoise_params(&p);
             p.iterations = denoiseIterations;
             Image denoised(width, height);
-            if (despeckle || meterGiven || localGiven || lensGiven)
+            if (despeckle || meterGiven || localGiven || lensGiven || gradeGiven)
                 hipScheduler->readPresented(nullptr, &p, nullptr, nullptr, denoised.pixels.get(), nullptr, nullptr);
             else if (glareGiven)
                 hipScheduler->readDisplayed(&p, nullptr, nullptr, denoised.pixels.get(), nullptr);
@@ -719,6 +887,8 @@ int main(int argc, char** argv)
             // (the image -o holds: the display chain as run() left the frame, through the view, at the view's size)
             viewed.reset(new Image(opt.view.outW, opt.view.outH));
             hipScheduler->readViewed(viewed->pixels.get());
+            if (gradeGiven)
+                gradeRan = hipScheduler->lastGrade(gradeSlopeUsed);
         }
     } catch (const std::exception& e) {
         std::cerr << "kajo_render: " << e.what() << std::endl;
@@ -770,6 +940,16 @@ int main(int argc, char** argv)
         }
         if (lensGiven && lensRan)
             std::printf(", \"lens_focus\": %.9g, \"lens_max_radius_px\": %.9g", (double)lensFocusUsed, (double)lensMaxRadiusPx);
+        if (gradeGiven && gradeRan) {
+            // (grade_slope: the slope the image -o holds was graded with, the white balance in it)
+            const KajoGradeOp& g = opt.grade.global;
+            std::printf(", \"grade_slope\": [%.9g, %.9g, %.9g], \"grade_offset\": [%.9g, %.9g, %.9g], \"grade_power\": [%.9g, %.9g, %.9g], "
+                        "\"grade_saturation\": %.9g, \"grade_regions\": %d",
+                        (double)gradeSlopeUsed[0], (double)gradeSlopeUsed[1], (double)gradeSlopeUsed[2], (double)g.offset[0], (double)g.offset[1],
+                        (double)g.offset[2], (double)g.power[0], (double)g.power[1], (double)g.power[2], (double)g.saturation, (int)opt.grade.nRegions);
+            if (!whiteBalance.empty())
+                std::printf(", \"grade_white_balance_kelvin\": %.9g, \"grade_white_balance_tint\": %.9g", whiteBalanceKelvin, whiteBalanceTint);
+        }
         if (viewGiven)
             std::printf(", \"view_out_w\": %d, \"view_out_h\": %d, \"view_filter\": \"%s\", \"view_scale_x\": %.9g, \"view_scale_y\": %.9g",
                         (int)opt.view.outW, (int)opt.view.outH, viewFilterNames[opt.view.filter],

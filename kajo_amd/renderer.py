@@ -378,8 +378,21 @@ class HipRenderer:
         capi.check(self._L.kajo_hip_view_argb8(self._h, C.byref(v), src.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def grade(self, despeckle: dict = None, denoise: dict = None, **params) -> np.ndarray:
+        """The frame after the grade (include/kajo_hip.h kajo_hip_grade): (H, W, 4) float32 sums over passes, as radiance(). params as
+        grade_params(): slope, offset, power (a number or three), saturation, white_balance (gains multiplied into the slope), regions
+        (a list of dicts: objects, amount and the op's keys; they need aov=True, matte=True). despeckle, denoise: the stages in front, as
+        present(). The accumulation, the AOVs, the matte tables and the counters are not touched."""
+        p = grade_params(**params)
+        s = None if despeckle is None else self._despeckle_params(**despeckle)
+        d = None if denoise is None else self._denoise_params(**denoise)
+        out = np.empty((self.height, self.width, 4), np.float32)
+        ref = lambda p: None if p is None else C.byref(p)
+        capi.check(self._L.kajo_hip_grade(self._h, ref(s), ref(d), C.byref(p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def present(self, despeckle: dict = None, denoise: dict = None, glare: dict = None, meter: dict = None, local: dict = None,
-                lens: dict = None, view: dict = None, **tone):
+                lens: dict = None, view: dict = None, grade: dict = None, **tone):
         """The display chain with the despeckle in front (include/kajo_hip.h kajo_hip_present_argb8): despeckle -> denoise -> glare ->
         tone mapping -> (argb8, scale) as tonemap(), every stage but the last optional. despeckle: a dict of despeckle()'s factor / rank /
         floor; the rest as display(). With despeckle None it is display(denoise, glare, **tone). meter: a dict of meter()'s params puts
@@ -388,7 +401,8 @@ class HipRenderer:
         of local()'s params puts the local tone mapping between the glare and the meter (kajo_hip_present_local_argb8; the call is
         routed there only when it is given). lens: a dict of lens()'s params puts the depth of field between the denoiser and the glare
         (kajo_hip_present_lens_argb8; likewise routed there only when it is given). view: a dict of view()'s params puts the view behind
-        the tone curves (kajo_hip_present_view_argb8; likewise): the array returned then has the view's shape (out_h, out_w)."""
+        the tone curves (kajo_hip_present_view_argb8; likewise): the array returned then has the view's shape (out_h, out_w). grade: a dict of
+        grade()'s params puts the grade between the denoiser and the lens (kajo_hip_present_grade_argb8; likewise)."""
         t = self._tone_params(**tone)
         s = None if despeckle is None else self._despeckle_params(**despeckle)
         d = None if denoise is None else self._denoise_params(**denoise)
@@ -396,6 +410,18 @@ class HipRenderer:
         argb8 = np.empty((self.height, self.width), np.uint32)
         scale = C.c_float()
         ref = lambda p: None if p is None else C.byref(p)
+        if grade is not None:
+            c = grade_params(**grade)
+            v = None if view is None else self._view_params(**view)
+            f = None if lens is None else self._lens_params(**lens)
+            l = None if local is None else self._local_params(**local)
+            m = None if meter is None else self._meter_params(**meter)
+            result = capi.KajoMeterResult()
+            if v is not None:
+                argb8 = np.empty((max(v.outH, 0), max(v.outW, 0)), np.uint32)
+            capi.check(self._L.kajo_hip_present_grade_argb8(self._h, ref(s), ref(d), C.byref(c), ref(f), ref(g), ref(l), ref(m), C.byref(t),
+                                                            ref(v), argb8.ctypes.data_as(C.c_void_p), C.byref(result)))
+            return argb8, (self.tone_scale() if m is None else self._meter_result(result))
         if view is not None:
             v = self._view_params(**view)
             f = None if lens is None else self._lens_params(**lens)
@@ -484,6 +510,72 @@ class HipRenderer:
         """The whole-frame AOVs (and coverage tables) of this handle from the owners' gathered tile buffers, device pointers in rank order
         (include/kajo_hip.h kajo_hip_compose_aov); None = the handle's own buffer where it is the frame's one owner."""
         capi.check(self._L.kajo_hip_compose_aov(self._h, C.c_void_p(gathered_aov_ptr), C.c_void_p(gathered_matte_ptr)))
+
+
+def _grade_op(op, slope=None, offset=None, power=None, saturation=None):
+    for field, value in (("slope", slope), ("offset", offset), ("power", power)):
+        if value is not None:
+            getattr(op, field)[:] = [float(v) for v in np.broadcast_to(np.asarray(value, np.float64), (3,))]
+    if saturation is not None:
+        op.saturation = float(saturation)
+
+
+def grade_params(slope=None, offset=None, power=None, saturation=None, white_balance=None, regions=()):
+    """KajoGradeParams (include/kajo_hip.h): the global op's slope, offset, power (a number or three; those left out keep the defaults 1, 0,
+    1) and saturation (1); white_balance = gains (grade_white_balance(), grade_neutral()) multiplied into the slope in binary64 and
+    rounded once; regions = up to four dicts of objects (ids as matte_mask() takes them), amount (1) and the op's keys. Nothing is
+    checked here: the library refuses what is out of range."""
+    p = capi.KajoGradeParams()
+    capi.lib().kajo_hip_default_grade_params(C.byref(p))
+    if white_balance is not None:
+        base = np.broadcast_to(np.asarray(1.0 if slope is None else slope, np.float64), (3,))
+        slope = base * np.asarray(white_balance, np.float64)
+    _grade_op(p.global_, slope, offset, power, saturation)
+    regions = list(regions)
+    p.nRegions = len(regions)
+    for r, spec in zip(p.regions, regions):
+        spec = dict(spec)
+        objects = [int(o) for o in np.asarray(spec.pop("objects"), np.int64).reshape(-1)]
+        r.n = len(objects)
+        r.objects[:min(r.n, capi.KAJO_GRADE_REGION_OBJECTS)] = objects[:capi.KAJO_GRADE_REGION_OBJECTS]
+        if "amount" in spec:
+            r.amount = float(spec.pop("amount"))
+        _grade_op(r.op, **spec)
+    return p
+
+
+def grade_pixels(rgb, masks=None, **params) -> np.ndarray:
+    """Host-only: the grade's rule over pixels of MEANS (include/kajo_hip.h kajo_hip_grade_pixels), the device's own lines compiled for
+    the host. rgb (..., 3) float32; masks (..., nRegions) float32, one plane per region; params as grade_params(), or params=a
+    KajoGradeParams."""
+    p = params["params"] if "params" in params else grade_params(**params)
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    n = rgb.size // 3
+    m = None
+    if masks is not None:
+        m = np.ascontiguousarray(masks, np.float32)
+        if m.size != n * max(p.nRegions, 0):
+            raise ValueError("masks must hold nRegions floats per pixel")
+    out = np.empty_like(rgb)
+    capi.check(capi.lib().kajo_hip_grade_pixels(C.byref(p), rgb.ctypes.data_as(C.c_void_p), None if m is None else m.ctypes.data_as(C.c_void_p), n,
+                                                out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def grade_white_balance(kelvin: float, tint: float = 0.0) -> np.ndarray:
+    """Host-only: the gains (3,) float32 that make a surface lit by a `kelvin` illuminant grey at its own luminance (include/kajo_hip.h
+    kajo_hip_grade_white_balance); tint in stops of green gain."""
+    g = (C.c_float * 3)()
+    capi.check(capi.lib().kajo_hip_grade_white_balance(float(kelvin), float(tint), C.byref(g)))
+    return np.array(g[:], np.float32)
+
+
+def grade_neutral(rgb) -> np.ndarray:
+    """Host-only: the gains (3,) float32 that make the pixel `rgb` grey at its own luminance (include/kajo_hip.h kajo_hip_grade_neutral)."""
+    src = (C.c_float * 3)(*[float(v) for v in rgb])
+    g = (C.c_float * 3)()
+    capi.check(capi.lib().kajo_hip_grade_neutral(C.byref(src), C.byref(g)))
+    return np.array(g[:], np.float32)
 
 
 def view_weights(src_n: int, a0: float, a1: float, out_n: int, filter="area"):
