@@ -1006,8 +1006,13 @@ int kajo_hip_kat_shade(kajo_hip_t h, int n, const float* origins, const float* d
                        uint64_t* finalStates);
 /* include/kajo_strictmath.h evaluated on the device, element-wise: fn 0 sin, 1 cos, 2 asin, 3 acos, 4 pow(x, y); and the two IEEE
    operations the STRICT / EXACT kernels form by hand (the reference's `/` and glm's sqrt, renderer/cpu/Raytracer.cpp:30-44):
-   fn 5 x / y, fn 6 sqrt(x). */
+   fn 5 x / y, fn 6 sqrt(x), fn 7 the root as the sphere tests of the walks form it (sqrt(x) but for negative subnormal x). */
 int kajo_hip_kat_strictmath(kajo_hip_t h, int fn, int n, const float* x, const float* y, float* out);
+/* The same functions (fn 0-4, 6 and 7; y is pow's exponent) at EVERY binary32 x, summed on the device. Binade b = sign * 256 + biased
+   exponent holds the arguments with bits b << 23 | m; sums[2 b] = sum over m of bits(r), sums[2 b + 1] = sum of bits(r) * (2 m + 1),
+   both mod 2^64, a NaN result counted as 0x7fc00000. sums: 1024 words of HOST memory. The host build of kajo_strictmath.h writes the
+   same table (tools/strictmath_binades.c). */
+int kajo_hip_kat_strictmath_sweep(kajo_hip_t h, int fn, float y, uint64_t* sums);
 
 const char* kajo_hip_last_error(void);
 const char* kajo_hip_version(void);

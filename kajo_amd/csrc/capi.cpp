@@ -49,6 +49,7 @@ int kajo_kat_shade_strict_launch(const RenderArgs*, unsigned grid, size_t lds, v
 int kajo_kat_trace_fast_launch(const KatTraceArgs*, unsigned grid, size_t lds, void* stream);
 int kajo_kat_trace_strict_launch(const KatTraceArgs*, unsigned grid, size_t lds, void* stream);
 int kajo_kat_math_launch(int fn, int n, const void* x, const void* y, void* out, void* stream);
+int kajo_kat_math_sweep_launch(int fn, float y, void* partial, void* stream); // 512 * 64 workgroups, a pair of 64-bit words each
 int kajo_aov_fast_launch(const AovArgs*, int instance, unsigned grid, size_t lds, void* stream);
 int kajo_aov_strict_launch(const AovArgs*, int instance, unsigned grid, size_t lds, void* stream);
 int kajo_aov_fast_set_lds(int instance, size_t lds);
@@ -3337,6 +3338,36 @@ int kajo_hip_kat_strictmath(kajo_hip_t h, int fn, int n, const float* x, const f
         return failHip(le, "kat math launch");
     HIP_TRY(hipMemcpyAsync(out, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    return KAJO_OK;
+}
+
+int kajo_hip_kat_strictmath_sweep(kajo_hip_t h, int fn, float y, uint64_t* sums)
+{
+    if (!h || !sums)
+        return fail(KAJO_E_INVALID, "null argument");
+    if (fn < 0 || fn > 7 || fn == 5)
+        return fail(KAJO_E_INVALID, "strictmath sweep: fn must be 0 sin, 1 cos, 2 asin, 3 acos, 4 pow, 6 sqrt or 7 the walk's sqrt (x / y is binary)");
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    const size_t perBinade = 64, words = 512 * perBinade * 2; // kernel_strict.hip KAJO_SWEEP_BLOCKS_PER_BINADE
+    DeviceBuffer dPartial;
+    HIP_TRY(dPartial.alloc(words * 8));
+    hipError_t le = (hipError_t)kajo_kat_math_sweep_launch(fn, y, dPartial.p, h->stream);
+    if (le != hipSuccess)
+        return failHip(le, "kat math sweep launch");
+    std::vector<uint64_t> partial(words);
+    HIP_TRY(hipMemcpyAsync(partial.data(), dPartial.p, words * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (size_t b = 0; b < 512; b++) {
+        uint64_t A = 0, B = 0;
+        for (size_t c = 0; c < perBinade; c++) {
+            A += partial[2 * (b * perBinade + c)];
+            B += partial[2 * (b * perBinade + c) + 1];
+        }
+        sums[2 * b] = A;
+        sums[2 * b + 1] = B;
+    }
     return KAJO_OK;
 }
 

@@ -490,6 +490,21 @@ class HipRenderer:
         capi.check(self._L.kajo_hip_kat_shade(self._h, n, p(o), p(d), p(st), p(rgb), p(fin)))
         return rgb, fin
 
+    def kat_strictmath(self, fn, x, y=None):
+        """include/kajo_strictmath.h (fn 0 sin, 1 cos, 2 asin, 3 acos, 4 pow) and the kernels' x / y (5) and sqrt (6), element-wise."""
+        x = np.ascontiguousarray(x, np.float32)
+        y = x if y is None else np.ascontiguousarray(np.broadcast_to(np.asarray(y, np.float32), x.shape))
+        out = np.zeros_like(x)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        capi.check(self._L.kajo_hip_kat_strictmath(self._h, fn, x.size, p(x), p(y), p(out)))
+        return out
+
+    def kat_strictmath_sweep(self, fn, y=0.0):
+        """The checksums (A, B) of fn (not 5) over every binary32 argument: a (512, 2) uint64 array, row = sign * 256 + biased exponent."""
+        sums = np.zeros((512, 2), np.uint64)
+        capi.check(self._L.kajo_hip_kat_strictmath_sweep(self._h, fn, float(y), sums.ctypes.data_as(C.c_void_p)))
+        return sums
+
     # -- multi-GPU plumbing ----------------------------------------------------------------
     def tile_buffer(self):
         ptr, nbytes = C.c_void_p(), C.c_size_t()

@@ -85,6 +85,13 @@ def test_strict_kernels_keep_their_register_budgets():
         body = asm[asm.index(k + ":"):]
         body = body[:body.index("s_endpgm")]
         assert not re.search(r"\n\s+flat_(load|store|atomic)", body), k
+    # the sweep of the strict math over every binary32 (kajo_hip_kat_strictmath_sweep): plain C++ around the header, measured 38 VGPRs,
+    # eight waves per SIMD, nothing spilled; its only memory accesses are the LDS reduction and one pair of global stores a workgroup
+    r = res["kajo_kat_math_sweep"]
+    assert r["Occupancy"] == 8 and r["VGPRs"] <= 48 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0 and r["ScratchSize"] == 0, r
+    body = asm[asm.index("kajo_kat_math_sweep:"):]
+    body = body[:body.index("s_endpgm")]
+    assert not re.search(r"\n\s+(flat_|global_load|global_atomic|scratch_)", body)
     # (the known-answer kernels walk the grid through a pointer of either home: the only flat accesses of the unit)
     for k in ("kajo_kat_shade_strict", "kajo_kat_trace_strict"):
         body = asm[asm.index(k + ":"):]
