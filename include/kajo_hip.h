@@ -993,8 +993,8 @@ int kajo_hip_launch_order(const uint32_t* waveTrips, uint32_t nBlocks, uint32_t 
 
 /* Known-answer hooks: run the kernels' OWN device functions on caller-supplied rays, so that the
    vectors captured from the compiled reference (tests/golden/kat_trace.npz, kat_shade.npz) can be
-   checked on the GPU function by function. All pointers are HOST memory; scenes whose hot records
-   exceed 48 KiB of LDS are refused.
+   checked on the GPU function by function. All pointers are HOST memory; kat_trace takes any scene
+   kajo_hip_create accepted, kat_shade refuses scenes whose hot records exceed 48 KiB of LDS.
      kat_trace: closest hit of Raytracer::trace (renderer/cpu/Raytracer.cpp:126-138) per ray: object index
                 (0 = miss, planes 1.., then spheres), ray.maxDistance, position, normal, tangent, binormal.
      kat_shade: trace + Shader::shade (renderer/cpu/Shader.cpp:113-178) of one path per ray from the given

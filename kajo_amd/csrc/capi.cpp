@@ -3232,8 +3232,7 @@ int kajo_hip_kat_trace(kajo_hip_t h, int n, const float* origins, const float* d
 {
     if (!h || n < 0 || !origins || !dirs || !objIndex || !t || !position || !normal || !tangent || !binormal)
         return fail(KAJO_E_INVALID, "null argument");
-    if (h->lds.hotBytes > 48 * 1024)
-        return fail(KAJO_E_INVALID, "known-answer entry points are limited to scenes whose hot records fit 48 KiB of LDS");
+    // (any scene create() accepted: its hot records are within the plan's 160 KiB, and the launcher opts in above 48 KiB)
     int rc = bind(h);
     if (rc || n == 0)
         return rc;

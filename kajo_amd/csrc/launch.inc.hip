@@ -102,8 +102,27 @@ extern "C" int KAJO_CAT(KAJO_KAT_SHADE_NAME, _launch)(const RenderArgs* args, un
 }
 
 #ifdef KAJO_KAT_TRACE_NAME
+// (the hot records of the largest scenes create() accepts: the same opt-in as _set_lds above, raised only, per device; called with the
+// handle's device current)
 extern "C" int KAJO_CAT(KAJO_KAT_TRACE_NAME, _launch)(const KatTraceArgs* args, unsigned grid, size_t ldsBytes, void* stream)
 {
+    if (ldsBytes > 48 * 1024) {
+        static size_t highWaterOfDevice[64] = {};
+        static std::mutex guard;
+        int device = 0;
+        hipError_t e = hipGetDevice(&device);
+        if (e != hipSuccess)
+            return (int)e;
+        if (device < 0 || device >= 64)
+            return (int)hipErrorInvalidDevice;
+        std::lock_guard<std::mutex> lock(guard);
+        if (ldsBytes > highWaterOfDevice[device]) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(KAJO_KAT_TRACE_NAME), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
+            if (e != hipSuccess)
+                return (int)e;
+            highWaterOfDevice[device] = ldsBytes;
+        }
+    }
     hipLaunchKernelGGL(KAJO_KAT_TRACE_NAME, dim3(grid), dim3(256), ldsBytes, static_cast<hipStream_t>(stream), *args);
     return (int)hipGetLastError();
 }

@@ -7,6 +7,11 @@
 //   host_san plan lds a.pod ...          kajo_amd/csrc/launch_plan.h kajoLdsPlan: a scene's LDS plan per staging (plain, no grid, no
 //                                        visibility lists) and numerics build
 //   host_san plan shape in.bin out.bin   launch_plan.h kajoLaunchShape over a table of launches
+//   host_san plan sizes a.pod ...        what a scene's size does to its staging (tests/test_scene_sizes_cpu.py): the plan's ldsTotal() per
+//                                        numerics build, the grid's cells per axis against the cells it wanted, the visibility lists' bins
+//                                        and their longest row of 16-bit offsets
+#include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -182,6 +187,53 @@ static int planLds(int argc, char** argv)
     return 0;
 }
 
+// Size facts of each scene file as kajo_hip_create stages it without flags: one line "<file>: field=value ...". gridWant*: the cells
+// per axis stage.cpp buildGrid asks for before its clamp to 128 (ext / side, restated from the staged bounds); shadowMaxRow: the most items
+// in one row of bins, which is the largest value a row's 16-bit offsets hold (shadowMaxOff16: read back from them).
+static int planSizes(int argc, char** argv)
+{
+    for (int a = 0; a < argc; a++) {
+        Pod pod;
+        if (int rc = pod.read(argv[a])) return rc;
+        kajo::StagedScene st;
+        kajo::stageScene(pod.sc, st, 48, true);
+        const KajoSceneLds b = kajoSceneLds(st);
+        printf("%s: nSpheres=%d nLights=%zu grid=%d lists=%d", argv[a], st.nSpheres, st.light.size(), st.gridEnabled, st.shadowEnabled);
+        for (Numerics k : {Numerics::Fast, Numerics::Strict, Numerics::Exact}) {
+            const KajoLdsPlan p = kajoLdsPlan(b.hotBytes, b.coldBytes, b.gridHeaderBytes, b.gridBytes, st.gridEnabled, st.shadowEnabled,
+                                              (int)st.light.size(), k);
+            const char* name = k == Numerics::Fast ? "Fast" : k == Numerics::Strict ? "Strict" : "Exact";
+            printf(" ldsTotal%s=%zu fits%s=%d", name, p.ldsTotal(), name, p.fits);
+        }
+        if (st.gridEnabled) {
+            double ext[3], vol = 1;
+            for (int k = 0; k < 3; k++) {
+                ext[k] = std::fmax((double)st.gridMax[k] - st.gridMin[k], 1e-3);
+                vol *= ext[k];
+            }
+            const double side = std::cbrt(vol / st.nSpheres);
+            uint32_t longest = 0;
+            for (size_t c = 0; c + 1 < st.gridCellStart.size(); c++)
+                longest = std::max(longest, st.gridCellStart[c + 1] - st.gridCellStart[c]);
+            const char axis[3] = {'X', 'Y', 'Z'};
+            for (int k = 0; k < 3; k++)
+                printf(" gridDim%c=%d gridWant%c=%d", axis[k], st.gridDim[k], axis[k], (int)std::ceil(ext[k] / side));
+            printf(" gridItems=%zu gridMaxCell=%u", st.gridItems.size(), longest);
+        }
+        if (st.shadowEnabled || st.shadowN) { // (shadowN without lists: built, then dropped for a row beyond 16 bits)
+            const size_t N = (size_t)st.shadowN, rows = st.light.size() * 6 * N;
+            uint32_t maxRow = 0, maxOff = 0;
+            for (size_t row = 0; row < rows; row++)
+                maxRow = std::max(maxRow, st.shadowStart[(row + 1) * N] - st.shadowStart[row * N]);
+            for (uint16_t o : st.shadowOff16)
+                maxOff = std::max(maxOff, (uint32_t)o);
+            printf(" shadowN=%d shadowItems=%zu shadowMaxRow=%u shadowMaxOff16=%u", st.shadowN, st.shadowItems.size(), maxRow, maxOff);
+        }
+        printf("\n");
+    }
+    return 0;
+}
+
 // Launch shapes: in.bin holds records of 11 uint32 (pixelBlocks, now, n, coldInLds, noSplit, mailboxOffset, perWaveBytes, passesDone,
 // grouped, orderValid, nParted); out.bin gets 6 per record (startsInside, endsInside, launchGroups, split, chunks, parted).
 static int planShape(int argc, char** argv)
@@ -215,6 +267,7 @@ static int plan(int argc, char** argv)
     const std::string what = argv[0];
     if (what == "lds") return planLds(argc - 1, argv + 1);
     if (what == "shape") return planShape(argc - 1, argv + 1);
+    if (what == "sizes") return planSizes(argc - 1, argv + 1);
     return 2;
 }
 
