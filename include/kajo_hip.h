@@ -144,6 +144,13 @@ extern "C" {
                                    KAJO_FLAG_AOV_MATTE; the same kernel instances (kajo_hip_aov_kernel). The frame of such a handle is
                                    at most 524288 x 262144 pixels, a tile at most 524280 a side (KAJO_E_INVALID). Handles without the
                                    flag allocate, launch and refuse what they did before. */
+#define KAJO_FLAG_NOISE 16384u /* the per-pixel noise estimate ("The noise estimate" below; kajo_hip_noise): create() allocates and zeroes a
+                                   baseline (16 bytes) and a moment record (32 bytes) per slot of the handle's tile buffer, for any tileIndex /
+                                   tileCount and in every numerics build. kajo_hip_render then cuts its launches so that none crosses an
+                                   absolute multiple of KAJO_NOISE_BATCH_PASSES -- the frame is the same bit for bit, KajoCounters.launches
+                                   rises -- and enqueues the update kernel of kajo_amd/csrc/noise.hip behind each launch that ends on one,
+                                   outside the timing events. No render, AOV or display kernel is changed for it. Handles without the flag
+                                   allocate, launch and return exactly what they did before. */
 
 typedef struct KajoParams {
     int32_t samplesPerPass; /* S: nominal samples per pixel per pass (reference: 32, Renderer.cpp:21);
@@ -168,7 +175,7 @@ typedef struct KajoCounters {
     uint64_t laneSlots;      /* 64 * wave-iterations of the trace loop: traversals / laneSlots = lane efficiency */
     double kernelMs;         /* summed device time of the render kernels (HIP events on the handle's stream; not the AOV kernel of
                                 KAJO_FLAG_AOV, which runs outside them) */
-    uint64_t launches;       /* render kernel launches */
+    uint64_t launches;       /* render kernel launches (a KAJO_FLAG_NOISE handle cuts them at every multiple of four passes: more of them) */
     uint64_t shadowQueries;  /* large scenes: shadow rays answered from the lights' visibility lists inside the light loop (they
                                 are not among `traversals`, which then counts camera and extension rays only) */
     uint64_t tailGroups;     /* of the last render launch: workgroups beyond one per pixel block -- the cheapest blocks of a large frame
@@ -951,6 +958,74 @@ int kajo_hip_present_grade_gathered_argb8_device(kajo_hip_t h, const void* gathe
                                                  const KajoGradeParams* grade, const KajoGlareParams* g, const KajoLocalParams* local,
                                                  const KajoMeterParams* meter, const KajoToneParams* tone, const KajoViewParams* view, void* dst,
                                                  KajoMeterResult* result);
+
+/* The noise estimate (KAJO_FLAG_NOISE): how noisy the frame is, pixel by pixel, from the frame's own passes -- batch means, in kernels of
+   their own (kajo_amd/csrc/noise.hip) on the handle's stream, float32 / binary64 IEEE arithmetic without contraction in every numerics
+   build: only its input, the accumulation, depends on FAST / EXACT / STRICT.
+   BATCHES. Batch b >= 1 is passes 4b-3 .. 4b by ABSOLUTE pass number (KAJO_NOISE_BATCH_PASSES = 4 = the group of the FAST / EXACT totals:
+   at such a boundary no group is in progress, so the tile buffer alone is the sum kajo_hip_read_radiance returns). Per slot of the owner's
+   tile buffer, when batch b completes:
+     T_b = the accumulation's float4 after pass 4b
+     D_b = T_b - T_(b-1) per channel, one float32 subtraction, T_0 = 0
+     y_b = 0.2126f * D.x + 0.7152f * D.y + 0.0722f * D.z          (the meter's weights; float32, left to right, not contracted, no clamp)
+     y_b finite:  n += 1;  s1 += (double)y;  s2 += (double)y * (double)y      (one binary64 multiply and one add, not fused)
+     otherwise:   bad += 1
+     then T_b is the new baseline
+   The record (s1, s2, n, bad) -- KajoNoiseMoments, 32 bytes -- is a function of (scene, parameters, passes rendered), as the frame is:
+   not of how the passes were cut into render() calls, launches or owners.
+   WHICH BATCHES COUNT: those of which this handle rendered all four passes since the last kajo_hip_reset or kajo_hip_set_pass_count.
+   kajo_hip_reset zeroes the records and the baseline. kajo_hip_set_pass_count(P) zeroes the records; the baseline is then the buffer as
+   it stands at the first boundary >= P (for P % 4 == 0: the buffer in front of the next launch), and the batches after it count.
+   EVALUATION (kajo_hip_noise; per pixel in binary64, results rounded to float32):
+     m   = s1 / (4 n)                              mean luminance per pass (n = 0: 0)
+     v   = max(s2 - s1 * s1 / n, 0) / (n - 1)      variance of the batch sums
+     se  = sqrt(v / n) / 4                         standard error of m
+     rel = se / (max(m, 0) + floor)                floor > 0 (default 1e-2), so that black pixels do not dominate
+     n < 2: se = rel = -1, "unknown"
+   HISTOGRAM, KAJO_NOISE_HIST_WORDS = 516 uint32 words: words 0..513 the meter's bins (KAJO_METER_BINS, the same bit-pattern rule) over
+   the float32 rel of the KNOWN pixels (n >= 2); word 514 the unknown pixels; word 515 the pixels with bad > 0 (which are counted among
+   the known or the unknown ones too). Words 0..514 add up to the owner's pixels. Integer counts: the histograms of several owners add
+   word by word to the whole frame's.
+   kajo_hip_noise_evaluate, pure host: known = the sum of words 0..513; rank r = min(known, max(1, ceil((double)q * known))); the bin is
+   the smallest b >= 0 whose cumulative count over bins 0..b reaches r; *value = that bin's centre -- the meter's centres for bins 1..513
+   (bin 513: 2^16), 2^-17 for bin 0 -- or -1 with known = 0.
+   Refusals: KAJO_E_INVALID, before a handle or a device is looked for, for NULL params, a floor that is not finite or not above 0 and a
+   quantile that is not finite or outside (0, 1]; then KAJO_E_INVALID for a NULL handle and KAJO_E_STATE for a handle created without
+   KAJO_FLAG_NOISE. The accumulation, the pass count and the counters (kernelMs included) are not touched. */
+#define KAJO_NOISE_BATCH_PASSES 4
+#define KAJO_NOISE_HIST_WORDS 516
+typedef struct KajoNoiseParams {
+    float floor;            /* > 0, finite (default 1e-2) */
+    float quantile;         /* in (0, 1] (default 0.95): KajoNoiseResult.quantileValue */
+} KajoNoiseParams;          /* 8 bytes */
+typedef struct KajoNoiseMoments {
+    double s1, s2;          /* sum and sum of squares of the finite batch luminances */
+    uint64_t n, bad;        /* batches with a finite, and with a not finite, luminance */
+} KajoNoiseMoments;         /* 32 bytes */
+typedef struct KajoNoiseResult {
+    int64_t pixels;         /* the owner's pixels: known + unknown */
+    int64_t known;          /* pixels with n >= 2 */
+    int64_t unknown;        /* pixels with n < 2 */
+    int64_t bad;            /* pixels with bad > 0 */
+    float quantileValue;    /* kajo_hip_noise_evaluate of the histogram at params.quantile; -1 with known = 0 */
+    int32_t reserved[3];    /* 0 */
+} KajoNoiseResult;          /* 48 bytes */
+void kajo_hip_default_noise_params(KajoNoiseParams* p); /* NULL is accepted */
+/* Pure host, no device and no handle. KAJO_E_INVALID: NULL hist or value, a quantile that is not finite or outside (0, 1]. */
+int kajo_hip_noise_evaluate(const uint32_t hist[KAJO_NOISE_HIST_WORDS], float quantile, float* value);
+/* The noise map of the handle's own pixels. mean, stderror, relative (float) and batches (uint32, n saturated at 2^32 - 1): HOST pointers
+   to WHOLE-FRAME row-major planes of width*height words, row 0 = top, of which only the pixels of this owner's tiles are written -- a
+   caller hands the same arrays to every owner and needs no gather. hist: HOST pointer to KAJO_NOISE_HIST_WORDS words, this owner's
+   histogram. Every out pointer may be NULL. An owner without a tile launches nothing and reports zeros. Waits.
+   COST: that of the whole FRAME, not of the owner's share of it. The kernel walks every 64x4 rectangle of the frame, every plane asked
+   for comes to the host whole (width*height words), and an owner of part of the frame (tileCount > 1) then walks all width*height pixels
+   on the host to copy its own out of a staging copy the handle keeps (4 * width*height words, allocated on the first such call). A
+   diagnostic to call per refresh, not per launch; NULL planes cost nothing, the histogram alone is 516 words. */
+int kajo_hip_noise(kajo_hip_t h, const KajoNoiseParams* params, float* mean, float* stderror, float* relative, uint32_t* batches, uint32_t* hist,
+                   KajoNoiseResult* result);
+/* For tests: the raw records. records: HOST pointer to a whole-frame row-major array of width*height KajoNoiseMoments, of which only the
+   pixels of this owner's tiles are written. KAJO_E_INVALID on a NULL argument, KAJO_E_STATE without KAJO_FLAG_NOISE. Waits. */
+int kajo_hip_read_noise_moments(kajo_hip_t h, KajoNoiseMoments* records);
 
 /* Use an existing HIP stream (hipStream_t passed as void*) instead of the handle's own. */
 int kajo_hip_set_stream(kajo_hip_t h, void* stream);

@@ -37,6 +37,9 @@ KAJO_FLAG_AOV = 1024  # first-hit albedo / normal / depth buffers over the beaut
 KAJO_FLAG_AOV_SPECULAR = 2048  # with KAJO_FLAG_AOV: the buffers are taken at the first non-delta hit, through ideal mirrors and glass
 KAJO_FLAG_AOV_MATTE = 4096  # with KAJO_FLAG_AOV: per-pixel (object id, sample count) tables over the AOVs' samples (kajo_hip_read_matte)
 KAJO_FLAG_AOV_TILED = 8192  # with KAJO_FLAG_AOV: the sums of the handle's own tiles, any tileIndex / tileCount (kajo_hip_compose_aov)
+KAJO_FLAG_NOISE = 16384  # the per-pixel noise estimate: batch moments beside the render, in kernels of their own (kajo_hip_noise)
+KAJO_NOISE_BATCH_PASSES = 4  # a batch of the noise estimate: passes 4b-3 .. 4b by absolute number
+KAJO_NOISE_HIST_WORDS = 516  # the meter's 514 bins over the relative error, the unknown pixels, the pixels with a bad batch
 KAJO_MATTE_SLOTS = 8
 KAJO_DENOISE_NO_DEMODULATE = 1  # KajoDenoiseParams.flags: filter the mean radiance itself, not radiance / albedo
 KAJO_TONE_CLAMP, KAJO_TONE_REINHARD, KAJO_TONE_ACES = 0, 1, 2  # KajoToneParams.curve
@@ -72,6 +75,7 @@ EXPORTS = [
     "kajo_hip_present_view_gathered_argb8_device",
     "kajo_hip_default_grade_params", "kajo_hip_grade_pixels", "kajo_hip_grade_white_balance", "kajo_hip_grade_neutral", "kajo_hip_grade",
     "kajo_hip_present_grade_argb8", "kajo_hip_present_grade_gathered_argb8_device",
+    "kajo_hip_default_noise_params", "kajo_hip_noise_evaluate", "kajo_hip_noise", "kajo_hip_read_noise_moments",
 ]
 
 
@@ -106,6 +110,19 @@ class KajoMeterResult(C.Structure):
     _fields_ = [("pixels", C.c_int64), ("nonfinite", C.c_int64), ("under", C.c_int64), ("over", C.c_int64), ("metered", C.c_int64),
                 ("anchorL", C.c_float), ("whiteL", C.c_float), ("exposure", C.c_float), ("minBin", C.c_int32), ("maxBin", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class KajoNoiseParams(C.Structure):
+    _fields_ = [("floor", C.c_float), ("quantile", C.c_float)]
+
+
+class KajoNoiseMoments(C.Structure):
+    _fields_ = [("s1", C.c_double), ("s2", C.c_double), ("n", C.c_uint64), ("bad", C.c_uint64)]
+
+
+class KajoNoiseResult(C.Structure):
+    _fields_ = [("pixels", C.c_int64), ("known", C.c_int64), ("unknown", C.c_int64), ("bad", C.c_int64), ("quantileValue", C.c_float),
+                ("reserved", C.c_int32 * 3)]
 
 
 class KajoLocalParams(C.Structure):
@@ -315,6 +332,13 @@ def lib():
             L.kajo_hip_aov_tile_buffers.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
                                                     C.POINTER(C.c_size_t)]
             L.kajo_hip_compose_aov.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "kajo_hip_noise"):  # (nor the noise estimate)
+            L.kajo_hip_default_noise_params.argtypes = [C.POINTER(KajoNoiseParams)]
+            L.kajo_hip_default_noise_params.restype = None
+            L.kajo_hip_noise_evaluate.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_float)]
+            L.kajo_hip_noise.argtypes = [C.c_void_p, C.POINTER(KajoNoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(KajoNoiseResult)]
+            L.kajo_hip_read_noise_moments.argtypes = [C.c_void_p, C.c_void_p]
         L.kajo_hip_kat_trace.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
         L.kajo_hip_kat_shade.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.kajo_hip_kat_strictmath.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -79,6 +79,9 @@ int kajo_view_launch(const void* src, int W, const void* tables, const void* fir
 size_t kajo_grade_block_bytes(void);
 int kajo_grade_launch(const void* src, const TileMap* map, int fromTiles, float passes, const void* block, int nRegions, const void* ids,
                       const void* counts, unsigned words, unsigned nObjects, float samples, void* out, void* stream);
+int kajo_noise_update_launch(const void* tiles, void* baseline, void* records, uint32_t slots, void* stream);
+int kajo_noise_map_launch(const void* records, const TileMap* map, int tileIndex, double floorL, void* mean, void* stdError, void* relative,
+                          void* batches, void* hist, void* stream);
 int kajo_compose_aov_launch(const void* gatheredAov, const void* gatheredMatte, const TileMap* map, void* aov, void* matte, void* stream);
 int kajo_matte_rank_launch(const void* ids, const void* counts, int W, int H, void* rankedIds, void* rankedCounts, void* stream);
 int kajo_matte_mask_launch(const void* ids, const void* counts, int W, int H, const void* selected, unsigned nObjects, float samples, void* mask,
@@ -302,6 +305,14 @@ struct KajoHip
     hipEvent_t gradeUploaded = nullptr; // the last upload has left gradeStaging
     bool gradePlanned = false;
     KajoGradeParams gradeLast{};
+    // the noise estimate (KAJO_FLAG_NOISE; noise.hip), at create: the baseline float4 [slotsPerOwner] and the moment records
+    // KajoNoiseMoments [slotsPerOwner] of the handle's own tile buffer; noiseRebase: the baseline is to be taken from the buffer at the next
+    // batch boundary, whose batch does not count (kajo_hip_set_pass_count). noiseOut, on the first kajo_hip_noise: four planes of W * H
+    // words (m, se, rel, n), then the histogram; noiseStaged, on the first kajo_hip_noise of an owner of part of the frame: the planes as
+    // the device wrote them, on the host, of which the owner's pixels are copied out
+    bool noise = false, noiseRebase = false;
+    DeviceBuffer noiseBase, noiseMoments, noiseOut;
+    std::vector<uint32_t> noiseStaged;
     int toneScaleState = 0; // the s of the most recent tone mapping: 0 none yet, 1 toneScale, 2 the scale word (auto exposure)
     float toneScale = 1.0f;
 };
@@ -891,6 +902,13 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
             }
         }
     }
+    if (p.flags & KAJO_FLAG_NOISE) {
+        h->noise = true;
+        CREATE_TRY(h->noiseBase.alloc(h->tileBytes));
+        CREATE_TRY(hipMemsetAsync(h->noiseBase.p, 0, h->tileBytes, h->stream));
+        CREATE_TRY(h->noiseMoments.alloc(2 * h->tileBytes));
+        CREATE_TRY(hipMemsetAsync(h->noiseMoments.p, 0, 2 * h->tileBytes, h->stream));
+    }
     CREATE_TRY(hipStreamSynchronize(h->stream));
 #undef CREATE_TRY
     *out = h;
@@ -977,8 +995,15 @@ int kajo_hip_render(kajo_hip_t h, int passes)
     const int home = (lds.coldInLds && (p.flags & KAJO_FLAG_NO_ONE_LIGHT)) ? 2 : lds.coldInLds;
     const int perLaunch = p.passesPerLaunch > 0 ? p.passesPerLaunch : 16;
     int left = passes;
+    // (the noise estimate: a baseline owed since kajo_hip_set_pass_count to a multiple of four is the buffer as it stands now)
+    if (h->noise && h->noiseRebase && h->passesDone % KAJO_NOISE_BATCH_PASSES == 0) {
+        HIP_TRY(hipMemcpyAsync(h->noiseBase.p, h->tiles.p, h->tileBytes, hipMemcpyDeviceToDevice, h->stream));
+        h->noiseRebase = false;
+    }
     while (left > 0) {
-        const int now = left < perLaunch ? left : perLaunch;
+        int now = left < perLaunch ? left : perLaunch;
+        if (h->noise) // no launch crosses an absolute multiple of the batch (the frame's bits do not depend on the cut)
+            now = std::min(now, KAJO_NOISE_BATCH_PASSES - h->passesDone % KAJO_NOISE_BATCH_PASSES);
         a.firstPass = h->passesDone + 1;
         a.nPasses = now;
         const KajoLaunchShape s = kajoLaunchShape(pixelBlocks, now, a.n, lds.coldInLds, p.flags & KAJO_FLAG_NO_SPLIT, a.mailboxOffset,
@@ -1067,6 +1092,16 @@ int kajo_hip_render(kajo_hip_t h, int passes)
             HIP_TRY((hipError_t)h->k->aov(&g, h->aovInstance, (unsigned)((blocks + 3) / 4), h->aovLds, h->stream));
             h->aovPasses += now;
         }
+        if (h->noise && (h->passesDone + now) % KAJO_NOISE_BATCH_PASSES == 0) {
+            // a batch boundary, behind the launch (and its fold) and outside the timing events: the batch into the moments -- or, where this
+            // handle did not render all of it, only the baseline
+            if (h->noiseRebase)
+                HIP_TRY(hipMemcpyAsync(h->noiseBase.p, h->tiles.p, h->tileBytes, hipMemcpyDeviceToDevice, h->stream));
+            else
+                HIP_TRY((hipError_t)kajo_noise_update_launch(h->tiles.p, h->noiseBase.p, h->noiseMoments.p,
+                                                             (uint32_t)((size_t)h->nTilesOwned * p.tileW * p.tileH), h->stream));
+            h->noiseRebase = false;
+        }
         if (a.waveTrips && s.split == 1 && s.chunks == 1) {
             h->tripsPending = true;
             a.waveTrips = nullptr; // later launches of this call keep the first measurement
@@ -1111,6 +1146,11 @@ int kajo_hip_reset(kajo_hip_t h)
         HIP_TRY(hipMemsetAsync(h->aovTiles.p, 0, aovTileBytes(h), h->stream));
     if (h->matteTiles)
         HIP_TRY(hipMemsetAsync(h->matteTiles.p, 0, matteTileBytes(h), h->stream));
+    if (h->noise) {
+        HIP_TRY(hipMemsetAsync(h->noiseBase.p, 0, h->tileBytes, h->stream));
+        HIP_TRY(hipMemsetAsync(h->noiseMoments.p, 0, 2 * h->tileBytes, h->stream));
+        h->noiseRebase = false;
+    }
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->aovComposed = h->matteComposed = false;
     h->aovPasses = 0;
@@ -1129,6 +1169,12 @@ int kajo_hip_set_pass_count(kajo_hip_t h, int passesDone)
     int rc = kajo_hip_wait(h);
     if (rc)
         return rc;
+    if (h->noise) {
+        // the moments start over; the baseline is the buffer at the first batch boundary from here on (kajo_hip_render)
+        HIP_TRY(hipMemsetAsync(h->noiseMoments.p, 0, 2 * h->tileBytes, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        h->noiseRebase = true;
+    }
     h->passesDone = passesDone;
     h->carryValid = false; // (a group in progress is not known apart from the buffer the caller declares: include/kajo_hip.h)
     h->frameValid = false;
@@ -2114,6 +2160,152 @@ int kajo_hip_present_metered_gathered_argb8_device(kajo_hip_t h, const void* gat
     if ((rc = meterAndPatch(h, img, meter, tone, result, &t))) // (the one wait: include/kajo_hip.h)
         return rc;
     return toneLaunch(h, img, t, dst);
+}
+
+} // extern "C"
+
+namespace
+{
+
+static_assert(sizeof(KajoNoiseParams) == 8 && sizeof(KajoNoiseMoments) == 32 && sizeof(KajoNoiseResult) == 48, "include/kajo_hip.h states the sizes");
+static_assert(KAJO_NOISE_BATCH_PASSES == KAJO_GROUP_PASSES, "a batch boundary is a group boundary: no group in progress, nothing in `carry`");
+static_assert(KAJO_NOISE_HIST_WORDS == KAJO_METER_BINS + 2, "the meter's bins, the unknown pixels, the pixels with bad > 0");
+
+bool quantileOk(float q)
+{
+    return std::isfinite(q) && q > 0.0f && q <= 1.0f;
+}
+
+// The refusals of KajoNoiseParams (KAJO_E_INVALID), before any device work and before the handle is looked at
+int checkNoise(const KajoNoiseParams* p)
+{
+    if (!p)
+        return fail(KAJO_E_INVALID, "null noise parameters");
+    if (!(std::isfinite(p->floor) && p->floor > 0.0f))
+        return fail(KAJO_E_INVALID, "noise floor must be finite and positive");
+    if (!quantileOk(p->quantile))
+        return fail(KAJO_E_INVALID, "noise quantile must be finite and in (0, 1]");
+    return KAJO_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void kajo_hip_default_noise_params(KajoNoiseParams* p)
+{
+    if (!p)
+        return;
+    p->floor = 1e-2f;
+    p->quantile = 0.95f;
+}
+
+int kajo_hip_noise_evaluate(const uint32_t hist[KAJO_NOISE_HIST_WORDS], float quantile, float* value)
+{
+    if (!quantileOk(quantile))
+        return fail(KAJO_E_INVALID, "noise quantile must be finite and in (0, 1]");
+    if (!hist || !value)
+        return fail(KAJO_E_INVALID, "null argument");
+    int64_t known = 0;
+    for (int b = 0; b < KAJO_METER_BINS; b++)
+        known += hist[b];
+    *value = -1.0f;
+    if (known == 0)
+        return KAJO_OK;
+    const int64_t rank = std::min(known, std::max((int64_t)1, (int64_t)std::ceil((double)quantile * (double)known)));
+    int64_t seen = 0;
+    int b = 0;
+    while (b < KAJO_METER_BINS - 1 && (seen += hist[b]) < rank)
+        b++;
+    *value = b == 0 ? 0x1p-17f : (float)meterCentre(b);
+    return KAJO_OK;
+}
+
+int kajo_hip_noise(kajo_hip_t h, const KajoNoiseParams* params, float* mean, float* stderror, float* relative, uint32_t* batches, uint32_t* hist,
+                   KajoNoiseResult* result)
+{
+    int rc = checkNoise(params);
+    if (rc)
+        return rc;
+    if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    if (!h->noise)
+        return fail(KAJO_E_STATE, "the handle was created without the noise flag");
+    if ((rc = bind(h)))
+        return rc;
+    uint32_t counts[KAJO_NOISE_HIST_WORDS] = {};
+    const size_t pixels = (size_t)h->W * h->H, plane = pixels * 4;
+    void* const dst[4] = {mean, stderror, relative, batches};
+    const bool part = h->map.tileCount > 1;
+    if (part && h->nTilesOwned > 0 && h->noiseStaged.size() < 4 * pixels)
+        h->noiseStaged.resize(4 * pixels);
+    if (h->nTilesOwned > 0) {
+        HIP_TRY(h->noiseOut.ensure(4 * plane + sizeof counts));
+        char* out = h->noiseOut.as<char>();
+        HIP_TRY(hipMemsetAsync(out + 4 * plane, 0, sizeof counts, h->stream));
+        hipError_t le = (hipError_t)kajo_noise_map_launch(h->noiseMoments.p, &h->map, h->params.tileIndex, (double)params->floor, out, out + plane,
+                                                          out + 2 * plane, out + 3 * plane, out + 4 * plane, h->stream);
+        if (le != hipSuccess)
+            return failHip(le, "noise map kernel launch");
+        for (int k = 0; k < 4; k++) {
+            if (!dst[k])
+                continue;
+            void* to = part ? (void*)(h->noiseStaged.data() + k * pixels) : dst[k];
+            HIP_TRY(hipMemcpyAsync(to, out + k * plane, plane, hipMemcpyDeviceToHost, h->stream));
+        }
+        HIP_TRY(hipMemcpyAsync(counts, out + 4 * plane, sizeof counts, hipMemcpyDeviceToHost, h->stream));
+    }
+    if ((rc = kajo_hip_wait(h)))
+        return rc;
+    if (part && h->nTilesOwned > 0 && (mean || stderror || relative || batches))
+        for (int y = 0; y < h->H; y++)
+            for (int x = 0; x < h->W; x++) {
+                int owner;
+                uint32_t slot;
+                kajoTileSlot(h->map, x, y, &owner, &slot);
+                if (owner != h->params.tileIndex)
+                    continue;
+                const size_t at = (size_t)y * h->W + x;
+                for (int k = 0; k < 4; k++)
+                    if (dst[k])
+                        static_cast<uint32_t*>(dst[k])[at] = h->noiseStaged[k * pixels + at];
+            }
+    if (hist)
+        std::memcpy(hist, counts, sizeof counts);
+    if (result) {
+        std::memset(result, 0, sizeof *result);
+        for (int b = 0; b < KAJO_METER_BINS; b++)
+            result->known += counts[b];
+        result->unknown = counts[KAJO_METER_BINS];
+        result->bad = counts[KAJO_METER_BINS + 1];
+        result->pixels = result->known + result->unknown;
+        return kajo_hip_noise_evaluate(counts, params->quantile, &result->quantileValue);
+    }
+    return KAJO_OK;
+}
+
+int kajo_hip_read_noise_moments(kajo_hip_t h, KajoNoiseMoments* records)
+{
+    if (!h || !records)
+        return fail(KAJO_E_INVALID, "null argument");
+    if (!h->noise)
+        return fail(KAJO_E_STATE, "the handle was created without the noise flag");
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    std::vector<KajoNoiseMoments> own((size_t)h->map.slotsPerOwner);
+    HIP_TRY(hipMemcpyAsync(own.data(), h->noiseMoments.p, own.size() * sizeof(KajoNoiseMoments), hipMemcpyDeviceToHost, h->stream));
+    if ((rc = kajo_hip_wait(h)))
+        return rc;
+    for (int y = 0; y < h->H; y++)
+        for (int x = 0; x < h->W; x++) {
+            int owner;
+            uint32_t slot;
+            kajoTileSlot(h->map, x, y, &owner, &slot);
+            if (owner == h->params.tileIndex)
+                records[(size_t)y * h->W + x] = own[slot];
+        }
+    return KAJO_OK;
 }
 
 } // extern "C"

@@ -91,6 +91,28 @@ struct Scheduler::Impl
 
     // Options::local changes the frame (include/kajo_hip.h: with compression 1 and detail 1 the output is the input)
     bool localActive() const { return opt.localOn && !(opt.local.compression == 1.0f && opt.local.detail == 1.0f); }
+    // Options::noise / noiseTarget: the handles keep the batch moments (KAJO_FLAG_NOISE)
+    bool noiseOn() const { return opt.noise || opt.noiseTarget > 0.0f; }
+    KajoNoiseParams noiseParams() const { return KajoNoiseParams{opt.noiseFloor, opt.noiseQuantile}; }
+    float noiseValue = -1; // Statistics::noise* of the last refresh
+    long long noiseKnown = 0, noiseUnknown = 0, noiseBad = 0;
+    // the owners' histograms added word by word, evaluated
+    void measureNoise()
+    {
+        const KajoNoiseParams p = noiseParams();
+        uint32_t sum[KAJO_NOISE_HIST_WORDS] = {}, own[KAJO_NOISE_HIST_WORDS];
+        for (kajo_hip_t h : handles) {
+            check(kajo_hip_noise(h, &p, nullptr, nullptr, nullptr, nullptr, own, nullptr), "kajo_hip_noise");
+            for (int i = 0; i < KAJO_NOISE_HIST_WORDS; i++)
+                sum[i] += own[i];
+        }
+        noiseKnown = 0;
+        for (int i = 0; i < KAJO_METER_BINS; i++)
+            noiseKnown += sum[i];
+        noiseUnknown = sum[KAJO_METER_BINS];
+        noiseBad = sum[KAJO_METER_BINS + 1];
+        check(kajo_hip_noise_evaluate(sum, p.quantile, &noiseValue), "kajo_hip_noise_evaluate");
+    }
     bool localRan = false; // lastLocalPivot()
     float localPivot = 0;
     void notePivot()
@@ -199,7 +221,8 @@ struct Scheduler::Impl
             p.flags = (numerics == Options::Strict ? KAJO_FLAG_STRICT : numerics == Options::Exact ? KAJO_FLAG_EXACT : 0u) | (opt.counters ? KAJO_FLAG_COUNTERS : 0u) |
                       (opt.aov ? KAJO_FLAG_AOV | (opt.aovSpecular ? KAJO_FLAG_AOV_SPECULAR : 0u) | (opt.matte ? KAJO_FLAG_AOV_MATTE : 0u) |
                                  (opt.aovTiled ? KAJO_FLAG_AOV_TILED : 0u)
-                               : 0u);
+                               : 0u) |
+                      (noiseOn() ? KAJO_FLAG_NOISE : 0u);
             p.device = opt.sameDevice ? 0 : g;
             p.tileIndex = g;
             p.tileCount = opt.gpus;
@@ -665,11 +688,23 @@ void Scheduler::readViewed(uint32_t* dst)
         d.notePivot();
 }
 
+void Scheduler::readNoise(float* mean, float* stderror, float* relative)
+{
+    Impl& d = *m_impl;
+    if (!d.noiseOn())
+        throw std::runtime_error("hip::Scheduler: readNoise needs Options::noise or Options::noiseTarget");
+    const KajoNoiseParams p = d.noiseParams();
+    for (kajo_hip_t h : d.handles)
+        check(kajo_hip_noise(h, &p, mean, stderror, relative, nullptr, nullptr, nullptr), "kajo_hip_noise");
+}
+
 void Scheduler::run()
 {
     Impl& d = *m_impl;
     const Options& o = d.opt;
-    const int budget = o.passes > 0 ? o.passes : (d.preview ? 0 : 16);
+    const bool stopRule = o.noiseTarget > 0.0f;
+    const int budget = stopRule && o.maxPasses > 0 ? o.maxPasses : o.passes > 0 ? o.passes : (d.preview ? 0 : 16);
+    int stoppedAt = 0;
     const std::thread::id self = std::this_thread::get_id();
     const auto t0 = std::chrono::steady_clock::now();
     int done = 0;
@@ -702,8 +737,11 @@ void Scheduler::run()
 
     // The SDL calls of the preview stay on this (the main) thread, as the reference requires
     // (cpu/Scheduler.cpp:64-81 marshals worker progress through a queue for the same reason).
-    while ((!d.preview || d.preview->processEvents()) && (budget == 0 || done < budget)) {
-        const int batch = autoBatch();
+    while ((!d.preview || d.preview->processEvents()) && (budget == 0 || done < budget) && !stoppedAt) {
+        int batch = autoBatch();
+        if (stopRule) // a refresh of the stop rule ends on a batch boundary of the estimate: whole batches, four passes at the least
+            batch = done % KAJO_NOISE_BATCH_PASSES ? KAJO_NOISE_BATCH_PASSES - done % KAJO_NOISE_BATCH_PASSES
+                                                   : std::max(batch / KAJO_NOISE_BATCH_PASSES, 1) * KAJO_NOISE_BATCH_PASSES;
         const int now = budget == 0 ? batch : (budget - done < batch ? budget - done : batch);
         const auto tb = std::chrono::steady_clock::now();
         for (kajo_hip_t h : d.handles)
@@ -713,6 +751,11 @@ void Scheduler::run()
         done += now;
         d.aovComposed = false;
         d.gatherAndResolve();
+        if (d.noiseOn()) {
+            d.measureNoise();
+            if (stopRule && d.noiseUnknown == 0 && d.noiseKnown > 0 && d.noiseValue <= o.noiseTarget)
+                stoppedAt = done;
+        }
         const double batchWall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count();
         batchMs.push_back(batchWall);
         batchPasses.push_back(now);
@@ -732,6 +775,13 @@ void Scheduler::run()
     d.stats.batchMs = batchMs;
     d.stats.batchPasses = batchPasses;
     d.stats.toneScale = d.toneScale;
+    if (d.noiseOn() && done > 0) {
+        d.stats.noiseQuantileValue = d.noiseValue;
+        d.stats.noiseKnownPx = d.noiseKnown;
+        d.stats.noiseUnknownPx = d.noiseUnknown;
+        d.stats.noiseBadPx = d.noiseBad;
+        d.stats.noiseStoppedAtPass = stoppedAt;
+    }
     if (o.despeckleOn && done > 0) {
         int64_t c[2] = {0, 0};
         check(kajo_hip_despeckle_counts(d.handles[0], c), "kajo_hip_despeckle_counts");

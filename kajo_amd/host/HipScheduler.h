@@ -116,6 +116,16 @@ struct Options
     bool gradeOn = false;
     KajoGradeParams grade = {};
     struct { int x = -1, y = -1; } gradeNeutralAt;
+    // The noise estimate (include/kajo_hip.h KAJO_FLAG_NOISE, kajo_hip_noise): every handle keeps the batch moments of its own tiles, and
+    // at each refresh run() adds the owners' histograms of the relative error. noiseTarget > 0 is the stop rule: run() ends when the
+    // noiseQuantile-th relative error is <= noiseTarget and every pixel is known (two batches of four passes), or after maxPasses (0 = the
+    // budget `passes` gives); its refreshes then end on multiples of four passes. noise = true keeps the moments without the rule
+    // (readNoise, Statistics::noise*). All off by default: every run then makes exactly the calls it made without these fields.
+    bool noise = false;
+    float noiseTarget = 0.0f;
+    float noiseQuantile = 0.95f;
+    float noiseFloor = 1e-2f;
+    int maxPasses = 0;
 };
 
 struct Statistics
@@ -129,6 +139,12 @@ struct Statistics
     std::vector<int> batchPasses;
     float toneScale = 1;   // the scale s the last image was tone-mapped with (Options::tone; 1 with the identity)
     long long clamped = 0, repaired = 0; // pixels of the last image the despeckle clamped and repaired (Options::despeckleOn)
+    // the noise estimate at the last refresh (Options::noise or noiseTarget; all owners' histograms added): the noiseQuantile-th relative
+    // error (-1: no pixel known), the pixels known, those with a batch that was not finite, and the pass the stop rule ended run() at (0:
+    // it did not)
+    float noiseQuantileValue = -1;
+    long long noiseKnownPx = 0, noiseUnknownPx = 0, noiseBadPx = 0;
+    int noiseStoppedAtPass = 0;
 };
 
 class Scheduler : public ::Scheduler
@@ -186,6 +202,9 @@ public:
     // the image of readPresented() with Options' own stages, through Options::view: dst = view.outW * view.outH words. Any number of GPUs
     // (the frame is composed on the first handle, as readPresented does). Throws where Options::viewOn is not set.
     void readViewed(uint32_t* dst);
+    // the noise map after run() (Options::noise or noiseTarget; include/kajo_hip.h kajo_hip_noise on every owner, into the same planes):
+    // W*H floats each -- mean luminance per pass, its standard error, the relative error -- any may be null. Any number of GPUs, no gather
+    void readNoise(float* mean, float* stderror, float* relative);
 
 private:
     struct Impl;

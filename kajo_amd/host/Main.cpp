@@ -125,6 +125,7 @@ int main(int argc, char** argv)
     bool despeckle = false;
     // meter options (include/kajo_hip.h KajoMeterParams): the raw text, checked after the loop
     std::string meterExposure, meterWhite;
+    std::string untilNoise, noiseQuantile, noiseFloor, maxPasses, noiseMapOut;
     // local tone mapping options (include/kajo_hip.h KajoLocalParams): the raw text, checked after the loop
     std::string localContrast, localDetail, localRange, localIterations, localPivot;
     // depth of field options (include/kajo_hip.h KajoLensParams): the raw text, checked after the loop
@@ -248,7 +249,16 @@ int main(int argc, char** argv)
                         "    --white-balance-at X,Y  the grade: the gains that make that pixel of the frame in front of the grade grey\n"
                         "    --grade-region IDS:key=v[:key=v...]  the grade: regrade the objects IDS (a comma-separated list of at most 16 ids, as\n"
                         "                    --matte-objects) by their coverage mattes; keys slope, offset, power (one number or R,G,B), saturation, amount\n"
-                        "                    (0..1, 1). Up to four times, applied in order. One GPU, or any --gpus with --aov-tiled\n",
+                        "                    (0..1, 1). Up to four times, applied in order. One GPU, or any --gpus with --aov-tiled\n"
+                        "    --until-noise E  render until converged (include/kajo_hip.h kajo_hip_noise; any --gpus): stop once the relative error of the\n"
+                        "                    mean luminance -- its standard error from batches of four passes, over the mean + the floor -- is <= E at\n"
+                        "                    the quantile Q of the pixels and every pixel has two batches; E >= 0 (0: never). --passes is then not the\n"
+                        "                    end: --max-passes is (--json: noise_quantile_value, noise_known_px, noise_bad_px, noise_stopped_at_pass)\n"
+                        "    --noise-quantile Q  --until-noise, --noise-map: the quantile, 0 < Q <= 1 (0.95)\n"
+                        "    --noise-floor F  --until-noise, --noise-map: the floor added to the mean, > 0 (0.01), so that black pixels do not dominate\n"
+                        "    --max-passes N  --until-noise: stop after N passes at the latest, N >= 1 (1024)\n"
+                        "    --noise-map FILE  also write the noise map as a 3-channel PFM: mean luminance per pass, its standard error, the relative\n"
+                        "                    error (-1 where a pixel has fewer than two batches); any --gpus\n",
                         args[0].c_str());
             return 1;
         } else if (a == "-w" && more) width = std::atoi(args[++i].c_str());
@@ -285,6 +295,11 @@ int main(int argc, char** argv)
         else if (a == "--despeckle-factor" && more) despeckleFactor = args[++i];
         else if (a == "--despeckle-rank" && more) despeckleRank = args[++i];
         else if (a == "--despeckle-floor" && more) despeckleFloor = args[++i];
+        else if (a == "--until-noise" && more) untilNoise = args[++i];
+        else if (a == "--noise-quantile" && more) noiseQuantile = args[++i];
+        else if (a == "--noise-floor" && more) noiseFloor = args[++i];
+        else if (a == "--max-passes" && more) maxPasses = args[++i];
+        else if (a == "--noise-map" && more) noiseMapOut = args[++i];
         else if (a == "--meter-exposure" && more) meterExposure = args[++i];
         else if (a == "--meter-white" && more) meterWhite = args[++i];
         else if (a == "--local-contrast" && more) localContrast = args[++i];
@@ -409,6 +424,47 @@ int main(int argc, char** argv)
             std::cerr << "kajo_render: --despeckle-floor must be a finite number >= 0" << std::endl;
             return 1;
         }
+    }
+    const bool noiseGiven = !untilNoise.empty() || !noiseMapOut.empty();
+    if (!noiseGiven && (!noiseQuantile.empty() || !noiseFloor.empty() || !maxPasses.empty())) {
+        std::cerr << "kajo_render: --noise-quantile, --noise-floor and --max-passes shape what --until-noise or --noise-map turn on: give them with one of the two" << std::endl;
+        return 1;
+    }
+    if (noiseGiven) {
+        // (before any device is opened: the refusals of kajo_hip_noise, with the option's name)
+        if (threeArg) {
+            std::cerr << "kajo_render: the noise options need the backend's options (without --three-arg)" << std::endl;
+            return 1;
+        }
+        opt.noise = true;
+        if (!untilNoise.empty()) {
+            if (!parseFloat(untilNoise, &opt.noiseTarget) || opt.noiseTarget < 0.0f) {
+                std::cerr << "kajo_render: --until-noise must be a finite number >= 0" << std::endl;
+                return 1;
+            }
+            // E = 0 is hip::Options' "no rule" (noiseTarget 0), and means "never": no estimate is <= 0, so a rule with that target would end
+            // no run. The run then takes --max-passes like any pass budget (opt.passes below) and reports the estimate it ends with.
+            opt.maxPasses = 1024;
+        }
+        if (!noiseQuantile.empty() && (!parseFloat(noiseQuantile, &opt.noiseQuantile) || opt.noiseQuantile <= 0.0f || opt.noiseQuantile > 1.0f)) {
+            std::cerr << "kajo_render: --noise-quantile must be a quantile in (0, 1]" << std::endl;
+            return 1;
+        }
+        if (!noiseFloor.empty() && (!parseFloat(noiseFloor, &opt.noiseFloor) || !(opt.noiseFloor > 0.0f))) {
+            std::cerr << "kajo_render: --noise-floor must be a finite number > 0" << std::endl;
+            return 1;
+        }
+        if (!maxPasses.empty()) {
+            char* end = nullptr;
+            const long n = std::strtol(maxPasses.c_str(), &end, 10);
+            if (untilNoise.empty() || end == maxPasses.c_str() || *end || n < 1 || n > 0x7ffffffe) {
+                std::cerr << "kajo_render: --max-passes must be a whole number >= 1, with --until-noise" << std::endl;
+                return 1;
+            }
+            opt.maxPasses = (int)n;
+        }
+        if (!untilNoise.empty())
+            opt.passes = opt.maxPasses; // (the preview's pass budget and the scheduler's: the rule ends the run before it, or it does)
     }
     const bool meterGiven = !meterExposure.empty() || !meterWhite.empty();
     if (meterGiven) {
@@ -829,6 +885,18 @@ int main(int argc, char** argv)
             if (!writePfm(hdrOut, width, height, 3, rgb.data()))
                 return 3;
         }
+        if (!noiseMapOut.empty()) {
+            const size_t count = (size_t)width * height;
+            std::vector<float> m(count), se(count), rel(count), rgb(count * 3);
+            hipScheduler->readNoise(m.data(), se.data(), rel.data());
+            for (size_t i = 0; i < count; i++) {
+                rgb[3 * i] = m[i];
+                rgb[3 * i + 1] = se[i];
+                rgb[3 * i + 2] = rel[i];
+            }
+            if (!writePfm(noiseMapOut, width, height, 3, rgb.data()))
+                return 3;
+        }
         if (!aovPrefix.empty()) {
             // the means: albedo and normal over every sample, depth over the samples that hit (0 where none did)
             const size_t count = (size_t)width * height;
@@ -955,6 +1023,9 @@ int main(int argc, char** argv)
                         (int)opt.view.outW, (int)opt.view.outH, viewFilterNames[opt.view.filter],
                         (viewRect.empty() ? (double)width : (double)opt.view.x1 - opt.view.x0) / opt.view.outW,
                         (viewRect.empty() ? (double)height : (double)opt.view.y1 - opt.view.y0) / opt.view.outH);
+        if (noiseGiven)
+            std::printf(", \"noise_quantile_value\": %.9g, \"noise_known_px\": %lld, \"noise_bad_px\": %lld, \"noise_stopped_at_pass\": %d",
+                        (double)s.noiseQuantileValue, s.noiseKnownPx, s.noiseBadPx, s.noiseStoppedAtPass);
         if (aovTiled)
             std::printf(", \"aov_tiled\": true");
         if (matteGiven)

@@ -14,11 +14,25 @@ from . import capi
 from .scene import Scene
 
 
+NOISE_MOMENTS = np.dtype([("s1", "<f8"), ("s2", "<f8"), ("n", "<u8"), ("bad", "<u8")])  # include/kajo_hip.h KajoNoiseMoments
+
+
+def noise_evaluate(hist, quantile: float = 0.95) -> float:
+    """The `quantile` of the relative error over the known pixels of a noise histogram -- one owner's, or the owners' added word by word
+    (include/kajo_hip.h kajo_hip_noise_evaluate; pure host). -1 where no pixel is known."""
+    hist = np.ascontiguousarray(hist, np.uint32)
+    if hist.shape != (capi.KAJO_NOISE_HIST_WORDS,):
+        raise ValueError("a noise histogram has %d words" % capi.KAJO_NOISE_HIST_WORDS)
+    value = C.c_float()
+    capi.check(capi.lib().kajo_hip_noise_evaluate(hist.ctypes.data_as(C.c_void_p), float(quantile), C.byref(value)))
+    return value.value
+
+
 class HipRenderer:
     def __init__(self, scene: Scene, width: int, height: int, spp: int = 32, depth_limit: int = 8,
                  seed: int = 0o715517, strict: bool = False, exact: bool = False, counters: bool = False, device: int = 0,
                  tile=(64, 16), tile_index: int = 0, tile_count: int = 1, passes_per_launch: int = 0, flags: int = 0,
-                 aov: bool = False, aov_specular: bool = False, matte: bool = False, aov_tiled: bool = False):
+                 aov: bool = False, aov_specular: bool = False, matte: bool = False, aov_tiled: bool = False, noise: bool = False):
         L = capi.lib()
         self._L = L
         self.scene = scene
@@ -34,6 +48,7 @@ class HipRenderer:
         p.flags |= capi.KAJO_FLAG_AOV_SPECULAR if aov_specular else 0  # (without aov the library refuses it)
         p.flags |= capi.KAJO_FLAG_AOV_MATTE if matte else 0  # (likewise)
         p.flags |= capi.KAJO_FLAG_AOV_TILED if aov_tiled else 0  # (likewise; with it aov takes any tile_index / tile_count)
+        p.flags |= capi.KAJO_FLAG_NOISE if noise else 0  # batch moments beside the render: noise(), noise_moments()
         p.device = device
         p.tileW, p.tileH = tile
         p.tileIndex, p.tileCount = tile_index, tile_count
@@ -102,6 +117,36 @@ class HipRenderer:
         c = capi.KajoCounters()
         capi.check(self._L.kajo_hip_counters(self._h, C.byref(c)))
         return {k: getattr(c, k) for k, _ in capi.KajoCounters._fields_}
+
+    def noise(self, floor: float = None, quantile: float = None, out: dict = None) -> dict:
+        """The noise map of the handle's own pixels (include/kajo_hip.h "The noise estimate", kajo_hip_noise; the handle needs noise=True):
+        mean, stderr, relative (H, W) float32 -- the mean luminance per pass, its standard error and stderr / (max(mean, 0) + floor), -1
+        where fewer than two batches of four passes have been counted -- batches (H, W) uint32, hist (516,) uint32 and the result's
+        fields pixels, known, unknown, bad, quantile_value. Arguments left None take kajo_hip_default_noise_params' values (floor 1e-2,
+        quantile 0.95). out: the dict of an earlier call (another owner's): its planes are written into, this owner's pixels only, so
+        that the owners of a frame fill one set of planes; its histogram is not added to."""
+        p = capi.KajoNoiseParams()
+        self._L.kajo_hip_default_noise_params(C.byref(p))
+        if floor is not None:
+            p.floor = float(floor)
+        if quantile is not None:
+            p.quantile = float(quantile)
+        shape = (self.height, self.width)
+        planes = {k: (out[k] if out is not None else np.zeros(shape, t))
+                  for k, t in (("mean", np.float32), ("stderr", np.float32), ("relative", np.float32), ("batches", np.uint32))}
+        hist = np.zeros(capi.KAJO_NOISE_HIST_WORDS, np.uint32)
+        r = capi.KajoNoiseResult()
+        capi.check(self._L.kajo_hip_noise(self._h, C.byref(p), *(planes[k].ctypes.data_as(C.c_void_p) for k in ("mean", "stderr", "relative", "batches")),
+                                          hist.ctypes.data_as(C.c_void_p), C.byref(r)))
+        return dict(planes, hist=hist, pixels=r.pixels, known=r.known, unknown=r.unknown, bad=r.bad, quantile_value=r.quantileValue)
+
+    def noise_moments(self, out: np.ndarray = None) -> np.ndarray:
+        """The raw batch moments (kajo_hip_read_noise_moments): (H, W) records with the fields s1, s2 (float64), n, bad (uint64), of which
+        this owner's pixels are written (into `out` where given)."""
+        if out is None:
+            out = np.zeros((self.height, self.width), NOISE_MOMENTS)
+        capi.check(self._L.kajo_hip_read_noise_moments(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def aov(self) -> dict:
         """First-hit AOVs (include/kajo_hip.h kajo_hip_read_aov; the handle needs aov=True): raw=(A, B), both (H, W, 4) float32 sums --
