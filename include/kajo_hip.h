@@ -151,6 +151,12 @@ extern "C" {
                                    rises -- and enqueues the update kernel of kajo_amd/csrc/noise.hip behind each launch that ends on one,
                                    outside the timing events. No render, AOV or display kernel is changed for it. Handles without the flag
                                    allocate, launch and return exactly what they did before. */
+#define KAJO_FLAG_ADAPTIVE 32768u /* with KAJO_FLAG_NOISE only (alone: KAJO_E_INVALID at create, before a device is looked for): adaptive
+                                   sampling ("Adaptive sampling" below; kajo_hip_set_adaptive): units of the frame whose noise estimate has
+                                   met a target are retired, and later launches render the others only. create() allocates a state word per
+                                   unit; until kajo_hip_set_adaptive is called nothing retires and the handle does what a KAJO_FLAG_NOISE
+                                   handle does. No render, AOV or display kernel is changed for it; handles without the flag allocate,
+                                   launch and return exactly what they did before. */
 
 typedef struct KajoParams {
     int32_t samplesPerPass; /* S: nominal samples per pixel per pass (reference: 32, Renderer.cpp:21);
@@ -167,7 +173,8 @@ typedef struct KajoParams {
 
 typedef struct KajoCounters {
     uint64_t passes;         /* passes rendered so far */
-    uint64_t paths;          /* camera paths traced = pixels * n^2 * passes */
+    uint64_t paths;          /* camera paths = pixels * n^2 * passes: the NOMINAL count, also on a KAJO_FLAG_ADAPTIVE handle, whose retired
+                                units trace none (the paths actually traced: KajoAdaptState.paths) */
     uint64_t traversals;     /* closest-hit scene walks (device counter; 0 without KAJO_FLAG_COUNTERS) */
     uint64_t vertices;       /* shaded path vertices (device counter) */
     uint64_t primitiveTests; /* traversals * (nPlanes + nSpheres): what walking every object costs; with
@@ -1026,6 +1033,81 @@ int kajo_hip_noise(kajo_hip_t h, const KajoNoiseParams* params, float* mean, flo
 /* For tests: the raw records. records: HOST pointer to a whole-frame row-major array of width*height KajoNoiseMoments, of which only the
    pixels of this owner's tiles are written. KAJO_E_INVALID on a NULL argument, KAJO_E_STATE without KAJO_FLAG_NOISE. Waits. */
 int kajo_hip_read_noise_moments(kajo_hip_t h, KajoNoiseMoments* records);
+
+/* Adaptive sampling (KAJO_FLAG_ADAPTIVE with KAJO_FLAG_NOISE): the passes go where the noise is. Kernels of their own
+   (kajo_amd/csrc/adapt_kernels.cpp, the rule in adapt_math.h) on the handle's stream, binary64 / float32 IEEE arithmetic without
+   contraction in every numerics build; the render kernels are launched over fewer workgroups and are not changed.
+   UNITS. A pixel block is 64 consecutive slots of the owner's tile buffer: one 8x8 block, one wave. A unit is the handle's launch block,
+   64 * wavesPerBlock consecutive slots (KajoAdaptState.unitSlots: 64, 128 or 256), gridBlocks of them. A unit is ACTIVE or RETIRED;
+   retirement is permanent until kajo_hip_reset.
+   THE DECISION is taken at the absolute pass numbers P with P % (4 * checkEvery) == 0 and P >= minPasses, behind the noise update of that
+   boundary: a function of (scene, parameters, P), not of how the passes are cut into kajo_hip_render calls or launches. Per slot
+     rel   = the noise estimate's evaluation of the slot's record in binary64 with THIS floor, rounded to float32 (what kajo_hip_noise's
+             `relative` plane holds for the same floor)
+     loud  = n < 2, or rel > target; the record's `bad` is ignored, so that a frame's NaN pixels do not hold a block forever. A slot
+             outside the image (or outside the owner's tiles) is never loud
+     a pixel block is QUIET when at most `allowance` of its pixels are loud; a unit retires when all its pixel blocks are quiet
+   The decision reads a unit's own records only: it does not depend on tileCount or on any other unit.
+   RENDERING. Launches after a decision cover the active units only: the grid is their number, the order the handle's cost order (image
+   order under KAJO_FLAG_NO_REORDER or before the first measurement) with the retired units taken out; launches of the SPLIT kernels
+   list the active units' pixel blocks. The launch shape (SPLIT or not, chunks) is chosen from the whole frame's block count, so a handle's
+   kernel kind does not change as units retire. With no unit active kajo_hip_render launches no render kernel and still counts the passes
+   (KajoCounters.launches stands still). AOV launches (KAJO_FLAG_AOV) stay whole-frame at every pass: the AOV buffers are those of a
+   plain handle bit for bit, and their cost does not shrink with the active set.
+   WHAT EVERY READER SEES. Behind every launch of an adaptive handle that has retired a unit, not only at boundaries, a retired slot of
+   the tile buffer is rewritten as baseline * f per channel (all four), f = (float)((double)P / (double)p), P the handle's pass count
+   after the launch, p = 4 n the slot's own pass count (n counts the finite batches only: a slot with bad > 0 holds more passes than 4 n,
+   is scaled by more than its due and reports 4 n in kajo_hip_adapt_passes -- its sum is as a rule not finite anyway); one float32
+   multiply, not contracted. (A retired slot with n = 0 -- possible only
+   with allowance > 0 -- is left as it is.) An active slot is not touched, and at a batch boundary the noise update runs for active slots
+   only, in the noise estimate's arithmetic to the bit; retired slots keep their records and their baseline. The tile buffer with pass
+   count P is then a uniform-equivalent sum: kajo_hip_resolve_*, kajo_hip_read_radiance, the gathered resolve, the whole present chain,
+   kajo_hip_noise and a multi-GPU gather work unchanged and know nothing of the flag.
+   BIAS, the known property of every such scheme: stopping on an estimate made from the samples themselves keeps the pixels whose early
+   samples happened to agree; a retired pixel is biased slightly toward its early mean. minPasses and allowance bound it.
+   An adaptive handle synchronises its stream once per decision (the state words come to the host, the order goes back).
+   OTHER CALLS. kajo_hip_reset makes every unit active again. kajo_hip_set_pass_count with a nonzero argument is refused (KAJO_E_STATE):
+   a restored buffer says nothing about per-block pass counts -- checkpoints of adaptive sessions are out of scope. */
+typedef struct KajoAdaptParams {
+    float target;           /* > 0: a pixel with rel <= target is not loud */
+    float floor;            /* > 0, finite (default 1e-2): the floor of rel, as KajoNoiseParams.floor */
+    int32_t minPasses;      /* >= 0 (default 16): no decision before it; rounded up to a multiple of checkEvery * 4 */
+    int32_t checkEvery;     /* 1 .. 65536 (default 4): batches between decisions */
+    int32_t allowance;      /* 0 .. 63 (default 0): loud pixels a quiet pixel block may have */
+    int32_t reserved[3];    /* 0 */
+} KajoAdaptParams;          /* 32 bytes */
+typedef struct KajoAdaptState {
+    int64_t units;          /* the handle's units */
+    int64_t activeUnits;
+    int64_t pixels;         /* the owner's pixels */
+    int64_t activePixels;   /* ... of active units */
+    int64_t paths;          /* camera paths actually traced since the last reset: active pixels * n^2, summed over the passes */
+    int32_t lastDecisionPass; /* the pass of the last decision; 0 = none yet */
+    int32_t unitSlots;      /* slots of a unit: 64 * wavesPerBlock */
+} KajoAdaptState;           /* 48 bytes */
+/* target 0 (to be set by the caller) and the defaults above. NULL is accepted. */
+void kajo_hip_default_adapt_params(KajoAdaptParams* p);
+/* Accepted only while the handle's pass count is 0 (after create or kajo_hip_reset), otherwise KAJO_E_STATE; until it is called an
+   adaptive handle retires nothing. KAJO_E_INVALID, before the handle is looked at: NULL params, a target that is not above 0 (or NaN), a
+   floor that is not finite or not above 0, minPasses < 0, checkEvery outside 1 .. 65536, allowance outside 0 .. 63, a nonzero reserved
+   word. Then KAJO_E_INVALID for a NULL handle and KAJO_E_STATE for a handle created without KAJO_FLAG_ADAPTIVE. */
+int kajo_hip_set_adaptive(kajo_hip_t h, const KajoAdaptParams* params);
+/* Waits. KAJO_E_INVALID on a NULL argument, KAJO_E_STATE without KAJO_FLAG_ADAPTIVE. */
+int kajo_hip_adapt_state(kajo_hip_t h, KajoAdaptState* state);
+/* The per-pixel pass count: the handle's pass count for a pixel of an active unit, 4 n for one of a retired unit. plane: HOST pointer to
+   a WHOLE-FRAME row-major plane of width*height words, of which only the pixels of this owner's tiles are written, as kajo_hip_noise
+   does. Waits. KAJO_E_INVALID on a NULL argument, KAJO_E_STATE without KAJO_FLAG_ADAPTIVE. */
+int kajo_hip_adapt_passes(kajo_hip_t h, uint32_t* plane);
+/* Pure host, no device and no handle: the kernel's rule (adapt_math.h, the same lines) over `count` records. loud[i] = 1 where record i
+   is loud (as a slot inside the image), else 0; *nLoud their number; either may be NULL. KAJO_E_INVALID: NULL records with count > 0,
+   count < 0, or the parameters' refusals above. */
+int kajo_hip_adapt_evaluate(const KajoNoiseMoments* records, int64_t count, const KajoAdaptParams* params, uint8_t* loud, int64_t* nLoud);
+/* Pure host: the launch order of an adaptive handle (adapt_math.h kajoAdaptOrder). order[nUnits]: the handle's order, the most expensive
+   unit first (NULL: image order); state[nUnits]: 0 = active, otherwise retired. out receives the active units in that order -- with
+   split != 0 their pixel blocks, unit * wavesPerBlock + k -- and may be NULL to ask for the number of words, which is returned; negative
+   = error (NULL state with nUnits > 0, wavesPerBlock outside 1 .. 4, an order word >= nUnits, a capacity too small). */
+int64_t kajo_hip_adapt_order(const uint32_t* order, uint32_t nUnits, const uint32_t* state, uint32_t wavesPerBlock, int32_t split, uint32_t* out,
+                             size_t capacity);
 
 /* Use an existing HIP stream (hipStream_t passed as void*) instead of the handle's own. */
 int kajo_hip_set_stream(kajo_hip_t h, void* stream);

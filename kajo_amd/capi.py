@@ -38,6 +38,7 @@ KAJO_FLAG_AOV_SPECULAR = 2048  # with KAJO_FLAG_AOV: the buffers are taken at th
 KAJO_FLAG_AOV_MATTE = 4096  # with KAJO_FLAG_AOV: per-pixel (object id, sample count) tables over the AOVs' samples (kajo_hip_read_matte)
 KAJO_FLAG_AOV_TILED = 8192  # with KAJO_FLAG_AOV: the sums of the handle's own tiles, any tileIndex / tileCount (kajo_hip_compose_aov)
 KAJO_FLAG_NOISE = 16384  # the per-pixel noise estimate: batch moments beside the render, in kernels of their own (kajo_hip_noise)
+KAJO_FLAG_ADAPTIVE = 32768  # with KAJO_FLAG_NOISE: units whose estimate has met a target retire, launches cover the others (kajo_hip_set_adaptive)
 KAJO_NOISE_BATCH_PASSES = 4  # a batch of the noise estimate: passes 4b-3 .. 4b by absolute number
 KAJO_NOISE_HIST_WORDS = 516  # the meter's 514 bins over the relative error, the unknown pixels, the pixels with a bad batch
 KAJO_MATTE_SLOTS = 8
@@ -76,6 +77,8 @@ EXPORTS = [
     "kajo_hip_default_grade_params", "kajo_hip_grade_pixels", "kajo_hip_grade_white_balance", "kajo_hip_grade_neutral", "kajo_hip_grade",
     "kajo_hip_present_grade_argb8", "kajo_hip_present_grade_gathered_argb8_device",
     "kajo_hip_default_noise_params", "kajo_hip_noise_evaluate", "kajo_hip_noise", "kajo_hip_read_noise_moments",
+    "kajo_hip_default_adapt_params", "kajo_hip_set_adaptive", "kajo_hip_adapt_state", "kajo_hip_adapt_passes", "kajo_hip_adapt_evaluate",
+    "kajo_hip_adapt_order",
 ]
 
 
@@ -123,6 +126,16 @@ class KajoNoiseMoments(C.Structure):
 class KajoNoiseResult(C.Structure):
     _fields_ = [("pixels", C.c_int64), ("known", C.c_int64), ("unknown", C.c_int64), ("bad", C.c_int64), ("quantileValue", C.c_float),
                 ("reserved", C.c_int32 * 3)]
+
+
+class KajoAdaptParams(C.Structure):
+    _fields_ = [("target", C.c_float), ("floor", C.c_float), ("minPasses", C.c_int32), ("checkEvery", C.c_int32), ("allowance", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class KajoAdaptState(C.Structure):
+    _fields_ = [("units", C.c_int64), ("activeUnits", C.c_int64), ("pixels", C.c_int64), ("activePixels", C.c_int64), ("paths", C.c_int64),
+                ("lastDecisionPass", C.c_int32), ("unitSlots", C.c_int32)]
 
 
 class KajoLocalParams(C.Structure):
@@ -339,6 +352,15 @@ def lib():
             L.kajo_hip_noise.argtypes = [C.c_void_p, C.POINTER(KajoNoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(KajoNoiseResult)]
             L.kajo_hip_read_noise_moments.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "kajo_hip_set_adaptive"):  # (nor adaptive sampling)
+            L.kajo_hip_default_adapt_params.argtypes = [C.POINTER(KajoAdaptParams)]
+            L.kajo_hip_default_adapt_params.restype = None
+            L.kajo_hip_set_adaptive.argtypes = [C.c_void_p, C.POINTER(KajoAdaptParams)]
+            L.kajo_hip_adapt_state.argtypes = [C.c_void_p, C.POINTER(KajoAdaptState)]
+            L.kajo_hip_adapt_passes.argtypes = [C.c_void_p, C.c_void_p]
+            L.kajo_hip_adapt_evaluate.argtypes = [C.c_void_p, C.c_int64, C.POINTER(KajoAdaptParams), C.c_void_p, C.POINTER(C.c_int64)]
+            L.kajo_hip_adapt_order.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_size_t]
+            L.kajo_hip_adapt_order.restype = C.c_int64
         L.kajo_hip_kat_trace.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
         L.kajo_hip_kat_shade.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.kajo_hip_kat_strictmath.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

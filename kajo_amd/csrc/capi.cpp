@@ -25,6 +25,7 @@
 #include "launch_plan.h"
 #include "view_weights.h"
 #include "grade_math.h"
+#include "adapt_math.h"
 
 // launchers defined next to their kernels (kernel_fast.hip, kernel_strict.hip, kernel_exact.hip, aux_kernels.hip)
 extern "C" {
@@ -82,6 +83,12 @@ int kajo_grade_launch(const void* src, const TileMap* map, int fromTiles, float 
 int kajo_noise_update_launch(const void* tiles, void* baseline, void* records, uint32_t slots, void* stream);
 int kajo_noise_map_launch(const void* records, const TileMap* map, int tileIndex, double floorL, void* mean, void* stdError, void* relative,
                           void* batches, void* hist, void* stream);
+int kajo_adapt_step_launch(void* tiles, void* baseline, void* records, const void* state, uint32_t slots, uint32_t unitShift, int boundary, int P,
+                           void* stream);
+int kajo_adapt_select_launch(const void* records, void* state, const AdaptGeom* geom, const AdaptRule* rule, uint32_t units, uint32_t unitThreads,
+                             void* stream);
+int kajo_adapt_passes_launch(const void* records, const void* state, const TileMap* map, int tileIndex, uint32_t unitShift, uint32_t P, void* plane,
+                             void* stream);
 int kajo_compose_aov_launch(const void* gatheredAov, const void* gatheredMatte, const TileMap* map, void* aov, void* matte, void* stream);
 int kajo_matte_rank_launch(const void* ids, const void* counts, int W, int H, void* rankedIds, void* rankedCounts, void* stream);
 int kajo_matte_mask_launch(const void* ids, const void* counts, int W, int H, const void* selected, unsigned nObjects, float samples, void* mask,
@@ -313,6 +320,19 @@ struct KajoHip
     bool noise = false, noiseRebase = false;
     DeviceBuffer noiseBase, noiseMoments, noiseOut;
     std::vector<uint32_t> noiseStaged;
+    // adaptive sampling (KAJO_FLAG_ADAPTIVE; adapt_kernels.cpp), at create: a state word per unit (launch block) on the device and, pinned, on
+    // the host; the in-image pixels of every unit. adaptSet: kajo_hip_set_adaptive has given the rule. Once a unit has retired
+    // (adaptRetired > 0) the launches take their order from adaptUnits (the handle's order without the retired units) or, the SPLIT
+    // kernels, adaptBlocks (their pixel blocks); adaptOut, on the first kajo_hip_adapt_passes: the plane
+    bool adaptive = false, adaptSet = false;
+    KajoAdaptParams adaptParams{};
+    AdaptGeom adaptGeom{};
+    DeviceBuffer adaptStateDev, adaptUnits, adaptBlocks, adaptOut;
+    uint32_t* adaptStateHost = nullptr; // [gridBlocks], pinned
+    std::vector<uint32_t> adaptUnitPixels, adaptStaged;
+    unsigned adaptShift = 6, adaptRetired = 0;
+    long long adaptPixels = 0, adaptActivePixels = 0, adaptPaths = 0;
+    int adaptLastDecision = 0;
     int toneScaleState = 0; // the s of the most recent tone mapping: 0 none yet, 1 toneScale, 2 the scale word (auto exposure)
     float toneScale = 1.0f;
 };
@@ -384,6 +404,8 @@ void destroy(KajoHip* h)
         (void)hipEventDestroy(h->gradeUploaded);
     if (h->gradeStaging)
         (void)hipHostFree(h->gradeStaging);
+    if (h->adaptStateHost)
+        (void)hipHostFree(h->adaptStateHost);
     if (h->ownStream && h->stream)
         (void)hipStreamDestroy(h->stream);
     delete h;
@@ -459,6 +481,63 @@ int updateBlockOrder(KajoHip* h)
     h->orderValid = true;
     h->hostOrder.swap(order);
     return partTheTail(h);
+}
+
+// adaptive sampling: every unit active again (the device's state words are zeroed by the caller)
+void adaptReactivate(KajoHip* h)
+{
+    if (!h->adaptive)
+        return;
+    std::memset(h->adaptStateHost, 0, (size_t)h->gridBlocks * sizeof(uint32_t));
+    h->adaptRetired = 0;
+    h->adaptActivePixels = h->adaptPixels;
+    h->adaptPaths = 0;
+    h->adaptLastDecision = 0;
+}
+
+int adaptUploadOrder(KajoHip* h);
+
+// A decision of an adaptive handle at passesDone, behind the noise update of that boundary: the select kernel over every unit, the state
+// words to the host -- the one synchronisation -- a cost order that waited for it, and the order of the launches from here on.
+int adaptDecide(KajoHip* h)
+{
+    const unsigned n = h->gridBlocks, w = h->lds.wavesPerBlock;
+    const AdaptRule rule{h->adaptParams.target, h->adaptParams.floor, (uint32_t)h->adaptParams.allowance};
+    HIP_TRY((hipError_t)kajo_adapt_select_launch(h->noiseMoments.p, h->adaptStateDev.p, &h->adaptGeom, &rule, n, 64u * w, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->adaptStateHost, h->adaptStateDev.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    int rc;
+    if (h->tripsPending && (rc = updateBlockOrder(h)))
+        return rc;
+    h->adaptLastDecision = h->passesDone;
+    unsigned retired = 0;
+    long long activePixels = 0;
+    for (unsigned u = 0; u < n; u++) {
+        if (h->adaptStateHost[u] != KAJO_ADAPT_ACTIVE)
+            retired++;
+        else
+            activePixels += h->adaptUnitPixels[u];
+    }
+    h->adaptRetired = retired;
+    h->adaptActivePixels = activePixels;
+    return adaptUploadOrder(h);
+}
+
+// The launch orders of an adaptive handle that has retired some of its units: the handle's order without them, and their pixel blocks
+int adaptUploadOrder(KajoHip* h)
+{
+    const unsigned n = h->gridBlocks, w = h->lds.wavesPerBlock;
+    if (!h->adaptive || h->adaptRetired == 0 || h->adaptRetired == n)
+        return KAJO_OK;
+    // (both orders, every time: the launch shape follows the passes of a launch, so one handle launches whole units for one cut of the
+    // passes and the SPLIT kernels' pixel blocks for another; neither list can be dropped)
+    std::vector<uint32_t> units, blocks;
+    const uint32_t* order = h->orderValid ? h->hostOrder.data() : nullptr;
+    kajoAdaptOrder(order, n, h->adaptStateHost, w, false, units);
+    kajoAdaptOrder(order, n, h->adaptStateHost, w, true, blocks);
+    HIP_TRY(hipMemcpy(h->adaptUnits.p, units.data(), units.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->adaptBlocks.p, blocks.data(), blocks.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return KAJO_OK;
 }
 
 int samplesPerAxis(const KajoParams& p)
@@ -729,6 +808,8 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
         return fail(KAJO_E_INVALID, "the matte flag keeps its coverage tables over the AOV flag's samples: set the AOV flag with it");
     if ((p.flags & KAJO_FLAG_AOV_TILED) && !(p.flags & KAJO_FLAG_AOV))
         return fail(KAJO_E_INVALID, "the tiled flag changes where the AOV flag's sums are kept: set the AOV flag with it");
+    if ((p.flags & KAJO_FLAG_ADAPTIVE) && !(p.flags & KAJO_FLAG_NOISE))
+        return fail(KAJO_E_INVALID, "the adaptive flag retires units by the noise flag's estimate: set the noise flag with it");
     // (aov.inc.hip: a wave of the tiled launch carries its block's corner and the tile's shape in 16-bit fields, in units of 8 pixels)
     if ((p.flags & KAJO_FLAG_AOV_TILED) && (width > 524288 || height > 262144 || p.tileW > 524280 || p.tileH > 524280))
         return fail(KAJO_E_INVALID, "tiled AOVs: the frame must be within 524288 x 262144 and a tile within 524280 pixels a side");
@@ -909,6 +990,33 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
         CREATE_TRY(h->noiseMoments.alloc(2 * h->tileBytes));
         CREATE_TRY(hipMemsetAsync(h->noiseMoments.p, 0, 2 * h->tileBytes, h->stream));
     }
+    if (p.flags & KAJO_FLAG_ADAPTIVE) {
+        h->adaptive = true;
+        const unsigned w = h->lds.wavesPerBlock;
+        if (w != 1 && w != 2 && w != 4) {
+            destroy(h);
+            return fail(KAJO_E_INVALID, "adaptive sampling: a unit is 64, 128 or 256 slots");
+        }
+        h->adaptShift = w == 1 ? 6 : w == 2 ? 7 : 8;
+        h->adaptGeom = AdaptGeom{width, height, p.tileW, p.tileH, m.tilesX, p.tileIndex, p.tileCount, h->nTilesOwned};
+        const size_t words = h->gridBlocks ? h->gridBlocks : 1;
+        CREATE_TRY(h->adaptStateDev.alloc(words * sizeof(uint32_t)));
+        CREATE_TRY(hipMemsetAsync(h->adaptStateDev.p, 0, words * sizeof(uint32_t), h->stream));
+        CREATE_TRY(h->adaptUnits.alloc(words * sizeof(uint32_t)));
+        CREATE_TRY(h->adaptBlocks.alloc(words * w * sizeof(uint32_t)));
+        CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->adaptStateHost), words * sizeof(uint32_t), hipHostMallocDefault));
+        std::memset(h->adaptStateHost, 0, words * sizeof(uint32_t));
+        h->adaptUnitPixels.assign(h->gridBlocks, 0u);
+        for (unsigned u = 0; u < h->gridBlocks; u++)
+            for (uint32_t s = 0; s < 64u * w; s++) {
+                int px, py;
+                if (kajo::adaptSlotPixel(h->adaptGeom, u * 64u * w + s, &px, &py))
+                    h->adaptUnitPixels[u]++;
+            }
+        for (uint32_t c : h->adaptUnitPixels)
+            h->adaptPixels += c;
+        h->adaptActivePixels = h->adaptPixels;
+    }
     CREATE_TRY(hipStreamSynchronize(h->stream));
 #undef CREATE_TRY
     *out = h;
@@ -1006,6 +1114,15 @@ int kajo_hip_render(kajo_hip_t h, int passes)
             now = std::min(now, KAJO_NOISE_BATCH_PASSES - h->passesDone % KAJO_NOISE_BATCH_PASSES);
         a.firstPass = h->passesDone + 1;
         a.nPasses = now;
+        // (adaptive sampling: once a unit has retired the launches cover the active units only, in the handle's order without the others;
+        // a decision may have brought a new cost order in between: the order is looked up launch by launch)
+        const bool shortGrid = h->adaptive && h->adaptRetired > 0;
+        const unsigned activeUnits = grid - (h->adaptive ? h->adaptRetired : 0u);
+        if (h->adaptive) {
+            a.blockOrder = shortGrid ? h->adaptUnits.as<const uint32_t>() : h->orderValid ? h->blockOrder.as<const uint32_t>() : nullptr;
+            if (shortGrid)
+                a.waveTrips = nullptr; // (the trips are measured by whole launches only; until a unit retires, as on any other handle)
+        }
         const KajoLaunchShape s = kajoLaunchShape(pixelBlocks, now, a.n, lds.coldInLds, p.flags & KAJO_FLAG_NO_SPLIT, a.mailboxOffset,
                                                   lds.perWaveBytes(false), h->passesDone, grouped, h->orderValid, h->nParted);
         if (s.startsInside || s.endsInside)
@@ -1015,13 +1132,17 @@ int kajo_hip_render(kajo_hip_t h, int passes)
         // buffer as it stands: the restored sum counts as complete groups)
         a.carryIn = s.startsInside && h->carryValid;
         a.carryOut = s.endsInside;
-        hipEvent_t e0, e1;
-        if ((rc = getEvent(h, &e0)) || (rc = getEvent(h, &e1)))
-            return rc;
-        HIP_TRY(hipEventRecord(e0, h->stream));
-        hipError_t le;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        hipError_t le = hipSuccess;
+        const bool launch = activeUnits > 0; // (adaptive sampling: with every unit retired the passes are counted, nothing is rendered)
+        if (launch) {
+            if ((rc = getEvent(h, &e0)) || (rc = getEvent(h, &e1)))
+                return rc;
+            HIP_TRY(hipEventRecord(e0, h->stream));
+        }
         h->lastTailGroups = 0;
-        if (s.chunks > 1 || s.split > 1) {
+        if (!launch) {
+        } else if (s.chunks > 1 || s.split > 1) {
             // the waves of a block divide the samples of every pass (behind the [pass][sample][pixel] table) or the passes (behind the
             // [pass][pixel] term table); one round or two: the launch order does not matter
             RenderArgs b = a;
@@ -1033,8 +1154,11 @@ int kajo_hip_render(kajo_hip_t h, int passes)
             lds.fillWaveLds(b, a.mailboxOffset + (size_t)now * (s.chunks > 1 ? a.n * a.n : 1) * 64 * 16, false);
             b.thrL = 1; // (short waves: holding a vertex only lengthens their tail -- configs[0] 18.9 against 16.5 G paths/s; 1-3 % on
                         // split frames below 720p)
-            le = (hipError_t)h->k->split(&b, (unsigned)pixelBlocks, 64 * waves, b.perWaveOffset + (size_t)waves * b.perWaveBytes, h->stream);
-        } else if (s.parted) {
+            if (shortGrid) // the active units' pixel blocks
+                b.blockOrder = h->adaptBlocks.as<const uint32_t>();
+            le = (hipError_t)h->k->split(&b, shortGrid ? activeUnits * lds.wavesPerBlock : (unsigned)pixelBlocks, 64 * waves,
+                                         b.perWaveOffset + (size_t)waves * b.perWaveBytes, h->stream);
+        } else if (s.parted && !shortGrid) { // (a noise handle's launches are of one group at the most: never parted)
             // the launch tail: the cheapest blocks as one workgroup per group of the launch (partTheTail)
             if ((rc = partedOrderFor(h, s.launchGroups))) {
                 h->eventPool.push_back(e0);
@@ -1052,15 +1176,17 @@ int kajo_hip_render(kajo_hip_t h, int passes)
                 le = (hipError_t)kajo_fold_parts_launch(h->tiles.p, h->side.p, b.sideStride, h->partedBlocks.as<const uint32_t>(), h->nParted, block,
                                                         s.launchGroups, h->stream);
         } else {
-            le = (hipError_t)h->k->render(&a, home, grid, block, lds.ldsTotal(), h->stream);
+            le = (hipError_t)h->k->render(&a, home, activeUnits, block, lds.ldsTotal(), h->stream);
         }
         if (le != hipSuccess) {
             h->eventPool.push_back(e0);
             h->eventPool.push_back(e1);
             return failHip(le, "render kernel launch");
         }
-        HIP_TRY(hipEventRecord(e1, h->stream));
-        h->pending.emplace_back(e0, e1);
+        if (launch) {
+            HIP_TRY(hipEventRecord(e1, h->stream));
+            h->pending.emplace_back(e0, e1);
+        }
         if (p.flags & KAJO_FLAG_AOV) {
             // the first-hit AOVs of the same passes, behind the render launch and outside its timing events (KajoCounters.kernelMs)
             AovArgs g;
@@ -1092,7 +1218,14 @@ int kajo_hip_render(kajo_hip_t h, int passes)
             HIP_TRY((hipError_t)h->k->aov(&g, h->aovInstance, (unsigned)((blocks + 3) / 4), h->aovLds, h->stream));
             h->aovPasses += now;
         }
-        if (h->noise && (h->passesDone + now) % KAJO_NOISE_BATCH_PASSES == 0) {
+        if (shortGrid) {
+            // adaptive sampling, behind every launch and outside the timing events: the retired slots extended to the new pass count and,
+            // at a batch boundary, the batch into the moments of the active ones (a handle that retires has rendered every pass: no rebase)
+            const int after = h->passesDone + now, boundary = after % KAJO_NOISE_BATCH_PASSES == 0;
+            HIP_TRY((hipError_t)kajo_adapt_step_launch(h->tiles.p, h->noiseBase.p, h->noiseMoments.p, h->adaptStateDev.p,
+                                                       (uint32_t)((size_t)h->nTilesOwned * p.tileW * p.tileH), h->adaptShift, boundary, after,
+                                                       h->stream));
+        } else if (h->noise && (h->passesDone + now) % KAJO_NOISE_BATCH_PASSES == 0) {
             // a batch boundary, behind the launch (and its fold) and outside the timing events: the batch into the moments -- or, where this
             // handle did not render all of it, only the baseline
             if (h->noiseRebase)
@@ -1106,10 +1239,17 @@ int kajo_hip_render(kajo_hip_t h, int passes)
             h->tripsPending = true;
             a.waveTrips = nullptr; // later launches of this call keep the first measurement
         }
-        h->launches++;
+        if (launch)
+            h->launches++;
         h->passesDone += now;
         h->carryValid = s.endsInside;
         left -= now;
+        if (h->adaptive) {
+            h->adaptPaths += h->adaptActivePixels * a.n * a.n * now;
+            if (h->adaptSet && activeUnits > 0 && !h->noiseRebase && h->passesDone >= h->adaptParams.minPasses &&
+                h->passesDone % (KAJO_NOISE_BATCH_PASSES * h->adaptParams.checkEvery) == 0 && (rc = adaptDecide(h)))
+                return rc;
+        }
     }
     h->frameValid = false;
     return KAJO_OK;
@@ -1123,6 +1263,8 @@ int kajo_hip_wait(kajo_hip_t h)
     if (rc)
         return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
+    // (an adaptive handle: trips are measured only while no unit has retired, and a decision applies a waiting cost order before it
+    // counts retirements, so no filtered order has to follow the update here)
     if (h->tripsPending && (rc = updateBlockOrder(h)))
         return rc;
     return drainEvents(h);
@@ -1151,7 +1293,10 @@ int kajo_hip_reset(kajo_hip_t h)
         HIP_TRY(hipMemsetAsync(h->noiseMoments.p, 0, 2 * h->tileBytes, h->stream));
         h->noiseRebase = false;
     }
+    if (h->adaptive)
+        HIP_TRY(hipMemsetAsync(h->adaptStateDev.p, 0, (size_t)h->gridBlocks * sizeof(uint32_t), h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    adaptReactivate(h);
     h->aovComposed = h->matteComposed = false;
     h->aovPasses = 0;
     h->passesDone = 0;
@@ -1166,9 +1311,16 @@ int kajo_hip_set_pass_count(kajo_hip_t h, int passesDone)
 {
     if (!h || passesDone < 0 || passesDone > 0x7ffffffe)
         return fail(KAJO_E_INVALID, "invalid argument");
+    if (h->adaptive && passesDone != 0)
+        return fail(KAJO_E_STATE, "an adaptive handle keeps a pass count per unit, which a restored buffer does not tell: set_pass_count is refused");
     int rc = kajo_hip_wait(h);
     if (rc)
         return rc;
+    if (h->adaptive) { // (to pass 0: the moments start over below, and so do the units)
+        HIP_TRY(hipMemsetAsync(h->adaptStateDev.p, 0, (size_t)h->gridBlocks * sizeof(uint32_t), h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        adaptReactivate(h);
+    }
     if (h->noise) {
         // the moments start over; the baseline is the buffer at the first batch boundary from here on (kajo_hip_render)
         HIP_TRY(hipMemsetAsync(h->noiseMoments.p, 0, 2 * h->tileBytes, h->stream));
@@ -2306,6 +2458,149 @@ int kajo_hip_read_noise_moments(kajo_hip_t h, KajoNoiseMoments* records)
                 records[(size_t)y * h->W + x] = own[slot];
         }
     return KAJO_OK;
+}
+
+static_assert(sizeof(KajoAdaptParams) == 32 && sizeof(KajoAdaptState) == 48, "include/kajo_hip.h states the sizes");
+
+// The refusals of KajoAdaptParams (KAJO_E_INVALID), before the handle is looked at
+static int checkAdapt(const KajoAdaptParams* p)
+{
+    if (!p)
+        return fail(KAJO_E_INVALID, "null adaptive parameters");
+    if (!(p->target > 0.0f))
+        return fail(KAJO_E_INVALID, "adaptive target must be above 0");
+    if (!(std::isfinite(p->floor) && p->floor > 0.0f))
+        return fail(KAJO_E_INVALID, "adaptive floor must be finite and positive");
+    if (p->minPasses < 0)
+        return fail(KAJO_E_INVALID, "adaptive minPasses must not be negative");
+    if (p->checkEvery < 1 || p->checkEvery > 65536)
+        return fail(KAJO_E_INVALID, "adaptive checkEvery must be in [1, 65536]");
+    if (p->allowance < 0 || p->allowance > 63)
+        return fail(KAJO_E_INVALID, "adaptive allowance must be in [0, 63]");
+    if (p->reserved[0] || p->reserved[1] || p->reserved[2])
+        return fail(KAJO_E_INVALID, "adaptive reserved words must be 0");
+    return KAJO_OK;
+}
+
+void kajo_hip_default_adapt_params(KajoAdaptParams* p)
+{
+    if (!p)
+        return;
+    std::memset(p, 0, sizeof *p);
+    p->floor = 1e-2f;
+    p->minPasses = 16;
+    p->checkEvery = 4;
+}
+
+int kajo_hip_set_adaptive(kajo_hip_t h, const KajoAdaptParams* params)
+{
+    int rc = checkAdapt(params);
+    if (rc)
+        return rc;
+    if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    if (!h->adaptive)
+        return fail(KAJO_E_STATE, "the handle was created without the adaptive flag");
+    if (h->passesDone != 0)
+        return fail(KAJO_E_STATE, "the adaptive parameters are set before the first pass (or after kajo_hip_reset)");
+    h->adaptParams = *params;
+    const long long step = (long long)KAJO_NOISE_BATCH_PASSES * params->checkEvery;
+    h->adaptParams.minPasses = (int32_t)std::min<long long>((params->minPasses + step - 1) / step * step, 0x7ffffffell);
+    h->adaptSet = true;
+    return KAJO_OK;
+}
+
+int kajo_hip_adapt_state(kajo_hip_t h, KajoAdaptState* state)
+{
+    if (!h || !state)
+        return fail(KAJO_E_INVALID, "null argument");
+    if (!h->adaptive)
+        return fail(KAJO_E_STATE, "the handle was created without the adaptive flag");
+    int rc = kajo_hip_wait(h);
+    if (rc)
+        return rc;
+    state->units = h->gridBlocks;
+    state->activeUnits = h->gridBlocks - h->adaptRetired;
+    state->pixels = h->adaptPixels;
+    state->activePixels = h->adaptActivePixels;
+    state->paths = h->adaptPaths;
+    state->lastDecisionPass = h->adaptLastDecision;
+    state->unitSlots = (int32_t)(64u * h->lds.wavesPerBlock);
+    return KAJO_OK;
+}
+
+int kajo_hip_adapt_passes(kajo_hip_t h, uint32_t* plane)
+{
+    if (!h || !plane)
+        return fail(KAJO_E_INVALID, "null argument");
+    if (!h->adaptive)
+        return fail(KAJO_E_STATE, "the handle was created without the adaptive flag");
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    if (h->nTilesOwned == 0)
+        return kajo_hip_wait(h);
+    const size_t pixels = (size_t)h->W * h->H;
+    const bool part = h->map.tileCount > 1;
+    if (part && h->adaptStaged.size() < pixels)
+        h->adaptStaged.resize(pixels);
+    HIP_TRY(h->adaptOut.ensure(pixels * 4));
+    hipError_t le = (hipError_t)kajo_adapt_passes_launch(h->noiseMoments.p, h->adaptStateDev.p, &h->map, h->params.tileIndex, h->adaptShift,
+                                                         (uint32_t)h->passesDone, h->adaptOut.p, h->stream);
+    if (le != hipSuccess)
+        return failHip(le, "adaptive pass plane kernel launch");
+    HIP_TRY(hipMemcpyAsync(part ? h->adaptStaged.data() : plane, h->adaptOut.p, pixels * 4, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = kajo_hip_wait(h)))
+        return rc;
+    if (part)
+        for (int y = 0; y < h->H; y++)
+            for (int x = 0; x < h->W; x++) {
+                int owner;
+                uint32_t slot;
+                kajoTileSlot(h->map, x, y, &owner, &slot);
+                if (owner == h->params.tileIndex)
+                    plane[(size_t)y * h->W + x] = h->adaptStaged[(size_t)y * h->W + x];
+            }
+    return KAJO_OK;
+}
+
+int kajo_hip_adapt_evaluate(const KajoNoiseMoments* records, int64_t count, const KajoAdaptParams* params, uint8_t* loud, int64_t* nLoud)
+{
+    int rc = checkAdapt(params);
+    if (rc)
+        return rc;
+    if (count < 0 || (count > 0 && !records))
+        return fail(KAJO_E_INVALID, "invalid argument");
+    const AdaptRule rule{params->target, params->floor, (uint32_t)params->allowance};
+    int64_t total = 0;
+    for (int64_t i = 0; i < count; i++) {
+        const bool is = kajo::adaptLoud(records[i].s1, records[i].s2, records[i].n, rule);
+        total += is;
+        if (loud)
+            loud[i] = is ? 1 : 0;
+    }
+    if (nLoud)
+        *nLoud = total;
+    return KAJO_OK;
+}
+
+int64_t kajo_hip_adapt_order(const uint32_t* order, uint32_t nUnits, const uint32_t* state, uint32_t wavesPerBlock, int32_t split, uint32_t* out,
+                             size_t capacity)
+{
+    if ((nUnits > 0 && !state) || wavesPerBlock < 1 || wavesPerBlock > 4)
+        return fail(KAJO_E_INVALID, "invalid argument");
+    if (order)
+        for (uint32_t i = 0; i < nUnits; i++)
+            if (order[i] >= nUnits)
+                return fail(KAJO_E_INVALID, "an order word names a unit the handle does not have");
+    std::vector<uint32_t> words;
+    kajoAdaptOrder(order, nUnits, state, wavesPerBlock, split != 0, words);
+    if (out) {
+        if (capacity < words.size())
+            return fail(KAJO_E_INVALID, "capacity too small");
+        std::copy(words.begin(), words.end(), out);
+    }
+    return (int64_t)words.size();
 }
 
 } // extern "C"

@@ -92,7 +92,25 @@ struct Scheduler::Impl
     // Options::local changes the frame (include/kajo_hip.h: with compression 1 and detail 1 the output is the input)
     bool localActive() const { return opt.localOn && !(opt.local.compression == 1.0f && opt.local.detail == 1.0f); }
     // Options::noise / noiseTarget: the handles keep the batch moments (KAJO_FLAG_NOISE)
-    bool noiseOn() const { return opt.noise || opt.noiseTarget > 0.0f; }
+    bool noiseOn() const { return opt.noise || opt.noiseTarget > 0.0f || adaptiveOn(); }
+    // Options::adaptiveTarget: the handles retire converged units (KAJO_FLAG_ADAPTIVE)
+    bool adaptiveOn() const { return opt.adaptiveTarget > 0.0f; }
+    KajoAdaptState adaptState{}; // the owners' states added, at the last refresh
+
+    void measureAdaptive()
+    {
+        adaptState = KajoAdaptState{};
+        for (kajo_hip_t h : handles) {
+            KajoAdaptState s;
+            check(kajo_hip_adapt_state(h, &s), "kajo_hip_adapt_state");
+            adaptState.units += s.units;
+            adaptState.activeUnits += s.activeUnits;
+            adaptState.pixels += s.pixels;
+            adaptState.activePixels += s.activePixels;
+            adaptState.paths += s.paths;
+            adaptState.lastDecisionPass = std::max(adaptState.lastDecisionPass, s.lastDecisionPass);
+        }
+    }
     KajoNoiseParams noiseParams() const { return KajoNoiseParams{opt.noiseFloor, opt.noiseQuantile}; }
     float noiseValue = -1; // Statistics::noise* of the last refresh
     long long noiseKnown = 0, noiseUnknown = 0, noiseBad = 0;
@@ -222,7 +240,7 @@ struct Scheduler::Impl
                       (opt.aov ? KAJO_FLAG_AOV | (opt.aovSpecular ? KAJO_FLAG_AOV_SPECULAR : 0u) | (opt.matte ? KAJO_FLAG_AOV_MATTE : 0u) |
                                  (opt.aovTiled ? KAJO_FLAG_AOV_TILED : 0u)
                                : 0u) |
-                      (noiseOn() ? KAJO_FLAG_NOISE : 0u);
+                      (noiseOn() ? KAJO_FLAG_NOISE : 0u) | (adaptiveOn() ? KAJO_FLAG_ADAPTIVE : 0u);
             p.device = opt.sameDevice ? 0 : g;
             p.tileIndex = g;
             p.tileCount = opt.gpus;
@@ -231,6 +249,18 @@ struct Scheduler::Impl
             check(kajo_hip_create(&pod, image->width, image->height, &p, &h), "kajo_hip_create");
             handles.push_back(h);
             devices.push_back(p.device);
+            if (adaptiveOn()) {
+                KajoAdaptParams a;
+                kajo_hip_default_adapt_params(&a);
+                a.target = opt.adaptiveTarget;
+                a.floor = opt.noiseFloor;
+                a.allowance = opt.adaptiveAllowance;
+                if (opt.adaptiveMinPasses > 0)
+                    a.minPasses = opt.adaptiveMinPasses;
+                if (opt.adaptiveEvery > 0)
+                    a.checkEvery = opt.adaptiveEvery;
+                check(kajo_hip_set_adaptive(h, &a), "kajo_hip_set_adaptive");
+            }
         }
         if (opt.gpus > 1 || opt.forceGather) {
             void* ptr = nullptr;
@@ -698,11 +728,22 @@ void Scheduler::readNoise(float* mean, float* stderror, float* relative)
         check(kajo_hip_noise(h, &p, mean, stderror, relative, nullptr, nullptr, nullptr), "kajo_hip_noise");
 }
 
+void Scheduler::readSamplePasses(uint32_t* plane)
+{
+    Impl& d = *m_impl;
+    if (!d.adaptiveOn())
+        throw std::runtime_error("hip::Scheduler: readSamplePasses needs Options::adaptiveTarget");
+    for (kajo_hip_t h : d.handles)
+        check(kajo_hip_adapt_passes(h, plane), "kajo_hip_adapt_passes");
+}
+
 void Scheduler::run()
 {
     Impl& d = *m_impl;
     const Options& o = d.opt;
-    const bool stopRule = o.noiseTarget > 0.0f;
+    const bool adaptive = d.adaptiveOn();
+    const bool stopRule = o.noiseTarget > 0.0f || adaptive; // (either rule: refreshes of whole batches, maxPasses the budget)
+    int adaptiveStoppedAt = 0;
     const int budget = stopRule && o.maxPasses > 0 ? o.maxPasses : o.passes > 0 ? o.passes : (d.preview ? 0 : 16);
     int stoppedAt = 0;
     const std::thread::id self = std::this_thread::get_id();
@@ -737,7 +778,7 @@ void Scheduler::run()
 
     // The SDL calls of the preview stay on this (the main) thread, as the reference requires
     // (cpu/Scheduler.cpp:64-81 marshals worker progress through a queue for the same reason).
-    while ((!d.preview || d.preview->processEvents()) && (budget == 0 || done < budget) && !stoppedAt) {
+    while ((!d.preview || d.preview->processEvents()) && (budget == 0 || done < budget) && !stoppedAt && !adaptiveStoppedAt) {
         int batch = autoBatch();
         if (stopRule) // a refresh of the stop rule ends on a batch boundary of the estimate: whole batches, four passes at the least
             batch = done % KAJO_NOISE_BATCH_PASSES ? KAJO_NOISE_BATCH_PASSES - done % KAJO_NOISE_BATCH_PASSES
@@ -753,8 +794,13 @@ void Scheduler::run()
         d.gatherAndResolve();
         if (d.noiseOn()) {
             d.measureNoise();
-            if (stopRule && d.noiseUnknown == 0 && d.noiseKnown > 0 && d.noiseValue <= o.noiseTarget)
+            if (o.noiseTarget > 0.0f && d.noiseUnknown == 0 && d.noiseKnown > 0 && d.noiseValue <= o.noiseTarget)
                 stoppedAt = done;
+        }
+        if (adaptive) {
+            d.measureAdaptive();
+            if (d.adaptState.activeUnits == 0)
+                adaptiveStoppedAt = done;
         }
         const double batchWall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count();
         batchMs.push_back(batchWall);
@@ -781,6 +827,12 @@ void Scheduler::run()
         d.stats.noiseUnknownPx = d.noiseUnknown;
         d.stats.noiseBadPx = d.noiseBad;
         d.stats.noiseStoppedAtPass = stoppedAt;
+    }
+    if (adaptive && done > 0) {
+        d.stats.adaptiveUnits = d.adaptState.units;
+        d.stats.adaptiveActiveUnits = d.adaptState.activeUnits;
+        d.stats.adaptivePaths = d.adaptState.paths;
+        d.stats.adaptiveStoppedAtPass = adaptiveStoppedAt;
     }
     if (o.despeckleOn && done > 0) {
         int64_t c[2] = {0, 0};

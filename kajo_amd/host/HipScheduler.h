@@ -126,6 +126,13 @@ struct Options
     float noiseQuantile = 0.95f;
     float noiseFloor = 1e-2f;
     int maxPasses = 0;
+    // Adaptive sampling (include/kajo_hip.h KAJO_FLAG_ADAPTIVE, kajo_hip_set_adaptive): adaptiveTarget > 0 creates the handles with the
+    // noise and the adaptive flag and gives them the rule (noiseFloor is its floor; adaptiveMinPasses / adaptiveEvery 0 = the library's
+    // defaults, 16 passes and every fourth batch). run() adds the handles' states at each refresh and ends when no unit is active, or
+    // after maxPasses (0 = the budget `passes` gives); its refreshes end on multiples of four passes. Together with noiseTarget:
+    // whichever rule ends first. 0 = off: every run then makes exactly the calls it made without these fields.
+    float adaptiveTarget = 0.0f;
+    int adaptiveAllowance = 0, adaptiveMinPasses = 0, adaptiveEvery = 0;
 };
 
 struct Statistics
@@ -145,6 +152,10 @@ struct Statistics
     float noiseQuantileValue = -1;
     long long noiseKnownPx = 0, noiseUnknownPx = 0, noiseBadPx = 0;
     int noiseStoppedAtPass = 0;
+    // adaptive sampling at the last refresh (Options::adaptiveTarget; the owners' states added): the units and those still active, the camera
+    // paths actually traced (`paths` above stays the nominal count), and the pass run() ended at because no unit was active (0: it did not)
+    long long adaptiveUnits = 0, adaptiveActiveUnits = 0, adaptivePaths = 0;
+    int adaptiveStoppedAtPass = 0;
 };
 
 class Scheduler : public ::Scheduler
@@ -205,6 +216,9 @@ public:
     // the noise map after run() (Options::noise or noiseTarget; include/kajo_hip.h kajo_hip_noise on every owner, into the same planes):
     // W*H floats each -- mean luminance per pass, its standard error, the relative error -- any may be null. Any number of GPUs, no gather
     void readNoise(float* mean, float* stderror, float* relative);
+    // the per-pixel pass count after run() (Options::adaptiveTarget; include/kajo_hip.h kajo_hip_adapt_passes on every owner, into the same
+    // plane): W*H words. Any number of GPUs, no gather
+    void readSamplePasses(uint32_t* plane);
 
 private:
     struct Impl;

@@ -126,6 +126,7 @@ int main(int argc, char** argv)
     // meter options (include/kajo_hip.h KajoMeterParams): the raw text, checked after the loop
     std::string meterExposure, meterWhite;
     std::string untilNoise, noiseQuantile, noiseFloor, maxPasses, noiseMapOut;
+    std::string adaptiveE, adaptiveAllowance, adaptiveMinPasses, adaptiveEvery, sampleMapOut;
     // local tone mapping options (include/kajo_hip.h KajoLocalParams): the raw text, checked after the loop
     std::string localContrast, localDetail, localRange, localIterations, localPivot;
     // depth of field options (include/kajo_hip.h KajoLensParams): the raw text, checked after the loop
@@ -257,6 +258,14 @@ int main(int argc, char** argv)
                         "    --noise-quantile Q  --until-noise, --noise-map: the quantile, 0 < Q <= 1 (0.95)\n"
                         "    --noise-floor F  --until-noise, --noise-map: the floor added to the mean, > 0 (0.01), so that black pixels do not dominate\n"
                         "    --max-passes N  --until-noise: stop after N passes at the latest, N >= 1 (1024)\n"
+                        "    --adaptive E    adaptive sampling (include/kajo_hip.h kajo_hip_set_adaptive; any --gpus): units of the frame whose pixels' relative\n"
+                        "                    error is <= E retire and later passes render the others; ends when none is active or after --max-passes\n"
+                        "                    (1024). With --until-noise: whichever rule ends first. --noise-floor is the rule's floor (--json:\n"
+                        "                    adaptive_active_units, adaptive_units, adaptive_paths, adaptive_stopped_at_pass)\n"
+                        "    --adaptive-allowance K  --adaptive: loud pixels a quiet 8x8 block may have, 0..63 (0)\n"
+                        "    --adaptive-min-passes N  --adaptive: no unit retires before pass N (16)\n"
+                        "    --adaptive-every B  --adaptive: batches of four passes between decisions (4)\n"
+                        "    --sample-map FILE.pfm  with --adaptive: also write the per-pixel pass count as a 1-channel PFM\n"
                         "    --noise-map FILE  also write the noise map as a 3-channel PFM: mean luminance per pass, its standard error, the relative\n"
                         "                    error (-1 where a pixel has fewer than two batches); any --gpus\n",
                         args[0].c_str());
@@ -300,6 +309,11 @@ int main(int argc, char** argv)
         else if (a == "--noise-floor" && more) noiseFloor = args[++i];
         else if (a == "--max-passes" && more) maxPasses = args[++i];
         else if (a == "--noise-map" && more) noiseMapOut = args[++i];
+        else if (a == "--adaptive" && more) adaptiveE = args[++i];
+        else if (a == "--adaptive-allowance" && more) adaptiveAllowance = args[++i];
+        else if (a == "--adaptive-min-passes" && more) adaptiveMinPasses = args[++i];
+        else if (a == "--adaptive-every" && more) adaptiveEvery = args[++i];
+        else if (a == "--sample-map" && more) sampleMapOut = args[++i];
         else if (a == "--meter-exposure" && more) meterExposure = args[++i];
         else if (a == "--meter-white" && more) meterWhite = args[++i];
         else if (a == "--local-contrast" && more) localContrast = args[++i];
@@ -425,12 +439,49 @@ int main(int argc, char** argv)
             return 1;
         }
     }
+    const bool adaptiveGiven = !adaptiveE.empty();
+    if (!adaptiveGiven && (!adaptiveAllowance.empty() || !adaptiveMinPasses.empty() || !adaptiveEvery.empty() || !sampleMapOut.empty())) {
+        std::cerr << "kajo_render: --adaptive-allowance, --adaptive-min-passes, --adaptive-every and --sample-map shape what --adaptive turns on: give them with it" << std::endl;
+        return 1;
+    }
     const bool noiseGiven = !untilNoise.empty() || !noiseMapOut.empty();
-    if (!noiseGiven && (!noiseQuantile.empty() || !noiseFloor.empty() || !maxPasses.empty())) {
+    if (!noiseGiven && !adaptiveGiven && (!noiseQuantile.empty() || !noiseFloor.empty() || !maxPasses.empty())) {
         std::cerr << "kajo_render: --noise-quantile, --noise-floor and --max-passes shape what --until-noise or --noise-map turn on: give them with one of the two" << std::endl;
         return 1;
     }
-    if (noiseGiven) {
+    if (adaptiveGiven) {
+        // (before any device is opened: the refusals of kajo_hip_set_adaptive, with the option's name)
+        if (threeArg) {
+            std::cerr << "kajo_render: the adaptive options need the backend's options (without --three-arg)" << std::endl;
+            return 1;
+        }
+        if (!parseFloat(adaptiveE, &opt.adaptiveTarget) || !(opt.adaptiveTarget > 0.0f)) {
+            std::cerr << "kajo_render: --adaptive must be a finite number > 0" << std::endl;
+            return 1;
+        }
+        auto whole = [](const std::string& text, long lo, long hi, int* out) {
+            char* end = nullptr;
+            const long n = std::strtol(text.c_str(), &end, 10);
+            if (end == text.c_str() || *end || n < lo || n > hi)
+                return false;
+            *out = (int)n;
+            return true;
+        };
+        if (!adaptiveAllowance.empty() && !whole(adaptiveAllowance, 0, 63, &opt.adaptiveAllowance)) {
+            std::cerr << "kajo_render: --adaptive-allowance must be a whole number in 0..63" << std::endl;
+            return 1;
+        }
+        if (!adaptiveMinPasses.empty() && !whole(adaptiveMinPasses, 1, 0x7ffffffe, &opt.adaptiveMinPasses)) {
+            std::cerr << "kajo_render: --adaptive-min-passes must be a whole number >= 1" << std::endl;
+            return 1;
+        }
+        if (!adaptiveEvery.empty() && !whole(adaptiveEvery, 1, 65536, &opt.adaptiveEvery)) {
+            std::cerr << "kajo_render: --adaptive-every must be a whole number in 1..65536" << std::endl;
+            return 1;
+        }
+        opt.maxPasses = 1024;
+    }
+    if (noiseGiven || adaptiveGiven) {
         // (before any device is opened: the refusals of kajo_hip_noise, with the option's name)
         if (threeArg) {
             std::cerr << "kajo_render: the noise options need the backend's options (without --three-arg)" << std::endl;
@@ -457,13 +508,13 @@ int main(int argc, char** argv)
         if (!maxPasses.empty()) {
             char* end = nullptr;
             const long n = std::strtol(maxPasses.c_str(), &end, 10);
-            if (untilNoise.empty() || end == maxPasses.c_str() || *end || n < 1 || n > 0x7ffffffe) {
+            if ((untilNoise.empty() && !adaptiveGiven) || end == maxPasses.c_str() || *end || n < 1 || n > 0x7ffffffe) {
                 std::cerr << "kajo_render: --max-passes must be a whole number >= 1, with --until-noise" << std::endl;
                 return 1;
             }
             opt.maxPasses = (int)n;
         }
-        if (!untilNoise.empty())
+        if (!untilNoise.empty() || adaptiveGiven)
             opt.passes = opt.maxPasses; // (the preview's pass budget and the scheduler's: the rule ends the run before it, or it does)
     }
     const bool meterGiven = !meterExposure.empty() || !meterWhite.empty();
@@ -897,6 +948,16 @@ int main(int argc, char** argv)
             if (!writePfm(noiseMapOut, width, height, 3, rgb.data()))
                 return 3;
         }
+        if (!sampleMapOut.empty()) {
+            const size_t count = (size_t)width * height;
+            std::vector<uint32_t> passesOf(count);
+            std::vector<float> plane(count);
+            hipScheduler->readSamplePasses(passesOf.data());
+            for (size_t i = 0; i < count; i++)
+                plane[i] = (float)passesOf[i];
+            if (!writePfm(sampleMapOut, width, height, 1, plane.data()))
+                return 3;
+        }
         if (!aovPrefix.empty()) {
             // the means: albedo and normal over every sample, depth over the samples that hit (0 where none did)
             const size_t count = (size_t)width * height;
@@ -1023,7 +1084,10 @@ int main(int argc, char** argv)
                         (int)opt.view.outW, (int)opt.view.outH, viewFilterNames[opt.view.filter],
                         (viewRect.empty() ? (double)width : (double)opt.view.x1 - opt.view.x0) / opt.view.outW,
                         (viewRect.empty() ? (double)height : (double)opt.view.y1 - opt.view.y0) / opt.view.outH);
-        if (noiseGiven)
+        if (adaptiveGiven)
+            std::printf(", \"adaptive_active_units\": %lld, \"adaptive_units\": %lld, \"adaptive_paths\": %lld, \"adaptive_stopped_at_pass\": %d",
+                        s.adaptiveActiveUnits, s.adaptiveUnits, s.adaptivePaths, s.adaptiveStoppedAtPass);
+        if (noiseGiven || adaptiveGiven)
             std::printf(", \"noise_quantile_value\": %.9g, \"noise_known_px\": %lld, \"noise_bad_px\": %lld, \"noise_stopped_at_pass\": %d",
                         (double)s.noiseQuantileValue, s.noiseKnownPx, s.noiseBadPx, s.noiseStoppedAtPass);
         if (aovTiled)

@@ -28,11 +28,53 @@ def noise_evaluate(hist, quantile: float = 0.95) -> float:
     return value.value
 
 
+class AdaptParams:
+    """The rule of adaptive sampling (include/kajo_hip.h KajoAdaptParams): a unit retires once every pixel block of it has at most
+    `allowance` pixels whose relative error is unknown or above `target`. Fields left None take kajo_hip_default_adapt_params' values
+    (floor 1e-2, min_passes 16, check_every 4 batches, allowance 0)."""
+
+    def __init__(self, target: float, floor: float = None, min_passes: int = None, check_every: int = None, allowance: int = None):
+        self.target, self.floor, self.min_passes, self.check_every, self.allowance = target, floor, min_passes, check_every, allowance
+
+    def pod(self) -> "capi.KajoAdaptParams":
+        p = capi.KajoAdaptParams()
+        capi.lib().kajo_hip_default_adapt_params(C.byref(p))
+        p.target = float(self.target)
+        for field, value in (("floor", self.floor), ("minPasses", self.min_passes), ("checkEvery", self.check_every), ("allowance", self.allowance)):
+            if value is not None:
+                setattr(p, field, float(value) if field == "floor" else int(value))
+        return p
+
+
+def adapt_evaluate(records, params) -> np.ndarray:
+    """Which records are loud under the rule (kajo_hip_adapt_evaluate; pure host, the kernel's own lines): a bool array of records' shape.
+    records: NOISE_MOMENTS; params: AdaptParams or a dict of its arguments."""
+    records = np.ascontiguousarray(records, NOISE_MOMENTS)
+    p = (params if isinstance(params, AdaptParams) else AdaptParams(**params)).pod()
+    loud = np.zeros(records.shape, np.uint8)
+    capi.check(capi.lib().kajo_hip_adapt_evaluate(records.ctypes.data_as(C.c_void_p), records.size, C.byref(p), loud.ctypes.data_as(C.c_void_p), None))
+    return loud.astype(bool)
+
+
+def adapt_order(order, state, waves_per_block: int, split: bool) -> np.ndarray:
+    """The launch order of an adaptive handle (kajo_hip_adapt_order; pure host): `order` (None: image order) without the units whose
+    state word is not 0; with split their pixel blocks."""
+    state = np.ascontiguousarray(state, np.uint32)
+    order = None if order is None else np.ascontiguousarray(order, np.uint32)
+    out = np.zeros(state.size * int(waves_per_block), np.uint32)
+    n = capi.lib().kajo_hip_adapt_order(None if order is None else order.ctypes.data_as(C.c_void_p), state.size, state.ctypes.data_as(C.c_void_p),
+                                        int(waves_per_block), int(bool(split)), out.ctypes.data_as(C.c_void_p), out.size)
+    if n < 0:
+        capi.check(int(n))
+    return out[:n]
+
+
 class HipRenderer:
     def __init__(self, scene: Scene, width: int, height: int, spp: int = 32, depth_limit: int = 8,
                  seed: int = 0o715517, strict: bool = False, exact: bool = False, counters: bool = False, device: int = 0,
                  tile=(64, 16), tile_index: int = 0, tile_count: int = 1, passes_per_launch: int = 0, flags: int = 0,
-                 aov: bool = False, aov_specular: bool = False, matte: bool = False, aov_tiled: bool = False, noise: bool = False):
+                 aov: bool = False, aov_specular: bool = False, matte: bool = False, aov_tiled: bool = False, noise: bool = False,
+                 adaptive=None):
         L = capi.lib()
         self._L = L
         self.scene = scene
@@ -49,6 +91,9 @@ class HipRenderer:
         p.flags |= capi.KAJO_FLAG_AOV_MATTE if matte else 0  # (likewise)
         p.flags |= capi.KAJO_FLAG_AOV_TILED if aov_tiled else 0  # (likewise; with it aov takes any tile_index / tile_count)
         p.flags |= capi.KAJO_FLAG_NOISE if noise else 0  # batch moments beside the render: noise(), noise_moments()
+        if adaptive is False:
+            adaptive = None
+        p.flags |= capi.KAJO_FLAG_ADAPTIVE if adaptive is not None else 0  # (without noise the library refuses it): adapt_state(), adapt_passes()
         p.device = device
         p.tileW, p.tileH = tile
         p.tileIndex, p.tileCount = tile_index, tile_count
@@ -59,6 +104,13 @@ class HipRenderer:
         capi.check(L.kajo_hip_create(C.byref(self._pod), self.width, self.height, C.byref(p), C.byref(h)))
         self._h = h
         self.passes = 0
+        # adaptive: AdaptParams or a dict of its arguments gives the rule at once; True only sets the flag (set_adaptive() later, or never)
+        if adaptive is not None and adaptive is not True:
+            try:
+                self.set_adaptive(adaptive)
+            except Exception:
+                self.close()
+                raise
 
     # -- lifecycle -------------------------------------------------------------------------
     def close(self):
@@ -146,6 +198,24 @@ class HipRenderer:
         if out is None:
             out = np.zeros((self.height, self.width), NOISE_MOMENTS)
         capi.check(self._L.kajo_hip_read_noise_moments(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def set_adaptive(self, params):
+        """The rule of an adaptive handle (kajo_hip_set_adaptive), accepted while no pass is rendered: AdaptParams or a dict of its arguments."""
+        p = (params if isinstance(params, AdaptParams) else AdaptParams(**params)).pod()
+        capi.check(self._L.kajo_hip_set_adaptive(self._h, C.byref(p)))
+
+    def adapt_state(self) -> dict:
+        """kajo_hip_adapt_state: units, activeUnits, pixels, activePixels, paths (actually traced), lastDecisionPass, unitSlots."""
+        s = capi.KajoAdaptState()
+        capi.check(self._L.kajo_hip_adapt_state(self._h, C.byref(s)))
+        return {k: getattr(s, k) for k, _ in capi.KajoAdaptState._fields_}
+
+    def adapt_passes(self, out: np.ndarray = None) -> np.ndarray:
+        """The per-pixel pass count (kajo_hip_adapt_passes): (H, W) uint32, of which this owner's pixels are written (into `out` where given)."""
+        if out is None:
+            out = np.zeros((self.height, self.width), np.uint32)
+        capi.check(self._L.kajo_hip_adapt_passes(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def aov(self) -> dict:

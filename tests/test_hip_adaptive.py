@@ -1,0 +1,339 @@
+"""Adaptive sampling (KAJO_FLAG_ADAPTIVE with KAJO_FLAG_NOISE; include/kajo_hip.h "Adaptive sampling", kajo_amd/csrc/adapt_kernels.cpp) on
+the GPU.
+
+The reference is a twin handle with KAJO_FLAG_NOISE alone, rendered four passes at a time: its frames and records after every batch. A
+numpy restatement of the rule finds every unit's retirement pass from the twin's records and forms what the adaptive handle must hold:
+the twin's frame and records at P for an active unit, twin(p) * (float)(P / p) and the records at p for a unit retired at p. Frame,
+records, pass plane and state are compared bit for bit, for every numerics build, ragged and multi-tile frames, a large-scene instance,
+the SPLIT and the unsplit kernels, any cut of the passes into calls, one owner and three, allowance 0 and 8."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from kajo_amd import capi
+from kajo_amd.renderer import HipRenderer, NOISE_MOMENTS
+from kajo_amd.tiles import TileLayout
+from scenes_extra import dense_scene
+
+pytestmark = pytest.mark.gpu
+
+SEED = 0o715517
+F32, F64 = np.float32, np.float64
+BUILDS = {"fast": {}, "exact": dict(exact=True), "strict": dict(strict=True)}
+CASES = {"spheres-41x23": ("spheres", 41, 23), "spheres-65x9": ("spheres", 65, 9), "spheres-100x75": ("spheres", 100, 75),
+         "grid60-41x23": ("grid60", 41, 23)}
+CUTS = ((32,), (4, 28), (1, 2, 29), (3, 5, 24), (1,) * 32)
+FLOOR = 1e-2
+PASSES = 32
+HUGE, TINY = 1e30, 1e-30
+
+
+@pytest.fixture(scope="module")
+def the_scenes(scenes):
+    return {"spheres": scenes["spheres_a169"], "grid60": dense_scene(scenes["spheres_a169"], 60, 3, seed=11)}
+
+
+def u32(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def same_records(a, b):
+    return all(np.array_equal(a[k].view(np.uint64), b[k].view(np.uint64)) for k in ("s1", "s2", "n", "bad"))
+
+
+_TWINS = {}
+
+
+def twin(sc, key, W, H, kw):
+    """frames[b], records[b] after batch b = 1 .. 8 of a KAJO_FLAG_NOISE handle (index 0: nothing rendered); rendered once per case"""
+    k = (key, W, H, tuple(sorted(kw.items())))
+    if k not in _TWINS:
+        with HipRenderer(sc, W, H, spp=4, seed=SEED, noise=True, **kw) as t:
+            frames, records = [np.zeros((H, W, 4), F32)], [t.noise_moments()]
+            for _ in range(PASSES // 4):
+                frames.append(t.render(4).radiance().copy())
+                records.append(t.noise_moments())
+            launches = t.counters()["launches"]
+        for a in frames + records:
+            a.setflags(write=False)
+        _TWINS[k] = (frames, records, launches)
+    return _TWINS[k]
+
+
+def rel32(rec, floor=FLOOR):
+    """the estimate's evaluation in float64, rounded to float32; -1 with fewer than two batches"""
+    n = rec["n"].astype(F64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        m = rec["s1"] / (4.0 * n)
+        v = np.maximum(rec["s2"] - rec["s1"] * rec["s1"] / n, 0.0) / (n - 1.0)
+        rel = (np.sqrt(v / n) / 4.0) / (np.maximum(m, 0.0) + F64(F32(floor)))
+    return np.where(rec["n"] >= 2, rel, -1.0).astype(F32)
+
+
+def unit_of(W, H, owners, unit_slots):
+    """per pixel: (owner, unit of the owner, pixel block of the owner)"""
+    ys, xs = np.mgrid[0:H, 0:W]
+    owner, slot = TileLayout(W, H, owners).owner_and_slot(xs, ys)
+    return owner, slot // unit_slots, slot // 64
+
+
+def restate(records, W, H, owners, unit_slots, target, allowance, passes=PASSES, min_passes=16, every=4):
+    """-> the pass every pixel's unit retired at (0: still active after `passes`)"""
+    owner, unit, block = unit_of(W, H, owners, unit_slots)
+    ukey = owner.astype(np.int64) * (1 << 32) + unit
+    bkey = owner.astype(np.int64) * (1 << 32) + block
+    retired = np.zeros((H, W), np.int64)
+    for P in range(4 * every, passes + 1, 4 * every):
+        if P < min_passes:
+            continue
+        rec = records[P // 4]
+        loud = (rec["n"] < 2) | (rel32(rec) > F32(target))
+        for u in np.unique(ukey[retired == 0]):
+            inside = ukey == u
+            quiet = all(loud[inside & (bkey == b)].sum() <= allowance for b in np.unique(bkey[inside]))
+            if quiet:
+                retired[inside] = P
+    return retired
+
+
+def expected(frames, records, retired, P=PASSES):
+    frame, rec = frames[P // 4].copy(), records[P // 4].copy()
+    for p in np.unique(retired[retired > 0]):
+        at = retired == p
+        f = F32(F64(P) / F64(p))
+        frame[at] = frames[p // 4][at] * f
+        rec[at] = records[p // 4][at]
+    return frame, rec, np.where(retired > 0, retired, P).astype(np.uint32)
+
+
+def median_target(records, W, H, unit_slots):
+    """the median of the units' worst relative error at pass 16"""
+    _, unit, _ = unit_of(W, H, 1, unit_slots)
+    rel = rel32(records[4])
+    assert (records[4]["n"] >= 2).all()
+    return float(F32(np.median([rel[unit == u].max() for u in np.unique(unit)])))
+
+
+HIP = None
+
+
+def tile_frame(parts, W, H):
+    """the owners' tile buffers, composed on the host"""
+    global HIP
+    HIP = HIP or C.CDLL("libamdhip64.so")
+    layout = TileLayout(W, H, len(parts))
+    g = np.zeros((len(parts), layout.slots_per_owner, 4), F32)
+    for i, p in enumerate(parts):
+        p.wait()
+        ptr, nbytes = p.tile_buffer()
+        assert nbytes == g[i].nbytes
+        assert HIP.hipMemcpy(g[i].ctypes.data_as(C.c_void_p), C.c_void_p(ptr), C.c_size_t(nbytes), C.c_int(2)) == 0
+    return layout.compose(g)
+
+
+def run(sc, W, H, cuts, owners, adaptive, **kw):
+    parts = [HipRenderer(sc, W, H, spp=4, seed=SEED, noise=True, adaptive=adaptive, tile_index=i, tile_count=owners, **kw) for i in range(owners)]
+    try:
+        rec, plane = np.zeros((H, W), NOISE_MOMENTS), np.zeros((H, W), np.uint32)
+        state = {}
+        for p in parts:
+            for c in cuts:
+                p.render(c)
+            p.noise_moments(out=rec)
+            p.adapt_passes(out=plane)
+            s = p.adapt_state()
+            for k, v in s.items():  # (the owners' counts add; an owner without a tile decides nothing)
+                state[k] = max(state.get(k, 0), v) if k in ("lastDecisionPass", "unitSlots") else state.get(k, 0) + v
+        frame = parts[0].radiance().copy() if owners == 1 else tile_frame(parts, W, H)
+        return frame, rec, plane, state
+    finally:
+        for p in parts:
+            p.close()
+
+
+def unit_slots_of(sc, W, H, **kw):
+    with HipRenderer(sc, W, H, spp=4, seed=SEED, noise=True, adaptive=True, **kw) as r:
+        return r.adapt_state()["unitSlots"]
+
+
+@pytest.mark.parametrize("nosplit", [False, True], ids=["split", "nosplit"])
+@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("build", list(BUILDS))
+def test_frame_records_pass_plane_and_state_are_the_restatement_bit_for_bit(the_scenes, build, case, nosplit):
+    key, W, H = CASES[case]
+    sc = the_scenes[key]
+    kw = dict(BUILDS[build], flags=capi.KAJO_FLAG_NO_SPLIT if nosplit else 0)
+    frames, records, _ = twin(sc, key, W, H, kw)
+    slots = unit_slots_of(sc, W, H, **kw)
+    target = median_target(records, W, H, slots)
+    for allowance in (0, 8):
+        params = dict(target=target, floor=FLOOR, allowance=allowance)
+        for owners in (1, 3):
+            retired = restate(records, W, H, owners, slots, target, allowance)
+            if allowance == 0:
+                assert (retired == 16).any() and (retired == 0).any(), (case, np.unique(retired))
+            frame, rec, plane = expected(frames, records, retired)
+            before = restate(records, W, H, owners, slots, target, allowance, passes=16)
+            paths = 4 * 16 * (W * H + int((before == 0).sum()))
+            composed = {}
+            for cuts in CUTS:
+                got = run(sc, W, H, cuts, owners, params, **kw)
+                why = (build, case, nosplit, allowance, owners, cuts)
+                assert np.array_equal(u32(got[0]), u32(frame)), why
+                assert same_records(got[1], rec), why
+                assert np.array_equal(got[2], plane), why
+                s = got[3]
+                assert (s["pixels"], s["activePixels"], s["paths"], s["unitSlots"]) == (W * H, int((retired == 0).sum()), paths, slots), (why, s)
+                # (a handle whose units have all retired decides nothing more)
+                assert s["lastDecisionPass"] == (PASSES if (before == 0).any() else 16), (why, s)
+                composed[owners] = s
+            if owners == 3:
+                one = run(sc, W, H, (PASSES,), 1, params, **kw)[3]
+                assert (composed[3]["units"], composed[3]["activeUnits"]) == (one["units"], one["activeUnits"]), (composed[3], one)
+            else:
+                # the units the image does not reach retire at the first decision; those it reaches, by the restatement
+                _, unit, _ = unit_of(W, H, 1, slots)
+                assert composed[1]["activeUnits"] == len(np.unique(unit[retired == 0])), (composed[1], case)
+
+
+def test_retired_slots_are_extended_behind_every_launch_not_only_at_boundaries(the_scenes):
+    sc, (W, H) = the_scenes["spheres"], (41, 23)
+    frames, records, _ = twin(sc, "spheres", W, H, dict(exact=True))
+    slots = unit_slots_of(sc, W, H, exact=True)
+    target = median_target(records, W, H, slots)
+    retired = restate(records, W, H, 1, slots, target, 0, passes=16)
+    with HipRenderer(sc, W, H, spp=4, seed=SEED, noise=True, exact=True) as t:
+        at18 = t.render(18).radiance().copy()
+    with HipRenderer(sc, W, H, spp=4, seed=SEED, noise=True, exact=True, adaptive=dict(target=target)) as r:
+        got = r.render(16).render(2).radiance()
+        plane = r.adapt_passes()
+        assert r.adapt_state()["lastDecisionPass"] == 16
+    want = np.where((retired > 0)[..., None], frames[4] * F32(F64(18) / F64(16)), at18)
+    assert (retired > 0).any() and (retired == 0).any()
+    assert np.array_equal(u32(got), u32(want))
+    assert np.array_equal(plane, np.where(retired > 0, 16, 18))
+
+
+@pytest.mark.parametrize("nosplit", [False, True], ids=["split", "nosplit"])
+def test_with_everything_retired_no_render_kernel_is_launched_and_the_image_stands(the_scenes, nosplit):
+    sc, (W, H) = the_scenes["spheres"], (100, 75)
+    kw = dict(exact=True, flags=capi.KAJO_FLAG_NO_SPLIT if nosplit else 0)
+    with HipRenderer(sc, W, H, spp=4, seed=SEED, noise=True, adaptive=dict(target=HUGE), **kw) as r:
+        r.render(16)
+        s = r.adapt_state()
+        assert (s["activeUnits"], s["activePixels"], s["lastDecisionPass"]) == (0, 0, 16) and s["units"] > 0
+        image, launches, frame = r.argb8().copy(), r.counters()["launches"], r.radiance().copy()
+        assert launches == 4
+        r.render(16)
+        c = r.counters()
+        assert (c["launches"], c["passes"]) == (launches, 32)
+        after = r.argb8()
+        channels = lambda a: np.stack([(a >> k) & 255 for k in (0, 8, 16, 24)], -1).astype(np.int64)
+        assert np.abs(channels(after) - channels(image)).max() <= 1
+        assert np.array_equal(u32(r.radiance()), u32(frame * F32(2)))
+        assert (r.adapt_passes() == 16).all()
+        s = r.adapt_state()
+        assert (s["paths"], s["lastDecisionPass"]) == (4 * 16 * W * H, 16)
+        # reset: every unit active again, and the rule may be given anew
+        r.reset()
+        s = r.adapt_state()
+        assert (s["activeUnits"], s["activePixels"], s["paths"], s["lastDecisionPass"]) == (s["units"], W * H, 0, 0)
+        r.set_adaptive(dict(target=TINY))
+        r.render(16)
+        assert np.array_equal(u32(r.radiance()), u32(frame))
+        with pytest.raises(capi.KajoError) as e:
+            r.set_adaptive(dict(target=HUGE))
+        assert e.value.code == capi.KAJO_E_STATE
+        with pytest.raises(capi.KajoError) as e:
+            r.set_pass_count(8)
+        assert e.value.code == capi.KAJO_E_STATE and r.counters()["passes"] == 16
+
+
+@pytest.mark.parametrize("build", list(BUILDS))
+@pytest.mark.parametrize("rule", ["unmet", "unset"])
+def test_a_target_nothing_meets_or_no_rule_at_all_is_the_noise_twin(the_scenes, build, rule):
+    sc, (W, H) = the_scenes["spheres"], (100, 75)
+    frames, records, launches = twin(sc, "spheres", W, H, BUILDS[build])
+    with HipRenderer(sc, W, H, spp=4, seed=SEED, noise=True, adaptive=dict(target=TINY) if rule == "unmet" else True, **BUILDS[build]) as r:
+        for c in (4,) * 8:
+            r.render(c)
+        assert np.array_equal(u32(r.radiance()), u32(frames[8])) and same_records(r.noise_moments(), records[8])
+        assert r.counters()["launches"] == launches
+        s = r.adapt_state()
+        assert s["activePixels"] == W * H and s["lastDecisionPass"] == (32 if rule == "unmet" else 0) and (r.adapt_passes() == 32).all()
+
+
+def test_the_aov_buffers_are_those_of_a_plain_handle(the_scenes):
+    sc, (W, H) = the_scenes["spheres"], (41, 23)
+    frames, records, _ = twin(sc, "spheres", W, H, dict(exact=True))
+    target = median_target(records, W, H, unit_slots_of(sc, W, H, exact=True))
+    with HipRenderer(sc, W, H, spp=4, seed=SEED, exact=True, aov=True) as plain:
+        want = plain.render(32).aov()
+    with HipRenderer(sc, W, H, spp=4, seed=SEED, exact=True, aov=True, noise=True, adaptive=dict(target=target)) as r:
+        got = r.render(32).aov()
+        s = r.adapt_state()
+        assert 0 < s["activeUnits"] < s["units"]
+    assert np.array_equal(u32(got["raw"][0]), u32(want["raw"][0])) and np.array_equal(u32(got["raw"][1]), u32(want["raw"][1]))
+
+
+def test_a_nan_in_the_accumulation_does_not_keep_its_unit_from_retiring(the_scenes):
+    sc, (W, H) = the_scenes["spheres"], (41, 23)
+    x, y = 17, 9
+    hip = C.CDLL("libamdhip64.so")
+    with HipRenderer(sc, W, H, spp=4, seed=SEED, exact=True, noise=True, adaptive=dict(target=HUGE)) as r:
+        r.render(8).wait()
+        _, slot = TileLayout(W, H, 1).owner_and_slot(x, y)
+        ptr, nbytes = r.tile_buffer()
+        assert 0 <= int(slot) * 16 + 16 <= nbytes
+        nan = np.full(4, np.nan, F32)
+        assert hip.hipMemcpy(C.c_void_p(ptr + int(slot) * 16), nan.ctypes.data_as(C.c_void_p), C.c_size_t(16), C.c_int(1)) == 0
+        r.render(8)
+        rec = r.noise_moments()
+        assert (rec["bad"][y, x], rec["n"][y, x]) == (2, 2)
+        s = r.adapt_state()
+        assert s["activeUnits"] == 0 and s["lastDecisionPass"] == 16
+        assert r.adapt_passes()[y, x] == 8
+
+
+# ---- the driver: hip::Scheduler's real gather path ------------------------------------------------------------------------------------
+
+import json  # noqa: E402
+import os  # noqa: E402
+import subprocess  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "kajo_amd", "host", "kajo_render")
+
+
+def driver(tmp_path, name, *extra):
+    out = str(tmp_path / (name + ".png"))
+    cmd = [BIN, "-w", "96", "-h", "54", "-r", "hip", "--spp", "4", "-o", out, "--json", "--sample-map", str(tmp_path / (name + ".pfm")), *extra]
+    p = subprocess.run(cmd + [os.path.join(ROOT, "kajo_amd", "data", "caustics.json")], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr
+    return json.loads(p.stdout.strip().splitlines()[-1]), open(out, "rb").read(), open(str(tmp_path / (name + ".pfm")), "rb").read()
+
+
+@pytest.mark.skipif(not os.path.exists(BIN), reason="kajo_render not built")
+def test_driver_adaptive_one_gpu_and_three_owners_write_the_same_image_and_sample_map(tmp_path):
+    # a target from the frame's own estimate: the 0.5 quantile of the relative error at 32 passes, so that some units retire and others do not
+    # (--batch 16 everywhere: the scheduler's own refreshes follow measured time, and a run that ends because no unit is active ends at a
+    # refresh; with fixed refreshes the pass a run ends at is the same for any number of owners)
+    probe, _, _ = driver(tmp_path, "p", "--adaptive", "1e-30", "--max-passes", "32", "--noise-quantile", "0.5", "--batch", "16")
+    E = probe["noise_quantile_value"]
+    assert E > 0 and probe["passes"] == 32 and probe["adaptive_stopped_at_pass"] == 0 and probe["adaptive_units"] > 0
+    one, png1, map1 = driver(tmp_path, "a", "--adaptive", repr(E), "--max-passes", "64", "--batch", "16")
+    three, png3, map3 = driver(tmp_path, "b", "--adaptive", repr(E), "--max-passes", "64", "--batch", "16", "--gpus", "3", "--same-device")
+    assert png1 == png3 and map1 == map3
+    for k in ("passes", "adaptive_active_units", "adaptive_units", "adaptive_paths", "adaptive_stopped_at_pass"):
+        assert one[k] == three[k], (k, one[k], three[k])
+    # (the first holds for any target: at 96x54 the units the image does not reach retire at pass 16. The second is the one that shows a
+    # retirement inside the image: fewer camera paths than pixels * n^2 * passes)
+    assert one["adaptive_active_units"] < one["adaptive_units"] and 0 < one["adaptive_paths"] < 96 * 54 * 4 * one["passes"]
+    plane = np.frombuffer(map1[-96 * 54 * 4:], "<f4")
+    assert plane.max() == one["passes"] or one["adaptive_stopped_at_pass"] == one["passes"]
+    assert (plane % 16 == 0).all() or plane.max() == one["passes"]
+    # with a target everything meets the run ends at the first refresh behind the first decision; with --until-noise too, whichever rule ends first
+    # (--batch 4: the scheduler looks at the states after every batch)
+    done, _, _ = driver(tmp_path, "c", "--adaptive", "1e30", "--until-noise", "1e-30", "--batch", "4")
+    assert (done["passes"], done["adaptive_stopped_at_pass"], done["adaptive_active_units"], done["noise_stopped_at_pass"]) == (16, 16, 0, 0)
