@@ -374,8 +374,29 @@ int kajo_hip_compose_aov(kajo_hip_t h, const void* gatheredAov, const void* gath
    accumulation, the AOV buffers, the pass count and the counters (kernelMs included) are not touched. Scratch (three float4 frames and
    one ARGB8 frame) is allocated on the first call and freed by kajo_hip_destroy.
    KAJO_E_INVALID: a NULL handle or params, iterations outside 0..8, a negative or non-finite sigma. KAJO_E_STATE: a handle created
-   without KAJO_FLAG_AOV, or with no pass rendered. */
+   without KAJO_FLAG_AOV, or with no pass rendered.
+   NOISE-GUIDED (KAJO_DENOISE_NOISE_GUIDED in flags, iterations >= 1; kajo_amd/csrc/denoise_guided.cpp): the filter above word for word --
+   the counted pixels, the guides, g(v), the taps, the weights, the NaN repair, the remodulation and .w -- with another v0: the MEASURED
+   variance of the pixel where there is one (SVGF steers this weight by the measured per-pixel variance and keeps the spatial estimate
+   for pixels without history). For a counted pixel p let m and se be the float32 words kajo_hip_noise returns for p in its mean and
+   stderror planes ("The noise estimate" below: its evaluation in binary64, rounded to float32). p is MEASURED when se >= 0 (n >= 2) and
+   m > 0; then
+     r = se / m;   t = r * l(e_0(p));   v0(p) = t * t          three float32 operations, not contracted
+   the relative error of the luminance carried over to the (demodulated) colour: exact where the albedo is grey, an approximation
+   elsewhere (the estimate is of the luminance of the radiance, the filter's l of radiance / albedo per channel). If that v0 is not
+   finite, p is not measured. A pixel that is not measured -- black in every batch (m = 0), fewer than two whole batches, a frame of
+   fewer than 8 passes -- takes the 3x3 spatial variance above, by the plain filter's expressions in their order: a handle on which no
+   pixel is measured gives the plain filter's output bit for bit. As se goes to 0 the luminance weight between pixels of different
+   luminance goes to 0: a converged frame is left alone. The records always describe the ACCUMULATION, also where the frame being
+   filtered is a despeckled, staged one (kajo_hip_present_argb8 and the chains behind it).
+   Where m and se come from: (b) the planes of kajo_hip_denoise_guide_planes while they are of the handle's pass count, else (a) the
+   handle's own records, evaluated on the device as kajo_hip_noise evaluates them -- a handle created with KAJO_FLAG_NOISE that owns the
+   whole frame (tileCount == 1; an adaptive handle too: retired slots keep their records). The output does not depend on which of the
+   two supplied the words. KAJO_E_STATE, from every entry point that takes `denoise`, where neither is at hand: the handle was created
+   without the noise flag, the uploaded planes are for another pass count, or the handle holds the records of part of the frame only.
+   With iterations == 0 the flag is ignored, as demodulation is. Flag bits other than 1 and 2 are ignored. */
 #define KAJO_DENOISE_NO_DEMODULATE 1u /* filter the mean radiance itself instead of radiance / albedo */
+#define KAJO_DENOISE_NOISE_GUIDED 2u  /* v0 from the measured per-pixel variance of KAJO_FLAG_NOISE where there is one (above) */
 typedef struct KajoDenoiseParams {
     int32_t iterations;   /* K, 0..8 (default 5) */
     uint32_t flags;       /* KAJO_DENOISE_* (default 0) */
@@ -386,6 +407,14 @@ typedef struct KajoDenoiseParams {
 } KajoDenoiseParams;
 void kajo_hip_default_denoise_params(KajoDenoiseParams* p); /* NULL is accepted */
 int kajo_hip_denoise(kajo_hip_t h, const KajoDenoiseParams* p, float* radiance, uint32_t* argb8);
+/* The noise-guided filter's m and se for a handle that does not hold the whole frame's records: the root of several owners, which has the
+   composed frame and the composed AOVs (KAJO_FLAG_AOV_TILED) but only its own tiles' records. mean, stderror: HOST pointers to
+   WHOLE-FRAME row-major planes of width*height floats, as every owner's kajo_hip_noise fills them into the same arrays. They are copied
+   into device memory (allocated on the first call, freed by kajo_hip_destroy) and stamped with the handle's current pass count; they
+   take precedence over the handle's own records while that stamp equals the pass count, and are dropped by NULL, NULL, kajo_hip_reset
+   and kajo_hip_set_pass_count. KAJO_E_INVALID, before the handle is looked at, for exactly one NULL plane; KAJO_E_INVALID for a NULL
+   handle. Waits. */
+int kajo_hip_denoise_guide_planes(kajo_hip_t h, const float* mean, const float* stderror);
 
 /* Exposure, tone curves and automatic exposure in the image resolve: a post-process over the handle's whole frame, in kernels of its own
    (kajo_amd/csrc/tonemap.inc.hip) on the handle's stream, compiled into each numerics build so that the mean and the display transform are

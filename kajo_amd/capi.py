@@ -43,6 +43,7 @@ KAJO_NOISE_BATCH_PASSES = 4  # a batch of the noise estimate: passes 4b-3 .. 4b 
 KAJO_NOISE_HIST_WORDS = 516  # the meter's 514 bins over the relative error, the unknown pixels, the pixels with a bad batch
 KAJO_MATTE_SLOTS = 8
 KAJO_DENOISE_NO_DEMODULATE = 1  # KajoDenoiseParams.flags: filter the mean radiance itself, not radiance / albedo
+KAJO_DENOISE_NOISE_GUIDED = 2  # KajoDenoiseParams.flags: v0 from the measured variance of KAJO_FLAG_NOISE where there is one
 KAJO_TONE_CLAMP, KAJO_TONE_REINHARD, KAJO_TONE_ACES = 0, 1, 2  # KajoToneParams.curve
 KAJO_TONE_AUTO_EXPOSURE = 1  # KajoToneParams.flags: scale the frame's log-average luminance to `key`
 KAJO_METER_BINS = 514  # words of a luminance histogram (kajo_hip_meter): bin 0 below 2^-16, 1..512 sixteen per stop, 513 from 2^16 up
@@ -79,6 +80,7 @@ EXPORTS = [
     "kajo_hip_default_noise_params", "kajo_hip_noise_evaluate", "kajo_hip_noise", "kajo_hip_read_noise_moments",
     "kajo_hip_default_adapt_params", "kajo_hip_set_adaptive", "kajo_hip_adapt_state", "kajo_hip_adapt_passes", "kajo_hip_adapt_evaluate",
     "kajo_hip_adapt_order",
+    "kajo_hip_denoise_guide_planes",
 ]
 
 
@@ -352,6 +354,8 @@ def lib():
             L.kajo_hip_noise.argtypes = [C.c_void_p, C.POINTER(KajoNoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(KajoNoiseResult)]
             L.kajo_hip_read_noise_moments.argtypes = [C.c_void_p, C.c_void_p]
+        if hasattr(L, "kajo_hip_denoise_guide_planes"):  # (nor the noise-guided denoiser)
+            L.kajo_hip_denoise_guide_planes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(L, "kajo_hip_set_adaptive"):  # (nor adaptive sampling)
             L.kajo_hip_default_adapt_params.argtypes = [C.POINTER(KajoAdaptParams)]
             L.kajo_hip_default_adapt_params.restype = None

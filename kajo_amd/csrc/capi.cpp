@@ -58,6 +58,9 @@ int kajo_aov_strict_set_lds(int instance, size_t lds);
 int kajo_denoise_launch(const void* src, const TileMap* map, int fromTiles, const void* albedoHits, const void* normalDepth, float passes,
                         float samples, int iterations, int demodulate, float sigmaLuminance, float sigmaNormal, float sigmaDepth, void* scratch, void** result,
                         void* stream);
+int kajo_denoise_guided_launch(const void* src, const TileMap* map, int fromTiles, const void* albedoHits, const void* normalDepth, float passes,
+                               float samples, int iterations, int demodulate, float sigmaLuminance, float sigmaNormal, float sigmaDepth,
+                               const void* records, const void* mean, const void* stdError, void* scratch, void** result, void* stream);
 int kajo_glare_plan(int W, int H, int levels, size_t* pixels);
 int kajo_glare_launch(const void* src, const TileMap* map, int fromTiles, float passes, int n, float strength, float threshold, void* scratch,
                       void* out, void* stream);
@@ -270,6 +273,10 @@ struct KajoHip
     DeviceBuffer matteScratch;
     // the denoiser's scratch (denoise.hip; kajo_hip_denoise), on its first call: float4 [3][W * H] (guide, two colour frames) + uint32 [W * H]
     DeviceBuffer denoise;
+    // the noise-guided denoiser's uploaded planes (denoise_guided.cpp; kajo_hip_denoise_guide_planes), on the first upload: float [2][W * H],
+    // m then se of the whole frame; guideStamp: the pass count they were uploaded at, -1 = none
+    DeviceBuffer guidePlanes;
+    int guideStamp = -1;
     // tone mapping (tonemap.inc.hip; kajo_hip_tonemap_*), on its first call: the scale word + the logavg partials (toneLaunch)
     DeviceBuffer tone;
     // glare (glare.hip; kajo_hip_glare, kajo_hip_display_*), on its first call: the pyramid of kajo_glare_plan at the most levels, then
@@ -659,7 +666,7 @@ const char* kajo_hip_version(void)
 {
     // (a comma, not a semicolon, in front of "view": tests/test_lens_cpu.py looks for "lens" in the LAST ';'-separated field, so the
     // stages added after the lens join that field; the next stage appends ", name" likewise)
-    return "kajo-hip 0.1 (gfx950; aov-matte; local; aov-tiled; lens, view, grade)";
+    return "kajo-hip 0.1 (gfx950; aov-matte; local; aov-tiled; lens, view, grade, denoise-guided)";
 }
 
 void kajo_hip_default_params(KajoParams* p)
@@ -1300,6 +1307,7 @@ int kajo_hip_reset(kajo_hip_t h)
     h->aovComposed = h->matteComposed = false;
     h->aovPasses = 0;
     h->passesDone = 0;
+    h->guideStamp = -1;
     h->carryValid = false;
     h->frameValid = false;
     h->kernelMs = 0.0;
@@ -1328,6 +1336,7 @@ int kajo_hip_set_pass_count(kajo_hip_t h, int passesDone)
         h->noiseRebase = true;
     }
     h->passesDone = passesDone;
+    h->guideStamp = -1;
     h->carryValid = false; // (a group in progress is not known apart from the buffer the caller declares: include/kajo_hip.h)
     h->frameValid = false;
     return KAJO_OK;
@@ -1558,6 +1567,12 @@ void kajo_hip_default_denoise_params(KajoDenoiseParams* p)
 namespace
 {
 
+// the planes of kajo_hip_denoise_guide_planes describe the frame as it stands
+bool guidePlanesValid(const KajoHip* h)
+{
+    return h->guidePlanes && h->guideStamp >= 0 && h->guideStamp == h->passesDone;
+}
+
 // kajo_hip_denoise's refusals of the parameters (before the handle is looked at) and of the handle
 int checkDenoise(kajo_hip_t h, const KajoDenoiseParams* p)
 {
@@ -1578,6 +1593,14 @@ int checkDenoise(kajo_hip_t h, const KajoDenoiseParams* p)
     // (tiled AOVs on an owner of part of the frame: the frame to filter is the composed one)
     if (h->map.tileCount != 1 && !h->frameValid)
         return fail(KAJO_E_STATE, "whole-frame output needs kajo_hip_compose() when tileCount > 1");
+    // the noise-guided filter needs every pixel's m and se: uploaded planes of this pass count, or the records of the frame's one owner
+    if ((p->flags & KAJO_DENOISE_NOISE_GUIDED) && p->iterations >= 1 && !guidePlanesValid(h) && !(h->noise && h->map.tileCount == 1)) {
+        if (h->guideStamp >= 0)
+            return fail(KAJO_E_STATE, "noise-guided denoise: the uploaded guide planes are for another pass count");
+        if (!h->noise)
+            return fail(KAJO_E_STATE, "noise-guided denoise: the handle was created without the noise flag and no guide planes are uploaded");
+        return fail(KAJO_E_STATE, "noise-guided denoise: the handle holds the records of part of the frame only and no guide planes are uploaded");
+    }
     return KAJO_OK;
 }
 
@@ -1600,10 +1623,22 @@ int denoiseFrame(KajoHip* h, const KajoDenoiseParams* p, void** out, const Image
             HIP_TRY(hipMemcpyAsync(*out, img.src, count * 16, hipMemcpyDeviceToDevice, h->stream));
     } else {
         const long long samples = std::max(aovSamples(h), 1LL);
-        hipError_t le = (hipError_t)kajo_denoise_launch(img.src, &h->map, img.fromTiles ? 1 : 0, h->aov.p, h->aov.as<char>() + count * 16,
+        hipError_t le;
+        if (p->flags & KAJO_DENOISE_NOISE_GUIDED) {
+            // (checkDenoise has seen one of the two sources at hand; the planes come first. The records describe the accumulation, also
+            // where the frame to filter is a staged one)
+            const bool planes = guidePlanesValid(h);
+            const float* m = planes ? h->guidePlanes.as<float>() : nullptr;
+            le = (hipError_t)kajo_denoise_guided_launch(img.src, &h->map, img.fromTiles ? 1 : 0, h->aov.p, h->aov.as<char>() + count * 16,
                                                         (float)h->passesDone, (float)samples, p->iterations,
                                                         (p->flags & KAJO_DENOISE_NO_DEMODULATE) ? 0 : 1, p->sigmaLuminance, p->sigmaNormal,
-                                                        p->sigmaDepth, scratch, out, h->stream);
+                                                        p->sigmaDepth, planes ? nullptr : h->noiseMoments.p, m, planes ? m + count : nullptr, scratch,
+                                                        out, h->stream);
+        } else
+            le = (hipError_t)kajo_denoise_launch(img.src, &h->map, img.fromTiles ? 1 : 0, h->aov.p, h->aov.as<char>() + count * 16,
+                                                 (float)h->passesDone, (float)samples, p->iterations,
+                                                 (p->flags & KAJO_DENOISE_NO_DEMODULATE) ? 0 : 1, p->sigmaLuminance, p->sigmaNormal,
+                                                 p->sigmaDepth, scratch, out, h->stream);
         if (le != hipSuccess)
             return failHip(le, "denoise kernel launch");
     }
@@ -1769,6 +1804,30 @@ int kajo_hip_denoise(kajo_hip_t h, const KajoDenoiseParams* p, float* radiance, 
     if (radiance)
         HIP_TRY(hipMemcpyAsync(radiance, out, count * 16, hipMemcpyDeviceToHost, h->stream));
     return kajo_hip_wait(h);
+}
+
+int kajo_hip_denoise_guide_planes(kajo_hip_t h, const float* mean, const float* stderror)
+{
+    if ((mean == nullptr) != (stderror == nullptr))
+        return fail(KAJO_E_INVALID, "guide planes: mean and stderror are given together or not at all");
+    if (!h)
+        return fail(KAJO_E_INVALID, "null handle");
+    if (!mean) {
+        h->guideStamp = -1;
+        return KAJO_OK;
+    }
+    int rc = bind(h);
+    if (rc)
+        return rc;
+    const size_t plane = (size_t)h->W * h->H * sizeof(float);
+    h->guideStamp = -1;
+    HIP_TRY(h->guidePlanes.ensure(2 * plane));
+    HIP_TRY(hipMemcpyAsync(h->guidePlanes.p, mean, plane, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->guidePlanes.as<char>() + plane, stderror, plane, hipMemcpyHostToDevice, h->stream));
+    if ((rc = kajo_hip_wait(h)))
+        return rc;
+    h->guideStamp = h->passesDone;
+    return KAJO_OK;
 }
 
 void kajo_hip_default_tone_params(KajoToneParams* p)

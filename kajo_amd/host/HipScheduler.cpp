@@ -92,7 +92,27 @@ struct Scheduler::Impl
     // Options::local changes the frame (include/kajo_hip.h: with compression 1 and detail 1 the output is the input)
     bool localActive() const { return opt.localOn && !(opt.local.compression == 1.0f && opt.local.detail == 1.0f); }
     // Options::noise / noiseTarget: the handles keep the batch moments (KAJO_FLAG_NOISE)
-    bool noiseOn() const { return opt.noise || opt.noiseTarget > 0.0f || adaptiveOn(); }
+    bool noiseOn() const { return opt.noise || opt.noiseTarget > 0.0f || adaptiveOn() || opt.denoiseNoiseGuided; }
+    // Options::denoiseNoiseGuided: the denoise parameters of a read with the flag set (*store); with several owners the whole frame's m and
+    // se from all of them, as readNoise fills them, on the first handle
+    std::vector<float> guideMean, guideSe;
+    const KajoDenoiseParams* guided(const KajoDenoiseParams* in, KajoDenoiseParams* store)
+    {
+        if (!opt.denoiseNoiseGuided || !in)
+            return in;
+        *store = *in;
+        store->flags |= KAJO_DENOISE_NOISE_GUIDED;
+        if (handles.size() > 1 && store->iterations >= 1) {
+            const size_t n = (size_t)image->width * image->height;
+            guideMean.assign(n, 0.0f);
+            guideSe.assign(n, -1.0f);
+            const KajoNoiseParams p = noiseParams();
+            for (kajo_hip_t h : handles)
+                check(kajo_hip_noise(h, &p, guideMean.data(), guideSe.data(), nullptr, nullptr, nullptr, nullptr), "kajo_hip_noise");
+            check(kajo_hip_denoise_guide_planes(handles[0], guideMean.data(), guideSe.data()), "kajo_hip_denoise_guide_planes");
+        }
+        return store;
+    }
     // Options::adaptiveTarget: the handles retire converged units (KAJO_FLAG_ADAPTIVE)
     bool adaptiveOn() const { return opt.adaptiveTarget > 0.0f; }
     KajoAdaptState adaptState{}; // the owners' states added, at the last refresh
@@ -214,6 +234,8 @@ struct Scheduler::Impl
             throw std::runtime_error("hip::Scheduler: grade regions need the coverage mattes (aov = true, matte = true)");
         if (opt.gradeOn && opt.grade.nRegions > 0 && opt.gpus != 1 && !opt.aovTiled)
             throw std::runtime_error("hip::Scheduler: grade regions with more than one GPU need aovTiled");
+        if (opt.denoiseNoiseGuided && !opt.aov)
+            throw std::runtime_error("hip::Scheduler: denoiseNoiseGuided steers the denoiser, which needs the AOVs (aov = true)");
         if (opt.aov && opt.gpus != 1 && !opt.aovTiled)
             throw std::runtime_error("hip::Scheduler: first-hit AOVs need the whole frame on one GPU (gpus = 1)");
         if (opt.sameDevice && opt.gather != Options::Copy)
@@ -565,19 +587,19 @@ void Scheduler::readMatteMask(const int32_t* objects, int n, float* mask, float*
 void Scheduler::readDenoised(const KajoDenoiseParams* params, float* radiance, uint32_t* argb8)
 {
     Impl& d = *m_impl;
-    KajoDenoiseParams p;
+    KajoDenoiseParams p, g;
     kajo_hip_default_denoise_params(&p);
     d.composeAov();
-    check(kajo_hip_denoise(d.handles[0], params ? params : &p, radiance, argb8), "kajo_hip_denoise");
+    check(kajo_hip_denoise(d.handles[0], d.guided(params ? params : &p, &g), radiance, argb8), "kajo_hip_denoise");
 }
 
 void Scheduler::readDenoisedTonemapped(const KajoDenoiseParams* params, const KajoToneParams* tone, uint32_t* argb8, float* scale)
 {
     Impl& d = *m_impl;
-    KajoDenoiseParams p;
+    KajoDenoiseParams p, g;
     kajo_hip_default_denoise_params(&p);
     d.composeAov();
-    check(kajo_hip_tonemap_argb8(d.handles[0], tone ? tone : &d.opt.tone, params ? params : &p, argb8, scale), "kajo_hip_tonemap_argb8");
+    check(kajo_hip_tonemap_argb8(d.handles[0], tone ? tone : &d.opt.tone, d.guided(params ? params : &p, &g), argb8, scale), "kajo_hip_tonemap_argb8");
 }
 
 void Scheduler::readDisplayed(const KajoDenoiseParams* denoise, const KajoGlareParams* glare, const KajoToneParams* tone, uint32_t* argb8, float* scale)
@@ -587,8 +609,11 @@ void Scheduler::readDisplayed(const KajoDenoiseParams* denoise, const KajoGlareP
         check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
         d.composed = true;
     }
-    if (denoise)
+    KajoDenoiseParams g;
+    if (denoise) {
         d.composeAov();
+        denoise = d.guided(denoise, &g);
+    }
     check(kajo_hip_display_argb8(d.handles[0], denoise, glare ? glare : &d.opt.glare, tone ? tone : &d.opt.tone, argb8, scale), "kajo_hip_display_argb8");
 }
 
@@ -608,6 +633,8 @@ void Scheduler::readPresented(const KajoDespeckleParams* despeckle, const KajoDe
     }
     if (denoise || d.opt.lensOn || (d.opt.gradeOn && d.opt.grade.nRegions > 0))
         d.composeAov();
+    KajoDenoiseParams guidedDenoise;
+    denoise = d.guided(denoise, &guidedDenoise);
     if (d.opt.gradeOn) {
         KajoGradeParams grade;
         d.gradeParams(despeckle, denoise, &grade);
@@ -726,6 +753,20 @@ void Scheduler::readNoise(float* mean, float* stderror, float* relative)
     const KajoNoiseParams p = d.noiseParams();
     for (kajo_hip_t h : d.handles)
         check(kajo_hip_noise(h, &p, mean, stderror, relative, nullptr, nullptr, nullptr), "kajo_hip_noise");
+}
+
+long long Scheduler::denoiseMeasuredPixels()
+{
+    Impl& d = *m_impl;
+    if (!d.opt.denoiseNoiseGuided)
+        throw std::runtime_error("hip::Scheduler: denoiseMeasuredPixels needs Options::denoiseNoiseGuided");
+    const size_t n = (size_t)d.image->width * d.image->height;
+    std::vector<float> m(n, 0.0f), se(n, -1.0f);
+    readNoise(m.data(), se.data(), nullptr);
+    long long measured = 0;
+    for (size_t i = 0; i < n; i++)
+        measured += se[i] >= 0.0f && m[i] > 0.0f ? 1 : 0;
+    return measured;
 }
 
 void Scheduler::readSamplePasses(uint32_t* plane)

@@ -133,6 +133,12 @@ struct Options
     // whichever rule ends first. 0 = off: every run then makes exactly the calls it made without these fields.
     float adaptiveTarget = 0.0f;
     int adaptiveAllowance = 0, adaptiveMinPasses = 0, adaptiveEvery = 0;
+    // The noise-guided denoiser (include/kajo_hip.h KAJO_DENOISE_NOISE_GUIDED): the handles are created with the noise flag, and the
+    // readDenoised*, readDisplayed and readPresented calls that are given denoise parameters (readDenoised*: or take the defaults) set the
+    // flag in them. With more than one GPU (aovTiled) every owner's kajo_hip_noise fills one set of planes, as readNoise does, which go
+    // to the first handle (kajo_hip_denoise_guide_planes) before the filter runs. Off by default: every run then makes exactly the calls
+    // it made without this field.
+    bool denoiseNoiseGuided = false;
 };
 
 struct Statistics
@@ -216,6 +222,9 @@ public:
     // the noise map after run() (Options::noise or noiseTarget; include/kajo_hip.h kajo_hip_noise on every owner, into the same planes):
     // W*H floats each -- mean luminance per pass, its standard error, the relative error -- any may be null. Any number of GPUs, no gather
     void readNoise(float* mean, float* stderror, float* relative);
+    // the pixels the noise-guided denoiser has a measurement for after run() (Options::denoiseNoiseGuided): se >= 0 and m > 0 in the
+    // owners' planes, counted on the host
+    long long denoiseMeasuredPixels();
     // the per-pixel pass count after run() (Options::adaptiveTarget; include/kajo_hip.h kajo_hip_adapt_passes on every owner, into the same
     // plane): W*H words. Any number of GPUs, no gather
     void readSamplePasses(uint32_t* plane);

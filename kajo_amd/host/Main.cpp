@@ -142,7 +142,7 @@ int main(int argc, char** argv)
     opt.passes = 16;
     opt.gpus = 1;
     std::string podPath;
-    bool verbose = false, json = false, threeArg = false, aovSpecular = false, aovTiled = false;
+    bool verbose = false, json = false, threeArg = false, aovSpecular = false, aovTiled = false, denoiseNoiseGuided = false;
     int closeAtEvent = 0;
     bool noPreview = false;
     for (size_t i = 1; i < args.size(); i++) {
@@ -210,6 +210,10 @@ int main(int argc, char** argv)
                         "    --denoise FILE  also write the frame denoised with those AOVs as guides, as a PNG (edge-aware A-trous filter,\n"
                         "                    include/kajo_hip.h kajo_hip_denoise; collects the AOVs; one GPU only, unless --aov-tiled)\n"
                         "    --denoise-iterations K  the filter's iterations, 0..8 (5)\n"
+                        "    --denoise-noise-guided  with --denoise: scale the filter's luminance weight by the measured per-pixel variance of the\n"
+                        "                    noise estimate where there is one (include/kajo_hip.h KAJO_DENOISE_NOISE_GUIDED); keeps the\n"
+                        "                    estimate as --noise-map does (launches are cut at multiples of four passes); one GPU, or any\n"
+                        "                    --gpus with --aov-tiled (--json: denoise_noise_guided, denoise_measured_px)\n"
                         "    --json          print run statistics as one JSON line (with a tone option: the scale applied, tone_scale; with a\n"
                         "                    matte option: matte_samples per pixel and matte_dropped_pixels, the pixels whose table was full; with a\n"
                         "                    meter option: meter_exposure, meter_white, meter_anchor, meter_metered, meter_under, meter_over, meter_stops)\n"
@@ -344,6 +348,7 @@ int main(int argc, char** argv)
         else if (a == "--matte-ids" && more) matteIdsOut = args[++i];
         else if (a == "--denoise" && more) denoiseOut = args[++i];
         else if (a == "--denoise-iterations" && more) denoiseIterations = std::atoi(args[++i].c_str());
+        else if (a == "--denoise-noise-guided") denoiseNoiseGuided = true;
         else if (a == "--json") json = true;
         else if (a == "-v") verbose = true;
         else if (!a.empty() && a[0] != '-') scenePath = a;
@@ -846,6 +851,13 @@ int main(int argc, char** argv)
         }
         opt.aov = true;
     }
+    if (denoiseNoiseGuided) {
+        if (denoiseOut.empty()) {
+            std::cerr << "kajo_render: --denoise-noise-guided needs --denoise: it steers that filter" << std::endl;
+            return 1;
+        }
+        opt.denoiseNoiseGuided = true; // (the handles keep the noise estimate, as with --noise-map)
+    }
 
     scene::Scene scene;
     if (!podPath.empty()) {
@@ -884,6 +896,7 @@ int main(int argc, char** argv)
     hip::Scheduler* hipScheduler = nullptr;
     opt.counters = json;
     long long matteSamples = 0, matteDroppedPixels = 0; // --json with a matte option
+    long long denoiseMeasuredPx = 0;                    // --json with --denoise-noise-guided
     KajoMeterResult metered = {};                       // --json with a meter option: of the image run() wrote
     float localPivotUsed = 0;                           // --json with --local-contrast: of the image run() wrote
     bool localRan = false;
@@ -1011,6 +1024,8 @@ int main(int argc, char** argv)
                 hipScheduler->readDenoised(&p, nullptr, denoised.pixels.get());
             if (!denoised.save(denoiseOut))
                 return 3;
+            if (denoiseNoiseGuided && json)
+                denoiseMeasuredPx = hipScheduler->denoiseMeasuredPixels();
         }
         if (viewGiven && !out.empty()) {
             // (the image -o holds: the display chain as run() left the frame, through the view, at the view's size)
@@ -1092,6 +1107,8 @@ int main(int argc, char** argv)
                         (double)s.noiseQuantileValue, s.noiseKnownPx, s.noiseBadPx, s.noiseStoppedAtPass);
         if (aovTiled)
             std::printf(", \"aov_tiled\": true");
+        if (denoiseNoiseGuided)
+            std::printf(", \"denoise_noise_guided\": true, \"denoise_measured_px\": %lld", denoiseMeasuredPx);
         if (matteGiven)
             std::printf(", \"matte_samples\": %lld, \"matte_dropped_pixels\": %lld", matteSamples, matteDroppedPixels);
         std::printf("}\n");

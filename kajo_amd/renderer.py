@@ -254,26 +254,42 @@ class HipRenderer:
         return mask, dominant
 
     def _denoise_params(self, iterations: int = 5, sigma_luminance: float = None, sigma_normal: float = None, sigma_depth: float = None,
-                        demodulate: bool = True):
+                        demodulate: bool = True, noise_guided: bool = False):
         p = capi.KajoDenoiseParams()
         self._L.kajo_hip_default_denoise_params(C.byref(p))
         p.iterations = int(iterations)
-        p.flags = 0 if demodulate else capi.KAJO_DENOISE_NO_DEMODULATE
+        p.flags = (0 if demodulate else capi.KAJO_DENOISE_NO_DEMODULATE) | (capi.KAJO_DENOISE_NOISE_GUIDED if noise_guided else 0)
         for field, value in (("sigmaLuminance", sigma_luminance), ("sigmaNormal", sigma_normal), ("sigmaDepth", sigma_depth)):
             if value is not None:
                 setattr(p, field, float(value))
         return p
 
     def denoise(self, iterations: int = 5, sigma_luminance: float = None, sigma_normal: float = None, sigma_depth: float = None,
-                demodulate: bool = True) -> dict:
+                demodulate: bool = True, noise_guided: bool = False) -> dict:
         """Edge-aware A-trous denoise of the frame guided by the first-hit AOVs (include/kajo_hip.h kajo_hip_denoise; the handle needs
         aov=True): radiance = (H, W, 4) float32 sums over passes, as radiance(); argb8 = (H, W) uint32, as argb8(). Sigmas left None take
-        kajo_hip_default_denoise_params' values. The accumulation and the AOVs are not touched."""
-        p = self._denoise_params(iterations, sigma_luminance, sigma_normal, sigma_depth, demodulate)
+        kajo_hip_default_denoise_params' values. noise_guided: the luminance weight is scaled by the measured per-pixel variance of the
+        noise estimate where there is one (KAJO_DENOISE_NOISE_GUIDED: the handle needs noise=True and the whole frame, or
+        denoise_guide_planes()). The accumulation, the AOVs and the noise records are not touched."""
+        p = self._denoise_params(iterations, sigma_luminance, sigma_normal, sigma_depth, demodulate, noise_guided)
         radiance = np.empty((self.height, self.width, 4), np.float32)
         argb8 = np.empty((self.height, self.width), np.uint32)
         capi.check(self._L.kajo_hip_denoise(self._h, C.byref(p), radiance.ctypes.data_as(C.c_void_p), argb8.ctypes.data_as(C.c_void_p)))
         return dict(radiance=radiance, argb8=argb8)
+
+    def denoise_guide_planes(self, mean, stderror):
+        """The whole frame's noise planes for the noise-guided denoiser of a handle that holds only part of the records
+        (kajo_hip_denoise_guide_planes): (H, W) float32 mean and stderr as every owner's noise(out=...) fills them, valid until the pass
+        count changes. None, None drops them."""
+        if mean is None and stderror is None:
+            capi.check(self._L.kajo_hip_denoise_guide_planes(self._h, None, None))
+            return
+        m, se = (None if a is None else np.ascontiguousarray(a, np.float32) for a in (mean, stderror))
+        for a in (m, se):
+            if a is not None and a.shape != (self.height, self.width):
+                raise ValueError("guide planes must be (height, width)")
+        capi.check(self._L.kajo_hip_denoise_guide_planes(self._h, None if m is None else m.ctypes.data_as(C.c_void_p),
+                                                         None if se is None else se.ctypes.data_as(C.c_void_p)))
 
     def tonemap(self, curve: str = "clamp", exposure: float = 0.0, white: float = 0.0, auto_exposure: bool = False, key: float = 0.18,
                 denoise: dict = None):
