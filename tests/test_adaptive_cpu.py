@@ -216,6 +216,131 @@ def test_the_filter_under_asan_and_ubsan(tmp_path):
     assert ": ok" in p.stdout
 
 
+# ---- the slot-to-pixel arithmetic is the tile map's inverse, at every tile shape -------------------------------------------------------
+
+SLOT_SOURCE = r"""
+// adaptSlotPixel (adapt_math.h) beside kajoTileSlot (render_args.h) as host code: for every case (W H tileW tileH owners) on the command
+// line, as 32-bit words on stdout: the slots per owner; (owner, slot) of every pixel, row-major, by kajoTileSlot; then for every owner and
+// every slot of its buffer (answer, px, py) by adaptSlotPixel. Map and geometry are filled as kajo_hip_create fills them (capi.cpp).
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "adapt_math.h"
+#include "render_args.h"
+
+int main(int argc, char** argv)
+{
+    for (int a = 1; a + 4 < argc; a += 5) {
+        TileMap m{};
+        m.W = atoi(argv[a]);
+        m.H = atoi(argv[a + 1]);
+        m.tileW = atoi(argv[a + 2]);
+        m.tileH = atoi(argv[a + 3]);
+        m.tileCount = atoi(argv[a + 4]);
+        m.tilesX = (m.W + m.tileW - 1) / m.tileW;
+        const int tilesY = (m.H + m.tileH - 1) / m.tileH, nTiles = m.tilesX * tilesY;
+        const int perOwner = (nTiles + m.tileCount - 1) / m.tileCount;
+        m.slotsPerOwner = perOwner * m.tileW * m.tileH;
+        std::vector<int32_t> out;
+        out.push_back(m.slotsPerOwner);
+        for (int y = 0; y < m.H; y++)
+            for (int x = 0; x < m.W; x++) {
+                int owner;
+                uint32_t slot;
+                kajoTileSlot(m, x, y, &owner, &slot);
+                out.push_back(owner);
+                out.push_back((int32_t)slot);
+            }
+        for (int o = 0; o < m.tileCount; o++) {
+            int owned = (nTiles - o + m.tileCount - 1) / m.tileCount;
+            if (owned < 0)
+                owned = 0;
+            const AdaptGeom g{m.W, m.H, m.tileW, m.tileH, m.tilesX, o, m.tileCount, owned};
+            for (uint32_t s = 0; s < (uint32_t)m.slotsPerOwner; s++) {
+                int px = -1, py = -1;
+                out.push_back(kajo::adaptSlotPixel(g, s, &px, &py) ? 1 : 0);
+                out.push_back(px);
+                out.push_back(py);
+            }
+        }
+        if (fwrite(out.data(), sizeof(int32_t), out.size(), stdout) != out.size())
+            return 1;
+    }
+    return 0;
+}
+"""
+SLOT_FRAMES = [(100, 75), (41, 23), (9, 200)]
+
+
+def _slot_cases():
+    from test_hip_tile_shapes import DEFAULT, TILES
+    assert DEFAULT == (64, 16) and DEFAULT not in TILES
+    return [(tile, frame, owners) for tile in TILES + [DEFAULT] for frame in SLOT_FRAMES for owners in (1, 3)]
+
+
+@pytest.fixture(scope="module")
+def host_slot_pixels(tmp_path_factory):
+    """case -> (slots per owner, kajoTileSlot's (H, W, 2), adaptSlotPixel's (owners, slots, 3)): the stand-alone program, one run"""
+    cxx = next((c for c in ("g++", "c++", "clang++") if shutil.which(c)), None)
+    if cxx is None:
+        pytest.skip("no C++ compiler")
+    d = tmp_path_factory.mktemp("adaptslot")
+    src, exe = str(d / "adapt_slots.cpp"), str(d / "adapt_slots")
+    with open(src, "w") as f:
+        f.write(SLOT_SOURCE)
+    r = subprocess.run([cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
+                        src, "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    cases = _slot_cases()
+    args = [str(v) for (tw, th), (w, h), owners in cases for v in (w, h, tw, th, owners)]
+    p = subprocess.run([exe, *args], capture_output=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    words = np.frombuffer(p.stdout, np.int32)
+    out, at = {}, 0
+    for case in cases:
+        _, (w, h), owners = case
+        slots = int(words[at])
+        forward = words[at + 1:at + 1 + 2 * w * h].reshape(h, w, 2)
+        at += 1 + 2 * w * h
+        out[case] = (slots, forward, words[at:at + 3 * owners * slots].reshape(owners, slots, 3))
+        at += 3 * owners * slots
+    assert at == words.size
+    return out
+
+
+def test_the_slot_to_pixel_arithmetic_is_the_exact_inverse_of_the_tile_map_at_every_tile_shape(host_slot_pixels):
+    """kajo::adaptSlotPixel against kajoTileSlot, both compiled as host code from the headers the kernels are compiled from: every tile
+    shape of tests/test_hip_tile_shapes.py and the default one, one owner and three, three ragged frames. Every pixel of the image goes
+    to a slot that comes back as that pixel; every other slot of every owner's buffer -- a ragged tile's outside part, a padding tile
+    beyond nTilesOwned -- is answered with false."""
+    from kajo_amd.tiles import TileLayout
+    cases = _slot_cases()
+    assert len(cases) == 7 * 3 * 2
+    for case in cases:
+        tile, (W, H), owners = case
+        slots, forward, back = host_slot_pixels[case]
+        lay = TileLayout(W, H, owners, tile)
+        assert slots == lay.slots_per_owner, case
+        owner, slot = forward[..., 0], forward[..., 1]
+        assert ((owner >= 0) & (owner < owners) & (slot >= 0) & (slot < slots)).all(), case
+        ys, xs = np.mgrid[0:H, 0:W]
+        # every in-image pixel round-trips
+        there = back[owner, slot]
+        wrong = (there[..., 0] != 1) | (there[..., 1] != xs) | (there[..., 2] != ys)
+        assert not wrong.any(), (case, np.argwhere(wrong)[:4], there[wrong][:4])
+        # ... and no other slot is answered with true: outside the image, or beyond the owner's tiles
+        used = np.zeros((owners, slots), bool)
+        used[owner, slot] = True
+        assert used.sum() == W * H, case  # (the map takes no slot twice)
+        assert np.array_equal(back[..., 0] == 1, used), (case, np.argwhere((back[..., 0] == 1) != used)[:4])
+        assert (~used).any() or (W % tile[0] == 0 and H % tile[1] == 0), case
+    # the cases hold a padding tile (three owners, a tile count that is no multiple of three) and an owner without a tile
+    assert any(TileLayout(W, H, o, t).n_tiles % o for t, (W, H), o in cases if o == 3)
+    assert any(TileLayout(W, H, o, t).n_tiles < o for t, (W, H), o in cases)
+
+
 # ---- the build -----------------------------------------------------------------------------------------------------------------------
 
 def _need_tools():

@@ -5,7 +5,10 @@ The reference is a twin handle with KAJO_FLAG_NOISE alone, rendered four passes 
 numpy restatement of the rule finds every unit's retirement pass from the twin's records and forms what the adaptive handle must hold:
 the twin's frame and records at P for an active unit, twin(p) * (float)(P / p) and the records at p for a unit retired at p. Frame,
 records, pass plane and state are compared bit for bit, for every numerics build, ragged and multi-tile frames, a large-scene instance,
-the SPLIT and the unsplit kernels, any cut of the passes into calls, one owner and three, allowance 0 and 8."""
+the SPLIT and the unsplit kernels, any cut of the passes into calls, one owner and three, allowance 0 and 8. (A slot with a batch that was
+not finite has p = 4 n below its unit's retirement pass: `expected` follows the header there.) Two frames large enough for the step and
+pass-plane kernels to stride beyond their 2048 workgroups are held to a vectorised restatement, itself held to the loop on the small
+cases. Other tile shapes: tests/test_hip_noise_tile_shapes.py."""
 import ctypes as C
 
 import numpy as np
@@ -71,16 +74,16 @@ def rel32(rec, floor=FLOOR):
     return np.where(rec["n"] >= 2, rel, -1.0).astype(F32)
 
 
-def unit_of(W, H, owners, unit_slots):
+def unit_of(W, H, owners, unit_slots, tile=(64, 16)):
     """per pixel: (owner, unit of the owner, pixel block of the owner)"""
     ys, xs = np.mgrid[0:H, 0:W]
-    owner, slot = TileLayout(W, H, owners).owner_and_slot(xs, ys)
+    owner, slot = TileLayout(W, H, owners, tile).owner_and_slot(xs, ys)
     return owner, slot // unit_slots, slot // 64
 
 
-def restate(records, W, H, owners, unit_slots, target, allowance, passes=PASSES, min_passes=16, every=4):
+def restate(records, W, H, owners, unit_slots, target, allowance, passes=PASSES, min_passes=16, every=4, tile=(64, 16)):
     """-> the pass every pixel's unit retired at (0: still active after `passes`)"""
-    owner, unit, block = unit_of(W, H, owners, unit_slots)
+    owner, unit, block = unit_of(W, H, owners, unit_slots, tile)
     ukey = owner.astype(np.int64) * (1 << 32) + unit
     bkey = owner.astype(np.int64) * (1 << 32) + block
     retired = np.zeros((H, W), np.int64)
@@ -97,14 +100,46 @@ def restate(records, W, H, owners, unit_slots, target, allowance, passes=PASSES,
     return retired
 
 
+def restate_fast(records, W, H, owners, unit_slots, target, allowance, passes=PASSES, min_passes=16, every=4, tile=(64, 16)):
+    """restate() without its loop over units: the loud pixels of every pixel block counted with np.bincount over the blocks' keys, a unit
+    quiet when none of its blocks is over the allowance (np.minimum.at over the blocks' units). The test below holds it equal to restate()
+    on every small case; the frames of many thousands of units use it."""
+    owner, unit, block = unit_of(W, H, owners, unit_slots, tile)
+    _, ui = np.unique(owner.astype(np.int64) * (1 << 32) + unit, return_inverse=True)
+    _, bi = np.unique(owner.astype(np.int64) * (1 << 32) + block, return_inverse=True)
+    ui, bi = ui.reshape(-1), bi.reshape(-1)
+    unit_of_block = np.zeros(bi.max() + 1, np.int64)
+    unit_of_block[bi] = ui  # (every pixel of a block lies in one unit)
+    assert np.array_equal(unit_of_block[bi], ui)
+    retired_unit = np.zeros(ui.max() + 1, np.int64)
+    for P in range(4 * every, passes + 1, 4 * every):
+        if P < min_passes:
+            continue
+        rec = records[P // 4]
+        loud = ((rec["n"] < 2) | (rel32(rec) > F32(target))).reshape(-1)
+        count = np.bincount(bi, weights=loud, minlength=unit_of_block.size).astype(np.int64)
+        quiet = np.ones(retired_unit.size, np.int64)
+        np.minimum.at(quiet, unit_of_block, (count <= allowance).astype(np.int64))
+        retired_unit[(quiet == 1) & (retired_unit == 0)] = P
+    return retired_unit[ui].reshape(H, W)
+
+
 def expected(frames, records, retired, P=PASSES):
+    """What the adaptive handle holds after P passes. A slot retired at p is its frame at p times (float)(P / (4 n)) and reports 4 n, n the
+    slot's own finite batches (include/kajo_hip.h "WHAT EVERY READER SEES"): p itself unless a batch of the slot was not finite; with n = 0
+    the slot is left as it was."""
     frame, rec = frames[P // 4].copy(), records[P // 4].copy()
+    plane = np.full(retired.shape, P, np.uint32)
     for p in np.unique(retired[retired > 0]):
         at = retired == p
-        f = F32(F64(P) / F64(p))
-        frame[at] = frames[p // 4][at] * f
-        rec[at] = records[p // 4][at]
-    return frame, rec, np.where(retired > 0, retired, P).astype(np.uint32)
+        base, r = frames[p // 4][at], records[p // 4][at]
+        own = 4.0 * r["n"].astype(F64)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            f = (F64(P) / own).astype(F32)
+            frame[at] = np.where((own > 0)[:, None], base * f[:, None], base)
+        rec[at] = r
+        plane[at] = (4 * r["n"]).astype(np.uint32)
+    return frame, rec, plane
 
 
 def median_target(records, W, H, unit_slots):
@@ -118,11 +153,11 @@ def median_target(records, W, H, unit_slots):
 HIP = None
 
 
-def tile_frame(parts, W, H):
+def tile_frame(parts, W, H, tile=(64, 16)):
     """the owners' tile buffers, composed on the host"""
     global HIP
     HIP = HIP or C.CDLL("libamdhip64.so")
-    layout = TileLayout(W, H, len(parts))
+    layout = TileLayout(W, H, len(parts), tile)
     g = np.zeros((len(parts), layout.slots_per_owner, 4), F32)
     for i, p in enumerate(parts):
         p.wait()
@@ -145,7 +180,7 @@ def run(sc, W, H, cuts, owners, adaptive, **kw):
             s = p.adapt_state()
             for k, v in s.items():  # (the owners' counts add; an owner without a tile decides nothing)
                 state[k] = max(state.get(k, 0), v) if k in ("lastDecisionPass", "unitSlots") else state.get(k, 0) + v
-        frame = parts[0].radiance().copy() if owners == 1 else tile_frame(parts, W, H)
+        frame = parts[0].radiance().copy() if owners == 1 else tile_frame(parts, W, H, kw.get("tile", (64, 16)))
         return frame, rec, plane, state
     finally:
         for p in parts:
@@ -195,6 +230,72 @@ def test_frame_records_pass_plane_and_state_are_the_restatement_bit_for_bit(the_
                 # the units the image does not reach retire at the first decision; those it reaches, by the restatement
                 _, unit, _ = unit_of(W, H, 1, slots)
                 assert composed[1]["activeUnits"] == len(np.unique(unit[retired == 0])), (composed[1], case)
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_the_vectorised_restatement_is_the_loop_on_every_small_case(the_scenes, case):
+    """restate_fast, which the frames of thousands of units need, against restate: the same retirement pass for every pixel, allowance 0
+    and 8, one owner and three, decisions at 16 and 32."""
+    key, W, H = CASES[case]
+    sc = the_scenes[key]
+    kw = dict(BUILDS["exact"], flags=0)
+    _, records, _ = twin(sc, key, W, H, kw)
+    slots = unit_slots_of(sc, W, H, **kw)
+    target = median_target(records, W, H, slots)
+    for allowance in (0, 8):
+        for owners in (1, 3):
+            slow = restate(records, W, H, owners, slots, target, allowance)
+            assert np.array_equal(restate_fast(records, W, H, owners, slots, target, allowance), slow), (case, allowance, owners)
+            assert np.array_equal(restate_fast(records, W, H, owners, slots, target, allowance, passes=16),
+                                  restate(records, W, H, owners, slots, target, allowance, passes=16)), (case, allowance, owners)
+            if allowance == 0:
+                assert (slow == 16).any() and (slow == 0).any(), (case, np.unique(slow))
+
+
+# The smallest frames, with one owner and the default tile, at which kajo_adapt_step's and kajo_adapt_passes' grids meet their cap
+# (adapt_kernels.cpp KAJO_ADAPT_MAX_GROUPS) and a workgroup strides: more than 2048 x 256 slots, more than 2048 rectangles of 64x4.
+MAX_GROUPS = 2048
+STRIDED = [((9, 8200), "fast"), ((9, 8200), "exact"), ((9, 8200), "strict"), ((1001, 523), "exact")]
+
+
+@pytest.mark.parametrize("size,build", STRIDED, ids=["%dx%d-%s" % (s + (b,)) for s, b in STRIDED])
+def test_strided_launches_give_the_restatement_beyond_the_first_2048_workgroups(the_scenes, size, build):
+    """20 passes cut (16, 4): one decision at 16, a step with retired units behind the second launch, a batch boundary at 20. The target is
+    the lower median of the worst relative error at pass 16 of the units beyond slot 524 288 -- the image's last tile row -- so that one of
+    them at least retires and one stays active there."""
+    sc, (W, H), P = the_scenes["spheres"], size, 20
+    kw = BUILDS[build]
+    lay = TileLayout(W, H, 1)
+    rects = ((W + 63) // 64) * ((H + 3) // 4)
+    assert lay.slots_per_owner > MAX_GROUPS * 256 and rects > MAX_GROUPS, (size, lay.slots_per_owner, rects)
+    with HipRenderer(sc, W, H, spp=4, seed=SEED, noise=True, **kw) as t:
+        frames, records = [np.zeros((H, W, 4), F32)], [t.noise_moments()]
+        for _ in range(P // 4):
+            frames.append(t.render(4).radiance().copy())
+            records.append(t.noise_moments())
+    slots = unit_slots_of(sc, W, H, **kw)
+    ys, xs = np.mgrid[0:H, 0:W]
+    beyond = lay.owner_and_slot(xs, ys)[1] >= MAX_GROUPS * 256
+    _, unit, _ = unit_of(W, H, 1, slots)
+    rel = rel32(records[4])
+    assert beyond.any() and (records[4]["n"][beyond] >= 2).all()
+    assert not np.isin(unit[~beyond], unit[beyond]).any()  # (a unit lies on one side)
+    worst = np.sort([rel[beyond][unit[beyond] == u].max() for u in np.unique(unit[beyond])])
+    target = float(worst[(len(worst) - 1) // 2])
+    assert len(worst) >= 2 and target > 0 and worst[-1] > target, (size, build, worst)
+    retired = restate_fast(records, W, H, 1, slots, target, 0, passes=P)
+    assert (retired[beyond] == 16).any() and (retired[beyond] == 0).any() and (retired[~beyond] == 16).any() and (retired[~beyond] == 0).any()
+    frame, rec, plane = expected(frames, records, retired, P=P)
+    got = run(sc, W, H, (16, 4), 1, dict(target=target, floor=FLOOR, allowance=0), **kw)
+    why = (size, build)
+    for where, at in (("beyond slot 524 288", beyond), ("the whole frame", np.ones((H, W), bool))):
+        assert np.array_equal(u32(got[0][at]), u32(frame[at])), (why, where)
+        assert same_records(got[1][at], rec[at]), (why, where)
+        assert np.array_equal(got[2][at], plane[at]), (why, where, np.argwhere((got[2] != plane) & at)[:4])
+    s = got[3]
+    active = int((retired == 0).sum())
+    assert (s["pixels"], s["activePixels"], s["paths"], s["unitSlots"]) == (W * H, active, 4 * (16 * W * H + 4 * active), slots), (why, s)
+    assert s["lastDecisionPass"] == 16 and s["activeUnits"] == len(np.unique(unit[retired == 0])), (why, s)
 
 
 def test_retired_slots_are_extended_behind_every_launch_not_only_at_boundaries(the_scenes):

@@ -6,7 +6,8 @@ differences and luminance, float64 moments): the records must be the same bits. 
 the float64 restatement -- the largest difference measured over every case below, FAST / EXACT / STRICT, both scenes, all five frames:
 0.5 ulp, that is, the float32 nearest to the float64 value -- and the histogram to the restatement's bins wherever rel is further than that from a bin edge. Then: the records do not
 depend on how the passes are cut into calls, launches or owners; the flag leaves the frame, the AOVs and the image alone; a NaN in the
-accumulation marks its own pixel and no other; reset / set_pass_count / fewer than two batches; and the driver's stop rule."""
+accumulation marks its own pixel and no other; reset / set_pass_count / fewer than two batches; the driver's stop rule; and two frames
+large enough for both kernels to stride beyond their 2048 workgroups. Other tile shapes: tests/test_hip_noise_tile_shapes.py."""
 import ctypes as C
 import json
 import os
@@ -100,6 +101,32 @@ def twin_frames(sc, W, H, batches, **kw):
 WORST = {"ulp": 0.0}
 
 
+def check_map(out, want, W, H, rows=slice(None)):
+    """noise()'s planes, histogram and counts against the restatement of the records `want`; `rows`: the planes of these rows alone (the
+    histogram and the counts are the whole frame's either way) -> the largest difference of the planes in float32 ulp"""
+    m, se, rel = restate_evaluation(want)
+    worst = max(ulps(out["mean"][rows], m[rows]).max(), ulps(out["stderr"][rows], se[rows]).max(), ulps(out["relative"][rows], rel[rows]).max())
+    assert worst <= ULPS, (W, H, rows, worst)
+    assert np.array_equal(out["batches"][rows], want["n"][rows].astype(np.uint32))
+    # the histogram: the device's own rel plane binned gives its words; its bins are the restatement's away from the bin edges
+    rel32 = rel.astype(F32)
+    lo, hi = rel32.copy(), rel32.copy()
+    for _ in range(ULPS):
+        lo, hi = np.nextafter(lo, F32(-np.inf)), np.nextafter(hi, F32(np.inf))
+    known = want["n"] >= 2
+    near_edge = known & (bin_of(np.maximum(lo, 0)) != bin_of(hi))
+    assert near_edge.sum() <= 0.001 * W * H, (near_edge.sum(), W * H)
+    assert np.array_equal(np.bincount(bin_of(out["relative"][known]), minlength=BINS), out["hist"][:BINS])
+    at = np.zeros((H, W), bool)
+    at[rows] = True
+    at &= known & ~near_edge
+    assert np.array_equal(bin_of(out["relative"])[at], bin_of(rel32)[at])
+    assert out["hist"][BINS] == (~known).sum() and out["hist"][BINS + 1] == (want["bad"] > 0).sum()
+    assert (out["pixels"], out["known"], out["unknown"], out["bad"]) == (W * H, known.sum(), (~known).sum(), (want["bad"] > 0).sum())
+    assert out["quantile_value"] == noise_evaluate(out["hist"], 0.95) and (out["quantile_value"] > 0) == bool(known.any())
+    return worst
+
+
 @pytest.mark.parametrize("scene", ["spheres", "grid60"])
 @pytest.mark.parametrize("build", list(BUILDS))
 @pytest.mark.parametrize("size", SIZES, ids=lambda s: "%dx%d" % s)
@@ -112,25 +139,48 @@ def test_records_are_the_restatement_bit_for_bit_and_the_map_within_two_ulp(the_
         out = r.noise(floor=FLOOR, quantile=0.95)
     assert (want["n"] + want["bad"] == 4).all() and (want["n"] == 4).mean() > 0.99
     assert same_records(got, want), (scene, build, size)
-    m, se, rel = restate_evaluation(want)
-    worst = max(ulps(out["mean"], m).max(), ulps(out["stderr"], se).max(), ulps(out["relative"], rel).max())
+    worst = check_map(out, want, W, H)
     WORST["ulp"] = max(WORST["ulp"], worst)
     print("%s %s %dx%d: largest difference %.3g ulp (largest so far %.3g)" % (scene, build, W, H, worst, WORST["ulp"]))
-    assert worst <= ULPS, (scene, build, size, worst)
-    assert np.array_equal(out["batches"], want["n"].astype(np.uint32))
-    # the histogram: the device's own rel plane binned gives its words; its bins are the restatement's away from the bin edges
-    rel32 = rel.astype(F32)
-    lo, hi = rel32.copy(), rel32.copy()
-    for _ in range(ULPS):
-        lo, hi = np.nextafter(lo, F32(-np.inf)), np.nextafter(hi, F32(np.inf))
-    known = want["n"] >= 2
-    near_edge = known & (bin_of(np.maximum(lo, 0)) != bin_of(hi))
-    assert near_edge.sum() <= 0.001 * W * H, (near_edge.sum(), W * H)
-    assert np.array_equal(np.bincount(bin_of(out["relative"][known]), minlength=BINS), out["hist"][:BINS])
-    assert np.array_equal(bin_of(out["relative"])[known & ~near_edge], bin_of(rel32)[known & ~near_edge])
-    assert out["hist"][BINS] == (~known).sum() and out["hist"][BINS + 1] == (want["bad"] > 0).sum()
-    assert (out["pixels"], out["known"], out["unknown"], out["bad"]) == (W * H, known.sum(), (~known).sum(), (want["bad"] > 0).sum())
-    assert out["quantile_value"] == noise_evaluate(out["hist"], 0.95) and (out["quantile_value"] > 0) == bool(known.any())
+
+
+# The smallest frames, with one owner and the default tile, at which both kernels' grids meet their cap (noise.hip KAJO_NOISE_MAX_GROUPS) and
+# a workgroup strides: more than 2048 x 256 slots for the update, more than 2048 rectangles of 64x4 for the map. 9x8200 is one tile wide
+# (1 x 513 tiles); 1001x523 is 16 x 33 tiles, ragged on both axes. Every frame below those sizes -- all the others of this module -- runs
+# each loop once.
+MAX_GROUPS = 2048
+STRIDED = [((9, 8200), "fast"), ((9, 8200), "exact"), ((9, 8200), "strict"), ((1001, 523), "exact")]
+
+
+def strided_sizes(W, H):
+    """-> (slots of the one owner's buffer, rectangles of the map kernel), both held above the caps"""
+    slots, rects = TileLayout(W, H, 1).slots_per_owner, ((W + 63) // 64) * ((H + 3) // 4)
+    assert slots > MAX_GROUPS * 256 and rects > MAX_GROUPS, (W, H, slots, rects)
+    return slots, rects
+
+
+@pytest.mark.parametrize("size,build", STRIDED, ids=["%dx%d-%s" % (s + (b,)) for s, b in STRIDED])
+def test_strided_launches_give_the_restatement_beyond_the_first_2048_workgroups(the_scenes, size, build):
+    """8 passes, two batches: se and rel are known. The slots beyond the first 524 288 and the rectangles beyond the first 2 048 are the
+    image's last tile row, the last 16 rows at the most: they are compared once more on their own, so that a failure there is named."""
+    sc, (W, H) = the_scenes["spheres"], size
+    slots, rects = strided_sizes(W, H)
+    ys, xs = np.mgrid[0:H, 0:W]
+    beyond = TileLayout(W, H, 1).owner_and_slot(xs, ys)[1] >= MAX_GROUPS * 256
+    last = slice(H - 16, H)
+    assert beyond.any() and not beyond[:H - 16].any()
+    assert 4 * (MAX_GROUPS // ((W + 63) // 64)) >= H - 16  # (rectangle 2048, row-major in rows of four, starts in the last 16 rows too)
+    want = restate_moments(twin_frames(sc, W, H, 2, **BUILDS[build]))
+    with HipRenderer(sc, W, H, spp=4, seed=SEED, noise=True, **BUILDS[build]) as r:
+        r.render(8)
+        got = r.noise_moments()
+        out = r.noise(floor=FLOOR, quantile=0.95)
+    assert (want["n"] + want["bad"] == 2).all() and (want["n"] == 2).mean() > 0.99 and (want["n"][last] == 2).any()
+    assert same_records(got[last], want[last]), (size, build, "the last 16 rows")
+    assert same_records(got, want), (size, build)
+    worst = check_map(out, want, W, H, rows=last)
+    worst = max(worst, check_map(out, want, W, H))
+    print("%s %dx%d: %d slots, %d rectangles, largest difference %.3g ulp" % (build, W, H, slots, rects, worst))
 
 
 def run_cuts(sc, W, H, cuts, ppl, owners, **kw):

@@ -19,7 +19,15 @@ Which test reaches which reader (all at every shape of TILES unless said):
   kajo_tone_*_tiles, kajo_glare_bright / apply, kajo_despeckle_*, denoise ..... test_post_stages_from_a_tiled_handle (one owner),
                                                                                 test_owners_through_the_device_paths (24x32, 40x32, 128x64)
   AOV, matte and KAT handles (which must NOT read the tile shape) ............. test_aov_and_mattes..., test_kat_trace...
-  kajo_fold_parts and the parted launch tail (64x16 and 32x32) ................ test_parted_tail_with_rows_outside_the_image"""
+  kajo_fold_parts and the parted launch tail (64x16 and 32x32) ................ test_parted_tail_with_rows_outside_the_image
+The readers that came with the noise estimate, adaptive sampling and the noise-guided denoiser are reached by
+tests/test_hip_noise_tile_shapes.py, which takes TILES, `same` and `bits` from here:
+  kajo_noise_map (kajoTileSlot), kajo_hip_read_noise_moments' host loop ....... test_noise_records_planes_and_histogram_are_the_default_tiles
+  kajo_adapt_passes (kajoTileSlot) ............................................ test_adaptive_units_of_one_pixel_block_do_not_depend_on_the_tile_shape,
+                                                                                test_adaptive_units_of_four_pixel_blocks_follow_the_tile_shape
+  kajo_adapt_select (kajo::adaptSlotPixel, adapt_math.h) ...................... the same two, and on the host, as kajoTileSlot's exact inverse,
+                                                                                tests/test_adaptive_cpu.py
+  kajo_denoise_guided_v0 (kajoTileSlot) ....................................... test_the_guided_denoiser_reads_its_records_through_the_tile_map"""
 import numpy as np
 import pytest
 
