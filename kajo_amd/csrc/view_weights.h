@@ -1,5 +1,5 @@
 // view_weights.h -- the host half of the view stage (include/kajo_hip.h "The view"): the weight rows of one axis and the two transfer
-// tables, in binary64, rounded to float32 last. Pure functions of their arguments: no device, no handle, no global state. capi.cpp's
+// tables, in binary64, rounded to float32 last. Pure functions of their arguments: no device, no handle, no global state. present.cpp's
 // kajo_hip_view_weights / kajo_hip_view_tables and the stage's launches go through them, so what a test reads is what the kernels read.
 #pragma once
 

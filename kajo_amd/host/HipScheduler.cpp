@@ -350,6 +350,21 @@ struct Scheduler::Impl
         lens->focusDistance = z;
     }
 
+    // Options switches on a stage of the display chain that changes the frame in front of the tone curves
+    bool chainOn() const { return localActive() || opt.meterOn || opt.despeckleOn || glareOn(); }
+
+    // The whole display chain on handle 0's own frame (include/kajo_hip.h: every smaller chain call is this one with stages NULL): the
+    // stages given, Options' local tone mapping and metering where they are on, tone NULL = Options::tone
+    void present(const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGradeParams* grade, const KajoLensParams* lens,
+                 const KajoGlareParams* glare, const KajoToneParams* tone, const KajoViewParams* view, uint32_t* argb8)
+    {
+        check(kajo_hip_present_grade_argb8(handles[0], despeckle, denoise, grade, lens, glare, localActive() ? &opt.local : nullptr,
+                                           opt.meterOn ? &opt.meter : nullptr, tone ? tone : &opt.tone, view, argb8, &metered),
+              "kajo_hip_present_grade_argb8");
+        if (localActive())
+            notePivot();
+    }
+
     // lastLens() of an image made with `lens`
     void noteLens(const KajoLensParams& lens)
     {
@@ -415,23 +430,11 @@ struct Scheduler::Impl
     {
         if (opt.gpus == 1 && !opt.forceGather) {
             // single owner: the library resolves from its own tile buffer
-            if (localActive()) {
-                check(kajo_hip_present_local_argb8(handles[0], opt.despeckleOn ? &opt.despeckle : nullptr, nullptr, glareOn() ? &opt.glare : nullptr,
-                                                   &opt.local, opt.meterOn ? &opt.meter : nullptr, &opt.tone, image->pixels.get(), &metered),
-                      "kajo_hip_present_local_argb8");
+            if (chainOn()) {
+                present(opt.despeckleOn ? &opt.despeckle : nullptr, nullptr, nullptr, nullptr, glareOn() ? &opt.glare : nullptr, nullptr, nullptr,
+                        image->pixels.get());
                 check(kajo_hip_tone_scale(handles[0], &toneScale), "kajo_hip_tone_scale");
-                notePivot();
-            } else if (opt.meterOn) {
-                check(kajo_hip_present_metered_argb8(handles[0], opt.despeckleOn ? &opt.despeckle : nullptr, nullptr, glareOn() ? &opt.glare : nullptr,
-                                                     &opt.meter, &opt.tone, image->pixels.get(), &metered),
-                      "kajo_hip_present_metered_argb8");
-                check(kajo_hip_tone_scale(handles[0], &toneScale), "kajo_hip_tone_scale");
-            } else if (opt.despeckleOn)
-                check(kajo_hip_present_argb8(handles[0], &opt.despeckle, nullptr, glareOn() ? &opt.glare : nullptr, &opt.tone, image->pixels.get(), &toneScale),
-                      "kajo_hip_present_argb8");
-            else if (glareOn())
-                check(kajo_hip_display_argb8(handles[0], nullptr, &opt.glare, &opt.tone, image->pixels.get(), &toneScale), "kajo_hip_display_argb8");
-            else if (toneIsIdentity())
+            } else if (toneIsIdentity())
                 check(kajo_hip_resolve_argb8(handles[0], image->pixels.get()), "kajo_hip_resolve_argb8");
             else
                 check(kajo_hip_tonemap_argb8(handles[0], &opt.tone, nullptr, image->pixels.get(), &toneScale), "kajo_hip_tonemap_argb8");
@@ -461,22 +464,14 @@ struct Scheduler::Impl
             }
         }
         composed = false;
-        if (localActive()) {
-            check(kajo_hip_present_local_gathered_argb8_device(handles[0], gathered, opt.despeckleOn ? &opt.despeckle : nullptr,
-                                                               glareOn() ? &opt.glare : nullptr, &opt.local, opt.meterOn ? &opt.meter : nullptr,
-                                                               &opt.tone, argbDevice, &metered),
-                  "kajo_hip_present_local_gathered_argb8_device");
-            notePivot();
-        } else if (opt.meterOn)
-            check(kajo_hip_present_metered_gathered_argb8_device(handles[0], gathered, opt.despeckleOn ? &opt.despeckle : nullptr,
-                                                                 glareOn() ? &opt.glare : nullptr, &opt.meter, &opt.tone, argbDevice, &metered),
-                  "kajo_hip_present_metered_gathered_argb8_device");
-        else if (opt.despeckleOn)
-            check(kajo_hip_present_gathered_argb8_device(handles[0], gathered, &opt.despeckle, glareOn() ? &opt.glare : nullptr, &opt.tone, argbDevice),
-                  "kajo_hip_present_gathered_argb8_device");
-        else if (glareOn())
-            check(kajo_hip_display_gathered_argb8_device(handles[0], gathered, &opt.glare, &opt.tone, argbDevice), "kajo_hip_display_gathered_argb8_device");
-        else if (toneIsIdentity())
+        if (chainOn()) {
+            check(kajo_hip_present_grade_gathered_argb8_device(handles[0], gathered, opt.despeckleOn ? &opt.despeckle : nullptr, nullptr,
+                                                               glareOn() ? &opt.glare : nullptr, localActive() ? &opt.local : nullptr,
+                                                               opt.meterOn ? &opt.meter : nullptr, &opt.tone, nullptr, argbDevice, &metered),
+                  "kajo_hip_present_grade_gathered_argb8_device");
+            if (localActive())
+                notePivot();
+        } else if (toneIsIdentity())
             check(kajo_hip_resolve_gathered_argb8_device(handles[0], gathered, argbDevice), "kajo_hip_resolve_gathered_argb8_device");
         else
             check(kajo_hip_tonemap_gathered_argb8_device(handles[0], gathered, &opt.tone, argbDevice), "kajo_hip_tonemap_gathered_argb8_device");
@@ -484,7 +479,7 @@ struct Scheduler::Impl
         checkHip(hipMemcpyAsync(image->pixels.get(), argbDevice, (size_t)image->width * image->height * 4, hipMemcpyDeviceToHost, streams[0]),
                  "hipMemcpyAsync(image)");
         checkHip(hipStreamSynchronize(streams[0]), "hipStreamSynchronize");
-        if (localActive() || opt.meterOn || opt.despeckleOn || glareOn() || !toneIsIdentity())
+        if (chainOn() || !toneIsIdentity())
             check(kajo_hip_tone_scale(handles[0], &toneScale), "kajo_hip_tone_scale"); // (the stream is drained: no wait left)
     }
     bool composed = false;
@@ -635,63 +630,17 @@ void Scheduler::readPresented(const KajoDespeckleParams* despeckle, const KajoDe
         d.composeAov();
     KajoDenoiseParams guidedDenoise;
     denoise = d.guided(denoise, &guidedDenoise);
-    if (d.opt.gradeOn) {
-        KajoGradeParams grade;
+    KajoGradeParams grade;
+    if (d.opt.gradeOn)
         d.gradeParams(despeckle, denoise, &grade);
-        KajoLensParams lens = d.opt.lens;
-        if (d.opt.lensOn)
-            d.focusLens(&lens);
-        check(kajo_hip_present_grade_argb8(d.handles[0], despeckle, denoise, &grade, d.opt.lensOn ? &lens : nullptr, glare ? glare : &d.opt.glare,
-                                           d.localActive() ? &d.opt.local : nullptr, d.opt.meterOn ? &d.opt.meter : nullptr,
-                                           tone ? tone : &d.opt.tone, nullptr, argb8, &d.metered),
-              "kajo_hip_present_grade_argb8");
-        if (d.localActive())
-            d.notePivot();
-        if (scale)
-            check(kajo_hip_tone_scale(d.handles[0], scale), "kajo_hip_tone_scale");
-        if (d.opt.lensOn)
-            d.noteLens(lens);
-    } else if (d.opt.lensOn) {
-        KajoLensParams lens = d.opt.lens;
-        if (d.opt.lensFocusAt.x >= 0) {
-            float z = 0;
-            check(kajo_hip_lens_depth_at(d.handles[0], d.opt.lensFocusAt.x, d.opt.lensFocusAt.y, &z), "kajo_hip_lens_depth_at");
-            if (!std::isfinite(z))
-                throw std::runtime_error("hip::Scheduler: the pixel to focus on (" + std::to_string(d.opt.lensFocusAt.x) + ", " +
-                                         std::to_string(d.opt.lensFocusAt.y) + ") is far (a miss, or no finite depth): nothing to focus on");
-            lens.focusDistance = z;
-        }
-        check(kajo_hip_present_lens_argb8(d.handles[0], despeckle, denoise, &lens, glare ? glare : &d.opt.glare,
-                                          d.opt.localOn ? &d.opt.local : nullptr, d.opt.meterOn ? &d.opt.meter : nullptr,
-                                          tone ? tone : &d.opt.tone, argb8, &d.metered),
-              "kajo_hip_present_lens_argb8");
-        if (d.localActive())
-            d.notePivot();
-        if (scale)
-            check(kajo_hip_tone_scale(d.handles[0], scale), "kajo_hip_tone_scale");
-        d.lensRadius.resize((size_t)d.image->width * d.image->height);
-        check(kajo_hip_lens_coc(d.handles[0], &lens, d.lensRadius.data(), nullptr), "kajo_hip_lens_coc");
-        d.lensFocus = lens.focusDistance;
-        d.lensMaxRadiusPx = 0;
-        for (float r : d.lensRadius)
-            d.lensMaxRadiusPx = std::max(d.lensMaxRadiusPx, r);
-        d.lensRan = true;
-    } else if (d.localActive()) {
-        check(kajo_hip_present_local_argb8(d.handles[0], despeckle, denoise, glare ? glare : &d.opt.glare, &d.opt.local,
-                                           d.opt.meterOn ? &d.opt.meter : nullptr, tone ? tone : &d.opt.tone, argb8, &d.metered),
-              "kajo_hip_present_local_argb8");
-        d.notePivot();
-        if (scale)
-            check(kajo_hip_tone_scale(d.handles[0], scale), "kajo_hip_tone_scale");
-    } else if (d.opt.meterOn) {
-        check(kajo_hip_present_metered_argb8(d.handles[0], despeckle, denoise, glare ? glare : &d.opt.glare, &d.opt.meter, tone ? tone : &d.opt.tone,
-                                             argb8, &d.metered),
-              "kajo_hip_present_metered_argb8");
-        if (scale)
-            check(kajo_hip_tone_scale(d.handles[0], scale), "kajo_hip_tone_scale");
-    } else
-        check(kajo_hip_present_argb8(d.handles[0], despeckle, denoise, glare ? glare : &d.opt.glare, tone ? tone : &d.opt.tone, argb8, scale),
-              "kajo_hip_present_argb8");
+    KajoLensParams lens = d.opt.lens;
+    if (d.opt.lensOn)
+        d.focusLens(&lens);
+    d.present(despeckle, denoise, d.opt.gradeOn ? &grade : nullptr, d.opt.lensOn ? &lens : nullptr, glare ? glare : &d.opt.glare, tone, nullptr, argb8);
+    if (scale)
+        check(kajo_hip_tone_scale(d.handles[0], scale), "kajo_hip_tone_scale");
+    if (d.opt.lensOn)
+        d.noteLens(lens);
     if (!despeckle)
         return;
     if (counts) {
@@ -714,35 +663,16 @@ void Scheduler::readViewed(uint32_t* dst)
     KajoLensParams lens = d.opt.lens;
     if (d.opt.lensOn) {
         d.composeAov();
-        if (d.opt.lensFocusAt.x >= 0) {
-            float z = 0;
-            check(kajo_hip_lens_depth_at(d.handles[0], d.opt.lensFocusAt.x, d.opt.lensFocusAt.y, &z), "kajo_hip_lens_depth_at");
-            if (!std::isfinite(z))
-                throw std::runtime_error("hip::Scheduler: the pixel to focus on (" + std::to_string(d.opt.lensFocusAt.x) + ", " +
-                                         std::to_string(d.opt.lensFocusAt.y) + ") is far (a miss, or no finite depth): nothing to focus on");
-            lens.focusDistance = z;
-        }
+        d.focusLens(&lens);
     }
+    KajoGradeParams grade;
     if (d.opt.gradeOn) {
         if (d.opt.grade.nRegions > 0)
             d.composeAov();
-        KajoGradeParams grade;
         d.gradeParams(d.opt.despeckleOn ? &d.opt.despeckle : nullptr, nullptr, &grade);
-        check(kajo_hip_present_grade_argb8(d.handles[0], d.opt.despeckleOn ? &d.opt.despeckle : nullptr, nullptr, &grade,
-                                           d.opt.lensOn ? &lens : nullptr, &d.opt.glare, d.localActive() ? &d.opt.local : nullptr,
-                                           d.opt.meterOn ? &d.opt.meter : nullptr, &d.opt.tone, &d.opt.view, dst, &d.metered),
-              "kajo_hip_present_grade_argb8");
-        if (d.localActive())
-            d.notePivot();
-        return;
     }
-    // (with every optional stage NULL the call routes itself to the call readPresented makes: the chain's image is the same words)
-    check(kajo_hip_present_view_argb8(d.handles[0], d.opt.despeckleOn ? &d.opt.despeckle : nullptr, nullptr, d.opt.lensOn ? &lens : nullptr,
-                                      &d.opt.glare, d.localActive() ? &d.opt.local : nullptr, d.opt.meterOn ? &d.opt.meter : nullptr, &d.opt.tone,
-                                      &d.opt.view, dst, &d.metered),
-          "kajo_hip_present_view_argb8");
-    if (d.localActive())
-        d.notePivot();
+    d.present(d.opt.despeckleOn ? &d.opt.despeckle : nullptr, nullptr, d.opt.gradeOn ? &grade : nullptr, d.opt.lensOn ? &lens : nullptr, &d.opt.glare,
+              nullptr, &d.opt.view, dst);
 }
 
 void Scheduler::readNoise(float* mean, float* stderror, float* relative)
