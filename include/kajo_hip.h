@@ -1138,7 +1138,9 @@ int kajo_hip_adapt_evaluate(const KajoNoiseMoments* records, int64_t count, cons
 int64_t kajo_hip_adapt_order(const uint32_t* order, uint32_t nUnits, const uint32_t* state, uint32_t wavesPerBlock, int32_t split, uint32_t* out,
                              size_t capacity);
 
-/* Use an existing HIP stream (hipStream_t passed as void*) instead of the handle's own. */
+/* Use an existing HIP stream (hipStream_t passed as void*) instead of the handle's own; NULL is the null stream. The call waits for the
+   stream the handle leaves, so work enqueued before it is complete before anything enqueued after it starts, whichever streams the two
+   are. The stream stays the caller's: kajo_hip_destroy waits for it and does not destroy it. */
 int kajo_hip_set_stream(kajo_hip_t h, void* stream);
 
 int kajo_hip_counters(kajo_hip_t h, KajoCounters* out);
