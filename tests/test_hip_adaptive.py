@@ -48,11 +48,12 @@ def same_records(a, b):
 _TWINS = {}
 
 
-def twin(sc, key, W, H, kw):
-    """frames[b], records[b] after batch b = 1 .. 8 of a KAJO_FLAG_NOISE handle (index 0: nothing rendered); rendered once per case"""
-    k = (key, W, H, tuple(sorted(kw.items())))
+def twin(sc, key, W, H, kw, spp=4):
+    """frames[b], records[b] after batch b = 1 .. 8 of a KAJO_FLAG_NOISE handle (index 0: nothing rendered); rendered once per case.
+    kw: the create keywords of the case (tests/test_hip_adaptive_launch_shapes.py: other sample counts, depths, launch lengths)"""
+    k = (key, W, H, spp, tuple(sorted(kw.items())))
     if k not in _TWINS:
-        with HipRenderer(sc, W, H, spp=4, seed=SEED, noise=True, **kw) as t:
+        with HipRenderer(sc, W, H, spp=spp, seed=SEED, noise=True, **kw) as t:
             frames, records = [np.zeros((H, W, 4), F32)], [t.noise_moments()]
             for _ in range(PASSES // 4):
                 frames.append(t.render(4).radiance().copy())
@@ -167,14 +168,17 @@ def tile_frame(parts, W, H, tile=(64, 16)):
     return layout.compose(g)
 
 
-def run(sc, W, H, cuts, owners, adaptive, **kw):
-    parts = [HipRenderer(sc, W, H, spp=4, seed=SEED, noise=True, adaptive=adaptive, tile_index=i, tile_count=owners, **kw) for i in range(owners)]
+def run(sc, W, H, cuts, owners, adaptive, spp=4, behind=None, **kw):
+    """behind: called with the owner's handle behind every render call (a wait, a look at the counters)"""
+    parts = [HipRenderer(sc, W, H, spp=spp, seed=SEED, noise=True, adaptive=adaptive, tile_index=i, tile_count=owners, **kw) for i in range(owners)]
     try:
         rec, plane = np.zeros((H, W), NOISE_MOMENTS), np.zeros((H, W), np.uint32)
         state = {}
         for p in parts:
             for c in cuts:
                 p.render(c)
+                if behind:
+                    behind(p)
             p.noise_moments(out=rec)
             p.adapt_passes(out=plane)
             s = p.adapt_state()
@@ -187,8 +191,8 @@ def run(sc, W, H, cuts, owners, adaptive, **kw):
             p.close()
 
 
-def unit_slots_of(sc, W, H, **kw):
-    with HipRenderer(sc, W, H, spp=4, seed=SEED, noise=True, adaptive=True, **kw) as r:
+def unit_slots_of(sc, W, H, spp=4, **kw):
+    with HipRenderer(sc, W, H, spp=spp, seed=SEED, noise=True, adaptive=True, **kw) as r:
         return r.adapt_state()["unitSlots"]
 
 

@@ -7,6 +7,9 @@
 //   host_san plan lds a.pod ...          kajo_amd/csrc/launch_plan.h kajoLdsPlan: a scene's LDS plan per staging (plain, no grid, no
 //                                        visibility lists) and numerics build
 //   host_san plan shape in.bin out.bin   launch_plan.h kajoLaunchShape over a table of launches
+//   host_san plan shape a.pod W H tileW tileH S fast|strict|exact flags tileIndex tileCount now passesDone [now passesDone ...]
+//                                        the plan and the launch shapes of a handle of that scene, frame, S, build and flags
+//                                        (tests/test_launch_shapes_cpu.py): kajoLdsPlan and kajoLaunchShape as create / render call them
 //   host_san plan sizes a.pod ...        what a scene's size does to its staging (tests/test_scene_sizes_cpu.py): the plan's ldsTotal() per
 //                                        numerics build, the grid's cells per axis against the cells it wanted, the visibility lists' bins
 //                                        and their longest row of 16-bit offsets
@@ -18,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "kajo_hip.h"
 #include "kajo_scene.h"
 #include "launch_order.h"
 #include "launch_plan.h"
@@ -261,11 +265,53 @@ static int planShape(int argc, char** argv)
     return 0;
 }
 
+// Launch shapes of a handle as kajo_hip_create / kajo_hip_render would plan them: one line "now=.. passesDone=..: field=value ..." per
+// launch. argv: a.pod W H tileW tileH S fast|strict|exact flags tileIndex tileCount, then now passesDone for every launch. The scene is
+// staged by the flags as create() stages it, the plan is kajoLdsPlan's, the pixel blocks are those of the owner's tiles and the shape is
+// kajoLaunchShape's. What kajo_hip_render itself derives from the plan is taken the way it takes it: n (handle.h samplesPerAxis),
+// `grouped` and `home`. parted: with an order and a tail to part (orderValid, nParted = 1), which is the most a launch can be.
+static int planShapeOf(int argc, char** argv)
+{
+    if (argc < 12 || (argc - 10) % 2 != 0) return 2;
+    Pod pod;
+    if (int rc = pod.read(argv[0])) return rc;
+    const int W = atoi(argv[1]), H = atoi(argv[2]), tileW = atoi(argv[3]), tileH = atoi(argv[4]), S = atoi(argv[5]);
+    const std::string build = argv[6];
+    if (build != "fast" && build != "strict" && build != "exact") return 2;
+    const Numerics numerics = build == "strict" ? Numerics::Strict : build == "exact" ? Numerics::Exact : Numerics::Fast;
+    const int flags = atoi(argv[7]), tileIndex = atoi(argv[8]), tileCount = atoi(argv[9]);
+    if (W < 1 || H < 1 || tileW < 8 || tileH < 8 || tileW % 8 || tileH % 8 || S < 1 || tileCount < 1 || tileIndex < 0 || tileIndex >= tileCount) return 2;
+    kajo::StagedScene st;
+    kajo::stageScene(pod.sc, st, (flags & KAJO_FLAG_NO_GRID) ? 0 : 48, !(flags & KAJO_FLAG_NO_SHADOW_LISTS));
+    const KajoSceneLds b = kajoSceneLds(st);
+    const KajoLdsPlan lds = kajoLdsPlan(b.hotBytes, b.coldBytes, b.gridHeaderBytes, b.gridBytes, st.gridEnabled, st.shadowEnabled, (int)st.light.size(), numerics);
+    if (!lds.fits) return 7;
+    const int nTiles = ((W + tileW - 1) / tileW) * ((H + tileH - 1) / tileH);
+    const int nTilesOwned = std::max(0, (nTiles - tileIndex + tileCount - 1) / tileCount);
+    const unsigned gridBlocks = (unsigned)((long long)nTilesOwned * ((tileW / 8) * (tileH / 8)) / lds.wavesPerBlock);
+    const unsigned long long pixelBlocks = (unsigned long long)gridBlocks * lds.wavesPerBlock;
+    const int n = (int)std::sqrt((double)(unsigned)S);
+    const bool grouped = lds.coldInLds && numerics != Numerics::Strict;
+    const int home = (lds.coldInLds && (flags & KAJO_FLAG_NO_ONE_LIGHT)) ? 2 : lds.coldInLds;
+    for (int a = 10; a + 1 < argc; a += 2) {
+        const int now = atoi(argv[a]), passesDone = atoi(argv[a + 1]);
+        if (now < 1 || passesDone < 0) return 2;
+        const KajoLaunchShape s = kajoLaunchShape(pixelBlocks, now, n, lds.coldInLds, (flags & KAJO_FLAG_NO_SPLIT) != 0, lds.mailboxOffset(),
+                                                  lds.perWaveBytes(false), passesDone, grouped, true, 1u);
+        printf("now=%d passesDone=%d: split=%u chunks=%u parted=%d startsInside=%d endsInside=%d launchGroups=%d wavesPerBlock=%u coldInLds=%d "
+               "home=%d grouped=%d n=%d gridBlocks=%u pixelBlocks=%llu ldsTotal=%zu\n",
+               now, passesDone, s.split, s.chunks, s.parted, s.startsInside, s.endsInside, s.launchGroups, lds.wavesPerBlock, lds.coldInLds, home,
+               grouped, n, gridBlocks, pixelBlocks, lds.ldsTotal());
+    }
+    return 0;
+}
+
 static int plan(int argc, char** argv)
 {
     if (argc < 1) return 2;
     const std::string what = argv[0];
     if (what == "lds") return planLds(argc - 1, argv + 1);
+    if (what == "shape" && argc - 1 > 2) return planShapeOf(argc - 1, argv + 1);
     if (what == "shape") return planShape(argc - 1, argv + 1);
     if (what == "sizes") return planSizes(argc - 1, argv + 1);
     return 2;
