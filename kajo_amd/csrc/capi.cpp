@@ -19,32 +19,25 @@ int kajo_adapt_passes_launch(const void* records, const void* state, const TileM
                              void* stream);
 }
 
+// kajo_hip_aov_kernel's names in the order of render_args.h KajoAovInstance: the five scene classes, with _spec, with _matte, with both
+#define AOV_CLASSES(p) p, p "_big", p "_big_lg", p "_biglist", p "_biglist_lg"
+#define AOV_NAMES(p) {AOV_CLASSES(p), AOV_CLASSES(p "_spec"), AOV_CLASSES(p "_matte"), AOV_CLASSES(p "_spec_matte")}
 const KernelSet kFastKernels = {kajo_render_fast_launch, kajo_render_fast_split_launch, kajo_render_fast_set_lds, kajo_resolve_fast_launch,
-                                       kajo_resolve_tiles_fast_launch, kajo_tone_fast_launch, kajo_aov_fast_launch, kajo_aov_fast_set_lds,
-                                       kajo_kat_trace_fast_launch, kajo_kat_shade_fast_launch,
-                                       {"kajo_aov_fast", "kajo_aov_fast_big", "kajo_aov_fast_big_lg", "kajo_aov_fast_biglist", "kajo_aov_fast_biglist_lg",
-                                       "kajo_aov_fast_spec", "kajo_aov_fast_spec_big", "kajo_aov_fast_spec_big_lg", "kajo_aov_fast_spec_biglist", "kajo_aov_fast_spec_biglist_lg",
-                                       "kajo_aov_fast_matte", "kajo_aov_fast_matte_big", "kajo_aov_fast_matte_big_lg", "kajo_aov_fast_matte_biglist", "kajo_aov_fast_matte_biglist_lg",
-                                       "kajo_aov_fast_spec_matte", "kajo_aov_fast_spec_matte_big", "kajo_aov_fast_spec_matte_big_lg", "kajo_aov_fast_spec_matte_biglist",
-                                       "kajo_aov_fast_spec_matte_biglist_lg"}};
+                                kajo_resolve_tiles_fast_launch, kajo_tone_fast_launch, kajo_aov_fast_launch, kajo_aov_fast_set_lds,
+                                kajo_kat_trace_fast_launch, kajo_kat_shade_fast_launch, AOV_NAMES("kajo_aov_fast")};
 const KernelSet kStrictKernels = {kajo_render_strict_launch, kajo_render_strict_split_launch, kajo_render_strict_set_lds, kajo_resolve_strict_launch,
-                                         kajo_resolve_tiles_strict_launch, kajo_tone_strict_launch, kajo_aov_strict_launch, kajo_aov_strict_set_lds,
-                                         kajo_kat_trace_strict_launch, kajo_kat_shade_strict_launch,
-                                         {"kajo_aov_strict", "kajo_aov_strict_big", "kajo_aov_strict_big_lg", "kajo_aov_strict_biglist", "kajo_aov_strict_biglist_lg",
-                                         "kajo_aov_strict_spec", "kajo_aov_strict_spec_big", "kajo_aov_strict_spec_big_lg", "kajo_aov_strict_spec_biglist", "kajo_aov_strict_spec_biglist_lg",
-                                         "kajo_aov_strict_matte", "kajo_aov_strict_matte_big", "kajo_aov_strict_matte_big_lg", "kajo_aov_strict_matte_biglist", "kajo_aov_strict_matte_biglist_lg",
-                                         "kajo_aov_strict_spec_matte", "kajo_aov_strict_spec_matte_big", "kajo_aov_strict_spec_matte_big_lg", "kajo_aov_strict_spec_matte_biglist",
-                                         "kajo_aov_strict_spec_matte_biglist_lg"}};
+                                  kajo_resolve_tiles_strict_launch, kajo_tone_strict_launch, kajo_aov_strict_launch, kajo_aov_strict_set_lds,
+                                  kajo_kat_trace_strict_launch, kajo_kat_shade_strict_launch, AOV_NAMES("kajo_aov_strict")};
 // The oracle's arithmetic in everything that decides (STRICT and EXACT): which walk, which hold policy, whose resolve. EXACT has render
 // and shading kernels of its own; the STRICT instances serve it for the rest (EXACT's camera rays, walk and normals are STRICT's arithmetic).
-const KernelSet kExactKernels = {kajo_render_exact_launch, kajo_render_exact_split_launch, kajo_render_exact_set_lds, kajo_resolve_strict_launch,
-                                        kajo_resolve_tiles_strict_launch, kajo_tone_strict_launch, kajo_aov_strict_launch, kajo_aov_strict_set_lds,
-                                        kajo_kat_trace_strict_launch, kajo_kat_shade_exact_launch,
-                                        {"kajo_aov_strict", "kajo_aov_strict_big", "kajo_aov_strict_big_lg", "kajo_aov_strict_biglist", "kajo_aov_strict_biglist_lg",
-                                         "kajo_aov_strict_spec", "kajo_aov_strict_spec_big", "kajo_aov_strict_spec_big_lg", "kajo_aov_strict_spec_biglist", "kajo_aov_strict_spec_biglist_lg",
-                                         "kajo_aov_strict_matte", "kajo_aov_strict_matte_big", "kajo_aov_strict_matte_big_lg", "kajo_aov_strict_matte_biglist", "kajo_aov_strict_matte_biglist_lg",
-                                         "kajo_aov_strict_spec_matte", "kajo_aov_strict_spec_matte_big", "kajo_aov_strict_spec_matte_big_lg", "kajo_aov_strict_spec_matte_biglist",
-                                         "kajo_aov_strict_spec_matte_biglist_lg"}};
+const KernelSet kExactKernels = [] {
+    KernelSet k = kStrictKernels;
+    k.render = kajo_render_exact_launch;
+    k.split = kajo_render_exact_split_launch;
+    k.setLds = kajo_render_exact_set_lds;
+    k.katShade = kajo_kat_shade_exact_launch;
+    return k;
+}();
 
 thread_local std::string g_error;
 
@@ -244,6 +237,12 @@ int adaptUploadOrder(KajoHip* h)
     return KAJO_OK;
 }
 
+// the whole-frame AOV sums: float4 [2][W * H]
+size_t aovFrameBytes(const KajoHip* h)
+{
+    return 2 * (size_t)h->W * h->H * 16;
+}
+
 // the coverage tables of a handle: ids and counts, a word each per slot
 size_t matteTableBytes(const KajoHip* h)
 {
@@ -268,6 +267,52 @@ size_t matteTileBytes(const KajoHip* h)
     return (size_t)h->map.slotsPerOwner * KAJO_MATTE_SLOTS * 8;
 }
 
+constexpr size_t kCounterBytes = 32 * sizeof(unsigned long long);
+
+// the batch moments of the noise estimate: KajoNoiseMoments [slotsPerOwner]
+size_t momentBytes(const KajoHip* h)
+{
+    return 2 * h->tileBytes;
+}
+
+// the state words of an adaptive handle's units, on the device and on the host
+size_t adaptStateBytes(const KajoHip* h)
+{
+    return (size_t)(h->gridBlocks ? h->gridBlocks : 1) * sizeof(uint32_t);
+}
+
+// Everything that sums passes, zeroed on the handle's stream: the buffers the handle has, each with its size. sums == false: only what
+// is estimated from the sums (the moments and the units' state), which kajo_hip_set_pass_count starts over beside a buffer it keeps.
+int clearAccumulators(KajoHip* h, bool sums)
+{
+    const auto zero = [h](const DeviceBuffer& b, size_t bytes) { return b ? hipMemsetAsync(b.p, 0, bytes, h->stream) : hipSuccess; };
+    if (sums) {
+        HIP_TRY(zero(h->tiles, h->tileBytes));
+        HIP_TRY(zero(h->counters, kCounterBytes));
+        HIP_TRY(zero(h->aov, aovFrameBytes(h)));
+        HIP_TRY(zero(h->matte, matteTableBytes(h)));
+        HIP_TRY(zero(h->aovTiles, aovTileBytes(h)));
+        HIP_TRY(zero(h->matteTiles, matteTileBytes(h)));
+        HIP_TRY(zero(h->noiseBase, h->tileBytes));
+    }
+    HIP_TRY(zero(h->noiseMoments, momentBytes(h)));
+    HIP_TRY(zero(h->adaptStateDev, adaptStateBytes(h)));
+    return KAJO_OK;
+}
+
+// f(index of the pixel in the row-major frame, its slot) for every pixel of the frame this owner has
+template <class F> void forOwnedPixels(const KajoHip* h, F f)
+{
+    for (int y = 0; y < h->H; y++)
+        for (int x = 0; x < h->W; x++) {
+            int owner;
+            uint32_t slot;
+            kajoTileSlot(h->map, x, y, &owner, &slot);
+            if (owner == h->params.tileIndex)
+                f((size_t)y * h->W + x, slot);
+        }
+}
+
 // the rays of the known-answer entry points as the kernels read them: float [n][6], origin then direction
 std::vector<float> packRays(int n, const float* origins, const float* dirs)
 {
@@ -277,6 +322,327 @@ std::vector<float> packRays(int n, const float* origins, const float* dirs)
         std::memcpy(&rays[6 * (size_t)i + 3], dirs + 3 * (size_t)i, 12);
     }
     return rays;
+}
+
+// ---- kajo_hip_create's steps -------------------------------------------------------------------------------------------------------
+
+// The scene staged by the flags, in device memory, and the view of it the kernels read; the LDS plan of the scene
+int uploadScene(KajoHip* h, const KajoScene& scene)
+{
+    const uint32_t flags = h->params.flags;
+    kajo::stageScene(scene, h->staged, (flags & KAJO_FLAG_NO_GRID) ? 0 : 48, !(flags & KAJO_FLAG_NO_SHADOW_LISTS));
+    const kajo::StagedScene& st = h->staged;
+    DSceneView& v = h->view;
+    HIP_TRY(upload(st.planeRow, &v.planeRow, h->sceneBuffers));
+    HIP_TRY(upload(st.planeDet, &v.planeDet, h->sceneBuffers));
+    HIP_TRY(upload(st.planeFrame, &v.planeFrame, h->sceneBuffers));
+    HIP_TRY(upload(st.sphereHot, &v.sphereHot, h->sceneBuffers));
+    HIP_TRY(upload(st.sphereHotOffset, &v.sphereHotOffset, h->sceneBuffers));
+    HIP_TRY(upload(st.sphereCold, &v.sphereCold, h->sceneBuffers));
+    HIP_TRY(upload(st.material, &v.material, h->sceneBuffers));
+    HIP_TRY(upload(st.light, &v.light, h->sceneBuffers));
+    HIP_TRY(upload(st.gridCellStart, &v.grid.cellStart, h->sceneBuffers));
+    HIP_TRY(upload(st.gridItems, &v.grid.items, h->sceneBuffers));
+    v.grid.enabled = st.gridEnabled;
+    v.grid.nCells = st.gridEnabled ? (int32_t)st.gridCellStart.size() - 1 : 0;
+    v.grid.nItems = (int32_t)st.gridItems.size();
+    for (int k = 0; k < 3; k++) {
+        v.grid.dim[k] = st.gridDim[k];
+        v.grid.bmin[k] = st.gridEnabled ? st.gridMin[k] : 0.f;
+        v.grid.bmax[k] = st.gridEnabled ? st.gridMax[k] : 0.f;
+        v.grid.cell[k] = st.gridEnabled ? st.gridCell[k] : 1.f;
+        v.grid.invCell[k] = st.gridEnabled ? 1.f / st.gridCell[k] : 1.f;
+        v.grid.center[k] = st.gridCenter[k];
+    }
+    v.grid.reach2 = st.gridReach2;
+    HIP_TRY(upload(st.shadowRowBase, &v.shadow.rowBase, h->sceneBuffers));
+    HIP_TRY(upload(st.shadowOff16, &v.shadow.off16, h->sceneBuffers));
+    HIP_TRY(upload(st.shadowPacked, &v.shadow.items, h->sceneBuffers));
+    HIP_TRY(upload(st.shadowInvKeyScale, &v.shadow.invKeyScale, h->sceneBuffers));
+    v.shadow.enabled = st.shadowEnabled ? 1 : 0;
+    v.shadow.n = st.shadowN;
+    v.nPlanes = st.nPlanes;
+    v.nSpheres = st.nSpheres;
+    v.nSphereHot = (int)st.sphereHot.size();
+    v.nLights = (int)st.light.size();
+    v.allTranslated = st.allTranslated;
+    v.planesRigid = st.planesRigid;
+    for (int i = 0; i < 3; i++) {
+        v.background[i] = st.background[i];
+        v.p1[i] = st.p1[i];
+        v.dp2[i] = st.p2[i] - st.p1[i]; // (p2 - p1), (p3 - p1) of Renderer.cpp:58
+        v.dp3[i] = st.p3[i] - st.p1[i];
+        v.origin[i] = st.origin[i];
+    }
+    h->lds = kajoLdsPlan(st, h->numerics);
+    v.grid.inLds = h->lds.gridInLds ? 1 : 0;
+    if (!h->lds.fits)
+        return fail(KAJO_E_INVALID, "scene exceeds the LDS staging limit: scene records + the waves' mailboxes must fit 160 KiB");
+    return KAJO_OK;
+}
+
+// The frame plan (the handle's base) and what follows from it before anything is allocated: its refusals, the large-LDS opt-ins, the
+// AOV kernel of the scene's class
+int planFrame(KajoHip* h)
+{
+    const KajoParams& p = h->params;
+    static_cast<KajoFramePlan&>(*h) = kajoFramePlan(h->W, h->H, p, h->lds, h->numerics);
+    if (h->tooManyBlocks)
+        return fail(KAJO_E_INVALID, "frame too large: 2^28 pixel blocks per handle at most");
+    if ((p.flags & KAJO_FLAG_ADAPTIVE) && !h->unitShift)
+        return fail(KAJO_E_INVALID, "adaptive sampling: a unit is 64, 128 or 256 slots");
+    h->noise = (p.flags & KAJO_FLAG_NOISE) != 0;
+    h->adaptive = (p.flags & KAJO_FLAG_ADAPTIVE) != 0;
+    if (h->lds.ldsTotal() > 48 * 1024)
+        HIP_TRY((hipError_t)h->k->setLds(h->lds.coldInLds, h->lds.ldsTotal()));
+    if (p.flags & KAJO_FLAG_AOV) {
+        // the AOV kernel of the scene's class -- small scenes: everything in LDS; large ones: the hot records (and the grid's cell lists where
+        // create() put them in LDS), per home of the cell lists and with or without visibility lists, as launch.inc.hip picks the render kernel
+        if (h->lds.coldInLds)
+            h->aovInstance = KAJO_AOV_SMALL;
+        else if (h->view.shadow.enabled)
+            h->aovInstance = h->view.grid.inLds ? KAJO_AOV_BIGLIST_LG : KAJO_AOV_BIGLIST;
+        else
+            h->aovInstance = h->view.grid.inLds ? KAJO_AOV_BIG_LG : KAJO_AOV_BIG;
+        if (p.flags & KAJO_FLAG_AOV_SPECULAR) // the same scene class, with the chain to the first non-delta hit
+            h->aovInstance += KAJO_AOV_SPEC_SMALL;
+        if (p.flags & KAJO_FLAG_AOV_MATTE) // ... with the coverage tables beside the sums
+            h->aovInstance += KAJO_AOV_MATTE_SMALL;
+        h->aovLds = h->lds.coldInLds ? h->lds.ldsBytes : h->lds.hotBytes;
+        if (h->aovLds > 48 * 1024)
+            HIP_TRY((hipError_t)h->k->aovSetLds(h->aovInstance, h->aovLds));
+        h->aovTiled = (p.flags & KAJO_FLAG_AOV_TILED) != 0;
+    }
+    return KAJO_OK;
+}
+
+// Every buffer that sums passes (clearAccumulators has the list), and the launch-order feedback
+int allocAccumulators(KajoHip* h)
+{
+    const uint32_t flags = h->params.flags;
+    HIP_TRY(h->tiles.alloc(h->tileBytes));
+    if (flags & KAJO_FLAG_COUNTERS)
+        HIP_TRY(h->counters.alloc(kCounterBytes));
+    if (h->gridBlocks && !(flags & KAJO_FLAG_NO_REORDER)) {
+        HIP_TRY(h->waveTrips.alloc((size_t)h->gridBlocks * h->lds.wavesPerBlock * sizeof(uint32_t)));
+        HIP_TRY(h->blockOrder.alloc((size_t)h->gridBlocks * sizeof(uint32_t)));
+    }
+    if (flags & KAJO_FLAG_AOV) {
+        // tiled: the sums of the handle's own tiles only (the whole-frame buffers: kajo_hip_compose_aov, on the handle it is called on)
+        HIP_TRY(h->aovTiled ? h->aovTiles.alloc(aovTileBytes(h)) : h->aov.alloc(aovFrameBytes(h)));
+        if (flags & KAJO_FLAG_AOV_MATTE)
+            HIP_TRY(h->aovTiled ? h->matteTiles.alloc(matteTileBytes(h)) : h->matte.alloc(matteTableBytes(h)));
+    }
+    if (h->noise) {
+        HIP_TRY(h->noiseBase.alloc(h->tileBytes));
+        HIP_TRY(h->noiseMoments.alloc(momentBytes(h)));
+    }
+    if (h->adaptive)
+        HIP_TRY(h->adaptStateDev.alloc(adaptStateBytes(h)));
+    return clearAccumulators(h, true);
+}
+
+// An adaptive handle's orders, its pinned copy of the state words and the in-image pixels of every unit
+int setupAdaptive(KajoHip* h)
+{
+    if (!h->adaptive)
+        return KAJO_OK;
+    const unsigned w = h->lds.wavesPerBlock;
+    HIP_TRY(h->adaptUnits.alloc(adaptStateBytes(h)));
+    HIP_TRY(h->adaptBlocks.alloc(adaptStateBytes(h) * w));
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->adaptStateHost), adaptStateBytes(h), hipHostMallocDefault));
+    std::memset(h->adaptStateHost, 0, adaptStateBytes(h));
+    h->adaptUnitPixels.assign(h->gridBlocks, 0u);
+    for (unsigned u = 0; u < h->gridBlocks; u++)
+        for (uint32_t s = 0; s < 64u * w; s++) {
+            int px, py;
+            if (kajo::adaptSlotPixel(h->adaptGeom, u * 64u * w + s, &px, &py))
+                h->adaptUnitPixels[u]++;
+        }
+    for (uint32_t c : h->adaptUnitPixels)
+        h->adaptPixels += c;
+    h->adaptActivePixels = h->adaptPixels;
+    return KAJO_OK;
+}
+
+// What every launch's arguments have in common (kajo_hip_render sets the passes, the order and the carry; launchAov the passes)
+void fillLaunchArgs(KajoHip* h)
+{
+    const KajoParams& p = h->params;
+    const KajoLdsPlan& lds = h->lds;
+    RenderArgs& a = h->renderArgs;
+    std::memset(&a, 0, sizeof a);
+    a.scene = h->view;
+    a.tiles = h->tiles.p;
+    a.W = h->W;
+    a.H = h->H;
+    a.n = h->n;
+    a.S = (float)(unsigned)p.samplesPerPass;
+    a.pixelWidth = 1.f / h->W;   // Renderer.cpp:39-42
+    a.pixelHeight = 1.f / h->H;
+    a.sampleWidth = a.pixelWidth / a.n;
+    a.sampleHeight = a.pixelHeight / a.n;
+    a.depthLimit = p.depthLimit;
+    a.seed = p.seed;
+    a.tileW = p.tileW;
+    a.tileH = p.tileH;
+    a.tilesX = h->map.tilesX;
+    a.tilesY = h->tilesY;
+    a.tileIndex = p.tileIndex;
+    a.tileCount = p.tileCount;
+    a.nTilesOwned = h->nTilesOwned;
+    a.counters = h->counters.as<unsigned long long>();
+    a.mailboxOffset = (uint32_t)lds.mailboxOffset();
+    a.stealWindow = lds.stealWindow;
+    a.carrySlots = (uint32_t)h->map.slotsPerOwner;
+    lds.fillWaveLds(a, a.mailboxOffset, true);
+    if (!(p.flags & KAJO_FLAG_AOV))
+        return;
+    AovArgs& g = h->aovArgs;
+    std::memset(&g, 0, sizeof g);
+    g.scene = h->view;
+    g.albedoHits = h->aovTiled ? h->aovTiles.p : h->aov.p;
+    g.slots = h->aovTiled ? (uint32_t)h->map.slotsPerOwner : (uint32_t)(h->W * h->H);
+    g.W = h->W;
+    g.H = h->H;
+    g.n = a.n;
+    g.pixelWidth = a.pixelWidth;
+    g.pixelHeight = a.pixelHeight;
+    g.sampleWidth = a.sampleWidth;
+    g.sampleHeight = a.sampleHeight;
+    g.seed = a.seed;
+    if (p.flags & KAJO_FLAG_AOV_MATTE)
+        g.matteIds = h->aovTiled ? h->matteTiles.p : h->matte.p;
+    unsigned long long blocks = (unsigned long long)((h->W + 7) / 8) * ((h->H + 7) / 8);
+    if (h->aovTiled) {
+        // one wave per 8x8 block of the handle's own tiles, in the tile buffer's order (an owner without a tile launches nothing)
+        blocks = (unsigned long long)h->nTilesOwned * (p.tileW / 8) * (p.tileH / 8);
+        g.tiledBlocks = (int32_t)blocks;
+        g.tileWaves = (uint32_t)(p.tileW / 8) | ((uint32_t)(p.tileH / 8) << 16);
+        g.tileIndex = p.tileIndex;
+        g.tileCount = p.tileCount;
+    }
+    h->aovGrid = (unsigned)((blocks + 3) / 4);
+}
+
+// ---- kajo_hip_render's steps -------------------------------------------------------------------------------------------------------
+
+// What the next launch covers and in which order. Adaptive sampling: once a unit has retired the launches cover the active units only,
+// in the handle's order without the others; a decision may have brought a new cost order in between, so the order is looked up launch
+// by launch. The trips are measured by whole launches only; until a unit retires, as on any other handle.
+struct LaunchOrder
+{
+    bool shortGrid;        // some unit has retired
+    unsigned activeUnits;  // workgroups of an unsplit launch; 0: every unit retired, the passes are counted and nothing is rendered
+    const uint32_t* units; // the order words of an unsplit launch, or null: image order
+    const uint32_t* pixelBlocks; // the SPLIT kernels': null (one round or two: the launch order does not matter), or the active units' pixel blocks
+    uint32_t* trips;       // where this launch records its waves' trips, or null
+};
+
+LaunchOrder launchOrder(const KajoHip* h, uint32_t* trips)
+{
+    LaunchOrder o;
+    o.shortGrid = h->adaptive && h->adaptRetired > 0;
+    o.activeUnits = (unsigned)h->gridBlocks - (h->adaptive ? h->adaptRetired : 0u);
+    o.units = o.shortGrid ? h->adaptUnits.as<const uint32_t>() : h->orderValid ? h->blockOrder.as<const uint32_t>() : nullptr;
+    o.pixelBlocks = o.shortGrid ? h->adaptBlocks.as<const uint32_t>() : nullptr;
+    o.trips = o.shortGrid ? nullptr : trips;
+    return o;
+}
+
+// One launch of the render kernel -- one of three arms by its shape -- between a pair of timing events (KajoCounters.kernelMs)
+int launchRender(KajoHip* h, const RenderArgs& a, const KajoLaunchShape& s, const LaunchOrder& o, int now)
+{
+    const KajoLdsPlan& lds = h->lds;
+    const unsigned block = 64 * lds.wavesPerBlock, grid = (unsigned)h->gridBlocks;
+    h->lastTailGroups = 0;
+    if (o.activeUnits == 0)
+        return KAJO_OK;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const auto between = [&]() -> int {
+        hipError_t le;
+        int rc;
+        HIP_TRY(hipEventRecord(e0, h->stream));
+        if (s.chunks > 1 || s.split > 1) {
+            // the waves of a block divide the samples of every pass (behind the [pass][sample][pixel] table) or the passes (behind the
+            // [pass][pixel] term table); one round or two: the launch order does not matter
+            RenderArgs b = a;
+            b.blockOrder = o.pixelBlocks;
+            b.waveTrips = nullptr;
+            if (s.chunks > 1)
+                b.sampleChunks = (int32_t)s.chunks;
+            const unsigned waves = s.chunks > 1 ? (unsigned)now * s.chunks : s.split;
+            lds.fillWaveLds(b, a.mailboxOffset + (size_t)now * (s.chunks > 1 ? a.n * a.n : 1) * 64 * 16, false);
+            b.thrL = 1; // (short waves: holding a vertex only lengthens their tail -- configs[0] 18.9 against 16.5 G paths/s; 1-3 % on
+                        // split frames below 720p)
+            le = (hipError_t)h->k->split(&b, o.shortGrid ? o.activeUnits * lds.wavesPerBlock : (unsigned)h->pixelBlocks, 64 * waves,
+                                         b.perWaveOffset + (size_t)waves * b.perWaveBytes, h->stream);
+        } else if (s.parted && !o.shortGrid) { // (a noise handle's launches are of one group at the most: never parted)
+            // the launch tail: the cheapest blocks as one workgroup per group of the launch (partTheTail)
+            if ((rc = partedOrderFor(h, s.launchGroups)))
+                return rc;
+            h->lastTailGroups = h->nParted * (unsigned)(s.launchGroups - 1);
+            RenderArgs b = a;
+            b.blockOrder = h->partedOrder[s.launchGroups].as<const uint32_t>();
+            b.side = h->side.p;
+            b.sideStride = h->nParted * block;
+            b.partedFirst = grid - h->nParted;
+            le = (hipError_t)h->k->render(&b, h->home, grid + h->lastTailGroups, block, lds.ldsTotal(), h->stream);
+            if (le == hipSuccess)
+                le = (hipError_t)kajo_fold_parts_launch(h->tiles.p, h->side.p, b.sideStride, h->partedBlocks.as<const uint32_t>(), h->nParted, block,
+                                                        s.launchGroups, h->stream);
+        } else {
+            le = (hipError_t)h->k->render(&a, h->home, o.activeUnits, block, lds.ldsTotal(), h->stream);
+        }
+        if (le != hipSuccess)
+            return failHip(le, "render kernel launch");
+        HIP_TRY(hipEventRecord(e1, h->stream));
+        return KAJO_OK;
+    };
+    int rc = getEvent(h, &e0);
+    if (!rc && !(rc = getEvent(h, &e1)))
+        rc = between();
+    if (rc) { // the one place a pair goes back to the pool unused
+        for (hipEvent_t e : {e0, e1})
+            if (e)
+                h->eventPool.push_back(e);
+        return rc;
+    }
+    h->pending.emplace_back(e0, e1);
+    return KAJO_OK;
+}
+
+// The first-hit AOVs of the same passes, behind the render launch and outside its timing events (KajoCounters.kernelMs)
+int launchAov(KajoHip* h, int now)
+{
+    AovArgs g = h->aovArgs;
+    g.firstPass = h->passesDone + 1;
+    g.nPasses = now;
+    HIP_TRY((hipError_t)h->k->aov(&g, h->aovInstance, h->aovGrid, h->aovLds, h->stream));
+    h->aovPasses += now;
+    return KAJO_OK;
+}
+
+// Behind every launch and outside the timing events: what the noise estimate and adaptive sampling do with the new passes
+int afterLaunch(KajoHip* h, int now, bool shortGrid)
+{
+    const int after = h->passesDone + now, boundary = after % KAJO_NOISE_BATCH_PASSES == 0;
+    const uint32_t slots = (uint32_t)((size_t)h->nTilesOwned * h->map.tileW * h->map.tileH);
+    if (shortGrid) {
+        // adaptive sampling: the retired slots extended to the new pass count and, at a batch boundary, the batch into the moments of the
+        // active ones (a handle that retires has rendered every pass: no rebase)
+        HIP_TRY((hipError_t)kajo_adapt_step_launch(h->tiles.p, h->noiseBase.p, h->noiseMoments.p, h->adaptStateDev.p, slots, h->unitShift, boundary,
+                                                   after, h->stream));
+    } else if (h->noise && boundary) {
+        // a batch boundary, behind the launch (and its fold): the batch into the moments -- or, where this handle did not render all of
+        // it, only the baseline
+        if (h->noiseRebase)
+            HIP_TRY(hipMemcpyAsync(h->noiseBase.p, h->tiles.p, h->tileBytes, hipMemcpyDeviceToDevice, h->stream));
+        else
+            HIP_TRY((hipError_t)kajo_noise_update_launch(h->tiles.p, h->noiseBase.p, h->noiseMoments.p, slots, h->stream));
+        h->noiseRebase = false;
+    }
+    return KAJO_OK;
 }
 
 } // namespace
@@ -408,58 +774,10 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
     if (!scene || !params || !out)
         return fail(KAJO_E_INVALID, "null argument");
     *out = nullptr;
-    if (width <= 0 || height <= 0 || (long long)width * height > (1ll << 31) - 1)
-        return fail(KAJO_E_INVALID, "image size out of range");
-    if (scene->nPlanes < 0 || scene->nSpheres < 0 || (scene->nPlanes && !scene->planes) || (scene->nSpheres && !scene->spheres))
-        return fail(KAJO_E_INVALID, "scene arrays inconsistent");
     KajoParams p = *params;
-    if (p.tileW == 0)
-        p.tileW = 64;
-    if (p.tileH == 0)
-        p.tileH = 16;
-    if (p.tileCount == 0)
-        p.tileCount = 1;
-    if (p.samplesPerPass < 1 || p.samplesPerPass > 65535)
-        return fail(KAJO_E_INVALID, "samplesPerPass must be in [1, 65535]");
-    if ((p.flags & KAJO_FLAG_STRICT) && (p.flags & KAJO_FLAG_EXACT))
-        return fail(KAJO_E_INVALID, "the strict and the exact flag name two different numerics builds: set one");
-    if (p.flags & KAJO_FLAG_COOP)
-        return fail(KAJO_E_INVALID, "KAJO_FLAG_COOP: the cooperative-traversal experiment is not built into this library (make -C kajo_amd/csrc experiments)");
-    if (p.flags & KAJO_FLAG_DEFERRED)
-        return fail(KAJO_E_INVALID, "KAJO_FLAG_DEFERRED: the deferred-shading experiment is not built into this library (make -C kajo_amd/csrc experiments)");
-    if (p.depthLimit < 0 || p.depthLimit > 1000) // (the reference's limit is 8)
-        return fail(KAJO_E_INVALID, "depthLimit must be in [0, 1000]");
-    if (p.tileW < 8 || p.tileH < 8 || (p.tileW & 7) || (p.tileH & 7) || (p.tileW * p.tileH) % 256)
-        return fail(KAJO_E_INVALID, "tile size must be multiples of 8 with tileW*tileH a multiple of 256");
-    if (p.tileCount < 1 || p.tileIndex < 0 || p.tileIndex >= p.tileCount)
-        return fail(KAJO_E_INVALID, "tileIndex/tileCount out of range");
-    if ((p.flags & KAJO_FLAG_AOV) && !(p.flags & KAJO_FLAG_AOV_TILED) && p.tileCount != 1)
-        return fail(KAJO_E_INVALID, "first-hit AOVs need the whole frame on one handle (tileCount 1)");
-    if ((p.flags & KAJO_FLAG_AOV_SPECULAR) && !(p.flags & KAJO_FLAG_AOV))
-        return fail(KAJO_E_INVALID, "the first-non-delta-hit flag changes what the AOV flag's buffers hold: set the AOV flag with it");
-    if ((p.flags & KAJO_FLAG_AOV_MATTE) && !(p.flags & KAJO_FLAG_AOV))
-        return fail(KAJO_E_INVALID, "the matte flag keeps its coverage tables over the AOV flag's samples: set the AOV flag with it");
-    if ((p.flags & KAJO_FLAG_AOV_TILED) && !(p.flags & KAJO_FLAG_AOV))
-        return fail(KAJO_E_INVALID, "the tiled flag changes where the AOV flag's sums are kept: set the AOV flag with it");
-    if ((p.flags & KAJO_FLAG_ADAPTIVE) && !(p.flags & KAJO_FLAG_NOISE))
-        return fail(KAJO_E_INVALID, "the adaptive flag retires units by the noise flag's estimate: set the noise flag with it");
-    // (aov.inc.hip: a wave of the tiled launch carries its block's corner and the tile's shape in 16-bit fields, in units of 8 pixels)
-    if ((p.flags & KAJO_FLAG_AOV_TILED) && (width > 524288 || height > 262144 || p.tileW > 524280 || p.tileH > 524280))
-        return fail(KAJO_E_INVALID, "tiled AOVs: the frame must be within 524288 x 262144 and a tile within 524280 pixels a side");
-
-    if (p.flags & (KAJO_FLAG_STRICT | KAJO_FLAG_EXACT)) {
-        // integrator.inc.hip kdiv / ksqrt: the IEEE quotient and root without the compiler's range scaling are exact while operands stay
-        // dozens of binades inside the float range, which a scene of ordinary coordinates guarantees; outside it STRICT would silently
-        // stop being the oracle
-        float lo = 0.f, hi = 0.f;
-        kajo::coordinateRange(*scene, &lo, &hi);
-        if (!(hi == hi) || (hi > 0.f && (lo < 0x1p-40f || hi > 0x1p40f))) {
-            char msg[256];
-            std::snprintf(msg, sizeof msg, "strict / exact numerics need the scene's non-zero coordinates within 2^-40 .. 2^40 in magnitude "
-                                           "(found %g .. %g): use the fast build or rescale the scene", (double)lo, (double)hi);
-            return fail(KAJO_E_INVALID, msg);
-        }
-    }
+    char msg[256];
+    if (const char* refusal = kajoCheckCreate(*scene, width, height, &p, msg))
+        return fail(KAJO_E_INVALID, refusal);
 
     int nDev = 0;
     hipError_t e = hipGetDeviceCount(&nDev);
@@ -468,191 +786,25 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
     if (p.device < 0 || p.device >= nDev)
         return fail(KAJO_E_INVALID, "device ordinal out of range");
 
-    KajoHip* h = new (std::nothrow) KajoHip;
+    // (whatever fails from here on: destroy() frees what the handle has so far)
+    std::unique_ptr<KajoHip, void (*)(KajoHip*)> h(new (std::nothrow) KajoHip, destroy);
     if (!h)
         return fail(KAJO_E_INVALID, "out of host memory");
     h->device = p.device;
     h->params = p;
     h->W = width;
     h->H = height;
-    h->numerics = (p.flags & KAJO_FLAG_STRICT) ? Numerics::Strict : (p.flags & KAJO_FLAG_EXACT) ? Numerics::Exact : Numerics::Fast;
+    h->numerics = kajoNumerics(p.flags);
     h->k = h->numerics == Numerics::Strict ? &kStrictKernels : h->numerics == Numerics::Exact ? &kExactKernels : &kFastKernels;
-#define CREATE_TRY(expr)                                                                                               \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) {                                                                                        \
-            destroy(h);                                                                                                \
-            return failHip(e_, #expr);                                                                                 \
-        }                                                                                                              \
-    } while (0)
-    CREATE_TRY(hipSetDevice(h->device));
-    CREATE_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->ownStream = true;
-
-    // ---- scene -----------------------------------------------------------------------------
-    kajo::stageScene(*scene, h->staged, (p.flags & KAJO_FLAG_NO_GRID) ? 0 : 48, !(p.flags & KAJO_FLAG_NO_SHADOW_LISTS));
-    const kajo::StagedScene& st = h->staged;
-    DSceneView& v = h->view;
-    CREATE_TRY(upload(st.planeRow, &v.planeRow, h->sceneBuffers));
-    CREATE_TRY(upload(st.planeDet, &v.planeDet, h->sceneBuffers));
-    CREATE_TRY(upload(st.planeFrame, &v.planeFrame, h->sceneBuffers));
-    CREATE_TRY(upload(st.sphereHot, &v.sphereHot, h->sceneBuffers));
-    CREATE_TRY(upload(st.sphereHotOffset, &v.sphereHotOffset, h->sceneBuffers));
-    CREATE_TRY(upload(st.sphereCold, &v.sphereCold, h->sceneBuffers));
-    CREATE_TRY(upload(st.material, &v.material, h->sceneBuffers));
-    CREATE_TRY(upload(st.light, &v.light, h->sceneBuffers));
-    CREATE_TRY(upload(st.gridCellStart, &v.grid.cellStart, h->sceneBuffers));
-    CREATE_TRY(upload(st.gridItems, &v.grid.items, h->sceneBuffers));
-    v.grid.enabled = st.gridEnabled;
-    v.grid.nCells = st.gridEnabled ? (int32_t)st.gridCellStart.size() - 1 : 0;
-    v.grid.nItems = (int32_t)st.gridItems.size();
-    for (int k = 0; k < 3; k++) {
-        v.grid.dim[k] = st.gridDim[k];
-        v.grid.bmin[k] = st.gridEnabled ? st.gridMin[k] : 0.f;
-        v.grid.bmax[k] = st.gridEnabled ? st.gridMax[k] : 0.f;
-        v.grid.cell[k] = st.gridEnabled ? st.gridCell[k] : 1.f;
-        v.grid.invCell[k] = st.gridEnabled ? 1.f / st.gridCell[k] : 1.f;
-        v.grid.center[k] = st.gridCenter[k];
-    }
-    v.grid.reach2 = st.gridReach2;
-    CREATE_TRY(upload(st.shadowRowBase, &v.shadow.rowBase, h->sceneBuffers));
-    CREATE_TRY(upload(st.shadowOff16, &v.shadow.off16, h->sceneBuffers));
-    CREATE_TRY(upload(st.shadowPacked, &v.shadow.items, h->sceneBuffers));
-    CREATE_TRY(upload(st.shadowInvKeyScale, &v.shadow.invKeyScale, h->sceneBuffers));
-    v.shadow.enabled = st.shadowEnabled ? 1 : 0;
-    v.shadow.n = st.shadowN;
-    v.nPlanes = st.nPlanes;
-    v.nSpheres = st.nSpheres;
-    v.nSphereHot = (int)st.sphereHot.size();
-    v.nLights = (int)st.light.size();
-    v.allTranslated = st.allTranslated;
-    v.planesRigid = st.planesRigid;
-    for (int i = 0; i < 3; i++) {
-        v.background[i] = st.background[i];
-        v.p1[i] = st.p1[i];
-        v.dp2[i] = st.p2[i] - st.p1[i]; // (p2 - p1), (p3 - p1) of Renderer.cpp:58
-        v.dp3[i] = st.p3[i] - st.p1[i];
-        v.origin[i] = st.origin[i];
-    }
-    const KajoSceneLds bytes = kajoSceneLds(st);
-    h->lds = kajoLdsPlan(bytes.hotBytes, bytes.coldBytes, bytes.gridHeaderBytes, bytes.gridBytes, st.gridEnabled, st.shadowEnabled, v.nLights, h->numerics);
-    v.grid.inLds = h->lds.gridInLds ? 1 : 0;
-    if (!h->lds.fits) {
-        destroy(h);
-        return fail(KAJO_E_INVALID, "scene exceeds the LDS staging limit: scene records + the waves' mailboxes must fit 160 KiB");
-    }
-    // ---- tiles -----------------------------------------------------------------------------
-    TileMap& m = h->map;
-    m.W = width;
-    m.H = height;
-    m.tileW = p.tileW;
-    m.tileH = p.tileH;
-    m.tilesX = (width + p.tileW - 1) / p.tileW;
-    m.tileCount = p.tileCount;
-    h->tilesY = (height + p.tileH - 1) / p.tileH;
-    h->nTiles = m.tilesX * h->tilesY;
-    h->tilesPerOwner = (h->nTiles + p.tileCount - 1) / p.tileCount;
-    h->nTilesOwned = (h->nTiles - p.tileIndex + p.tileCount - 1) / p.tileCount;
-    if (h->nTilesOwned < 0)
-        h->nTilesOwned = 0;
-    m.slotsPerOwner = h->tilesPerOwner * p.tileW * p.tileH;
-    h->tileBytes = (size_t)m.slotsPerOwner * 16;
-    // (FAST / EXACT handles of small scenes that order their launches render the tail of a launch in parts: partTheTail)
-    h->partsAllowed = h->lds.coldInLds && h->numerics != Numerics::Strict && !(p.flags & (KAJO_FLAG_NO_SPLIT | KAJO_FLAG_NO_REORDER));
-    CREATE_TRY(h->tiles.alloc(h->tileBytes));
-    CREATE_TRY(hipMemsetAsync(h->tiles.p, 0, h->tileBytes, h->stream));
-    if (p.flags & KAJO_FLAG_COUNTERS) {
-        CREATE_TRY(h->counters.alloc(32 * sizeof(unsigned long long)));
-        CREATE_TRY(hipMemsetAsync(h->counters.p, 0, 32 * sizeof(unsigned long long), h->stream));
-    }
-    {
-        const unsigned wavesPerBlock = h->lds.wavesPerBlock;
-        const int wavesPerTile = (p.tileW / 8) * (p.tileH / 8);
-        h->gridBlocks = (unsigned)((long long)h->nTilesOwned * wavesPerTile / wavesPerBlock);
-        if ((long long)h->nTilesOwned * wavesPerTile / wavesPerBlock >= (1ll << 28)) { // (render_args.h: an order word has 28 bits for the block)
-            destroy(h);
-            return fail(KAJO_E_INVALID, "frame too large: 2^28 pixel blocks per handle at most");
-        }
-        if (h->gridBlocks && !(p.flags & KAJO_FLAG_NO_REORDER)) {
-            CREATE_TRY(h->waveTrips.alloc((size_t)h->gridBlocks * wavesPerBlock * sizeof(uint32_t)));
-            CREATE_TRY(h->blockOrder.alloc((size_t)h->gridBlocks * sizeof(uint32_t)));
-        }
-    }
-    if (h->lds.ldsTotal() > 48 * 1024)
-        CREATE_TRY((hipError_t)h->k->setLds(h->lds.coldInLds, h->lds.ldsTotal()));
-    if (p.flags & KAJO_FLAG_AOV) {
-        // the AOV kernel of the scene's class -- small scenes: everything in LDS; large ones: the hot records (and the grid's cell lists where
-        // create() put them in LDS), per home of the cell lists and with or without visibility lists, as launch.inc.hip picks the render kernel
-        if (h->lds.coldInLds)
-            h->aovInstance = KAJO_AOV_SMALL;
-        else if (v.shadow.enabled)
-            h->aovInstance = v.grid.inLds ? KAJO_AOV_BIGLIST_LG : KAJO_AOV_BIGLIST;
-        else
-            h->aovInstance = v.grid.inLds ? KAJO_AOV_BIG_LG : KAJO_AOV_BIG;
-        if (p.flags & KAJO_FLAG_AOV_SPECULAR) // the same scene class, with the chain to the first non-delta hit
-            h->aovInstance += KAJO_AOV_SPEC_SMALL;
-        if (p.flags & KAJO_FLAG_AOV_MATTE) // ... with the coverage tables beside the sums
-            h->aovInstance += KAJO_AOV_MATTE_SMALL;
-        h->aovLds = h->lds.coldInLds ? h->lds.ldsBytes : h->lds.hotBytes;
-        if (h->aovLds > 48 * 1024)
-            CREATE_TRY((hipError_t)h->k->aovSetLds(h->aovInstance, h->aovLds));
-        h->aovTiled = (p.flags & KAJO_FLAG_AOV_TILED) != 0;
-        if (h->aovTiled) {
-            // the sums of the handle's own tiles only (the whole-frame buffers: kajo_hip_compose_aov, on the handle it is called on)
-            CREATE_TRY(h->aovTiles.alloc(aovTileBytes(h)));
-            CREATE_TRY(hipMemsetAsync(h->aovTiles.p, 0, aovTileBytes(h), h->stream));
-            if (p.flags & KAJO_FLAG_AOV_MATTE) {
-                CREATE_TRY(h->matteTiles.alloc(matteTileBytes(h)));
-                CREATE_TRY(hipMemsetAsync(h->matteTiles.p, 0, matteTileBytes(h), h->stream));
-            }
-        } else {
-            const size_t bytes = 2 * (size_t)width * height * 16;
-            CREATE_TRY(h->aov.alloc(bytes));
-            CREATE_TRY(hipMemsetAsync(h->aov.p, 0, bytes, h->stream));
-            if (p.flags & KAJO_FLAG_AOV_MATTE) {
-                const size_t tables = matteTableBytes(h);
-                CREATE_TRY(h->matte.alloc(tables));
-                CREATE_TRY(hipMemsetAsync(h->matte.p, 0, tables, h->stream));
-            }
-        }
-    }
-    if (p.flags & KAJO_FLAG_NOISE) {
-        h->noise = true;
-        CREATE_TRY(h->noiseBase.alloc(h->tileBytes));
-        CREATE_TRY(hipMemsetAsync(h->noiseBase.p, 0, h->tileBytes, h->stream));
-        CREATE_TRY(h->noiseMoments.alloc(2 * h->tileBytes));
-        CREATE_TRY(hipMemsetAsync(h->noiseMoments.p, 0, 2 * h->tileBytes, h->stream));
-    }
-    if (p.flags & KAJO_FLAG_ADAPTIVE) {
-        h->adaptive = true;
-        const unsigned w = h->lds.wavesPerBlock;
-        if (w != 1 && w != 2 && w != 4) {
-            destroy(h);
-            return fail(KAJO_E_INVALID, "adaptive sampling: a unit is 64, 128 or 256 slots");
-        }
-        h->adaptShift = w == 1 ? 6 : w == 2 ? 7 : 8;
-        h->adaptGeom = AdaptGeom{width, height, p.tileW, p.tileH, m.tilesX, p.tileIndex, p.tileCount, h->nTilesOwned};
-        const size_t words = h->gridBlocks ? h->gridBlocks : 1;
-        CREATE_TRY(h->adaptStateDev.alloc(words * sizeof(uint32_t)));
-        CREATE_TRY(hipMemsetAsync(h->adaptStateDev.p, 0, words * sizeof(uint32_t), h->stream));
-        CREATE_TRY(h->adaptUnits.alloc(words * sizeof(uint32_t)));
-        CREATE_TRY(h->adaptBlocks.alloc(words * w * sizeof(uint32_t)));
-        CREATE_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->adaptStateHost), words * sizeof(uint32_t), hipHostMallocDefault));
-        std::memset(h->adaptStateHost, 0, words * sizeof(uint32_t));
-        h->adaptUnitPixels.assign(h->gridBlocks, 0u);
-        for (unsigned u = 0; u < h->gridBlocks; u++)
-            for (uint32_t s = 0; s < 64u * w; s++) {
-                int px, py;
-                if (kajo::adaptSlotPixel(h->adaptGeom, u * 64u * w + s, &px, &py))
-                    h->adaptUnitPixels[u]++;
-            }
-        for (uint32_t c : h->adaptUnitPixels)
-            h->adaptPixels += c;
-        h->adaptActivePixels = h->adaptPixels;
-    }
-    CREATE_TRY(hipStreamSynchronize(h->stream));
-#undef CREATE_TRY
-    *out = h;
+    int rc;
+    if ((rc = uploadScene(h.get(), *scene)) || (rc = planFrame(h.get())) || (rc = allocAccumulators(h.get())) || (rc = setupAdaptive(h.get())))
+        return rc;
+    fillLaunchArgs(h.get());
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    *out = h.release();
     return KAJO_OK;
 }
 
@@ -697,67 +849,22 @@ int kajo_hip_render(kajo_hip_t h, int passes)
         h->passesDone += passes;
         return KAJO_OK;
     }
-    const KajoParams& p = h->params;
-    const KajoLdsPlan& lds = h->lds;
-    RenderArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.scene = h->view;
-    a.tiles = h->tiles.p;
-    a.W = h->W;
-    a.H = h->H;
-    a.n = samplesPerAxis(p);
-    a.S = (float)(unsigned)p.samplesPerPass;
-    a.pixelWidth = 1.f / h->W;   // Renderer.cpp:39-42
-    a.pixelHeight = 1.f / h->H;
-    a.sampleWidth = a.pixelWidth / a.n;
-    a.sampleHeight = a.pixelHeight / a.n;
-    a.depthLimit = p.depthLimit;
-    a.seed = p.seed;
-    a.tileW = p.tileW;
-    a.tileH = p.tileH;
-    a.tilesX = h->map.tilesX;
-    a.tilesY = h->tilesY;
-    a.tileIndex = p.tileIndex;
-    a.tileCount = p.tileCount;
-    a.nTilesOwned = h->nTilesOwned;
-    a.counters = h->counters.as<unsigned long long>();
-    a.mailboxOffset = (uint32_t)lds.mailboxOffset();
-    a.stealWindow = lds.stealWindow;
-    a.carrySlots = (uint32_t)h->map.slotsPerOwner;
-    a.blockOrder = h->orderValid ? h->blockOrder.as<const uint32_t>() : nullptr;
-    a.waveTrips = (h->waveTrips && !h->orderValid) ? h->waveTrips.as<uint32_t>() : nullptr; // measure once, on the first launch
-    lds.fillWaveLds(a, a.mailboxOffset, true);
-
-    const unsigned block = 64 * lds.wavesPerBlock;
-    const unsigned grid = h->gridBlocks;
-    const unsigned long long pixelBlocks = (unsigned long long)grid * lds.wavesPerBlock;
-    const bool grouped = lds.coldInLds && h->numerics != Numerics::Strict; // (integrator.inc.hip GROUPS: FAST / EXACT kernels of small scenes)
-    // (coldInLds 2: the small-scene instance of any number of lights although the scene has one, KAJO_FLAG_NO_ONE_LIGHT)
-    const int home = (lds.coldInLds && (p.flags & KAJO_FLAG_NO_ONE_LIGHT)) ? 2 : lds.coldInLds;
-    const int perLaunch = p.passesPerLaunch > 0 ? p.passesPerLaunch : 16;
-    int left = passes;
+    RenderArgs a = h->renderArgs;
+    uint32_t* trips = (h->waveTrips && !h->orderValid) ? h->waveTrips.as<uint32_t>() : nullptr; // measure once, on the first launch
     // (the noise estimate: a baseline owed since kajo_hip_set_pass_count to a multiple of four is the buffer as it stands now)
     if (h->noise && h->noiseRebase && h->passesDone % KAJO_NOISE_BATCH_PASSES == 0) {
         HIP_TRY(hipMemcpyAsync(h->noiseBase.p, h->tiles.p, h->tileBytes, hipMemcpyDeviceToDevice, h->stream));
         h->noiseRebase = false;
     }
-    while (left > 0) {
-        int now = left < perLaunch ? left : perLaunch;
-        if (h->noise) // no launch crosses an absolute multiple of the batch (the frame's bits do not depend on the cut)
-            now = std::min(now, KAJO_NOISE_BATCH_PASSES - h->passesDone % KAJO_NOISE_BATCH_PASSES);
+    for (int left = passes, now; left > 0; left -= now) {
+        // cut, order, shape
+        now = kajoLaunchPasses(left, h->params.passesPerLaunch, h->noise, h->passesDone);
+        const LaunchOrder o = launchOrder(h, trips);
+        const KajoLaunchShape s = kajoLaunchShape(*h, h->lds, h->params.flags, now, h->passesDone, h->orderValid, h->nParted);
         a.firstPass = h->passesDone + 1;
         a.nPasses = now;
-        // (adaptive sampling: once a unit has retired the launches cover the active units only, in the handle's order without the others;
-        // a decision may have brought a new cost order in between: the order is looked up launch by launch)
-        const bool shortGrid = h->adaptive && h->adaptRetired > 0;
-        const unsigned activeUnits = grid - (h->adaptive ? h->adaptRetired : 0u);
-        if (h->adaptive) {
-            a.blockOrder = shortGrid ? h->adaptUnits.as<const uint32_t>() : h->orderValid ? h->blockOrder.as<const uint32_t>() : nullptr;
-            if (shortGrid)
-                a.waveTrips = nullptr; // (the trips are measured by whole launches only; until a unit retires, as on any other handle)
-        }
-        const KajoLaunchShape s = kajoLaunchShape(pixelBlocks, now, a.n, lds.coldInLds, p.flags & KAJO_FLAG_NO_SPLIT, a.mailboxOffset,
-                                                  lds.perWaveBytes(false), h->passesDone, grouped, h->orderValid, h->nParted);
+        a.blockOrder = o.units;
+        a.waveTrips = o.trips;
         if (s.startsInside || s.endsInside)
             HIP_TRY(h->carry.ensure(2 * h->tileBytes));
         a.carry = h->carry.p;
@@ -765,121 +872,22 @@ int kajo_hip_render(kajo_hip_t h, int passes)
         // buffer as it stands: the restored sum counts as complete groups)
         a.carryIn = s.startsInside && h->carryValid;
         a.carryOut = s.endsInside;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        hipError_t le = hipSuccess;
-        const bool launch = activeUnits > 0; // (adaptive sampling: with every unit retired the passes are counted, nothing is rendered)
-        if (launch) {
-            if ((rc = getEvent(h, &e0)) || (rc = getEvent(h, &e1)))
-                return rc;
-            HIP_TRY(hipEventRecord(e0, h->stream));
-        }
-        h->lastTailGroups = 0;
-        if (!launch) {
-        } else if (s.chunks > 1 || s.split > 1) {
-            // the waves of a block divide the samples of every pass (behind the [pass][sample][pixel] table) or the passes (behind the
-            // [pass][pixel] term table); one round or two: the launch order does not matter
-            RenderArgs b = a;
-            b.blockOrder = nullptr;
-            b.waveTrips = nullptr;
-            if (s.chunks > 1)
-                b.sampleChunks = (int32_t)s.chunks;
-            const unsigned waves = s.chunks > 1 ? (unsigned)now * s.chunks : s.split;
-            lds.fillWaveLds(b, a.mailboxOffset + (size_t)now * (s.chunks > 1 ? a.n * a.n : 1) * 64 * 16, false);
-            b.thrL = 1; // (short waves: holding a vertex only lengthens their tail -- configs[0] 18.9 against 16.5 G paths/s; 1-3 % on
-                        // split frames below 720p)
-            if (shortGrid) // the active units' pixel blocks
-                b.blockOrder = h->adaptBlocks.as<const uint32_t>();
-            le = (hipError_t)h->k->split(&b, shortGrid ? activeUnits * lds.wavesPerBlock : (unsigned)pixelBlocks, 64 * waves,
-                                         b.perWaveOffset + (size_t)waves * b.perWaveBytes, h->stream);
-        } else if (s.parted && !shortGrid) { // (a noise handle's launches are of one group at the most: never parted)
-            // the launch tail: the cheapest blocks as one workgroup per group of the launch (partTheTail)
-            if ((rc = partedOrderFor(h, s.launchGroups))) {
-                h->eventPool.push_back(e0);
-                h->eventPool.push_back(e1);
-                return rc;
-            }
-            h->lastTailGroups = h->nParted * (unsigned)(s.launchGroups - 1);
-            RenderArgs b = a;
-            b.blockOrder = h->partedOrder[s.launchGroups].as<const uint32_t>();
-            b.side = h->side.p;
-            b.sideStride = h->nParted * block;
-            b.partedFirst = grid - h->nParted;
-            le = (hipError_t)h->k->render(&b, home, grid + h->lastTailGroups, block, lds.ldsTotal(), h->stream);
-            if (le == hipSuccess)
-                le = (hipError_t)kajo_fold_parts_launch(h->tiles.p, h->side.p, b.sideStride, h->partedBlocks.as<const uint32_t>(), h->nParted, block,
-                                                        s.launchGroups, h->stream);
-        } else {
-            le = (hipError_t)h->k->render(&a, home, activeUnits, block, lds.ldsTotal(), h->stream);
-        }
-        if (le != hipSuccess) {
-            h->eventPool.push_back(e0);
-            h->eventPool.push_back(e1);
-            return failHip(le, "render kernel launch");
-        }
-        if (launch) {
-            HIP_TRY(hipEventRecord(e1, h->stream));
-            h->pending.emplace_back(e0, e1);
-        }
-        if (p.flags & KAJO_FLAG_AOV) {
-            // the first-hit AOVs of the same passes, behind the render launch and outside its timing events (KajoCounters.kernelMs)
-            AovArgs g;
-            std::memset(&g, 0, sizeof g);
-            g.scene = h->view;
-            g.albedoHits = h->aovTiled ? h->aovTiles.p : h->aov.p;
-            g.slots = h->aovTiled ? (uint32_t)h->map.slotsPerOwner : (uint32_t)(h->W * h->H);
-            g.W = h->W;
-            g.H = h->H;
-            g.n = a.n;
-            g.pixelWidth = a.pixelWidth;
-            g.pixelHeight = a.pixelHeight;
-            g.sampleWidth = a.sampleWidth;
-            g.sampleHeight = a.sampleHeight;
-            g.firstPass = a.firstPass;
-            g.nPasses = now;
-            g.seed = a.seed;
-            if (p.flags & KAJO_FLAG_AOV_MATTE)
-                g.matteIds = h->aovTiled ? h->matteTiles.p : h->matte.p;
-            unsigned long long blocks = (unsigned long long)((h->W + 7) / 8) * ((h->H + 7) / 8);
-            if (h->aovTiled) {
-                // one wave per 8x8 block of the handle's own tiles, in the tile buffer's order (nTilesOwned > 0 here: no empty grid)
-                blocks = (unsigned long long)h->nTilesOwned * (p.tileW / 8) * (p.tileH / 8);
-                g.tiledBlocks = (int32_t)blocks;
-                g.tileWaves = (uint32_t)(p.tileW / 8) | ((uint32_t)(p.tileH / 8) << 16);
-                g.tileIndex = p.tileIndex;
-                g.tileCount = p.tileCount;
-            }
-            HIP_TRY((hipError_t)h->k->aov(&g, h->aovInstance, (unsigned)((blocks + 3) / 4), h->aovLds, h->stream));
-            h->aovPasses += now;
-        }
-        if (shortGrid) {
-            // adaptive sampling, behind every launch and outside the timing events: the retired slots extended to the new pass count and,
-            // at a batch boundary, the batch into the moments of the active ones (a handle that retires has rendered every pass: no rebase)
-            const int after = h->passesDone + now, boundary = after % KAJO_NOISE_BATCH_PASSES == 0;
-            HIP_TRY((hipError_t)kajo_adapt_step_launch(h->tiles.p, h->noiseBase.p, h->noiseMoments.p, h->adaptStateDev.p,
-                                                       (uint32_t)((size_t)h->nTilesOwned * p.tileW * p.tileH), h->adaptShift, boundary, after,
-                                                       h->stream));
-        } else if (h->noise && (h->passesDone + now) % KAJO_NOISE_BATCH_PASSES == 0) {
-            // a batch boundary, behind the launch (and its fold) and outside the timing events: the batch into the moments -- or, where this
-            // handle did not render all of it, only the baseline
-            if (h->noiseRebase)
-                HIP_TRY(hipMemcpyAsync(h->noiseBase.p, h->tiles.p, h->tileBytes, hipMemcpyDeviceToDevice, h->stream));
-            else
-                HIP_TRY((hipError_t)kajo_noise_update_launch(h->tiles.p, h->noiseBase.p, h->noiseMoments.p,
-                                                             (uint32_t)((size_t)h->nTilesOwned * p.tileW * p.tileH), h->stream));
-            h->noiseRebase = false;
-        }
-        if (a.waveTrips && s.split == 1 && s.chunks == 1) {
+        // launch, AOV, after-launch
+        if ((rc = launchRender(h, a, s, o, now)) || ((h->params.flags & KAJO_FLAG_AOV) && (rc = launchAov(h, now))) ||
+            (rc = afterLaunch(h, now, o.shortGrid)))
+            return rc;
+        // bookkeeping
+        if (o.trips && s.split == 1 && s.chunks == 1) {
             h->tripsPending = true;
-            a.waveTrips = nullptr; // later launches of this call keep the first measurement
+            trips = nullptr; // later launches of this call keep the first measurement
         }
-        if (launch)
+        if (o.activeUnits > 0)
             h->launches++;
         h->passesDone += now;
         h->carryValid = s.endsInside;
-        left -= now;
         if (h->adaptive) {
-            h->adaptPaths += h->adaptActivePixels * a.n * a.n * now;
-            if (h->adaptSet && activeUnits > 0 && !h->noiseRebase && h->passesDone >= h->adaptParams.minPasses &&
+            h->adaptPaths += h->adaptActivePixels * h->n * h->n * now;
+            if (h->adaptSet && o.activeUnits > 0 && !h->noiseRebase && h->passesDone >= h->adaptParams.minPasses &&
                 h->passesDone % (KAJO_NOISE_BATCH_PASSES * h->adaptParams.checkEvery) == 0 && (rc = adaptDecide(h)))
                 return rc;
         }
@@ -908,28 +916,11 @@ int kajo_hip_reset(kajo_hip_t h)
     if (!h)
         return fail(KAJO_E_INVALID, "null handle");
     int rc = kajo_hip_wait(h);
-    if (rc)
+    if (rc || (rc = clearAccumulators(h, true)))
         return rc;
-    HIP_TRY(hipMemsetAsync(h->tiles.p, 0, h->tileBytes, h->stream));
-    if (h->counters)
-        HIP_TRY(hipMemsetAsync(h->counters.p, 0, 32 * sizeof(unsigned long long), h->stream));
-    if (h->aov)
-        HIP_TRY(hipMemsetAsync(h->aov.p, 0, 2 * (size_t)h->W * h->H * 16, h->stream));
-    if (h->matte)
-        HIP_TRY(hipMemsetAsync(h->matte.p, 0, matteTableBytes(h), h->stream));
-    if (h->aovTiles)
-        HIP_TRY(hipMemsetAsync(h->aovTiles.p, 0, aovTileBytes(h), h->stream));
-    if (h->matteTiles)
-        HIP_TRY(hipMemsetAsync(h->matteTiles.p, 0, matteTileBytes(h), h->stream));
-    if (h->noise) {
-        HIP_TRY(hipMemsetAsync(h->noiseBase.p, 0, h->tileBytes, h->stream));
-        HIP_TRY(hipMemsetAsync(h->noiseMoments.p, 0, 2 * h->tileBytes, h->stream));
-        h->noiseRebase = false;
-    }
-    if (h->adaptive)
-        HIP_TRY(hipMemsetAsync(h->adaptStateDev.p, 0, (size_t)h->gridBlocks * sizeof(uint32_t), h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     adaptReactivate(h);
+    h->noiseRebase = false;
     h->aovComposed = h->matteComposed = false;
     h->aovPasses = 0;
     h->passesDone = 0;
@@ -950,15 +941,13 @@ int kajo_hip_set_pass_count(kajo_hip_t h, int passesDone)
     int rc = kajo_hip_wait(h);
     if (rc)
         return rc;
-    if (h->adaptive) { // (to pass 0: the moments start over below, and so do the units)
-        HIP_TRY(hipMemsetAsync(h->adaptStateDev.p, 0, (size_t)h->gridBlocks * sizeof(uint32_t), h->stream));
+    if (h->noise) {
+        // the moments start over (an adaptive handle, to pass 0: and so do the units); the baseline is the buffer at the first batch
+        // boundary from here on (kajo_hip_render)
+        if ((rc = clearAccumulators(h, false)))
+            return rc;
         HIP_TRY(hipStreamSynchronize(h->stream));
         adaptReactivate(h);
-    }
-    if (h->noise) {
-        // the moments start over; the baseline is the buffer at the first batch boundary from here on (kajo_hip_render)
-        HIP_TRY(hipMemsetAsync(h->noiseMoments.p, 0, 2 * h->tileBytes, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
         h->noiseRebase = true;
     }
     h->passesDone = passesDone;
@@ -1025,7 +1014,7 @@ int kajo_hip_compose_aov(kajo_hip_t h, const void* gatheredAov, const void* gath
     int rc = bind(h);
     if (rc)
         return rc;
-    HIP_TRY(h->aov.ensure(2 * (size_t)h->W * h->H * 16));
+    HIP_TRY(h->aov.ensure(aovFrameBytes(h)));
     if (gatheredMatte)
         HIP_TRY(h->matte.ensure(matteTableBytes(h)));
     HIP_TRY((hipError_t)kajo_compose_aov_launch(gatheredAov, gatheredMatte, &h->map, h->aov.p, gatheredMatte ? h->matte.p : nullptr, h->stream));
@@ -1272,18 +1261,11 @@ int kajo_hip_noise(kajo_hip_t h, const KajoNoiseParams* params, float* mean, flo
     if ((rc = kajo_hip_wait(h)))
         return rc;
     if (part && h->nTilesOwned > 0 && (mean || stderror || relative || batches))
-        for (int y = 0; y < h->H; y++)
-            for (int x = 0; x < h->W; x++) {
-                int owner;
-                uint32_t slot;
-                kajoTileSlot(h->map, x, y, &owner, &slot);
-                if (owner != h->params.tileIndex)
-                    continue;
-                const size_t at = (size_t)y * h->W + x;
-                for (int k = 0; k < 4; k++)
-                    if (dst[k])
-                        static_cast<uint32_t*>(dst[k])[at] = h->noiseStaged[k * pixels + at];
-            }
+        forOwnedPixels(h, [&](size_t at, uint32_t) {
+            for (int k = 0; k < 4; k++)
+                if (dst[k])
+                    static_cast<uint32_t*>(dst[k])[at] = h->noiseStaged[k * pixels + at];
+        });
     if (hist)
         std::memcpy(hist, counts, sizeof counts);
     if (result) {
@@ -1311,14 +1293,7 @@ int kajo_hip_read_noise_moments(kajo_hip_t h, KajoNoiseMoments* records)
     HIP_TRY(hipMemcpyAsync(own.data(), h->noiseMoments.p, own.size() * sizeof(KajoNoiseMoments), hipMemcpyDeviceToHost, h->stream));
     if ((rc = kajo_hip_wait(h)))
         return rc;
-    for (int y = 0; y < h->H; y++)
-        for (int x = 0; x < h->W; x++) {
-            int owner;
-            uint32_t slot;
-            kajoTileSlot(h->map, x, y, &owner, &slot);
-            if (owner == h->params.tileIndex)
-                records[(size_t)y * h->W + x] = own[slot];
-        }
+    forOwnedPixels(h, [&](size_t at, uint32_t slot) { records[at] = own[slot]; });
     return KAJO_OK;
 }
 
@@ -1407,7 +1382,7 @@ int kajo_hip_adapt_passes(kajo_hip_t h, uint32_t* plane)
     if (part && h->adaptStaged.size() < pixels)
         h->adaptStaged.resize(pixels);
     HIP_TRY(h->adaptOut.ensure(pixels * 4));
-    hipError_t le = (hipError_t)kajo_adapt_passes_launch(h->noiseMoments.p, h->adaptStateDev.p, &h->map, h->params.tileIndex, h->adaptShift,
+    hipError_t le = (hipError_t)kajo_adapt_passes_launch(h->noiseMoments.p, h->adaptStateDev.p, &h->map, h->params.tileIndex, h->unitShift,
                                                          (uint32_t)h->passesDone, h->adaptOut.p, h->stream);
     if (le != hipSuccess)
         return failHip(le, "adaptive pass plane kernel launch");
@@ -1415,14 +1390,7 @@ int kajo_hip_adapt_passes(kajo_hip_t h, uint32_t* plane)
     if ((rc = kajo_hip_wait(h)))
         return rc;
     if (part)
-        for (int y = 0; y < h->H; y++)
-            for (int x = 0; x < h->W; x++) {
-                int owner;
-                uint32_t slot;
-                kajoTileSlot(h->map, x, y, &owner, &slot);
-                if (owner == h->params.tileIndex)
-                    plane[(size_t)y * h->W + x] = h->adaptStaged[(size_t)y * h->W + x];
-            }
+        forOwnedPixels(h, [&](size_t at, uint32_t) { plane[at] = h->adaptStaged[at]; });
     return KAJO_OK;
 }
 

@@ -1,7 +1,9 @@
 // handle.h -- what the two halves of libkajo_hip.so's C ABI share: the KajoHip handle and its device buffers, the kernels' launchers and
 // one numerics build's set of them, the error text of kajo_hip_last_error, and the preamble of every image output (the device bound,
-// something rendered, the image to read). capi.cpp: create, render, compose, the readers, noise, adaptive sampling, the known-answer entry
-// points, the counters. present.cpp: the display stages and their chain. Private to those two files; inline functions, no symbols.
+// something rendered, the image to read). capi.cpp: create (its steps), the list of what accumulates, render (its steps), compose, the
+// readers, noise, adaptive sampling, the known-answer entry points, the counters. present.cpp: the display stages and their chain.
+// launch_plan.h: create's refusals, the frame plan (the handle's base), the LDS plan, the cut of the passes and the launch shape, without
+// HIP. Private to those two files; inline functions, no symbols.
 #ifndef KAJO_HANDLE_H
 #define KAJO_HANDLE_H
 
@@ -15,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <new>
 #include <string>
 #include <utility>
@@ -161,7 +164,8 @@ struct DeviceBuffer
     explicit operator bool() const { return p != nullptr; }
 };
 
-struct KajoHip
+// (KajoFramePlan, launch_plan.h: the tile map and the owner's share of it, the launch grid, what every launch has in common)
+struct KajoHip : KajoFramePlan
 {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -174,9 +178,6 @@ struct KajoHip
     DSceneView view{};
     std::vector<DeviceBuffer> sceneBuffers;
     KajoLdsPlan lds; // launch_plan.h
-    TileMap map{};
-    int tilesY = 0, nTiles = 0, nTilesOwned = 0, tilesPerOwner = 0;
-    size_t tileBytes = 0;
     DeviceBuffer tiles; // float4[slotsPerOwner]
     DeviceBuffer frame; // float4[W*H], lazily
     DeviceBuffer argb;  // uint32[W*H], lazily
@@ -186,7 +187,6 @@ struct KajoHip
     DeviceBuffer waveTrips;  // uint32 [grid * wavesPerBlock]
     DeviceBuffer blockOrder; // uint32 [grid]
     bool orderValid = false, tripsPending = false;
-    unsigned gridBlocks = 0;
     // launch tail (updateBlockOrder / partTheTail): the cost-sorted order on the host, how many of its last (cheapest) blocks are rendered in
     // parts, those blocks, and per number of parts G = 2 .. 8 the order with each of them expanded into G workgroups (built on first use)
     std::vector<uint32_t> hostOrder;
@@ -194,7 +194,6 @@ struct KajoHip
     DeviceBuffer partedBlocks;               // uint32 [nParted]
     unsigned nParted = 0;
     DeviceBuffer side;         // float4 [kMaxParts - 1][nParted * block threads]: the later parts' group sums of one launch
-    bool partsAllowed = false; // FAST / EXACT handle of a small scene that orders its launches and may divide them
     // FAST / EXACT, small scenes (render_args.h): a launch that ends inside a group of four passes leaves the group so far and the total of
     // the complete groups here
     DeviceBuffer carry;          // float4 [2][slotsPerOwner], on first need
@@ -202,6 +201,10 @@ struct KajoHip
     int waveSlots = 0;           // waves the chip holds at once with this handle's kernel (updateBlockOrder)
     unsigned lastTailGroups = 0; // KajoCounters.tailGroups
     int passesDone = 0;
+    // what every launch's arguments have in common, filled at create (kajo_hip_render sets the passes, the order and the carry)
+    RenderArgs renderArgs{};
+    AovArgs aovArgs{};
+    unsigned aovGrid = 0; // workgroups of an AOV launch: four 8x8 pixel blocks each
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; // kernel timing
     std::vector<hipEvent_t> eventPool;
     double kernelMs = 0.0;
@@ -285,11 +288,10 @@ struct KajoHip
     // kernels, adaptBlocks (their pixel blocks); adaptOut, on the first kajo_hip_adapt_passes: the plane
     bool adaptive = false, adaptSet = false;
     KajoAdaptParams adaptParams{};
-    AdaptGeom adaptGeom{};
     DeviceBuffer adaptStateDev, adaptUnits, adaptBlocks, adaptOut;
     uint32_t* adaptStateHost = nullptr; // [gridBlocks], pinned
     std::vector<uint32_t> adaptUnitPixels, adaptStaged;
-    unsigned adaptShift = 6, adaptRetired = 0;
+    unsigned adaptRetired = 0;
     long long adaptPixels = 0, adaptActivePixels = 0, adaptPaths = 0;
     int adaptLastDecision = 0;
     int toneScaleState = 0; // the s of the most recent tone mapping: 0 none yet, 1 toneScale, 2 the scale word (auto exposure)
@@ -313,11 +315,6 @@ inline int composeOwn(KajoHip* h)
     HIP_TRY((hipError_t)kajo_compose_launch(h->tiles.p, &h->map, h->frame.p, h->stream));
     h->frameValid = true;
     return KAJO_OK;
-}
-
-inline int samplesPerAxis(const KajoParams& p)
-{
-    return (int)std::sqrt((double)(unsigned)p.samplesPerPass); // Renderer.cpp:38
 }
 
 // camera samples summed into the AOVs

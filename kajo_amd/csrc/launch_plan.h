@@ -1,11 +1,18 @@
-// launch_plan.h -- how a handle uses the LDS and shapes its launches, as plain host arithmetic (capi.cpp kajo_hip_create / kajo_hip_render;
-// tools/host_san.cpp runs it for the host-only tests). Static functions: no symbols of libkajo_hip.so's.
+// launch_plan.h -- what kajo_hip_create refuses and derives from a frame, how a handle uses the LDS, cuts its passes into launches and
+// shapes them, as plain host arithmetic (capi.cpp kajo_hip_create / kajo_hip_render; tools/host_san.cpp and the programs inside
+// tests/test_tiles_cpu.py and tests/test_adaptive_cpu.py run the same lines for the host-only tests). Static functions, no HIP: no symbols
+// of libkajo_hip.so's.
 #ifndef KAJO_LAUNCH_PLAN_H
 #define KAJO_LAUNCH_PLAN_H
 
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 
+#include "kajo_hip.h"
+
+#include "adapt_math.h"
 #include "render_args.h"
 #include "stage.h"
 #include "tuning.h"
@@ -14,6 +21,74 @@ constexpr int kMaxParts = 8; // workgroups a block of the launch tail is rendere
 
 // numerics build a handle runs (include/kajo_hip.h)
 enum class Numerics { Fast, Strict, Exact };
+
+static inline Numerics kajoNumerics(uint32_t flags)
+{
+    return (flags & KAJO_FLAG_STRICT) ? Numerics::Strict : (flags & KAJO_FLAG_EXACT) ? Numerics::Exact : Numerics::Fast;
+}
+
+static inline int samplesPerAxis(const KajoParams& p)
+{
+    return (int)sqrt((double)(unsigned)p.samplesPerPass); // Renderer.cpp:38
+}
+
+// The parameter refusals of kajo_hip_create (KAJO_E_INVALID), which it issues before it looks for a device, in its order: the sentence of
+// the first check that fails, or null. *p: the caller's parameters; the defaults are applied to it (tile 0 -> 64x16, tileCount 0 -> 1).
+// msg: room for the one sentence that names what it found.
+static inline const char* kajoCheckCreate(const KajoScene& scene, int width, int height, KajoParams* params, char (&msg)[256])
+{
+    KajoParams& p = *params;
+    if (width <= 0 || height <= 0 || (long long)width * height > (1ll << 31) - 1)
+        return "image size out of range";
+    if (scene.nPlanes < 0 || scene.nSpheres < 0 || (scene.nPlanes && !scene.planes) || (scene.nSpheres && !scene.spheres))
+        return "scene arrays inconsistent";
+    if (p.tileW == 0)
+        p.tileW = 64;
+    if (p.tileH == 0)
+        p.tileH = 16;
+    if (p.tileCount == 0)
+        p.tileCount = 1;
+    if (p.samplesPerPass < 1 || p.samplesPerPass > 65535)
+        return "samplesPerPass must be in [1, 65535]";
+    if ((p.flags & KAJO_FLAG_STRICT) && (p.flags & KAJO_FLAG_EXACT))
+        return "the strict and the exact flag name two different numerics builds: set one";
+    if (p.flags & KAJO_FLAG_COOP)
+        return "KAJO_FLAG_COOP: the cooperative-traversal experiment is not built into this library (make -C kajo_amd/csrc experiments)";
+    if (p.flags & KAJO_FLAG_DEFERRED)
+        return "KAJO_FLAG_DEFERRED: the deferred-shading experiment is not built into this library (make -C kajo_amd/csrc experiments)";
+    if (p.depthLimit < 0 || p.depthLimit > 1000) // (the reference's limit is 8)
+        return "depthLimit must be in [0, 1000]";
+    if (p.tileW < 8 || p.tileH < 8 || (p.tileW & 7) || (p.tileH & 7) || ((long long)p.tileW * p.tileH) % 256)
+        return "tile size must be multiples of 8 with tileW*tileH a multiple of 256";
+    if (p.tileCount < 1 || p.tileIndex < 0 || p.tileIndex >= p.tileCount)
+        return "tileIndex/tileCount out of range";
+    if ((p.flags & KAJO_FLAG_AOV) && !(p.flags & KAJO_FLAG_AOV_TILED) && p.tileCount != 1)
+        return "first-hit AOVs need the whole frame on one handle (tileCount 1)";
+    if ((p.flags & KAJO_FLAG_AOV_SPECULAR) && !(p.flags & KAJO_FLAG_AOV))
+        return "the first-non-delta-hit flag changes what the AOV flag's buffers hold: set the AOV flag with it";
+    if ((p.flags & KAJO_FLAG_AOV_MATTE) && !(p.flags & KAJO_FLAG_AOV))
+        return "the matte flag keeps its coverage tables over the AOV flag's samples: set the AOV flag with it";
+    if ((p.flags & KAJO_FLAG_AOV_TILED) && !(p.flags & KAJO_FLAG_AOV))
+        return "the tiled flag changes where the AOV flag's sums are kept: set the AOV flag with it";
+    if ((p.flags & KAJO_FLAG_ADAPTIVE) && !(p.flags & KAJO_FLAG_NOISE))
+        return "the adaptive flag retires units by the noise flag's estimate: set the noise flag with it";
+    // (aov.inc.hip: a wave of the tiled launch carries its block's corner and the tile's shape in 16-bit fields, in units of 8 pixels)
+    if ((p.flags & KAJO_FLAG_AOV_TILED) && (width > 524288 || height > 262144 || p.tileW > 524280 || p.tileH > 524280))
+        return "tiled AOVs: the frame must be within 524288 x 262144 and a tile within 524280 pixels a side";
+    if (p.flags & (KAJO_FLAG_STRICT | KAJO_FLAG_EXACT)) {
+        // integrator.inc.hip kdiv / ksqrt: the IEEE quotient and root without the compiler's range scaling are exact while operands stay
+        // dozens of binades inside the float range, which a scene of ordinary coordinates guarantees; outside it STRICT would silently
+        // stop being the oracle
+        float lo = 0.f, hi = 0.f;
+        kajo::coordinateRange(scene, &lo, &hi);
+        if (!(hi == hi) || (hi > 0.f && (lo < 0x1p-40f || hi > 0x1p40f))) {
+            snprintf(msg, sizeof msg, "strict / exact numerics need the scene's non-zero coordinates within 2^-40 .. 2^40 in magnitude "
+                                      "(found %g .. %g): use the fast build or rescale the scene", (double)lo, (double)hi);
+            return msg;
+        }
+    }
+    return nullptr;
+}
 
 // What a scene puts in LDS (device_scene.h / integrator.inc.hip renderBody): hot records always, cold records in the small-scene kernels,
 // the grid's header and -- if it fits -- its cell lists in the large-scene ones.
@@ -148,6 +223,72 @@ static inline KajoLdsPlan kajoLdsPlan(size_t hotBytes, size_t coldBytes, size_t 
     return p;
 }
 
+static inline KajoLdsPlan kajoLdsPlan(const kajo::StagedScene& st, Numerics numerics)
+{
+    const KajoSceneLds b = kajoSceneLds(st);
+    return kajoLdsPlan(b.hotBytes, b.coldBytes, b.gridHeaderBytes, b.gridBytes, st.gridEnabled, st.shadowEnabled, (int)st.light.size(), numerics);
+}
+
+// What kajo_hip_create derives from the frame, the parameters (defaults applied: kajoCheckCreate) and the scene's plan: the owner's share
+// of the tiles, its launch grid, and what every launch of the handle has in common. 64-bit where a frame create accepts could overflow.
+struct KajoFramePlan
+{
+    TileMap map{};
+    int tilesY = 0, nTiles = 0, nTilesOwned = 0, tilesPerOwner = 0;
+    size_t tileBytes = 0;              // float4 [map.slotsPerOwner]
+    unsigned long long gridBlocks = 0; // workgroups of a whole launch (the units of adaptive sampling): the owner's pixel blocks / wavesPerBlock
+    bool tooManyBlocks = false;        // ... 2^28 or more (render_args.h: an order word has 28 bits for the block): create refuses the frame
+    unsigned long long pixelBlocks = 0; // the owner's 8x8 pixel blocks in whole launch blocks
+    int n = 0;                         // samplesPerAxis
+    bool grouped = false;              // integrator.inc.hip GROUPS: FAST / EXACT kernels of small scenes
+    int home = 0;                      // launch.inc.hip: coldInLds, or 2: the small-scene instance of any number of lights although the scene
+                                       // has one (KAJO_FLAG_NO_ONE_LIGHT)
+    bool partsAllowed = false;         // FAST / EXACT handle of a small scene that orders its launches and may divide them (capi.cpp partTheTail)
+    unsigned unitShift = 0;            // adaptive sampling: a unit is 1 << unitShift slots; 0: neither 64, 128 nor 256, create refuses the flag
+    AdaptGeom adaptGeom{};
+};
+
+static inline KajoFramePlan kajoFramePlan(int W, int H, const KajoParams& p, const KajoLdsPlan& lds, Numerics numerics)
+{
+    KajoFramePlan f;
+    TileMap& m = f.map;
+    m.W = W;
+    m.H = H;
+    m.tileW = p.tileW;
+    m.tileH = p.tileH;
+    m.tilesX = (int32_t)(((long long)W + p.tileW - 1) / p.tileW);
+    m.tileCount = p.tileCount;
+    f.tilesY = (int)(((long long)H + p.tileH - 1) / p.tileH);
+    f.nTiles = m.tilesX * f.tilesY;
+    f.tilesPerOwner = (int)(((long long)f.nTiles + p.tileCount - 1) / p.tileCount);
+    f.nTilesOwned = (int)(((long long)f.nTiles - p.tileIndex + p.tileCount - 1) / p.tileCount);
+    if (f.nTilesOwned < 0)
+        f.nTilesOwned = 0;
+    m.slotsPerOwner = (int32_t)((long long)f.tilesPerOwner * p.tileW * p.tileH);
+    f.tileBytes = (size_t)m.slotsPerOwner * 16;
+    f.gridBlocks = (unsigned long long)f.nTilesOwned * (p.tileW / 8) * (p.tileH / 8) / lds.wavesPerBlock;
+    f.tooManyBlocks = f.gridBlocks >= (1ull << 28);
+    f.pixelBlocks = f.gridBlocks * lds.wavesPerBlock;
+    f.n = samplesPerAxis(p);
+    f.grouped = lds.coldInLds && numerics != Numerics::Strict;
+    f.home = (lds.coldInLds && (p.flags & KAJO_FLAG_NO_ONE_LIGHT)) ? 2 : lds.coldInLds;
+    f.partsAllowed = f.grouped && !(p.flags & (KAJO_FLAG_NO_SPLIT | KAJO_FLAG_NO_REORDER));
+    f.unitShift = lds.wavesPerBlock == 1 ? 6 : lds.wavesPerBlock == 2 ? 7 : lds.wavesPerBlock == 4 ? 8 : 0;
+    f.adaptGeom = AdaptGeom{W, H, p.tileW, p.tileH, m.tilesX, p.tileIndex, p.tileCount, f.nTilesOwned};
+    return f;
+}
+
+// The passes of the next launch of kajo_hip_render with `left` to go: passesPerLaunch at the most (0: 16) and, on a handle with the noise
+// flag, none across an absolute multiple of the batch (the frame's bits do not depend on the cut)
+static inline int kajoLaunchPasses(int left, int passesPerLaunch, bool noise, int passesDone)
+{
+    const int perLaunch = passesPerLaunch > 0 ? passesPerLaunch : 16;
+    int now = left < perLaunch ? left : perLaunch;
+    if (noise && now > KAJO_NOISE_BATCH_PASSES - passesDone % KAJO_NOISE_BATCH_PASSES)
+        now = KAJO_NOISE_BATCH_PASSES - passesDone % KAJO_NOISE_BATCH_PASSES;
+    return now;
+}
+
 // The shape of one launch of kajo_hip_render: how it joins the groups of four passes, and how many waves share a pixel block.
 struct KajoLaunchShape
 {
@@ -208,6 +349,14 @@ static inline KajoLaunchShape kajoLaunchShape(unsigned long long pixelBlocks, in
     }
     s.parted = s.chunks == 1 && s.split == 1 && grouped && orderValid && nParted && s.launchGroups >= 2 && s.launchGroups <= kMaxParts;
     return s;
+}
+
+// ... of a handle's launch of `now` passes behind passesDone
+static inline KajoLaunchShape kajoLaunchShape(const KajoFramePlan& f, const KajoLdsPlan& lds, uint32_t flags, int now, int passesDone, bool orderValid,
+                                              unsigned nParted)
+{
+    return kajoLaunchShape(f.pixelBlocks, now, f.n, lds.coldInLds, (flags & KAJO_FLAG_NO_SPLIT) != 0, lds.mailboxOffset(), lds.perWaveBytes(false),
+                           passesDone, f.grouped, orderValid, nParted);
 }
 
 #endif

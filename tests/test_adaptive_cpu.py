@@ -221,28 +221,24 @@ def test_the_filter_under_asan_and_ubsan(tmp_path):
 SLOT_SOURCE = r"""
 // adaptSlotPixel (adapt_math.h) beside kajoTileSlot (render_args.h) as host code: for every case (W H tileW tileH owners) on the command
 // line, as 32-bit words on stdout: the slots per owner; (owner, slot) of every pixel, row-major, by kajoTileSlot; then for every owner and
-// every slot of its buffer (answer, px, py) by adaptSlotPixel. Map and geometry are filled as kajo_hip_create fills them (capi.cpp).
+// every slot of its buffer (answer, px, py) by adaptSlotPixel. Map and geometry are the ones kajo_hip_create fills: launch_plan.h
+// kajoFramePlan's, owner by owner.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
-#include "adapt_math.h"
-#include "render_args.h"
+#include "launch_plan.h"
 
 int main(int argc, char** argv)
 {
     for (int a = 1; a + 4 < argc; a += 5) {
-        TileMap m{};
-        m.W = atoi(argv[a]);
-        m.H = atoi(argv[a + 1]);
-        m.tileW = atoi(argv[a + 2]);
-        m.tileH = atoi(argv[a + 3]);
-        m.tileCount = atoi(argv[a + 4]);
-        m.tilesX = (m.W + m.tileW - 1) / m.tileW;
-        const int tilesY = (m.H + m.tileH - 1) / m.tileH, nTiles = m.tilesX * tilesY;
-        const int perOwner = (nTiles + m.tileCount - 1) / m.tileCount;
-        m.slotsPerOwner = perOwner * m.tileW * m.tileH;
+        KajoParams p{};
+        p.tileW = atoi(argv[a + 2]);
+        p.tileH = atoi(argv[a + 3]);
+        p.tileCount = atoi(argv[a + 4]);
+        const int W = atoi(argv[a]), H = atoi(argv[a + 1]);
+        const TileMap m = kajoFramePlan(W, H, p, KajoLdsPlan(), Numerics::Fast).map;
         std::vector<int32_t> out;
         out.push_back(m.slotsPerOwner);
         for (int y = 0; y < m.H; y++)
@@ -254,10 +250,8 @@ int main(int argc, char** argv)
                 out.push_back((int32_t)slot);
             }
         for (int o = 0; o < m.tileCount; o++) {
-            int owned = (nTiles - o + m.tileCount - 1) / m.tileCount;
-            if (owned < 0)
-                owned = 0;
-            const AdaptGeom g{m.W, m.H, m.tileW, m.tileH, m.tilesX, o, m.tileCount, owned};
+            p.tileIndex = o;
+            const AdaptGeom g = kajoFramePlan(W, H, p, KajoLdsPlan(), Numerics::Fast).adaptGeom;
             for (uint32_t s = 0; s < (uint32_t)m.slotsPerOwner; s++) {
                 int px = -1, py = -1;
                 out.push_back(kajo::adaptSlotPixel(g, s, &px, &py) ? 1 : 0);

@@ -57,6 +57,7 @@ def shape(tmp_path_factory, scenes):
             row["line"] = line
         return rows
 
+    run.exe = exe
     return run
 
 
@@ -152,6 +153,20 @@ def test_chunks_2_needs_a_frame_of_512_pixel_blocks(shape):
     assert (big["pixelBlocks"], big["chunks"]) == (512, 2), big["line"]
     assert (below["pixelBlocks"], below["chunks"]) == (448, 4), below["line"]
     assert all(at(size)["chunks"] == 4 for size in ((41, 23), (72, 40)))
+
+
+@pytest.mark.parametrize("noise", [True, False], ids=["noise", "plain"])
+@pytest.mark.parametrize("ppl", [0, 1, 2, 3, 16])
+def test_the_cuts_of_kajo_hip_render_are_the_ones_this_table_is_built_from(shape, ppl, noise):
+    """launches() (tests/adaptive_shape_cases.py) restates the cut rule; `host_san plan cuts` prints kajoLaunchPasses, which kajo_hip_render
+    calls: for every entry of CUTS, from pass 0 and from pass 5"""
+    for cuts in CUTS:
+        for done in (0, 5):
+            args = [shape.exe, "plan", "cuts", ppl, int(noise), done, *cuts]
+            out = subprocess.run([str(a) for a in args], capture_output=True, text=True, check=True).stdout.split()
+            got = list(zip(map(int, out[0::2]), map(int, out[1::2])))
+            assert got == launches(cuts, ppl, noise, done), (cuts, ppl, noise, done)
+            assert sum(now for now, _ in got) == sum(cuts)
 
 
 def test_the_tool_refuses_what_create_refuses(shape):

@@ -273,10 +273,18 @@ def test_the_device_code_of_every_kernel_from_before_is_unchanged_function_by_fu
 def test_the_kernels_live_in_a_unit_of_their_own_which_every_numerics_build_links():
     """No render, AOV or display source names them, and no other unit's compile line names the new one (that their device code is what it was is
     the test above)."""
+    # (launch_plan.h: host arithmetic which no device source includes -- asserted below; kajo_hip_create's validation, which it holds, names
+    # the flag in the refusal of the adaptive flag without it, as capi.cpp did while the validation was there)
+    host_only = {"launch_plan.h": ("handle.h",), "handle.h": ("capi.cpp", "present.cpp")}
     for name in os.listdir(CSRC):
+        if name.endswith((".hip", ".h", ".cpp")):
+            text = open(os.path.join(CSRC, name)).read()
+            for header, users in host_only.items():
+                assert ('#include "%s"' % header in text) == (name in users), (name, header)
         if name.endswith((".hip", ".h")) and name != "noise.hip":
             text = open(os.path.join(CSRC, name)).read()
-            assert not re.search(r'#include\s+"noise\.hip"', text) and "kajo_noise" not in text and "KAJO_FLAG_NOISE" not in text, name
+            assert not re.search(r'#include\s+"noise\.hip"', text) and "kajo_noise" not in text, name
+            assert "KAJO_FLAG_NOISE" not in text or name == "launch_plan.h", name
     text = open(os.path.join(CSRC, "noise.hip")).read()
     assert re.findall(r'#include "([^"]+)"', text) == ["render_args.h"]
     plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, "all", "tune"], capture_output=True, text=True, check=True).stdout

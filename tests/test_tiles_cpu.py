@@ -56,27 +56,22 @@ def test_layout_is_a_bijection_onto_distinct_slots(case):
 
 SOURCE = r"""
 // kajoTileSlot as host code: for every case (W H tileW tileH owners) on the command line, the slots per owner and then (owner, slot)
-// of every pixel, row-major, as 32-bit words on stdout. The map is filled as kajo_hip_create fills it (capi.cpp).
+// of every pixel, row-major, as 32-bit words on stdout. The map is the one kajo_hip_create fills: launch_plan.h kajoFramePlan's.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
-#include "render_args.h"
+#include "launch_plan.h"
 
 int main(int argc, char** argv)
 {
     for (int a = 1; a + 4 < argc; a += 5) {
-        TileMap m{};
-        m.W = atoi(argv[a]);
-        m.H = atoi(argv[a + 1]);
-        m.tileW = atoi(argv[a + 2]);
-        m.tileH = atoi(argv[a + 3]);
-        m.tileCount = atoi(argv[a + 4]);
-        m.tilesX = (m.W + m.tileW - 1) / m.tileW;
-        const int tilesY = (m.H + m.tileH - 1) / m.tileH;
-        const int perOwner = (m.tilesX * tilesY + m.tileCount - 1) / m.tileCount;
-        m.slotsPerOwner = perOwner * m.tileW * m.tileH;
+        KajoParams p{};
+        p.tileW = atoi(argv[a + 2]);
+        p.tileH = atoi(argv[a + 3]);
+        p.tileCount = atoi(argv[a + 4]);
+        const TileMap m = kajoFramePlan(atoi(argv[a]), atoi(argv[a + 1]), p, KajoLdsPlan(), Numerics::Fast).map;
         std::vector<uint32_t> out;
         out.push_back((uint32_t)m.slotsPerOwner);
         for (int y = 0; y < m.H; y++)

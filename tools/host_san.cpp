@@ -9,7 +9,10 @@
 //   host_san plan shape in.bin out.bin   launch_plan.h kajoLaunchShape over a table of launches
 //   host_san plan shape a.pod W H tileW tileH S fast|strict|exact flags tileIndex tileCount now passesDone [now passesDone ...]
 //                                        the plan and the launch shapes of a handle of that scene, frame, S, build and flags
-//                                        (tests/test_launch_shapes_cpu.py): kajoLdsPlan and kajoLaunchShape as create / render call them
+//                                        (tests/test_launch_shapes_cpu.py): kajoCheckCreate, kajoLdsPlan, kajoFramePlan and kajoLaunchShape,
+//                                        the functions create / render call
+//   host_san plan cuts passesPerLaunch noise passesDone call [call ...]
+//                                        launch_plan.h kajoLaunchPasses: "now passesDone" of every launch kajo_hip_render cuts the calls into
 //   host_san plan sizes a.pod ...        what a scene's size does to its staging (tests/test_scene_sizes_cpu.py): the plan's ldsTotal() per
 //                                        numerics build, the grid's cells per axis against the cells it wanted, the visibility lists' bins
 //                                        and their longest row of 16-bit offsets
@@ -147,11 +150,9 @@ static int order(int argc, char** argv)
 static int tiles(int argc, char** argv)
 {
     if (argc != 5) return 2;
-    TileMap m{};
-    m.W = atoi(argv[0]); m.H = atoi(argv[1]); m.tileW = atoi(argv[2]); m.tileH = atoi(argv[3]); m.tileCount = atoi(argv[4]);
-    m.tilesX = (m.W + m.tileW - 1) / m.tileW;
-    const int tilesY = (m.H + m.tileH - 1) / m.tileH, nTiles = m.tilesX * tilesY, perOwner = (nTiles + m.tileCount - 1) / m.tileCount;
-    m.slotsPerOwner = perOwner * m.tileW * m.tileH;
+    KajoParams p{};
+    p.tileW = atoi(argv[2]); p.tileH = atoi(argv[3]); p.tileCount = atoi(argv[4]);
+    const TileMap m = kajoFramePlan(atoi(argv[0]), atoi(argv[1]), p, KajoLdsPlan(), Numerics::Fast).map; // (the map as kajo_hip_create fills it)
     std::vector<unsigned char> taken((size_t)m.tileCount * m.slotsPerOwner, 0);
     for (int y = 0; y < m.H; y++)
         for (int x = 0; x < m.W; x++) {
@@ -177,10 +178,8 @@ static int planLds(int argc, char** argv)
             const bool grid = strcmp(staging, "no_grid") != 0, lists = strcmp(staging, "no_shadow_lists") != 0;
             kajo::StagedScene st;
             kajo::stageScene(pod.sc, st, grid ? 48 : 0, lists); // (as kajo_hip_create stages with KAJO_FLAG_NO_GRID / NO_SHADOW_LISTS)
-            const KajoSceneLds b = kajoSceneLds(st);
             for (Numerics k : {Numerics::Fast, Numerics::Strict, Numerics::Exact}) {
-                const KajoLdsPlan p = kajoLdsPlan(b.hotBytes, b.coldBytes, b.gridHeaderBytes, b.gridBytes, st.gridEnabled, st.shadowEnabled,
-                                                  (int)st.light.size(), k);
+                const KajoLdsPlan p = kajoLdsPlan(st, k);
                 printf("%s %s %s: big=%d coldInLds=%d gridInLds=%d stealWindow=%d helpBytes=%d accBytes=%d thrL=%d holdTrips=%d hotBytes=%zu "
                        "ldsBytes=%zu wavesPerBlock=%u fits=%d\n",
                        argv[a], staging, k == Numerics::Fast ? "fast" : k == Numerics::Strict ? "strict" : "exact", p.big, p.coldInLds, p.gridInLds,
@@ -201,11 +200,9 @@ static int planSizes(int argc, char** argv)
         if (int rc = pod.read(argv[a])) return rc;
         kajo::StagedScene st;
         kajo::stageScene(pod.sc, st, 48, true);
-        const KajoSceneLds b = kajoSceneLds(st);
         printf("%s: nSpheres=%d nLights=%zu grid=%d lists=%d", argv[a], st.nSpheres, st.light.size(), st.gridEnabled, st.shadowEnabled);
         for (Numerics k : {Numerics::Fast, Numerics::Strict, Numerics::Exact}) {
-            const KajoLdsPlan p = kajoLdsPlan(b.hotBytes, b.coldBytes, b.gridHeaderBytes, b.gridBytes, st.gridEnabled, st.shadowEnabled,
-                                              (int)st.light.size(), k);
+            const KajoLdsPlan p = kajoLdsPlan(st, k);
             const char* name = k == Numerics::Fast ? "Fast" : k == Numerics::Strict ? "Strict" : "Exact";
             printf(" ldsTotal%s=%zu fits%s=%d", name, p.ldsTotal(), name, p.fits);
         }
@@ -265,44 +262,56 @@ static int planShape(int argc, char** argv)
     return 0;
 }
 
-// Launch shapes of a handle as kajo_hip_create / kajo_hip_render would plan them: one line "now=.. passesDone=..: field=value ..." per
-// launch. argv: a.pod W H tileW tileH S fast|strict|exact flags tileIndex tileCount, then now passesDone for every launch. The scene is
-// staged by the flags as create() stages it, the plan is kajoLdsPlan's, the pixel blocks are those of the owner's tiles and the shape is
-// kajoLaunchShape's. What kajo_hip_render itself derives from the plan is taken the way it takes it: n (handle.h samplesPerAxis),
-// `grouped` and `home`. parted: with an order and a tail to part (orderValid, nParted = 1), which is the most a launch can be.
+// Launch shapes of a handle as kajo_hip_create / kajo_hip_render plan them, through the functions they call: one line "now=..
+// passesDone=..: field=value ..." per launch. argv: a.pod W H tileW tileH S fast|strict|exact flags tileIndex tileCount, then now
+// passesDone for every launch. kajoCheckCreate refuses what create refuses (exit code 2), the scene is staged by the flags as create()
+// stages it, the plans are kajoLdsPlan's (7: it does not fit) and kajoFramePlan's, the shape is kajoLaunchShape's. parted: with an order
+// and a tail to part (orderValid, nParted = 1), which is the most a launch can be.
 static int planShapeOf(int argc, char** argv)
 {
     if (argc < 12 || (argc - 10) % 2 != 0) return 2;
     Pod pod;
     if (int rc = pod.read(argv[0])) return rc;
-    const int W = atoi(argv[1]), H = atoi(argv[2]), tileW = atoi(argv[3]), tileH = atoi(argv[4]), S = atoi(argv[5]);
     const std::string build = argv[6];
     if (build != "fast" && build != "strict" && build != "exact") return 2;
-    const Numerics numerics = build == "strict" ? Numerics::Strict : build == "exact" ? Numerics::Exact : Numerics::Fast;
-    const int flags = atoi(argv[7]), tileIndex = atoi(argv[8]), tileCount = atoi(argv[9]);
-    if (W < 1 || H < 1 || tileW < 8 || tileH < 8 || tileW % 8 || tileH % 8 || S < 1 || tileCount < 1 || tileIndex < 0 || tileIndex >= tileCount) return 2;
+    KajoParams p{};
+    p.samplesPerPass = atoi(argv[5]);
+    p.flags = (uint32_t)atoi(argv[7]) | (build == "strict" ? KAJO_FLAG_STRICT : build == "exact" ? KAJO_FLAG_EXACT : 0u);
+    p.tileW = atoi(argv[3]); p.tileH = atoi(argv[4]); p.tileIndex = atoi(argv[8]); p.tileCount = atoi(argv[9]);
+    const int W = atoi(argv[1]), H = atoi(argv[2]);
+    char msg[256];
+    if (kajoCheckCreate(pod.sc, W, H, &p, msg)) return 2;
     kajo::StagedScene st;
-    kajo::stageScene(pod.sc, st, (flags & KAJO_FLAG_NO_GRID) ? 0 : 48, !(flags & KAJO_FLAG_NO_SHADOW_LISTS));
-    const KajoSceneLds b = kajoSceneLds(st);
-    const KajoLdsPlan lds = kajoLdsPlan(b.hotBytes, b.coldBytes, b.gridHeaderBytes, b.gridBytes, st.gridEnabled, st.shadowEnabled, (int)st.light.size(), numerics);
+    kajo::stageScene(pod.sc, st, (p.flags & KAJO_FLAG_NO_GRID) ? 0 : 48, !(p.flags & KAJO_FLAG_NO_SHADOW_LISTS));
+    const KajoLdsPlan lds = kajoLdsPlan(st, kajoNumerics(p.flags));
     if (!lds.fits) return 7;
-    const int nTiles = ((W + tileW - 1) / tileW) * ((H + tileH - 1) / tileH);
-    const int nTilesOwned = std::max(0, (nTiles - tileIndex + tileCount - 1) / tileCount);
-    const unsigned gridBlocks = (unsigned)((long long)nTilesOwned * ((tileW / 8) * (tileH / 8)) / lds.wavesPerBlock);
-    const unsigned long long pixelBlocks = (unsigned long long)gridBlocks * lds.wavesPerBlock;
-    const int n = (int)std::sqrt((double)(unsigned)S);
-    const bool grouped = lds.coldInLds && numerics != Numerics::Strict;
-    const int home = (lds.coldInLds && (flags & KAJO_FLAG_NO_ONE_LIGHT)) ? 2 : lds.coldInLds;
+    const KajoFramePlan f = kajoFramePlan(W, H, p, lds, kajoNumerics(p.flags));
+    if (f.tooManyBlocks) return 2;
     for (int a = 10; a + 1 < argc; a += 2) {
         const int now = atoi(argv[a]), passesDone = atoi(argv[a + 1]);
         if (now < 1 || passesDone < 0) return 2;
-        const KajoLaunchShape s = kajoLaunchShape(pixelBlocks, now, n, lds.coldInLds, (flags & KAJO_FLAG_NO_SPLIT) != 0, lds.mailboxOffset(),
-                                                  lds.perWaveBytes(false), passesDone, grouped, true, 1u);
+        const KajoLaunchShape s = kajoLaunchShape(f, lds, p.flags, now, passesDone, true, 1u);
         printf("now=%d passesDone=%d: split=%u chunks=%u parted=%d startsInside=%d endsInside=%d launchGroups=%d wavesPerBlock=%u coldInLds=%d "
-               "home=%d grouped=%d n=%d gridBlocks=%u pixelBlocks=%llu ldsTotal=%zu\n",
-               now, passesDone, s.split, s.chunks, s.parted, s.startsInside, s.endsInside, s.launchGroups, lds.wavesPerBlock, lds.coldInLds, home,
-               grouped, n, gridBlocks, pixelBlocks, lds.ldsTotal());
+               "home=%d grouped=%d n=%d gridBlocks=%llu pixelBlocks=%llu ldsTotal=%zu\n",
+               now, passesDone, s.split, s.chunks, s.parted, s.startsInside, s.endsInside, s.launchGroups, lds.wavesPerBlock, lds.coldInLds, f.home,
+               f.grouped, f.n, f.gridBlocks, f.pixelBlocks, lds.ldsTotal());
     }
+    return 0;
+}
+
+// The launches kajo_hip_render cuts calls into: "now passesDone" per launch. argv: passesPerLaunch noise(0|1) passesDone, then the passes
+// of every call.
+static int planCuts(int argc, char** argv)
+{
+    if (argc < 4) return 2;
+    const int perLaunch = atoi(argv[0]), noise = atoi(argv[1]);
+    int done = atoi(argv[2]);
+    if (perLaunch < 0 || done < 0) return 2;
+    for (int a = 3; a < argc; a++)
+        for (int left = atoi(argv[a]), now; left > 0; left -= now, done += now) {
+            now = kajoLaunchPasses(left, perLaunch, noise != 0, done);
+            printf("%d %d\n", now, done);
+        }
     return 0;
 }
 
@@ -311,6 +320,7 @@ static int plan(int argc, char** argv)
     if (argc < 1) return 2;
     const std::string what = argv[0];
     if (what == "lds") return planLds(argc - 1, argv + 1);
+    if (what == "cuts") return planCuts(argc - 1, argv + 1);
     if (what == "shape" && argc - 1 > 2) return planShapeOf(argc - 1, argv + 1);
     if (what == "shape") return planShape(argc - 1, argv + 1);
     if (what == "sizes") return planSizes(argc - 1, argv + 1);
