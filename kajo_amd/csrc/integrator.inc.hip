@@ -532,7 +532,10 @@ KDEV void gridWalk(const DSceneView& sc, const LdsScene& lds, F3 O, F3 d, float 
 // registers hold: a wave walks as long as its longest lane.
 // LISTS_SCENE: the scene is known to have visibility lists -- and so (stage.cpp buildShadowLists / buildGrid) a closed room, the grid, rigid
 // planes and nothing but (centre, radius) spheres: the kernel instances of such scenes carry one plane loop and the grid walk, nothing else.
-template <bool GRID, int GHOME = 0, bool LISTS_SCENE = false>
+// SIMPLE: the scene is known to have rigid planes and nothing but (centre, radius) spheres (launch.inc.hip picks the kernel): a small-scene
+// kernel instantiated with it carries one plane loop and one sphere loop (kernel_exact_simple.cpp); every other scene runs the kernels
+// that carry the general loops beside them.
+template <bool GRID, int GHOME = 0, bool LISTS_SCENE = false, bool SIMPLE = false>
 KDEV Hit trace(const DSceneView& sc, const LdsScene& lds, F3 O, F3 d, bool hasRay = true)
 {
     float tMax = __builtin_inff(); // Ray.cpp:10-13; minDistance = 0
@@ -550,7 +553,7 @@ KDEV Hit trace(const DSceneView& sc, const LdsScene& lds, F3 O, F3 d, bool hasRa
     uint32_t kMax = 0x7f800000u; // +inf
     uint32_t idV = 1;
     asm volatile("" : "+v"(idV));
-    if (LISTS_SCENE || sc.planesRigid) {
+    if (LISTS_SCENE || SIMPLE || sc.planesRigid) {
         // |det - 1| <= 2^-20 for every plane: t * det is t to within its own rounding, and the
         // second sign test repeats the first
         for (int i = 0; i < np; i++) {
@@ -570,7 +573,7 @@ KDEV Hit trace(const DSceneView& sc, const LdsScene& lds, F3 O, F3 d, bool hasRa
     } else
 #endif
 #if KAJO_STRICT
-    if (LISTS_SCENE || sc.planesRigid) {
+    if (LISTS_SCENE || SIMPLE || sc.planesRigid) {
         // Every determinant within 2^-20 of 1 (all of the reference's data/ scenes: rotations and translations): t * det has the sign
         // of t -- a positive factor cannot make a product negative, and -0 stays -0, which `< 0` does not hold for either -- so
         // Raytracer.cpp:115's `t < ray.min` repeats :85-86's `t < 0` and is not asked again. The same t, the same t * det.
@@ -636,7 +639,7 @@ KDEV Hit trace(const DSceneView& sc, const LdsScene& lds, F3 O, F3 d, bool hasRa
         }
     }
 #if !KAJO_STRICT
-    if (sc.allTranslated) {
+    if (SIMPLE || sc.allTranslated) {
         // every sphere is (centre, radius): a = d.d is one value per ray and the two roots are
         // (-h -+ sqrt(h^2 - a c)) / a. The walk compares a * t (the division is done once, for the winner);
         // the smaller non-negative root is the smaller bit pattern of the two (see above: a negative root and
@@ -665,7 +668,7 @@ KDEV Hit trace(const DSceneView& sc, const LdsScene& lds, F3 O, F3 d, bool hasRa
     }
 #endif
 #if KAJO_STRICT && !KAJO_IEEE_BY_COMPILER
-    if (sc.allTranslated) {
+    if (SIMPLE || sc.allTranslated) {
         // Every sphere a (centre, radius) record (all of the reference's data/ scenes): the loop of sphereCandidate's translated branch
         // with what does not depend on the sphere taken out of it -- a = d.d, -4a, and the refined reciprocal of a that kdiv(q, a)
         // forms (the same v_rcp and two FMAs on the same operand: the same value) -- and no branch on the record's kind per
@@ -1425,7 +1428,7 @@ KDEV LdsScene stageToLds(const DSceneView& sc, unsigned char* ldsRaw)
 // light's visibility lists (lightReached) instead of costing the lane a trip of its own through the grid: the light loop of a
 // vertex runs to its end in ONE trip, as Shader::sampleLights does (Shader.cpp:50-86), and every trip's walk carries camera and
 // extension rays only. Same draws, same tests, same sums in the same order: the buffer does not change by a bit.
-template <bool COLD_LDS, bool KAT, bool SPLIT = false, bool LISTS = false, bool ONE_LIGHT = false, int GHOME = 0>
+template <bool COLD_LDS, bool KAT, bool SPLIT = false, bool LISTS = false, bool ONE_LIGHT = false, int GHOME = 0, bool SIMPLE = false>
 KDEV void renderBody(const RenderArgs& args, unsigned char* ldsRaw)
 {
     const DSceneView& sc = args.scene;
@@ -1817,7 +1820,7 @@ KDEV void renderBody(const RenderArgs& args, unsigned char* ldsRaw)
 
         KAJO_STAMP(0); // camera-ray block
         // ---- one ray per lane through the whole scene ------------------------------------------
-        const Hit hit = trace<!COLD_LDS, GHOME, LISTS>(sc, lds, O, d, mode == MODE_EXTEND || mode == MODE_SHADOW);
+        const Hit hit = trace<!COLD_LDS, GHOME, LISTS, SIMPLE>(sc, lds, O, d, mode == MODE_EXTEND || mode == MODE_SHADOW);
         KAJO_STAMP(1); // traversal
         if (counting) {
             ctrTraversals += __builtin_popcountll(activeMask);
@@ -1871,7 +1874,7 @@ KDEV void renderBody(const RenderArgs& args, unsigned char* ldsRaw)
                 ctrVertices += 1; // (unconditionally: an inline constant, where `counting` as an addend would be one more live register)
                 const F3 view = d;
                 vP = O + d * hit.t; // Raytracer.cpp:134-135
-                vN = hitNormal<LISTS>(sc, lds, hit, O, d);
+                vN = hitNormal<LISTS || SIMPLE>(sc, lds, hit, O, d);
                 vId = hit.id;
                 vE = collectEmission ? f3(m1.x, m1.y, m1.z) : f3(0.0f, 0.0f, 0.0f); // Shader.cpp:121
                 float pc;
@@ -2389,7 +2392,7 @@ KDEV void renderBody(const RenderArgs& args, unsigned char* ldsRaw)
                     // with three lights (profiles/r04_inline_shadow.txt). The FAST loop does not have the registers for it: at
                     // five waves per SIMD it spills 47 (-26 %), at four it loses the fifth wave (-10 %).
                     ctrShadow += 1;
-                    const Hit sh = trace<false>(sc, lds, O, l);
+                    const Hit sh = trace<false, 0, false, SIMPLE>(sc, lds, O, l);
                     if (sh.id == np + 1 + si) {
 #if KAJO_RSTRICT
                         vLd = vLd + pendContrib;
@@ -2609,6 +2612,16 @@ KDEV void renderBody(const RenderArgs& args, unsigned char* ldsRaw)
 
 } // namespace
 
+#ifdef KAJO_SIMPLE_KERNEL_NAME
+// A unit of one kernel (kernel_exact_simple.cpp): the one-light small-scene kernel for scenes of rigid planes and (centre, radius) spheres
+// (trace SIMPLE), without the loops for general records. launch.inc.hip sends such scenes here; the kernels below, in the build's own unit,
+// stay what they were and serve every other scene.
+extern "C" __global__ void __launch_bounds__(256, KAJO_WAVES_PER_SIMD) KAJO_SIMPLE_KERNEL_NAME(const RenderArgs args)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ldsRaw[];
+    renderBody<true, false, false, false, true, 0, true>(args, ldsRaw);
+}
+#else
 // whole scene in LDS
 #ifdef KAJO_KERNEL_NAME_LIGHTS
 // (FAST: scenes with exactly one light have an instance of their own, see PRESAMPLE; it carries the mode's plain name because it is
@@ -2760,3 +2773,4 @@ extern "C" __global__ void __launch_bounds__(256) KAJO_RESOLVE_TILES_NAME(const 
     dst[(size_t)y * map.W + x] = ((uint32_t)al << 24) | ((uint32_t)out[0] << 16) | ((uint32_t)out[1] << 8) | (uint32_t)out[2];
 }
 #endif
+#endif // KAJO_SIMPLE_KERNEL_NAME

@@ -10,6 +10,7 @@
 #define KAJO_INLINE_SHADOW 1 // small scenes of several lights answer shadow rays inside the light loop, as the STRICT build does
 #endif
 #define KAJO_KERNEL_NAME kajo_render_exact
+#define KAJO_SIMPLE_LAUNCH kajo_render_exact_simple // (launch.inc.hip: scenes of rigid planes and (centre, radius) spheres; kernel_exact_simple.cpp)
 #define KAJO_KERNEL_NAME_LIGHTS kajo_render_exact_lights
 #define KAJO_KERNEL_NAME_BIG kajo_render_exact_big
 #define KAJO_KERNEL_NAME_BIGLIST kajo_render_exact_biglist

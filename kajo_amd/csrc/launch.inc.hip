@@ -3,6 +3,12 @@
 #define KAJO_CAT2(a, b) a##b
 #define KAJO_CAT(a, b) KAJO_CAT2(a, b)
 
+#ifdef KAJO_SIMPLE_LAUNCH
+// the build's one-light small-scene kernel without the loops for general records, in a unit of its own (kernel_exact_simple.cpp)
+extern "C" int KAJO_CAT(KAJO_SIMPLE_LAUNCH, _launch)(const RenderArgs* args, unsigned grid, unsigned block, size_t ldsBytes, void* stream);
+extern "C" int KAJO_CAT(KAJO_SIMPLE_LAUNCH, _set_lds)(size_t ldsBytes);
+#endif
+
 // coldInLds: 1 = whole scene staged in LDS (KAJO_KERNEL_NAME; FAST: its one-light instance for scenes of one light, 2 = never that one),
 // 0 = cold records stay global (the scene's shadow.enabled picks the kernel that answers shadow queries from the lights' visibility lists)
 extern "C" int KAJO_CAT(KAJO_KERNEL_NAME, _launch)(const RenderArgs* args, int coldInLds, unsigned grid, unsigned block,
@@ -11,6 +17,12 @@ extern "C" int KAJO_CAT(KAJO_KERNEL_NAME, _launch)(const RenderArgs* args, int c
 #ifdef KAJO_KERNEL_NAME_LIGHTS
     if (coldInLds && (args->scene.nLights != 1 || coldInLds == 2))
         hipLaunchKernelGGL(KAJO_KERNEL_NAME_LIGHTS, dim3(grid), dim3(block), ldsBytes, static_cast<hipStream_t>(stream), *args);
+    else
+#endif
+#ifdef KAJO_SIMPLE_LAUNCH
+    // a one-light scene of rigid planes and (centre, radius) spheres: the kernel that carries no other loops (integrator.inc.hip trace SIMPLE)
+    if (coldInLds && args->scene.allTranslated && args->scene.planesRigid)
+        return KAJO_CAT(KAJO_SIMPLE_LAUNCH, _launch)(args, grid, block, ldsBytes, stream);
     else
 #endif
     if (coldInLds)
@@ -56,6 +68,10 @@ extern "C" int KAJO_CAT(KAJO_KERNEL_NAME, _set_lds)(int coldInLds, size_t ldsByt
         return (int)hipSuccess;
     if (coldInLds) {
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(KAJO_KERNEL_NAME), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
+#ifdef KAJO_SIMPLE_LAUNCH
+        if (e == hipSuccess)
+            e = (hipError_t)KAJO_CAT(KAJO_SIMPLE_LAUNCH, _set_lds)(ldsBytes);
+#endif
 #ifdef KAJO_KERNEL_NAME_LIGHTS
         if (e == hipSuccess)
             e = hipFuncSetAttribute(reinterpret_cast<const void*>(KAJO_KERNEL_NAME_LIGHTS), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes);
