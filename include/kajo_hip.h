@@ -995,6 +995,105 @@ int kajo_hip_present_grade_gathered_argb8_device(kajo_hip_t h, const void* gathe
                                                  const KajoMeterParams* meter, const KajoToneParams* tone, const KajoViewParams* view, void* dst,
                                                  KajoMeterResult* result);
 
+/* The encode: the finished frame as a 10- or 16-bit integer image, a half-float image or a PQ (SMPTE ST 2084) signal, with optional
+   dither -- in place of the tone kernels' undithered 8-bit word, behind the same chain. One kernel of its own
+   (kajo_amd/csrc/encode.cpp, arithmetic in encode_math.h) on the handle's stream, compiled once with IEEE float32 arithmetic, correctly
+   rounded division and no contraction in every numerics build. THE DEVICE EVALUATES NO pow, exp OR log: the transfer functions are tables
+   formed on the host in binary64 and rounded once to float32; the kernel looks up, subtracts, multiplies, adds, compares and converts in
+   the order written here, so the kernel, kajo_hip_encode_pixels (the host's twin, the same source lines) and a restatement in any IEEE
+   arithmetic give the same words. Off by default: no other entry point changes. Definition -- P = the handle's pass count, F = the
+   frame the tone kernels would be handed (the accumulation, or what the stages in front left); per pixel (px, py) of the whole frame:
+     1  m = F.rgb / P                one division per channel; the pixel COUNTS where all three channels of m are finite
+     2  x = m * s                    s = 2^exposure, formed on the host as the tone mapping's
+     3  y = curve(x)                 CLAMP, REINHARD or ACES: "Exposure, tone curves" above, the same expressions in the same order, with
+                                     max(t, 0) = t > 0 ? t : 0 (NaN and -0 give +0) and min(t, 1) = t < 1 ? t : 1; l(x) is summed left to
+                                     right. A pixel that does not count is mapped by CLAMP. y lies in [0, 1].
+     4  v = T(y)                     the integer formats; LINEAR: v = y. T is a table of E = 128 knots per binade over [2^-32, 1): knot
+                                     y_i is the float32 whose top 16 bits (sign, exponent, 7 bits of mantissa) are (95 << 7) + i and
+                                     whose other bits are 0, i = 0 .. 4096 (y_4096 = 1). With T64 the transfer in binary64,
+                                       T_i = (float)T64(y_i),  S_i = (float)((T64(y_i+1) - T64(y_i)) / (y_i+1 - y_i))
+                                       2^-32 <= y < 1:  v = min(T_i + (y - y_i) * S_i, T_i+1), i from y's top bits; the subtraction is
+                                                        exact, the multiply and the add round once each, the min keeps v non-decreasing
+                                       y >= 1:          v = T_4096 = (float)T64(1)
+                                       y < 2^-32:       v = y * (float)(T64(2^-32) / 2^-32)
+                                     T64: GAMMA22 y^(1/2.2) (the resolve's curve); SRGB 12.92 y for y <= 0.0031308, else 1.055 y^(1/2.4)
+                                     - 0.055 (IEC 61966-2-1); PQ ((c1 + c2 L^m1) / (1 + c3 L^m1))^m2 with L = y * peakNits / 10000, m1 =
+                                     2610/16384, m2 = 2523/4096 * 128, c1 = 3424/4096, c2 = 2413/4096 * 32, c3 = 2392/4096 * 32 (the
+                                     ST 2084 inverse EOTF: y = 1 is shown at peakNits). The table stays within 0.1 of a 16-bit code of
+                                     T64 for every float32 y (the sweep that chose E).
+     5  code = floor(v * M + d), clamped to [0, M]; M = 255, 1023 or 65535; the multiply and the add round once each. d = 0.5 without
+        DITHER; with it d = ((float)(hash >> 8) + 0.5) * 2^-24 in float32 (the sum rounds to even from 2^23 on: d lies in (0, 1]), where,
+        in uint32 arithmetic, channel = 0, 1, 2 for r, g, b:
+              h = py * 0x85EBCA6B;  h ^= channel * 0xC2B2AE35;  h ^= ditherSeed;
+              h ^= h >> 16;  h *= 0x7FEB352D;  h ^= h >> 15;  h *= 0x846CA68B;  h ^= h >> 16;
+              hash = h + px * 0x9E3779B9
+        (a scrambled word per row, channel and seed, then a golden-ratio step per pixel along the row). px, py are frame coordinates:
+        the image does not depend on who owns which tile.
+     6  RGBA16F stores v = y (LINEAR; no other transfer) rounded to the nearest binary16, ties to even, by integer operations; with
+        SCENE the curve is skipped and min(max(x, 0), 65504) is stored, NaN giving 0.
+   Words: ARGB8 0xFF << 24 | r << 16 | g << 8 | b (the resolve's layout); RGB10A2 3 << 30 | r << 20 | g << 10 | b; RGBA16 four
+   little-endian uint16 r, g, b, a = 65535 (8 bytes, one store); RGBA16F four binary16 r, g, b, a = 1.0 (8 bytes). Row-major, row 0 =
+   top, width*height words, nothing beyond kajo_hip_encode_bytes.
+   ARGB8 + GAMMA22 without dither is NOT the resolve's image bit for bit: the resolve raises to 1/2.2 with its build's own pow, this
+   stage reads a table; the two differ by at most one code at a small share of the pixels (DESIGN.md section 6q has the measured figure).
+   Refusals of the parameters (KAJO_E_INVALID, before the handle is looked at), in this order: NULL; an unknown format; an unknown
+   transfer; an unknown flag bit; a non-zero reserved word; RGBA16F with a transfer other than LINEAR; SCENE with a format other than
+   RGBA16F; DITHER with RGBA16F; with PQ a peakNits that is not finite or not in (0, 10000]. They stand where the view's do: behind the
+   tone parameters' own refusals (the two automatic exposures among them), in front of the denoiser's. Behind them
+   KAJO_TONE_AUTO_EXPOSURE is refused: its scale is formed inside the tone launch, which this stage replaces -- use metered exposure (a
+   KajoMeterParams in the chain), which is patched into the tone parameters on the host and works with the encode. A view is not
+   combined with an encode (the view resamples ARGB8 words): the encoded entry points take none. The accumulation, the AOVs, the pass
+   count and the counters (kernelMs included) are not touched; the table (32776 bytes) is uploaded when the transfer or peakNits differ
+   from the last call's, the image buffer is allocated on first use; both are freed by kajo_hip_destroy. */
+#define KAJO_ENCODE_ARGB8 0u
+#define KAJO_ENCODE_RGB10A2 1u
+#define KAJO_ENCODE_RGBA16 2u
+#define KAJO_ENCODE_RGBA16F 3u
+#define KAJO_TRANSFER_GAMMA22 0u
+#define KAJO_TRANSFER_SRGB 1u
+#define KAJO_TRANSFER_PQ 2u
+#define KAJO_TRANSFER_LINEAR 3u
+#define KAJO_ENCODE_DITHER 1u          /* KajoEncodeParams.flags: integer formats only */
+#define KAJO_ENCODE_SCENE 2u           /* KajoEncodeParams.flags: RGBA16F only, scene-linear x without the curve */
+#define KAJO_ENCODE_TABLE_WORDS 8194   /* floats of a transfer table: (T_i, S_i) interleaved, i = 0 .. 4096; the last pair is (T64(1), the slope below 2^-32) */
+typedef struct KajoEncodeParams {
+    uint32_t format;      /* KAJO_ENCODE_* (default ARGB8) */
+    uint32_t transfer;    /* KAJO_TRANSFER_* (default GAMMA22) */
+    uint32_t flags;       /* KAJO_ENCODE_DITHER, KAJO_ENCODE_SCENE (default 0) */
+    float peakNits;       /* PQ: the luminance y = 1 is shown at, in (0, 10000] (default 1000) */
+    uint32_t ditherSeed;  /* change it per frame for a temporal dither (default 0) */
+    uint32_t reserved[3]; /* 0 */
+} KajoEncodeParams;       /* 32 bytes */
+void kajo_hip_default_encode_params(KajoEncodeParams* p); /* NULL is accepted */
+/* *bytes = the size of a width x height image in p's format (4 or 8 bytes a pixel). The parameters' refusals; width, height >= 1. */
+int kajo_hip_encode_bytes(const KajoEncodeParams* p, int width, int height, size_t* bytes);
+/* The table of a transfer (GAMMA22, SRGB, PQ; peakNits is read for PQ only): KAJO_ENCODE_TABLE_WORDS floats. Pure host code. Returns the
+   word count; table may be NULL (the size query), otherwise capacity >= the count. LINEAR has no table (KAJO_E_INVALID). */
+int kajo_hip_encode_table(uint32_t transfer, float peakNits, float* table, size_t capacity);
+/* The definition over n pixels of MEANS (m of step 1), pure host code compiled from the kernel's own lines: meanRgb = n * 3 floats, the
+   pixels row-major in a rectangle rowWidth wide whose first pixel is (x0, y0) of the frame (pixel i: px = x0 + i % rowWidth, py = y0 +
+   i / rowWidth; they matter to the dither only). out: n words of the format. The refusals above (tone included); rowWidth >= 1. */
+int kajo_hip_encode_pixels(const KajoEncodeParams* encode, const KajoToneParams* tone, const float* meanRgb, int64_t n, int32_t x0, int32_t y0,
+                           int32_t rowWidth, void* out);
+/* The stage alone over the handle's whole frame (tileCount 1, or a composed handle, as kajo_hip_tonemap_argb8): dst = HOST pointer to
+   kajo_hip_encode_bytes bytes, may be NULL. Waits. */
+int kajo_hip_encode(kajo_hip_t h, const KajoEncodeParams* encode, const KajoToneParams* tone, void* dst);
+/* The whole chain with the encode in place of the 8-bit word: despeckle -> denoise -> grade -> lens -> glare -> local -> meter -> tone
+   curve -> encode, every stage but the last two optional (NULL). kajo_hip_present_grade_argb8 without a view up to the tone curve: the
+   words are kajo_hip_encode_pixels of the frame those stages leave, with the tone parameters the meter patched. dst = HOST pointer to
+   kajo_hip_encode_bytes bytes (may be NULL); *result as there. Waits. (The name starts with the stage, as kajo_hip_encode: the
+   kajo_hip_present_* names are the ARGB8 chain's.) */
+int kajo_hip_encode_present(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGradeParams* grade,
+                            const KajoLensParams* lens, const KajoGlareParams* g, const KajoLocalParams* local, const KajoMeterParams* meter,
+                            const KajoToneParams* tone, const KajoEncodeParams* encode, void* dst, KajoMeterResult* result);
+/* The twin of kajo_hip_present_grade_gathered_argb8_device, its stages but the view: gathered tile buffers (NULL = the handle's own when
+   tileCount == 1) into DEVICE memory, dst = kajo_hip_encode_bytes bytes, 8-byte aligned for the 8-byte formats. Asynchronous on the
+   handle's stream: no wait beyond the meter's (a change of transfer or peakNits may wait for the previous upload of the table to leave
+   its staging, never for a kernel). The image is the same bits for any number of tile owners, dither included. */
+int kajo_hip_encode_present_gathered_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle, const KajoGradeParams* grade,
+                                            const KajoGlareParams* g, const KajoLocalParams* local, const KajoMeterParams* meter,
+                                            const KajoToneParams* tone, const KajoEncodeParams* encode, void* dst, KajoMeterResult* result);
+
 /* The noise estimate (KAJO_FLAG_NOISE): how noisy the frame is, pixel by pixel, from the frame's own passes -- batch means, in kernels of
    their own (kajo_amd/csrc/noise.hip) on the handle's stream, float32 / binary64 IEEE arithmetic without contraction in every numerics
    build: only its input, the accumulation, depends on FAST / EXACT / STRICT.

@@ -53,6 +53,12 @@ KAJO_VIEW_NEAREST, KAJO_VIEW_AREA, KAJO_VIEW_TRIANGLE, KAJO_VIEW_LANCZOS3 = 0, 1
 KAJO_VIEW_FILTERS = {"nearest": KAJO_VIEW_NEAREST, "area": KAJO_VIEW_AREA, "triangle": KAJO_VIEW_TRIANGLE, "lanczos3": KAJO_VIEW_LANCZOS3}
 KAJO_VIEW_MAX_SCALE, KAJO_VIEW_MAX_TAPS, KAJO_VIEW_MAX_OUT = 64, 384, 16384  # the view's limits: minification, taps of a row, output edge
 KAJO_GRADE_MAX_REGIONS, KAJO_GRADE_REGION_OBJECTS = 4, 16  # KajoGradeParams: regions of a grade, object ids of a region
+KAJO_ENCODE_ARGB8, KAJO_ENCODE_RGB10A2, KAJO_ENCODE_RGBA16, KAJO_ENCODE_RGBA16F = 0, 1, 2, 3  # KajoEncodeParams.format
+KAJO_ENCODE_FORMATS = {"argb8": KAJO_ENCODE_ARGB8, "rgb10a2": KAJO_ENCODE_RGB10A2, "rgba16": KAJO_ENCODE_RGBA16, "rgba16f": KAJO_ENCODE_RGBA16F}
+KAJO_TRANSFER_GAMMA22, KAJO_TRANSFER_SRGB, KAJO_TRANSFER_PQ, KAJO_TRANSFER_LINEAR = 0, 1, 2, 3  # KajoEncodeParams.transfer
+KAJO_TRANSFERS = {"gamma22": KAJO_TRANSFER_GAMMA22, "srgb": KAJO_TRANSFER_SRGB, "pq": KAJO_TRANSFER_PQ, "linear": KAJO_TRANSFER_LINEAR}
+KAJO_ENCODE_DITHER, KAJO_ENCODE_SCENE = 1, 2  # KajoEncodeParams.flags
+KAJO_ENCODE_TABLE_WORDS = 8194  # floats of a transfer table (kajo_hip_encode_table)
 KAJO_LOCAL_PIVOT_METERED = 1  # KajoLocalParams.flags: the pivot is the frame's own pivotPercentile-th luminance
 
 # every symbol include/kajo_hip.h declares
@@ -81,6 +87,8 @@ EXPORTS = [
     "kajo_hip_default_adapt_params", "kajo_hip_set_adaptive", "kajo_hip_adapt_state", "kajo_hip_adapt_passes", "kajo_hip_adapt_evaluate",
     "kajo_hip_adapt_order",
     "kajo_hip_denoise_guide_planes",
+    "kajo_hip_default_encode_params", "kajo_hip_encode_bytes", "kajo_hip_encode_table", "kajo_hip_encode_pixels", "kajo_hip_encode",
+    "kajo_hip_encode_present", "kajo_hip_encode_present_gathered_device",
 ]
 
 
@@ -153,6 +161,11 @@ class KajoLensParams(C.Structure):
 class KajoViewParams(C.Structure):
     _fields_ = [("x0", C.c_float), ("y0", C.c_float), ("x1", C.c_float), ("y1", C.c_float), ("outW", C.c_int32), ("outH", C.c_int32),
                 ("filter", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class KajoEncodeParams(C.Structure):
+    _fields_ = [("format", C.c_uint32), ("transfer", C.c_uint32), ("flags", C.c_uint32), ("peakNits", C.c_float), ("ditherSeed", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
 
 
 class KajoGradeOp(C.Structure):
@@ -340,6 +353,23 @@ def lib():
                                                                        C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams),
                                                                        C.POINTER(KajoToneParams), C.POINTER(KajoViewParams), C.c_void_p,
                                                                        C.POINTER(KajoMeterResult)]
+        if hasattr(L, "kajo_hip_encode"):  # (nor the encode)
+            L.kajo_hip_default_encode_params.argtypes = [C.POINTER(KajoEncodeParams)]
+            L.kajo_hip_default_encode_params.restype = None
+            L.kajo_hip_encode_bytes.argtypes = [C.POINTER(KajoEncodeParams), C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+            L.kajo_hip_encode_table.argtypes = [C.c_uint32, C.c_float, C.c_void_p, C.c_size_t]
+            L.kajo_hip_encode_pixels.argtypes = [C.POINTER(KajoEncodeParams), C.POINTER(KajoToneParams), C.c_void_p, C.c_int64, C.c_int32,
+                                                 C.c_int32, C.c_int32, C.c_void_p]
+            L.kajo_hip_encode.argtypes = [C.c_void_p, C.POINTER(KajoEncodeParams), C.POINTER(KajoToneParams), C.c_void_p]
+            L.kajo_hip_encode_present.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams),
+                                                  C.POINTER(KajoGradeParams), C.POINTER(KajoLensParams), C.POINTER(KajoGlareParams),
+                                                  C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams),
+                                                  C.POINTER(KajoEncodeParams), C.c_void_p, C.POINTER(KajoMeterResult)]
+            L.kajo_hip_encode_present_gathered_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams),
+                                                                  C.POINTER(KajoGradeParams), C.POINTER(KajoGlareParams),
+                                                                  C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams),
+                                                                  C.POINTER(KajoToneParams), C.POINTER(KajoEncodeParams), C.c_void_p,
+                                                                  C.POINTER(KajoMeterResult)]
         if hasattr(L, "kajo_hip_read_matte"):  # (nor the mattes)
             L.kajo_hip_read_matte.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
             L.kajo_hip_matte_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

@@ -274,6 +274,16 @@ struct KajoHip : KajoFramePlan
     hipEvent_t gradeUploaded = nullptr; // the last upload has left gradeStaging
     bool gradePlanned = false;
     KajoGradeParams gradeLast{};
+    // the encode (encode.cpp; kajo_hip_encode, kajo_hip_encode_present and its gathered twin), on its first call: the image for the host
+    // (grown when a wider format asks); the transfer's table, uploaded from the pinned block `encodeStaging` only when the transfer or
+    // the peak luminance differ from the last upload's
+    DeviceBuffer encodeOut, encodeTable;
+    size_t encodeOutBytes = 0;
+    void* encodeStaging = nullptr;
+    hipEvent_t encodeUploaded = nullptr; // the last upload has left encodeStaging
+    bool encodePlanned = false;
+    uint32_t encodeTransfer = 0;
+    float encodePeak = 0.0f;
     // the noise estimate (the handle's `noise`; noise.hip), at create: the baseline float4 [slotsPerOwner] and the moment records
     // KajoNoiseMoments [slotsPerOwner] of the handle's own tile buffer; noiseRebase: the baseline is to be taken from the buffer at the next
     // batch boundary, whose batch does not count (kajo_hip_set_pass_count). noiseOut, on the first kajo_hip_noise: four planes of W * H

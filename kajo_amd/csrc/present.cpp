@@ -1,10 +1,18 @@
 // present.cpp -- libkajo_hip.so: the display path of include/kajo_hip.h. The stages (denoise, tone, glare, despeckle, meter, local, lens,
-// view, grade), each with its refusals, its scratch layout and the helpers of its own entry points; then the chain
-//     despeckle -> denoise -> grade -> lens -> glare -> local -> meter -> tone -> view
+// view, grade, encode), each with its refusals, its scratch layout and the helpers of its own entry points; then the chain
+//     despeckle -> denoise -> grade -> lens -> glare -> local -> meter -> tone -> view, or -> encode in place of the tone kernels' word
 // as one description (Chain), one check (checkChain) and one run (runChain), and every kajo_hip_tonemap_*, kajo_hip_display_*,
-// kajo_hip_present_* entry point, kajo_hip_glare, _local, _lens, _grade and _meter as a wrapper that fills the description. The handle
-// and what it shares with capi.cpp: handle.h.
+// kajo_hip_present_* entry point, kajo_hip_glare, _local, _lens, _grade, _meter, _encode and _encode_present as a wrapper that fills the
+// description. The handle and what it shares with capi.cpp: handle.h. The encode's host half: encode_host.h.
 #include "handle.h"
+
+#include "encode_host.h"
+
+// encode.cpp's launcher (its argument block is encode_math.h's)
+extern "C" {
+size_t kajo_encode_table_words(void);
+int kajo_encode_launch(const void* src, const TileMap* map, int fromTiles, const kajo::EncodeArgs* a, const void* table, void* dst, void* stream);
+}
 
 extern "C" {
 
@@ -1161,6 +1169,151 @@ int kajo_hip_grade_neutral(const float rgb[3], float gains[3])
 namespace
 {
 
+// The refusals of KajoEncodeParams (KAJO_E_INVALID), before any device work and before the handle is looked at
+int checkEncode(const KajoEncodeParams* p)
+{
+    const char* refusal = kajo::encodeRefusal(p);
+    return refusal ? fail(KAJO_E_INVALID, refusal) : KAJO_OK;
+}
+
+// ... and of the tone parameters beside an encode: their scale would be formed inside the tone launch, which the encode replaces
+int checkEncodeTone(const KajoToneParams* tone)
+{
+    if (tone->flags & KAJO_TONE_AUTO_EXPOSURE)
+        return fail(KAJO_E_INVALID, "the encode takes no automatic exposure from the tone parameters (their scale is formed inside the tone "
+                                    "launch): use metered exposure, a meter stage in the chain, which patches the tone parameters on the host");
+    return KAJO_OK;
+}
+
+bool encodeTabled(const KajoEncodeParams* p)
+{
+    return p->format != KAJO_ENCODE_RGBA16F && p->transfer != KAJO_TRANSFER_LINEAR;
+}
+
+kajo::EncodeArgs encodeArgsOf(const KajoEncodeParams* p, const ToneArgs& t, float passes)
+{
+    kajo::EncodeArgs a{};
+    a.format = p->format;
+    a.transfer = p->transfer;
+    a.flags = p->flags;
+    a.curve = t.curve;
+    a.scale = t.exposureScale;
+    a.white = t.white;
+    a.seed = p->ditherSeed;
+    a.passes = passes;
+    return a;
+}
+
+// Form the table of *p's transfer and upload it, unless it is the last call's (the event discipline of viewPlan and gradePlan)
+int encodePlan(KajoHip* h, const KajoEncodeParams* p)
+{
+    const float peak = p->transfer == KAJO_TRANSFER_PQ ? p->peakNits : 0.0f;
+    if (h->encodePlanned && h->encodeTransfer == p->transfer && h->encodePeak == peak)
+        return KAJO_OK;
+    h->encodePlanned = false;
+    if (kajo_encode_table_words() != (size_t)kajo::kEncodeTableWords)
+        return fail(KAJO_E_INVALID, "encode table layout mismatch");
+    const size_t bytes = (size_t)kajo::kEncodeTableWords * sizeof(float);
+    if (!h->encodeUploaded)
+        HIP_TRY(hipEventCreateWithFlags(&h->encodeUploaded, hipEventDisableTiming));
+    else
+        HIP_TRY(hipEventSynchronize(h->encodeUploaded)); // (the copy before this one has left the staging block; kernels are not waited for)
+    if (!h->encodeStaging)
+        HIP_TRY(hipHostMalloc(&h->encodeStaging, bytes, hipHostMallocDefault));
+    HIP_TRY(h->encodeTable.ensure(bytes));
+    kajo::encodeTable(p->transfer, peak, static_cast<float*>(h->encodeStaging));
+    HIP_TRY(hipMemcpyAsync(h->encodeTable.p, h->encodeStaging, bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipEventRecord(h->encodeUploaded, h->stream));
+    h->encodeTransfer = p->transfer;
+    h->encodePeak = peak;
+    h->encodePlanned = true;
+    return KAJO_OK;
+}
+
+// Enqueue the encode of an image (tiles through h->map's geometry, or a row-major frame) into dst (device, W * H words of the format).
+// Checked by checkEncode, device bound. The handle's tone scale (kajo_hip_tone_scale) stays the last tone mapping's.
+int encodeLaunch(KajoHip* h, Image img, const ToneArgs& t, const KajoEncodeParams* p, void* dst)
+{
+    int rc;
+    if (encodeTabled(p) && (rc = encodePlan(h, p)))
+        return rc;
+    const kajo::EncodeArgs a = encodeArgsOf(p, t, (float)h->passesDone);
+    hipError_t le = (hipError_t)kajo_encode_launch(img.src, &h->map, img.fromTiles ? 1 : 0, &a, encodeTabled(p) ? h->encodeTable.p : nullptr, dst, h->stream);
+    if (le != hipSuccess)
+        return failHip(le, "encode kernel launch");
+    return KAJO_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void kajo_hip_default_encode_params(KajoEncodeParams* p)
+{
+    if (!p)
+        return;
+    std::memset(p, 0, sizeof *p);
+    p->format = KAJO_ENCODE_ARGB8;
+    p->transfer = KAJO_TRANSFER_GAMMA22;
+    p->peakNits = 1000.0f;
+}
+
+int kajo_hip_encode_bytes(const KajoEncodeParams* p, int width, int height, size_t* bytes)
+{
+    int rc = checkEncode(p);
+    if (rc)
+        return rc;
+    if (width < 1 || height < 1)
+        return fail(KAJO_E_INVALID, "width and height must be at least 1");
+    if (!bytes)
+        return fail(KAJO_E_INVALID, "null argument");
+    *bytes = (size_t)width * (size_t)height * kajo::encodePixelBytes(p->format);
+    return KAJO_OK;
+}
+
+int kajo_hip_encode_table(uint32_t transfer, float peakNits, float* table, size_t capacity)
+{
+    if (transfer > KAJO_TRANSFER_LINEAR)
+        return fail(KAJO_E_INVALID, "unknown encode transfer");
+    if (transfer == KAJO_TRANSFER_LINEAR)
+        return fail(KAJO_E_INVALID, "the linear transfer has no table");
+    if (transfer == KAJO_TRANSFER_PQ && !(std::isfinite(peakNits) && peakNits > 0.0f && peakNits <= 10000.0f))
+        return fail(KAJO_E_INVALID, "encode peak luminance must be finite and in (0, 10000] nits");
+    if (table) {
+        if (capacity < (size_t)kajo::kEncodeTableWords)
+            return fail(KAJO_E_INVALID, "table array too small");
+        kajo::encodeTable(transfer, peakNits, table);
+    }
+    return kajo::kEncodeTableWords;
+}
+
+int kajo_hip_encode_pixels(const KajoEncodeParams* encode, const KajoToneParams* tone, const float* meanRgb, int64_t n, int32_t x0, int32_t y0,
+                           int32_t rowWidth, void* out)
+{
+    ToneArgs t{};
+    int rc = toneArgsOf(tone, &t);
+    if (rc)
+        return rc;
+    if ((rc = checkEncode(encode)) || (rc = checkEncodeTone(tone)))
+        return rc;
+    if (n < 0 || (n > 0 && (!meanRgb || !out)))
+        return fail(KAJO_E_INVALID, "null argument");
+    if (rowWidth < 1)
+        return fail(KAJO_E_INVALID, "encode row width must be at least 1");
+    std::vector<float> table;
+    if (encodeTabled(encode)) {
+        table.resize(kajo::kEncodeTableWords);
+        kajo::encodeTable(encode->transfer, encode->transfer == KAJO_TRANSFER_PQ ? encode->peakNits : 0.0f, table.data());
+    }
+    kajo::encodePixels(encodeArgsOf(encode, t, 1.0f), table.data(), meanRgb, n, x0, y0, rowWidth, out);
+    return KAJO_OK;
+}
+
+} // extern "C"
+
+namespace
+{
+
 // Where a chain's image goes
 enum ChainSink
 {
@@ -1168,6 +1321,8 @@ enum ChainSink
     kSinkMeter,      // the histogram of that frame (dst, may be null) and its evaluation (result), to the host
     kSinkHostArgb,   // the ARGB8 image through the handle's own frame to the host (dst null: likewise)
     kSinkDeviceArgb, // the ARGB8 image to a device pointer; nothing is waited for beyond what the stages wait for themselves
+    kSinkHostEncoded,   // the encoded image (Chain::encode) through the handle's own buffer to the host (dst null: likewise)
+    kSinkDeviceEncoded, // the encoded image to a device pointer, as kSinkDeviceArgb
 };
 
 // stages an entry point refuses to run without (the tone parameters: every ARGB8 sink)
@@ -1193,6 +1348,7 @@ struct Chain
     const KajoMeterParams* meter = nullptr;
     const KajoToneParams* tone = nullptr;
     const KajoViewParams* view = nullptr;
+    const KajoEncodeParams* encode = nullptr; // the encoded sinks: in place of the tone kernels' word; no view beside it
     unsigned need = 0;
     // the source: the handle's own frame, or gathered tile buffers (tiles null: the handle's own tiles, which must be the whole frame)
     bool gathered = false;
@@ -1210,7 +1366,7 @@ struct Chain
 };
 
 // Every refusal of a chain, before any device work, in the header's order: the stages' parameters (despeckle, grade, lens, glare, local,
-// meter, tone, the two automatic exposures, view), the denoiser's parameters and its handle rules, then the handle (null, the grade's
+// meter, tone, the two automatic exposures, view or encode), the denoiser's parameters and its handle rules, then the handle (null, the grade's
 // state, the lens's, the view against the frame). -> c.toneArgs, c.rect
 int checkChain(kajo_hip_t h, Chain& c)
 {
@@ -1227,7 +1383,8 @@ int checkChain(kajo_hip_t h, Chain& c)
         return rc;
     if ((c.meter || (c.need & kNeedMeter)) && (rc = checkMeter(c.meter)))
         return rc;
-    if (c.sink == kSinkHostArgb || c.sink == kSinkDeviceArgb) {
+    const bool encoded = c.sink == kSinkHostEncoded || c.sink == kSinkDeviceEncoded;
+    if (c.sink == kSinkHostArgb || c.sink == kSinkDeviceArgb || encoded) {
         if ((rc = toneArgsOf(c.tone, &c.toneArgs)))
             return rc;
         if (c.meter && (c.tone->flags & KAJO_TONE_AUTO_EXPOSURE))
@@ -1235,13 +1392,15 @@ int checkChain(kajo_hip_t h, Chain& c)
     }
     if (c.view && (rc = checkView(c.view)))
         return rc;
+    if (encoded && ((rc = checkEncode(c.encode)) || (rc = checkEncodeTone(c.tone))))
+        return rc;
     if (c.gathered && c.grade && c.grade->nRegions > 0)
         return fail(KAJO_E_INVALID, "grade regions need the whole frame's coverage tables: kajo_hip_present_grade_argb8 on the root");
     if (c.denoise && (rc = checkDenoise(h, c.denoise)))
         return rc;
     if (!h)
         return fail(KAJO_E_INVALID, c.nullHandle);
-    if (c.sink == kSinkDeviceArgb && !c.dst)
+    if ((c.sink == kSinkDeviceArgb || c.sink == kSinkDeviceEncoded) && !c.dst)
         return fail(KAJO_E_INVALID, "null argument");
     if (c.grade && (rc = checkGradeHandle(h, c.grade, !c.gathered)))
         return rc;
@@ -1301,6 +1460,17 @@ int runChain(KajoHip* h, const Chain& c)
     ToneArgs t = c.toneArgs;
     if (c.meter && (rc = meterAndPatch(h, img, c.meter, c.tone, c.result, &t)))
         return rc;
+    if (c.sink == kSinkDeviceEncoded)
+        return encodeLaunch(h, img, t, c.encode, c.dst);
+    if (c.sink == kSinkHostEncoded) {
+        const size_t encodedBytes = count * kajo::encodePixelBytes(c.encode->format);
+        HIP_TRY(growBuffer(h->encodeOut, &h->encodeOutBytes, encodedBytes));
+        if ((rc = encodeLaunch(h, img, t, c.encode, h->encodeOut.p)))
+            return rc;
+        if (c.dst)
+            HIP_TRY(hipMemcpyAsync(c.dst, h->encodeOut.p, encodedBytes, hipMemcpyDeviceToHost, h->stream));
+        return kajo_hip_wait(h);
+    }
     if (c.sink == kSinkDeviceArgb) {
         if (!c.view || c.rect.copy)
             return toneLaunch(h, img, t, c.dst);
@@ -1606,6 +1776,52 @@ int kajo_hip_present_grade_gathered_argb8_device(kajo_hip_t h, const void* gathe
     c.view = view;
     if (view && !grade)
         c.nullHandle = "null handle";
+    return present(h, c);
+}
+
+int kajo_hip_encode(kajo_hip_t h, const KajoEncodeParams* encode, const KajoToneParams* tone, void* dst)
+{
+    Chain c;
+    c.sink = kSinkHostEncoded;
+    c.dst = dst;
+    c.tone = tone;
+    c.encode = encode;
+    return present(h, c);
+}
+
+int kajo_hip_encode_present(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGradeParams* grade,
+                            const KajoLensParams* lens, const KajoGlareParams* g, const KajoLocalParams* local, const KajoMeterParams* meter,
+                            const KajoToneParams* tone, const KajoEncodeParams* encode, void* dst, KajoMeterResult* result)
+{
+    Chain c;
+    c.sink = kSinkHostEncoded;
+    c.dst = dst;
+    c.result = result;
+    c.despeckle = despeckle;
+    c.denoise = denoise;
+    c.grade = grade;
+    c.lens = lens;
+    c.glare = g;
+    c.local = local;
+    c.meter = meter;
+    c.tone = tone;
+    c.encode = encode;
+    return present(h, c);
+}
+
+int kajo_hip_encode_present_gathered_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle, const KajoGradeParams* grade,
+                                            const KajoGlareParams* g, const KajoLocalParams* local, const KajoMeterParams* meter,
+                                            const KajoToneParams* tone, const KajoEncodeParams* encode, void* dst, KajoMeterResult* result)
+{
+    Chain c = gatheredChain(gathered, dst, result);
+    c.sink = kSinkDeviceEncoded;
+    c.despeckle = despeckle;
+    c.grade = grade;
+    c.glare = g;
+    c.local = local;
+    c.meter = meter;
+    c.tone = tone;
+    c.encode = encode;
     return present(h, c);
 }
 

@@ -73,6 +73,8 @@ struct Scheduler::Impl
     std::vector<ncclComm_t> comms;
     void* gathered = nullptr;         // on device 0: gpus consecutive tile buffers
     void* argbDevice = nullptr;       // on device 0: the resolved image of a gathered frame, before it goes to Image::pixels
+    void* encodedDevice = nullptr;    // on device 0: the encoded image of a gathered frame (readEncoded), grown on demand
+    size_t encodedBytes = 0;
     size_t tileBytes = 0;
     // Options::aovTiled with a gather: on device 0, gpus consecutive AOV tile buffers and (Options::matte) matte tile buffers
     void* aovGathered = nullptr;
@@ -182,6 +184,8 @@ struct Scheduler::Impl
         }
         if (argbDevice)
             (void)hipFree(argbDevice);
+        if (encodedDevice)
+            (void)hipFree(encodedDevice);
         if (aovGathered)
             (void)hipFree(aovGathered);
         if (matteGathered)
@@ -673,6 +677,62 @@ void Scheduler::readViewed(uint32_t* dst)
     }
     d.present(d.opt.despeckleOn ? &d.opt.despeckle : nullptr, nullptr, d.opt.gradeOn ? &grade : nullptr, d.opt.lensOn ? &lens : nullptr, &d.opt.glare,
               nullptr, &d.opt.view, dst);
+}
+
+void Scheduler::readEncoded(const KajoEncodeParams* encode, void* dst)
+{
+    Impl& d = *m_impl;
+    const KajoDespeckleParams* despeckle = d.opt.despeckleOn ? &d.opt.despeckle : nullptr;
+    const KajoLocalParams* local = d.localActive() ? &d.opt.local : nullptr;
+    const KajoMeterParams* meter = d.opt.meterOn ? &d.opt.meter : nullptr;
+    const bool wholeFrame = d.opt.lensOn || (d.opt.gradeOn && (d.opt.grade.nRegions > 0 || d.opt.gradeNeutralAt.x >= 0));
+    KajoGradeParams grade;
+    if (d.gathered && !wholeFrame) {
+        // several owners: straight from the gathered tile buffers, as run()'s refreshes
+        size_t bytes = 0;
+        check(kajo_hip_encode_bytes(encode, d.image->width, d.image->height, &bytes), "kajo_hip_encode_bytes");
+        checkHip(hipSetDevice(d.devices[0]), "hipSetDevice");
+        if (d.encodedBytes < bytes) {
+            if (d.encodedDevice)
+                checkHip(hipFree(d.encodedDevice), "hipFree(encoded image)");
+            d.encodedDevice = nullptr;
+            d.encodedBytes = 0;
+            checkHip(hipMalloc(&d.encodedDevice, bytes), "hipMalloc(encoded image)");
+            d.encodedBytes = bytes;
+        }
+        if (d.opt.gradeOn)
+            d.gradeParams(despeckle, nullptr, &grade);
+        check(kajo_hip_encode_present_gathered_device(d.handles[0], d.gathered, despeckle, d.opt.gradeOn ? &grade : nullptr,
+                                                      d.glareOn() ? &d.opt.glare : nullptr, local, meter, &d.opt.tone, encode, d.encodedDevice,
+                                                      &d.metered),
+              "kajo_hip_encode_present_gathered_device");
+        if (local)
+            d.notePivot();
+        checkHip(hipMemcpyAsync(dst, d.encodedDevice, bytes, hipMemcpyDeviceToHost, d.streams[0]), "hipMemcpyAsync(encoded image)");
+        checkHip(hipStreamSynchronize(d.streams[0]), "hipStreamSynchronize");
+        return;
+    }
+    if (d.gathered && !d.composed) { // (as readDisplayed)
+        check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
+        d.composed = true;
+    }
+    KajoLensParams lens = d.opt.lens;
+    if (d.opt.lensOn) {
+        d.composeAov();
+        d.focusLens(&lens);
+    }
+    if (d.opt.gradeOn) {
+        if (d.opt.grade.nRegions > 0)
+            d.composeAov();
+        d.gradeParams(despeckle, nullptr, &grade);
+    }
+    check(kajo_hip_encode_present(d.handles[0], despeckle, nullptr, d.opt.gradeOn ? &grade : nullptr, d.opt.lensOn ? &lens : nullptr,
+                                  d.glareOn() ? &d.opt.glare : nullptr, local, meter, &d.opt.tone, encode, dst, &d.metered),
+          "kajo_hip_encode_present");
+    if (local)
+        d.notePivot();
+    if (d.opt.lensOn)
+        d.noteLens(lens);
 }
 
 void Scheduler::readNoise(float* mean, float* stderror, float* relative)

@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "Scheduler.h"
-#include "kajo_hip.h" // KajoToneParams (Options::tone), KajoGlareParams (Options::glare), KajoDespeckleParams (Options::despeckle), KajoMeterParams, KajoLocalParams, KajoLensParams, KajoViewParams, KajoGradeParams
+#include "kajo_hip.h" // KajoToneParams (Options::tone), KajoGlareParams (Options::glare), KajoDespeckleParams (Options::despeckle), KajoMeterParams, KajoLocalParams, KajoLensParams, KajoViewParams, KajoGradeParams, KajoEncodeParams
 
 class Image;
 class Preview;
@@ -219,6 +219,12 @@ public:
     // the image of readPresented() with Options' own stages, through Options::view: dst = view.outW * view.outH words. Any number of GPUs
     // (the frame is composed on the first handle, as readPresented does). Throws where Options::viewOn is not set.
     void readViewed(uint32_t* dst);
+    // the image of readPresented() with Options' own stages, through the encode in place of the 8-bit word (include/kajo_hip.h "The
+    // encode"): dst = kajo_hip_encode_bytes bytes of encode's format. With several owners (or Options::forceGather) the gathered tile
+    // buffers go through kajo_hip_encode_present_gathered_device; with the stages that need the whole frame's AOVs (Options::lensOn, grade
+    // regions, gradeNeutralAt) the frame is composed on the first handle, as readViewed does, and kajo_hip_encode_present runs there. The
+    // view takes no part. The library's refusals (the tone parameters' automatic exposure among them) are thrown.
+    void readEncoded(const KajoEncodeParams* encode, void* dst);
     // the noise map after run() (Options::noise or noiseTarget; include/kajo_hip.h kajo_hip_noise on every owner, into the same planes):
     // W*H floats each -- mean luminance per pass, its standard error, the relative error -- any may be null. Any number of GPUs, no gather
     void readNoise(float* mean, float* stderror, float* relative);

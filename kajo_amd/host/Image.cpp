@@ -47,24 +47,11 @@ void chunk(std::vector<unsigned char>& out, const char* type, const std::vector<
     be32(out, crc32(&out[start], out.size() - start));
 }
 
-} // namespace
-
-bool Image::save(const std::string& fileName) const
+// raw scanlines (a filter byte 0 in front of each) -> a PNG file of that bit depth and colour type; cicp: four bytes of a cICP chunk
+// in front of the image data, or null
+bool writePng(const std::string& fileName, int width, int height, int bitDepth, int colourType, const std::vector<unsigned char>& raw,
+              const unsigned char* cicp)
 {
-    // raw scanlines: filter byte 0 + RGBA (the reference swaps R and B for its encoder the same way,
-    // renderer/Image.cpp:34-38)
-    std::vector<unsigned char> raw;
-    raw.reserve((size_t)height * (1 + 4 * (size_t)width));
-    for (int y = 0; y < height; y++) {
-        raw.push_back(0);
-        for (int x = 0; x < width; x++) {
-            uint32_t p = pixels[(size_t)y * width + x];
-            raw.push_back((p >> 16) & 0xff);
-            raw.push_back((p >> 8) & 0xff);
-            raw.push_back(p & 0xff);
-            raw.push_back((p >> 24) & 0xff);
-        }
-    }
     // zlib stream of stored blocks
     std::vector<unsigned char> z;
     z.push_back(0x78);
@@ -91,12 +78,14 @@ bool Image::save(const std::string& fileName) const
     std::vector<unsigned char> ihdr;
     be32(ihdr, (uint32_t)width);
     be32(ihdr, (uint32_t)height);
-    ihdr.push_back(8); // bit depth
-    ihdr.push_back(6); // RGBA
+    ihdr.push_back((unsigned char)bitDepth);
+    ihdr.push_back((unsigned char)colourType);
     ihdr.push_back(0);
     ihdr.push_back(0);
     ihdr.push_back(0);
     chunk(png, "IHDR", ihdr);
+    if (cicp)
+        chunk(png, "cICP", std::vector<unsigned char>(cicp, cicp + 4));
     chunk(png, "IDAT", z);
     chunk(png, "IEND", {});
 
@@ -108,6 +97,46 @@ bool Image::save(const std::string& fileName) const
     bool ok = std::fwrite(png.data(), 1, png.size(), f) == png.size();
     ok = std::fclose(f) == 0 && ok;
     return ok;
+}
+
+} // namespace
+
+bool Image::save(const std::string& fileName) const
+{
+    // raw scanlines: filter byte 0 + RGBA (the reference swaps R and B for its encoder the same way,
+    // renderer/Image.cpp:34-38)
+    std::vector<unsigned char> raw;
+    raw.reserve((size_t)height * (1 + 4 * (size_t)width));
+    for (int y = 0; y < height; y++) {
+        raw.push_back(0);
+        for (int x = 0; x < width; x++) {
+            uint32_t p = pixels[(size_t)y * width + x];
+            raw.push_back((p >> 16) & 0xff);
+            raw.push_back((p >> 8) & 0xff);
+            raw.push_back(p & 0xff);
+            raw.push_back((p >> 24) & 0xff);
+        }
+    }
+    return writePng(fileName, width, height, 8, 6, raw, nullptr); // 8 bits, RGBA
+}
+
+bool writePng16(const std::string& fileName, int width, int height, const uint16_t* rgba, bool pq)
+{
+    // raw scanlines: filter byte 0 + R, G, B, two bytes each, the high one first
+    std::vector<unsigned char> raw;
+    raw.reserve((size_t)height * (1 + 6 * (size_t)width));
+    for (int y = 0; y < height; y++) {
+        raw.push_back(0);
+        for (int x = 0; x < width; x++)
+            for (int k = 0; k < 3; k++) {
+                const uint16_t v = rgba[((size_t)y * width + x) * 4 + k];
+                raw.push_back((unsigned char)(v >> 8));
+                raw.push_back((unsigned char)(v & 0xff));
+            }
+    }
+    // cICP: colour primaries 1 (BT.709, the renderer's), transfer 16 (SMPTE ST 2084), matrix 0 (RGB), full range
+    static const unsigned char kPq[4] = {1, 16, 0, 1};
+    return writePng(fileName, width, height, 16, 2, raw, pq ? kPq : nullptr); // 16 bits, RGB
 }
 
 bool writePfm(const std::string& fileName, int width, int height, int channels, const float* topRowFirst)

@@ -24,6 +24,11 @@ public:
     bool save(const std::string& path) const;
 };
 
+// Writes a 16-bit RGB PNG (big-endian samples, stored deflate blocks as Image::save) from width * height * 4 uint16 r, g, b, a, top row
+// first, as the encode's RGBA16 words lie in memory; the alpha is not written. pq: the samples are a PQ signal -- a cICP chunk (1, 16,
+// 0, 1) says so. false on I/O failure.
+bool writePng16(const std::string& path, int width, int height, const uint16_t* rgba, bool pq);
+
 // Writes a little-endian PFM ("PF" for channels = 3, "Pf" for 1): width * height * channels floats given top row first, stored bottom row
 // first as the format requires; false on I/O failure.
 bool writePfm(const std::string& path, int width, int height, int channels, const float* topRowFirst);

@@ -133,6 +133,8 @@ int main(int argc, char** argv)
     std::string lensAperture, lensFocus, lensFocusAt, lensMaxRadius;
     // view options (include/kajo_hip.h KajoViewParams): the raw text, checked after the loop
     std::string outputSize, viewRect, viewFilter, supersample;
+    std::string png16Out, transferName, peakNits, ditherSeed;
+    bool dither = false;
     // grade options (include/kajo_hip.h KajoGradeParams): the raw text, checked after the loop
     std::string gradeSlope, gradeOffset, gradePower, gradeSaturation, whiteBalance, whiteBalanceAt;
     std::vector<std::string> gradeRegions;
@@ -271,7 +273,16 @@ int main(int argc, char** argv)
                         "    --adaptive-every B  --adaptive: batches of four passes between decisions (4)\n"
                         "    --sample-map FILE.pfm  with --adaptive: also write the per-pixel pass count as a 1-channel PFM\n"
                         "    --noise-map FILE  also write the noise map as a 3-channel PFM: mean luminance per pass, its standard error, the relative\n"
-                        "                    error (-1 where a pixel has fewer than two batches); any --gpus\n",
+                        "                    error (-1 where a pixel has fewer than two batches); any --gpus\n"
+                        "    --png16 FILE.png  also write the image of the whole chain as a 16-bit RGB PNG (include/kajo_hip.h \"The encode\": RGBA16 words\n"
+                        "                    in place of the 8-bit ones, big-endian samples); any --gpus. Not with --auto-exposure (--meter-exposure works)\n"
+                        "                    (--json: encode_format, encode_transfer, encode_peak_nits, encode_dither)\n"
+                        "    --transfer gamma22|srgb|pq  --png16: the transfer function (gamma22, the resolve's curve); pq writes a SMPTE ST 2084 signal\n"
+                        "                    and a cICP chunk (1, 16, 0, 1)\n"
+                        "    --peak-nits N   --png16 --transfer pq: the luminance a display value of 1 is shown at, 0 < N <= 10000 (1000)\n"
+                        "    --dither        write -o through the encode's ARGB8 words with dither instead of the undithered resolve; any --gpus. Not with\n"
+                        "                    a view option or --auto-exposure\n"
+                        "    --dither-seed N  --dither: the seed of the pattern, 0 .. 4294967295 (0)\n",
                         args[0].c_str());
             return 1;
         } else if (a == "-w" && more) width = std::atoi(args[++i].c_str());
@@ -333,6 +344,11 @@ int main(int argc, char** argv)
         else if (a == "--view" && more) viewRect = args[++i];
         else if (a == "--view-filter" && more) viewFilter = args[++i];
         else if (a == "--supersample" && more) supersample = args[++i];
+        else if (a == "--png16" && more) png16Out = args[++i];
+        else if (a == "--transfer" && more) transferName = args[++i];
+        else if (a == "--peak-nits" && more) peakNits = args[++i];
+        else if (a == "--dither") dither = true;
+        else if (a == "--dither-seed" && more) ditherSeed = args[++i];
         else if (a == "--grade-slope" && more) gradeSlope = args[++i];
         else if (a == "--grade-offset" && more) gradeOffset = args[++i];
         else if (a == "--grade-power" && more) gradePower = args[++i];
@@ -599,6 +615,68 @@ int main(int argc, char** argv)
         }
     }
     const bool viewGiven = !outputSize.empty() || !viewRect.empty() || !viewFilter.empty() || !supersample.empty();
+    // the encode: --png16 (RGBA16 words, a transfer) and --dither (ARGB8 words with dither for -o). Before any device is opened: the
+    // refusals, with the option's name
+    const bool encodeGiven = !png16Out.empty() || dither || !transferName.empty() || !peakNits.empty() || !ditherSeed.empty();
+    const char* transferNames[] = {"gamma22", "srgb", "pq", "linear"};
+    KajoEncodeParams encode16, encode8;
+    kajo_hip_default_encode_params(&encode16);
+    kajo_hip_default_encode_params(&encode8);
+    if (encodeGiven) {
+        if (threeArg) {
+            std::cerr << "kajo_render: the encode options need the options constructor (without --three-arg)" << std::endl;
+            return 1;
+        }
+        if (png16Out.empty() && (!transferName.empty() || !peakNits.empty())) {
+            std::cerr << "kajo_render: --transfer and --peak-nits belong to --png16" << std::endl;
+            return 1;
+        }
+        if (!dither && !ditherSeed.empty()) {
+            std::cerr << "kajo_render: --dither-seed belongs to --dither" << std::endl;
+            return 1;
+        }
+        if (toneAuto) {
+            std::cerr << "kajo_render: --png16 and --dither take no --auto-exposure (its scale is formed inside the tone mapping they replace): "
+                         "use --meter-exposure" << std::endl;
+            return 1;
+        }
+        if (dither && viewGiven) {
+            std::cerr << "kajo_render: --dither and a view option are not combined: the view resamples 8-bit words" << std::endl;
+            return 1;
+        }
+        encode16.format = KAJO_ENCODE_RGBA16;
+        if (!transferName.empty()) {
+            if (transferName == "gamma22") encode16.transfer = KAJO_TRANSFER_GAMMA22;
+            else if (transferName == "srgb") encode16.transfer = KAJO_TRANSFER_SRGB;
+            else if (transferName == "pq") encode16.transfer = KAJO_TRANSFER_PQ;
+            else {
+                std::cerr << "kajo_render: --transfer must be gamma22, srgb or pq" << std::endl;
+                return 1;
+            }
+        }
+        if (!peakNits.empty()) {
+            if (encode16.transfer != KAJO_TRANSFER_PQ) {
+                std::cerr << "kajo_render: --peak-nits belongs to --transfer pq" << std::endl;
+                return 1;
+            }
+            if (!parseFloat(peakNits, &encode16.peakNits) || !(encode16.peakNits > 0.0f && encode16.peakNits <= 10000.0f)) {
+                std::cerr << "kajo_render: --peak-nits: encode peak luminance must be finite and in (0, 10000] nits" << std::endl;
+                return 1;
+            }
+        }
+        if (dither) {
+            encode8.flags = KAJO_ENCODE_DITHER;
+            if (!ditherSeed.empty()) {
+                char* end = nullptr;
+                const unsigned long long seed = std::strtoull(ditherSeed.c_str(), &end, 10);
+                if (end == ditherSeed.c_str() || *end != '\0' || ditherSeed[0] == '-' || seed > 0xffffffffull) {
+                    std::cerr << "kajo_render: --dither-seed N must be in 0..4294967295" << std::endl;
+                    return 1;
+                }
+                encode8.ditherSeed = (uint32_t)seed;
+            }
+        }
+    }
     const char* viewFilterNames[] = {"nearest", "area", "triangle", "lanczos3"};
     if (viewGiven) {
         // (before any device is opened: the refusals of the view, with the option's name)
@@ -1034,6 +1112,18 @@ int main(int argc, char** argv)
             if (gradeGiven)
                 gradeRan = hipScheduler->lastGrade(gradeSlopeUsed);
         }
+        if (dither && !out.empty()) {
+            // (the image -o holds: the whole chain as run() left the frame, through the encode's ARGB8 words with dither)
+            hipScheduler->readEncoded(&encode8, image->pixels.get());
+            if (gradeGiven)
+                gradeRan = hipScheduler->lastGrade(gradeSlopeUsed);
+        }
+        if (!png16Out.empty()) {
+            std::vector<uint16_t> words((size_t)width * height * 4);
+            hipScheduler->readEncoded(&encode16, words.data());
+            if (!writePng16(png16Out, width, height, words.data(), encode16.transfer == KAJO_TRANSFER_PQ))
+                return 3;
+        }
     } catch (const std::exception& e) {
         std::cerr << "kajo_render: " << e.what() << std::endl;
         return 2;
@@ -1099,6 +1189,17 @@ int main(int argc, char** argv)
                         (int)opt.view.outW, (int)opt.view.outH, viewFilterNames[opt.view.filter],
                         (viewRect.empty() ? (double)width : (double)opt.view.x1 - opt.view.x0) / opt.view.outW,
                         (viewRect.empty() ? (double)height : (double)opt.view.y1 - opt.view.y0) / opt.view.outH);
+        if (encodeGiven) {
+            // (of --png16 where it is given, else of -o through --dither)
+            const KajoEncodeParams& e = png16Out.empty() ? encode8 : encode16;
+            std::printf(", \"encode_format\": \"%s\", \"encode_transfer\": \"%s\", \"encode_peak_nits\": ", png16Out.empty() ? "argb8" : "rgba16",
+                        transferNames[e.transfer]);
+            if (e.transfer == KAJO_TRANSFER_PQ)
+                std::printf("%.9g", (double)e.peakNits);
+            else
+                std::printf("null");
+            std::printf(", \"encode_dither\": %s", dither ? "true" : "false");
+        }
         if (adaptiveGiven)
             std::printf(", \"adaptive_active_units\": %lld, \"adaptive_units\": %lld, \"adaptive_paths\": %lld, \"adaptive_stopped_at_pass\": %d",
                         s.adaptiveActiveUnits, s.adaptiveUnits, s.adaptivePaths, s.adaptiveStoppedAtPass);

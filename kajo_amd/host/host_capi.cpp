@@ -1,8 +1,9 @@
 // host_capi.cpp -- C entry points over the host-side scene loader, for tests: parse a Kajo JSON
-// scene (or build the reference's test scene) into the flat arrays of include/kajo_scene.h.
+// scene (or build the reference's test scene) into the flat arrays of include/kajo_scene.h; and the driver's 16-bit PNG writer.
 #include <cstring>
 #include <string>
 
+#include "Image.h"
 #include "kajo_scene.h"
 #include "scene/Scene.h"
 
@@ -46,6 +47,12 @@ int kajo_host_parse(const char* text, float aspect, int* nSpheres, int* nPlanes)
 void kajo_host_export(float background[4], float view[16], float proj[16], KajoSphere* spheres, KajoPlane* planes)
 {
     exportScene(background, view, proj, spheres, planes);
+}
+
+// Image.cpp's writePng16: 0 on success
+int kajo_host_write_png16(const char* path, int width, int height, const uint16_t* rgba, int pq)
+{
+    return writePng16(path, width, height, rgba, pq != 0) ? 0 : -1;
 }
 
 } // extern "C"

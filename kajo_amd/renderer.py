@@ -522,8 +522,23 @@ class HipRenderer:
         capi.check(self._L.kajo_hip_grade(self._h, ref(s), ref(d), C.byref(p), out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def _encoded_array(self, e):
+        if e.format in (capi.KAJO_ENCODE_ARGB8, capi.KAJO_ENCODE_RGB10A2):
+            return np.empty((self.height, self.width), np.uint32)
+        return np.empty((self.height, self.width, 4), np.float16 if e.format == capi.KAJO_ENCODE_RGBA16F else np.uint16)
+
+    def encode(self, encode: dict = None, **tone) -> np.ndarray:
+        """The encode stage alone over the handle's frame (include/kajo_hip.h kajo_hip_encode): exposure and tone curve as tonemap()'s
+        (no automatic exposure), then the transfer, the dither and the format of encode_params(**encode) -> (H, W) uint32 for "argb8"
+        and "rgb10a2", (H, W, 4) uint16 for "rgba16", (H, W, 4) float16 for "rgba16f". Nothing of the handle's state is touched."""
+        e = encode_params(**(encode or {}))
+        t = self._tone_params(**tone)
+        out = self._encoded_array(e)
+        capi.check(self._L.kajo_hip_encode(self._h, C.byref(e), C.byref(t), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def present(self, despeckle: dict = None, denoise: dict = None, glare: dict = None, meter: dict = None, local: dict = None,
-                lens: dict = None, view: dict = None, grade: dict = None, **tone):
+                lens: dict = None, view: dict = None, grade: dict = None, encode: dict = None, **tone):
         """The display chain with the despeckle in front (include/kajo_hip.h kajo_hip_present_argb8): despeckle -> denoise -> glare ->
         tone mapping -> (argb8, scale) as tonemap(), every stage but the last optional. despeckle: a dict of despeckle()'s factor / rank /
         floor; the rest as display(). With despeckle None it is display(denoise, glare, **tone). meter: a dict of meter()'s params puts
@@ -533,8 +548,27 @@ class HipRenderer:
         routed there only when it is given). lens: a dict of lens()'s params puts the depth of field between the denoiser and the glare
         (kajo_hip_present_lens_argb8; likewise routed there only when it is given). view: a dict of view()'s params puts the view behind
         the tone curves (kajo_hip_present_view_argb8; likewise): the array returned then has the view's shape (out_h, out_w). grade: a dict of
-        grade()'s params puts the grade between the denoiser and the lens (kajo_hip_present_grade_argb8; likewise)."""
+        grade()'s params puts the grade between the denoiser and the lens (kajo_hip_present_grade_argb8; likewise). encode: a dict of
+        encode_params()'s arguments puts the encode in place of the 8-bit word (kajo_hip_encode_present; no view beside it): the array
+        returned is encode()'s, the second value the result dict of meter() with a meter and None without."""
         t = self._tone_params(**tone)
+        if encode is not None:
+            if view is not None:
+                raise ValueError("a view and an encode are not combined: the view resamples ARGB8 words")
+            ref = lambda p: None if p is None else C.byref(p)
+            e = encode_params(**encode)
+            s = None if despeckle is None else self._despeckle_params(**despeckle)
+            d = None if denoise is None else self._denoise_params(**denoise)
+            c = None if grade is None else grade_params(**grade)
+            f = None if lens is None else self._lens_params(**lens)
+            g = None if glare is None else self._glare_params(**glare)
+            l = None if local is None else self._local_params(**local)
+            m = None if meter is None else self._meter_params(**meter)
+            result = capi.KajoMeterResult()
+            out = self._encoded_array(e)
+            capi.check(self._L.kajo_hip_encode_present(self._h, ref(s), ref(d), ref(c), ref(f), ref(g), ref(l), ref(m), C.byref(t), C.byref(e),
+                                                       out.ctypes.data_as(C.c_void_p), C.byref(result)))
+            return out, (None if m is None else self._meter_result(result))
         s = None if despeckle is None else self._despeckle_params(**despeckle)
         d = None if denoise is None else self._denoise_params(**denoise)
         g = None if glare is None else self._glare_params(**glare)
@@ -722,6 +756,52 @@ def grade_neutral(rgb) -> np.ndarray:
     g = (C.c_float * 3)()
     capi.check(capi.lib().kajo_hip_grade_neutral(C.byref(src), C.byref(g)))
     return np.array(g[:], np.float32)
+
+
+def encode_params(format="argb8", transfer=None, dither: bool = False, scene: bool = False, peak_nits: float = None, dither_seed: int = 0):
+    """KajoEncodeParams (include/kajo_hip.h "The encode"): format "argb8" | "rgb10a2" | "rgba16" | "rgba16f", transfer "gamma22" | "srgb" |
+    "pq" | "linear" (or the KAJO_ENCODE_* / KAJO_TRANSFER_* values; the transfer defaults to "linear" for "rgba16f", else to "gamma22"),
+    dither, scene (scene-linear halves), peak_nits for "pq", dither_seed."""
+    p = capi.KajoEncodeParams()
+    capi.lib().kajo_hip_default_encode_params(C.byref(p))
+    p.format = capi.KAJO_ENCODE_FORMATS[format] if isinstance(format, str) else int(format)
+    if transfer is None:
+        transfer = "linear" if p.format == capi.KAJO_ENCODE_RGBA16F else "gamma22"
+    p.transfer = capi.KAJO_TRANSFERS[transfer] if isinstance(transfer, str) else int(transfer)
+    p.flags = (capi.KAJO_ENCODE_DITHER if dither else 0) | (capi.KAJO_ENCODE_SCENE if scene else 0)
+    if peak_nits is not None:
+        p.peakNits = float(peak_nits)
+    p.ditherSeed = int(dither_seed) & 0xFFFFFFFF
+    return p
+
+
+def encode_table(transfer="gamma22", peak_nits: float = 1000.0) -> np.ndarray:
+    """The table of a transfer (include/kajo_hip.h kajo_hip_encode_table): (4097, 2) float32 rows (T_i, S_i); the last row is (T64(1),
+    the slope below 2^-32). Host code: no device is opened."""
+    t = capi.KAJO_TRANSFERS[transfer] if isinstance(transfer, str) else int(transfer)
+    out = np.zeros(capi.KAJO_ENCODE_TABLE_WORDS, np.float32)
+    n = capi.lib().kajo_hip_encode_table(t, float(peak_nits), out.ctypes.data_as(C.c_void_p), out.size)
+    if n < 0:
+        capi.check(n)
+    return out[:n].reshape(-1, 2)
+
+
+def encode_pixels(mean_rgb, encode: dict = None, x0: int = 0, y0: int = 0, row_width: int = None, curve: str = "clamp", exposure: float = 0.0,
+                  white: float = 0.0) -> np.ndarray:
+    """The encode over an array (..., 3) of MEANS on the host, the kernel's own lines (include/kajo_hip.h kajo_hip_encode_pixels) -> n
+    words, uint32 or uint64 by the format. The pixels are row-major in a rectangle row_width wide (default: all in one row) whose first
+    pixel is (x0, y0) of the frame; that matters to the dither only."""
+    e = encode if isinstance(encode, capi.KajoEncodeParams) else encode_params(**(encode or {}))
+    curves = {"clamp": capi.KAJO_TONE_CLAMP, "reinhard": capi.KAJO_TONE_REINHARD, "aces": capi.KAJO_TONE_ACES}
+    t = capi.KajoToneParams()
+    capi.lib().kajo_hip_default_tone_params(C.byref(t))
+    t.curve, t.exposure, t.white = curves[curve], float(exposure), float(white)
+    m = np.ascontiguousarray(mean_rgb, np.float32).reshape(-1, 3)
+    wide = e.format in (capi.KAJO_ENCODE_RGBA16, capi.KAJO_ENCODE_RGBA16F)
+    out = np.zeros(len(m), np.uint64 if wide else np.uint32)
+    capi.check(capi.lib().kajo_hip_encode_pixels(C.byref(e), C.byref(t), m.ctypes.data_as(C.c_void_p), len(m), int(x0), int(y0),
+                                                 int(row_width or max(len(m), 1)), out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 def view_weights(src_n: int, a0: float, a1: float, out_n: int, filter="area"):
