@@ -34,7 +34,8 @@ def render_cuts(sc, w, h, cuts, owners=1, warm=0, **kw):
     """The frame after sum(cuts) passes rendered as len(cuts) render calls, composed from `owners` tile owners. warm: passes rendered (and
     discarded by a reset) first, so that the handle has measured its launch order and parts the tail of the launches that allow it."""
     import torch
-    parts = [HipRenderer(sc, w, h, seed=SEED, passes_per_launch=16, tile_index=i, tile_count=owners, **kw) for i in range(owners)]
+    kw.setdefault("passes_per_launch", 16)
+    parts = [HipRenderer(sc, w, h, seed=SEED, tile_index=i, tile_count=owners, **kw) for i in range(owners)]
     try:
         tail = 0
         for p in parts:

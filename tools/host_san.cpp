@@ -15,7 +15,8 @@
 //                                        launch_plan.h kajoLaunchPasses: "now passesDone" of every launch kajo_hip_render cuts the calls into
 //   host_san plan sizes a.pod ...        what a scene's size does to its staging (tests/test_scene_sizes_cpu.py): the plan's ldsTotal() per
 //                                        numerics build, the grid's cells per axis against the cells it wanted, the visibility lists' bins
-//                                        and their longest row of 16-bit offsets
+//                                        and their longest row of 16-bit offsets; and the staged scene's allTranslated, planesRigid and
+//                                        roomClosed beside nLights (tests/test_one_light_routing_cpu.py: which small-scene kernel it runs)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -201,6 +202,8 @@ static int planSizes(int argc, char** argv)
         kajo::StagedScene st;
         kajo::stageScene(pod.sc, st, 48, true);
         printf("%s: nSpheres=%d nLights=%zu grid=%d lists=%d", argv[a], st.nSpheres, st.light.size(), st.gridEnabled, st.shadowEnabled);
+        // (what launch.inc.hip's choice among the small-scene kernels reads: tests/test_one_light_routing_cpu.py)
+        printf(" allTranslated=%d planesRigid=%d roomClosed=%d", st.allTranslated, st.planesRigid, st.roomClosed ? 1 : 0);
         for (Numerics k : {Numerics::Fast, Numerics::Strict, Numerics::Exact}) {
             const KajoLdsPlan p = kajoLdsPlan(st, k);
             const char* name = k == Numerics::Fast ? "Fast" : k == Numerics::Strict ? "Strict" : "Exact";
