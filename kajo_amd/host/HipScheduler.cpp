@@ -93,6 +93,14 @@ struct Scheduler::Impl
 
     // Options::local changes the frame (include/kajo_hip.h: with compression 1 and detail 1 the output is the input)
     bool localActive() const { return opt.localOn && !(opt.local.compression == 1.0f && opt.local.detail == 1.0f); }
+
+    // A stage's parameters where Options has it change the frame, else null: what run()'s refreshes and readEncoded hand the chain calls.
+    // (readPresented and readViewed hand the glare &opt.glare whatever its strength, not glareOrNull(): the two look mergeable by the
+    // header's "strength 0 makes the output the input", and are left as they are.)
+    const KajoDespeckleParams* despeckleOrNull() const { return opt.despeckleOn ? &opt.despeckle : nullptr; }
+    const KajoGlareParams* glareOrNull() const { return glareOn() ? &opt.glare : nullptr; }
+    const KajoLocalParams* localOrNull() const { return localActive() ? &opt.local : nullptr; }
+    const KajoMeterParams* meterOrNull() const { return opt.meterOn ? &opt.meter : nullptr; }
     // Options::noise / noiseTarget: the handles keep the batch moments (KAJO_FLAG_NOISE)
     bool noiseOn() const { return opt.noise || opt.noiseTarget > 0.0f || adaptiveOn() || opt.denoiseNoiseGuided; }
     // Options::denoiseNoiseGuided: the denoise parameters of a read with the flag set (*store); with several owners the whole frame's m and
@@ -317,8 +325,6 @@ struct Scheduler::Impl
         }
     }
 
-    // Options::aovTiled: the whole-frame AOVs (and the float frame the denoiser filters) on handle 0, for the readers that need them. One
-    // exchange per buffer by the frame's own mechanism, then the two compose kernels; nothing where they are at hand already.
     // the grade's parameters for an image: Options::grade, with the gains of Options::gradeNeutralAt -- from the chain's frame in front of
     // the grade (kajo_hip_grade with the identity returns it) -- multiplied into the global slope in binary64 and rounded once
     void gradeParams(const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, KajoGradeParams* out)
@@ -362,8 +368,8 @@ struct Scheduler::Impl
     void present(const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGradeParams* grade, const KajoLensParams* lens,
                  const KajoGlareParams* glare, const KajoToneParams* tone, const KajoViewParams* view, uint32_t* argb8)
     {
-        check(kajo_hip_present_grade_argb8(handles[0], despeckle, denoise, grade, lens, glare, localActive() ? &opt.local : nullptr,
-                                           opt.meterOn ? &opt.meter : nullptr, tone ? tone : &opt.tone, view, argb8, &metered),
+        check(kajo_hip_present_grade_argb8(handles[0], despeckle, denoise, grade, lens, glare, localOrNull(), meterOrNull(), tone ? tone : &opt.tone,
+                                           view, argb8, &metered),
               "kajo_hip_present_grade_argb8");
         if (localActive())
             notePivot();
@@ -381,104 +387,149 @@ struct Scheduler::Impl
         lensRan = true;
     }
 
+    // One buffer of the owner-to-GPU-0 exchange: on device 0, `gpus` consecutive parts of `bytes` each, owner g's at g * bytes
+    // (type: of the RCCL exchange, four-byte elements; copyName: of the copy, for its error)
+    struct GatherBuffer
+    {
+        void* onDevice0;
+        size_t bytes;
+        ncclDataType_t type;
+        const char* copyName;
+    };
+    // Every owner's part of each buffer -> GPU 0; sourcesOf(g, src) names owner g's part of each. RCCL: per owner
+    // and buffer a send on the owner's communicator and stream and a receive on those of GPU 0, ALL inside one group. Copy: per owner a
+    // wait for its stream, then the copies on GPU 0's.
+    template <class SourcesOf>
+    void gatherToDevice0(const std::vector<GatherBuffer>& buffers, SourcesOf sourcesOf)
+    {
+        const bool rccl = opt.gather == Options::Rccl;
+        if (rccl)
+            checkNccl(ncclGroupStart(), "ncclGroupStart");
+        for (int g = 0; g < opt.gpus; g++) {
+            void* src[2] = {nullptr, nullptr};
+            sourcesOf(g, src);
+            if (!rccl) {
+                check(kajo_hip_wait(handles[g]), "kajo_hip_wait");
+                checkHip(hipSetDevice(devices[0]), "hipSetDevice");
+            }
+            for (size_t i = 0; i < buffers.size(); i++) {
+                const GatherBuffer& b = buffers[i];
+                char* dst = static_cast<char*>(b.onDevice0) + (size_t)g * b.bytes;
+                if (rccl) {
+                    checkNccl(ncclSend(src[i], b.bytes / 4, b.type, 0, comms[g], streams[g]), "ncclSend");
+                    checkNccl(ncclRecv(dst, b.bytes / 4, b.type, g, comms[0], streams[0]), "ncclRecv");
+                } else
+                    checkHip(hipMemcpyAsync(dst, src[i], b.bytes, hipMemcpyDefault, streams[0]), b.copyName);
+            }
+        }
+        if (rccl)
+            checkNccl(ncclGroupEnd(), "ncclGroupEnd");
+    }
+
+    // several owners (or the forced gather): the whole float frame on handle 0, from the last gather
+    void composeFrame()
+    {
+        if (gathered && !composed) {
+            check(kajo_hip_compose(handles[0], gathered), "kajo_hip_compose");
+            composed = true;
+        }
+    }
+
+    // Options::aovTiled: the whole-frame AOVs (and the float frame the denoiser filters) on handle 0, for the readers that need them. One
+    // exchange of the AOV and the matte buffers by the frame's own mechanism, then the two compose kernels; nothing where they are at hand
+    // already.
     void composeAov()
     {
         if (!opt.aov || !opt.aovTiled || aovComposed)
             return;
-        if (!gathered) { // single owner: its own tile buffers
-            check(kajo_hip_compose_aov(handles[0], nullptr, nullptr), "kajo_hip_compose_aov");
-            aovComposed = true;
-            return;
+        if (gathered) {
+            std::vector<GatherBuffer> buffers = {{aovGathered, aovTileBytes, ncclFloat, "hipMemcpyAsync(AOV gather)"}};
+            if (matteGathered)
+                buffers.push_back({matteGathered, matteTileBytes, ncclUint32, "hipMemcpyAsync(matte gather)"});
+            gatherToDevice0(buffers, [&](int g, void** src) {
+                check(kajo_hip_aov_tile_buffers(handles[g], &src[0], nullptr, &src[1], nullptr), "kajo_hip_aov_tile_buffers");
+            });
+            composeFrame();
         }
-        if (opt.gather == Options::Rccl) {
-            checkNccl(ncclGroupStart(), "ncclGroupStart");
-            for (int g = 0; g < opt.gpus; g++) {
-                void *a = nullptr, *m = nullptr;
-                check(kajo_hip_aov_tile_buffers(handles[g], &a, nullptr, &m, nullptr), "kajo_hip_aov_tile_buffers");
-                checkNccl(ncclSend(a, aovTileBytes / 4, ncclFloat, 0, comms[g], streams[g]), "ncclSend");
-                checkNccl(ncclRecv(static_cast<char*>(aovGathered) + (size_t)g * aovTileBytes, aovTileBytes / 4, ncclFloat, g, comms[0], streams[0]),
-                          "ncclRecv");
-                if (matteGathered) {
-                    checkNccl(ncclSend(m, matteTileBytes / 4, ncclUint32, 0, comms[g], streams[g]), "ncclSend");
-                    checkNccl(ncclRecv(static_cast<char*>(matteGathered) + (size_t)g * matteTileBytes, matteTileBytes / 4, ncclUint32, g, comms[0],
-                                       streams[0]),
-                              "ncclRecv");
-                }
-            }
-            checkNccl(ncclGroupEnd(), "ncclGroupEnd");
-        } else {
-            for (int g = 0; g < opt.gpus; g++) {
-                void *a = nullptr, *m = nullptr;
-                check(kajo_hip_aov_tile_buffers(handles[g], &a, nullptr, &m, nullptr), "kajo_hip_aov_tile_buffers");
-                check(kajo_hip_wait(handles[g]), "kajo_hip_wait");
-                checkHip(hipSetDevice(devices[0]), "hipSetDevice");
-                checkHip(hipMemcpyAsync(static_cast<char*>(aovGathered) + (size_t)g * aovTileBytes, a, aovTileBytes, hipMemcpyDefault, streams[0]),
-                         "hipMemcpyAsync(AOV gather)");
-                if (matteGathered)
-                    checkHip(hipMemcpyAsync(static_cast<char*>(matteGathered) + (size_t)g * matteTileBytes, m, matteTileBytes, hipMemcpyDefault,
-                                            streams[0]),
-                             "hipMemcpyAsync(matte gather)");
-            }
-        }
-        if (!composed) { // the float frame from the last gather, as readRadiance: the denoiser filters it
-            check(kajo_hip_compose(handles[0], gathered), "kajo_hip_compose");
-            composed = true;
-        }
+        // (a single owner: from its own tile buffers, aovGathered and matteGathered null)
         check(kajo_hip_compose_aov(handles[0], aovGathered, matteGathered), "kajo_hip_compose_aov");
         aovComposed = true;
     }
 
+    // What a chain call on handle 0's whole frame takes for the denoiser, the grade and the lens: the parameters, or null without the stage
+    struct ChainStages
+    {
+        const KajoDenoiseParams* denoise = nullptr;
+        const KajoGradeParams* grade = nullptr;
+        const KajoLensParams* lens = nullptr;
+        KajoDenoiseParams denoiseStore;
+        KajoGradeParams gradeStore;
+        KajoLensParams lensStore;
+    };
+
+    // Before readPresented's, readViewed's and readEncoded's chain call on the whole frame: the frame composed, the AOVs where a stage reads
+    // them, then the parameters. gradeBeforeLens: readPresented forms the grade's (kajo_hip_grade) before it focuses the lens
+    // (kajo_hip_lens_depth_at), the other two after; both calls only read the frame, and each reader keeps its order.
+    void prepareChain(const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, bool gradeBeforeLens, ChainStages& c)
+    {
+        composeFrame();
+        if (denoise || opt.lensOn || (opt.gradeOn && opt.grade.nRegions > 0))
+            composeAov();
+        c.denoise = guided(denoise, &c.denoiseStore);
+        if (opt.gradeOn && gradeBeforeLens)
+            gradeParams(despeckle, c.denoise, &c.gradeStore);
+        if (opt.lensOn) {
+            c.lensStore = opt.lens;
+            focusLens(&c.lensStore);
+            c.lens = &c.lensStore;
+        }
+        if (opt.gradeOn && !gradeBeforeLens)
+            gradeParams(despeckle, c.denoise, &c.gradeStore);
+        c.grade = opt.gradeOn ? &c.gradeStore : nullptr;
+    }
+
     // One exchange per displayed frame: every owner's tile buffer -> GPU 0; then the image straight
     // from the gathered buffers into Image::pixels (the float frame is composed only when readRadiance() asks for it).
+    // The image of a refresh: the chain where Options turns a stage of it on, else the plain resolve or the tone mapping alone. From handle
+    // 0's own tile buffer into host words, or from the gathered buffers into device words.
+    void resolveInto(bool fromGathered, void* dst)
+    {
+        uint32_t* words = static_cast<uint32_t*>(dst);
+        if (chainOn()) {
+            if (!fromGathered)
+                return present(despeckleOrNull(), nullptr, nullptr, nullptr, glareOrNull(), nullptr, nullptr, words);
+            check(kajo_hip_present_grade_gathered_argb8_device(handles[0], gathered, despeckleOrNull(), nullptr, glareOrNull(), localOrNull(),
+                                                               meterOrNull(), &opt.tone, nullptr, dst, &metered),
+                  "kajo_hip_present_grade_gathered_argb8_device");
+            if (localActive())
+                notePivot();
+        } else if (toneIsIdentity()) {
+            if (fromGathered)
+                check(kajo_hip_resolve_gathered_argb8_device(handles[0], gathered, dst), "kajo_hip_resolve_gathered_argb8_device");
+            else
+                check(kajo_hip_resolve_argb8(handles[0], words), "kajo_hip_resolve_argb8");
+        } else if (fromGathered)
+            check(kajo_hip_tonemap_gathered_argb8_device(handles[0], gathered, &opt.tone, dst), "kajo_hip_tonemap_gathered_argb8_device");
+        else
+            check(kajo_hip_tonemap_argb8(handles[0], &opt.tone, nullptr, words, &toneScale), "kajo_hip_tonemap_argb8");
+    }
+
     void gatherAndResolve()
     {
         if (opt.gpus == 1 && !opt.forceGather) {
             // single owner: the library resolves from its own tile buffer
-            if (chainOn()) {
-                present(opt.despeckleOn ? &opt.despeckle : nullptr, nullptr, nullptr, nullptr, glareOn() ? &opt.glare : nullptr, nullptr, nullptr,
-                        image->pixels.get());
+            resolveInto(false, image->pixels.get());
+            if (chainOn())
                 check(kajo_hip_tone_scale(handles[0], &toneScale), "kajo_hip_tone_scale");
-            } else if (toneIsIdentity())
-                check(kajo_hip_resolve_argb8(handles[0], image->pixels.get()), "kajo_hip_resolve_argb8");
-            else
-                check(kajo_hip_tonemap_argb8(handles[0], &opt.tone, nullptr, image->pixels.get(), &toneScale), "kajo_hip_tonemap_argb8");
             return;
         }
-        const size_t count = tileBytes / sizeof(float);
-        if (opt.gather == Options::Rccl) {
-            checkNccl(ncclGroupStart(), "ncclGroupStart");
-            for (int g = 0; g < opt.gpus; g++) {
-                void* src = nullptr;
-                size_t bytes = 0;
-                check(kajo_hip_tile_buffer(handles[g], &src, &bytes), "kajo_hip_tile_buffer");
-                checkNccl(ncclSend(src, count, ncclFloat, 0, comms[g], streams[g]), "ncclSend");
-                checkNccl(ncclRecv(static_cast<char*>(gathered) + (size_t)g * tileBytes, count, ncclFloat, g, comms[0], streams[0]),
-                          "ncclRecv");
-            }
-            checkNccl(ncclGroupEnd(), "ncclGroupEnd");
-        } else {
-            for (int g = 0; g < opt.gpus; g++) {
-                void* src = nullptr;
-                size_t bytes = 0;
-                check(kajo_hip_tile_buffer(handles[g], &src, &bytes), "kajo_hip_tile_buffer");
-                check(kajo_hip_wait(handles[g]), "kajo_hip_wait");
-                checkHip(hipSetDevice(devices[0]), "hipSetDevice");
-                checkHip(hipMemcpyAsync(static_cast<char*>(gathered) + (size_t)g * tileBytes, src, bytes, hipMemcpyDefault, streams[0]),
-                         "hipMemcpyAsync(gather)");
-            }
-        }
+        // (every owner's tile buffer has the size of the first's, tileBytes: the tile map gives each the same number of slots)
+        gatherToDevice0({{gathered, tileBytes, ncclFloat, "hipMemcpyAsync(gather)"}}, [&](int g, void** src) {
+            size_t bytes = 0;
+            check(kajo_hip_tile_buffer(handles[g], &src[0], &bytes), "kajo_hip_tile_buffer");
+        });
         composed = false;
-        if (chainOn()) {
-            check(kajo_hip_present_grade_gathered_argb8_device(handles[0], gathered, opt.despeckleOn ? &opt.despeckle : nullptr, nullptr,
-                                                               glareOn() ? &opt.glare : nullptr, localActive() ? &opt.local : nullptr,
-                                                               opt.meterOn ? &opt.meter : nullptr, &opt.tone, nullptr, argbDevice, &metered),
-                  "kajo_hip_present_grade_gathered_argb8_device");
-            if (localActive())
-                notePivot();
-        } else if (toneIsIdentity())
-            check(kajo_hip_resolve_gathered_argb8_device(handles[0], gathered, argbDevice), "kajo_hip_resolve_gathered_argb8_device");
-        else
-            check(kajo_hip_tonemap_gathered_argb8_device(handles[0], gathered, &opt.tone, argbDevice), "kajo_hip_tonemap_gathered_argb8_device");
+        resolveInto(true, argbDevice);
         checkHip(hipSetDevice(devices[0]), "hipSetDevice");
         checkHip(hipMemcpyAsync(image->pixels.get(), argbDevice, (size_t)image->width * image->height * 4, hipMemcpyDeviceToHost, streams[0]),
                  "hipMemcpyAsync(image)");
@@ -549,10 +600,7 @@ bool Scheduler::lastLens(float* focusDistance, float* maxRadiusPx) const
 void Scheduler::readRadiance(float* dst)
 {
     Impl& d = *m_impl;
-    if (d.gathered && !d.composed) { // several owners (or the forced gather): the whole float frame from the last gather
-        check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
-        d.composed = true;
-    }
+    d.composeFrame();
     check(kajo_hip_read_radiance(d.handles[0], dst), "kajo_hip_read_radiance");
 }
 
@@ -604,10 +652,7 @@ void Scheduler::readDenoisedTonemapped(const KajoDenoiseParams* params, const Ka
 void Scheduler::readDisplayed(const KajoDenoiseParams* denoise, const KajoGlareParams* glare, const KajoToneParams* tone, uint32_t* argb8, float* scale)
 {
     Impl& d = *m_impl;
-    if (d.gathered && !d.composed) { // several owners (or the forced gather): the whole float frame from the last gather, as readRadiance
-        check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
-        d.composed = true;
-    }
+    d.composeFrame();
     KajoDenoiseParams g;
     if (denoise) {
         d.composeAov();
@@ -620,34 +665,20 @@ void Scheduler::readPresented(const KajoDespeckleParams* despeckle, const KajoDe
                               const KajoToneParams* tone, uint32_t* argb8, float* scale, long long counts[2])
 {
     Impl& d = *m_impl;
-    if (!despeckle && d.opt.despeckleOn)
-        despeckle = &d.opt.despeckle;
+    if (!despeckle)
+        despeckle = d.despeckleOrNull();
     if (counts)
         counts[0] = counts[1] = 0;
     if (!despeckle && !d.opt.meterOn && !d.localActive() && !d.opt.lensOn && !d.opt.gradeOn)
         return readDisplayed(denoise, glare, tone, argb8, scale);
-    if (d.gathered && !d.composed) { // (as readDisplayed)
-        check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
-        d.composed = true;
-    }
-    if (denoise || d.opt.lensOn || (d.opt.gradeOn && d.opt.grade.nRegions > 0))
-        d.composeAov();
-    KajoDenoiseParams guidedDenoise;
-    denoise = d.guided(denoise, &guidedDenoise);
-    KajoGradeParams grade;
-    if (d.opt.gradeOn)
-        d.gradeParams(despeckle, denoise, &grade);
-    KajoLensParams lens = d.opt.lens;
-    if (d.opt.lensOn)
-        d.focusLens(&lens);
-    d.present(despeckle, denoise, d.opt.gradeOn ? &grade : nullptr, d.opt.lensOn ? &lens : nullptr, glare ? glare : &d.opt.glare, tone, nullptr, argb8);
+    Impl::ChainStages c;
+    d.prepareChain(despeckle, denoise, true, c);
+    d.present(despeckle, c.denoise, c.grade, c.lens, glare ? glare : &d.opt.glare, tone, nullptr, argb8);
     if (scale)
         check(kajo_hip_tone_scale(d.handles[0], scale), "kajo_hip_tone_scale");
-    if (d.opt.lensOn)
-        d.noteLens(lens);
-    if (!despeckle)
-        return;
-    if (counts) {
+    if (c.lens)
+        d.noteLens(*c.lens);
+    if (despeckle && counts) {
         int64_t c[2] = {0, 0};
         check(kajo_hip_despeckle_counts(d.handles[0], c), "kajo_hip_despeckle_counts");
         counts[0] = c[0];
@@ -660,31 +691,17 @@ void Scheduler::readViewed(uint32_t* dst)
     Impl& d = *m_impl;
     if (!d.opt.viewOn)
         throw std::runtime_error("hip::Scheduler: readViewed needs Options::viewOn");
-    if (d.gathered && !d.composed) { // (as readDisplayed)
-        check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
-        d.composed = true;
-    }
-    KajoLensParams lens = d.opt.lens;
-    if (d.opt.lensOn) {
-        d.composeAov();
-        d.focusLens(&lens);
-    }
-    KajoGradeParams grade;
-    if (d.opt.gradeOn) {
-        if (d.opt.grade.nRegions > 0)
-            d.composeAov();
-        d.gradeParams(d.opt.despeckleOn ? &d.opt.despeckle : nullptr, nullptr, &grade);
-    }
-    d.present(d.opt.despeckleOn ? &d.opt.despeckle : nullptr, nullptr, d.opt.gradeOn ? &grade : nullptr, d.opt.lensOn ? &lens : nullptr, &d.opt.glare,
-              nullptr, &d.opt.view, dst);
+    Impl::ChainStages c;
+    d.prepareChain(d.despeckleOrNull(), nullptr, false, c);
+    // (no noteLens here, unlike readPresented and readEncoded: lastLens() has never been of a viewed image)
+    d.present(d.despeckleOrNull(), nullptr, c.grade, c.lens, &d.opt.glare, nullptr, &d.opt.view, dst);
 }
 
 void Scheduler::readEncoded(const KajoEncodeParams* encode, void* dst)
 {
     Impl& d = *m_impl;
-    const KajoDespeckleParams* despeckle = d.opt.despeckleOn ? &d.opt.despeckle : nullptr;
-    const KajoLocalParams* local = d.localActive() ? &d.opt.local : nullptr;
-    const KajoMeterParams* meter = d.opt.meterOn ? &d.opt.meter : nullptr;
+    const KajoDespeckleParams* despeckle = d.despeckleOrNull();
+    const KajoLocalParams* local = d.localOrNull();
     const bool wholeFrame = d.opt.lensOn || (d.opt.gradeOn && (d.opt.grade.nRegions > 0 || d.opt.gradeNeutralAt.x >= 0));
     KajoGradeParams grade;
     if (d.gathered && !wholeFrame) {
@@ -702,9 +719,8 @@ void Scheduler::readEncoded(const KajoEncodeParams* encode, void* dst)
         }
         if (d.opt.gradeOn)
             d.gradeParams(despeckle, nullptr, &grade);
-        check(kajo_hip_encode_present_gathered_device(d.handles[0], d.gathered, despeckle, d.opt.gradeOn ? &grade : nullptr,
-                                                      d.glareOn() ? &d.opt.glare : nullptr, local, meter, &d.opt.tone, encode, d.encodedDevice,
-                                                      &d.metered),
+        check(kajo_hip_encode_present_gathered_device(d.handles[0], d.gathered, despeckle, d.opt.gradeOn ? &grade : nullptr, d.glareOrNull(), local,
+                                                      d.meterOrNull(), &d.opt.tone, encode, d.encodedDevice, &d.metered),
               "kajo_hip_encode_present_gathered_device");
         if (local)
             d.notePivot();
@@ -712,27 +728,15 @@ void Scheduler::readEncoded(const KajoEncodeParams* encode, void* dst)
         checkHip(hipStreamSynchronize(d.streams[0]), "hipStreamSynchronize");
         return;
     }
-    if (d.gathered && !d.composed) { // (as readDisplayed)
-        check(kajo_hip_compose(d.handles[0], d.gathered), "kajo_hip_compose");
-        d.composed = true;
-    }
-    KajoLensParams lens = d.opt.lens;
-    if (d.opt.lensOn) {
-        d.composeAov();
-        d.focusLens(&lens);
-    }
-    if (d.opt.gradeOn) {
-        if (d.opt.grade.nRegions > 0)
-            d.composeAov();
-        d.gradeParams(despeckle, nullptr, &grade);
-    }
-    check(kajo_hip_encode_present(d.handles[0], despeckle, nullptr, d.opt.gradeOn ? &grade : nullptr, d.opt.lensOn ? &lens : nullptr,
-                                  d.glareOn() ? &d.opt.glare : nullptr, local, meter, &d.opt.tone, encode, dst, &d.metered),
+    Impl::ChainStages c;
+    d.prepareChain(despeckle, nullptr, false, c);
+    check(kajo_hip_encode_present(d.handles[0], despeckle, nullptr, c.grade, c.lens, d.glareOrNull(), local, d.meterOrNull(), &d.opt.tone, encode, dst,
+                                  &d.metered),
           "kajo_hip_encode_present");
     if (local)
         d.notePivot();
-    if (d.opt.lensOn)
-        d.noteLens(lens);
+    if (c.lens)
+        d.noteLens(*c.lens);
 }
 
 void Scheduler::readNoise(float* mean, float* stderror, float* relative)
