@@ -204,7 +204,10 @@ int kajo_hip_destroy(kajo_hip_t h); /* NULL is accepted */
    The frame after P passes is a function of the scene, the parameters and P alone -- not of how the passes were cut into render()
    calls, launches (passesPerLaunch), workgroups or GPUs. STRICT adds the passes' terms radiance / S to a pixel's total one by one, as
    the reference does (Renderer.cpp:70-71); FAST and EXACT (small scenes) add them in groups of four passes by absolute number
-   (1-4, 5-8, ...): a group is summed from zero in pass order, then added to the total; a group in progress is added last. */
+   (1-4, 5-8, ...): a group is summed from zero in pass order, then added to the total; a group in progress is added last.
+   Across PROCESSES the same holds for a session continued through kajo_hip_checkpoint_save / kajo_hip_checkpoint_restore, at any pass
+   count; through kajo_hip_set_pass_count and a restored tile buffer it holds for FAST / EXACT only at pass counts that are multiples of
+   four (KAJO_GROUP_PASSES), since the summands of a group in progress are not in that buffer. */
 int kajo_hip_render(kajo_hip_t h, int passes);
 int kajo_hip_wait(kajo_hip_t h);
 /* Zero the accumulation (and the AOV buffers, their sample count and the coverage tables of KAJO_FLAG_AOV_MATTE) and restart the pass
@@ -216,7 +219,9 @@ int kajo_hip_reset(kajo_hip_t h);
    it, so the caller restores the buffer of the session being continued through kajo_hip_tile_buffer() first (or calls
    kajo_hip_reset() and set_pass_count(0)). FAST / EXACT: a passesDone inside a group of four continues from the buffer as
    one sum (the passes of the group so far are not known apart). Pass numbers run to 2^31 - 2. The AOV buffers of KAJO_FLAG_AOV are not
-   touched: later passes are traced with their own pass numbers' streams and added to them; nor are the tables of KAJO_FLAG_AOV_MATTE. */
+   touched: later passes are traced with their own pass numbers' streams and added to them; nor are the tables of KAJO_FLAG_AOV_MATTE.
+   To continue a session exactly -- inside a group, with its noise moments, its AOVs, its counters or its adaptive state -- use
+   kajo_hip_checkpoint_save and kajo_hip_checkpoint_restore ("Checkpoints" below) instead. */
 int kajo_hip_set_pass_count(kajo_hip_t h, int passesDone);
 
 /* Whole-frame outputs; valid when tileCount == 1, or on a handle that has been composed.
@@ -1236,6 +1241,104 @@ int kajo_hip_adapt_evaluate(const KajoNoiseMoments* records, int64_t count, cons
    = error (NULL state with nUnits > 0, wavesPerBlock outside 1 .. 4, an order word >= nUnits, a capacity too small). */
 int64_t kajo_hip_adapt_order(const uint32_t* order, uint32_t nUnits, const uint32_t* state, uint32_t wavesPerBlock, int32_t split, uint32_t* out,
                              size_t capacity);
+
+/* Checkpoints (kajo_amd/csrc/checkpoint.cpp, checkpoint_kernels.cpp, the arithmetic in checkpoint_math.h): a handle's whole accumulated state as a
+   self-describing blob, and a restore after which every later pass and every reader gives what the uninterrupted handle gives, bit for
+   bit -- the cut of the passes across processes. No render, AOV or display kernel is changed for it; a handle that never calls these
+   entry points allocates, launches and returns what it did.
+   A SECTION is one handle's state. CANONICAL ORDER of a per-pixel plane: the handle's own in-image pixels in image row-major order, y
+   ascending then x ascending, without the pixels of tiles the handle does not own; for tileCount 1 the plain W x H row-major frame.
+   Padding slots and slots outside the image never reach the blob. Planes (KAJO_CKPT_*), each present exactly when the handle keeps it:
+     SUM            4 words per pixel   the accumulation, always
+     CARRY          8                   FAST / EXACT, small scenes: the total of the complete groups of four passes, then the group in
+                                        progress -- only while the pass count stands inside a group
+     AOV            8                   KAJO_FLAG_AOV: A then B (the tile buffers of KAJO_FLAG_AOV_TILED, else the whole-frame sums)
+     MATTE          16                  KAJO_FLAG_AOV_MATTE: the 8 ids, then the 8 counts
+     NOISE_BASE     4                   KAJO_FLAG_NOISE: the baseline of the batch in progress
+     NOISE_MOMENTS  8                   KAJO_FLAG_NOISE: KajoNoiseMoments as 32-bit words
+   and, not per pixel: ADAPT (KAJO_FLAG_ADAPTIVE: the parameters of kajo_hip_set_adaptive, whether they were set, the retired count, the
+   paths traced, the last decision, then the state word of every unit) and COUNTERS (KAJO_FLAG_COUNTERS: the four device work counters as
+   eight 32-bit words). Scalars in the header: the pass count, the AOVs' pass count, whether a noise baseline is owed. kernelMs and
+   launches travel in a TRAILER of 16 bytes that belongs neither to the state nor to its digests. Not saved, because they do not affect
+   the bits: the launch-order feedback (measured again), every display stage's scratch, uploaded guide planes.
+   LAYOUT, little-endian: KajoCheckpointHeader (its magic "KAJOCKPT", KAJO_CKPT_VERSION), nPlanes KajoCheckpointPlane entries (kind, words
+   per pixel, byte offset from the blob's start, bytes, digest), the planes at 16-byte aligned offsets, the trailer.
+   FINGERPRINT: a 64-bit hash (checkpoint_math.h kajoCkptMix, chained) of the KajoScene -- its fields in front of the two pointers, then the
+   sphere and plane arrays -- and of W, H, S, the depth limit, the seed and the flags that choose what is computed (STRICT, EXACT, NO_GRID,
+   NO_SHADOW_LISTS, NO_ONE_LIGHT, AOV_SPECULAR), not of the tile layout, passesPerLaunch or the flags that say which planes exist.
+   DIGEST of a per-pixel plane of w words per pixel: the sum modulo 2^64 over its words of mix(mix(p * w + j) ^ b), p = y * W + x the
+   pixel's index in the WHOLE frame, j the word, b its 32 bits, mix the splitmix64 finaliser. It depends neither on the tile layout nor on
+   the order of summation; the digests of the owners of one frame add up to the whole frame's. ADAPT and COUNTERS: word i counts as pixel
+   i of one word. kajo_hip_checkpoint_save and kajo_hip_digest compute the per-pixel digests on the device.
+   kajo_hip_checkpoint_bytes, _save, _restore and kajo_hip_digest are SYNCHRONOUS: they wait for the handle's stream as kajo_hip_wait does
+   and return when the blob (the handle) is complete.
+   kajo_hip_checkpoint_info, pure host (no device, no handle): magic, version, sizes and offsets against `bytes`, and every plane's digest
+   recomputed; a truncated or altered blob is KAJO_E_INVALID with a message that names the plane.
+   kajo_hip_checkpoint_restore runs info's checks, then holds the fingerprint and the set of planes (CARRY aside) against what the handle
+   keeps, and only then touches the handle: a refused restore (KAJO_E_INVALID) leaves it as it was. A HIP error behind the checks
+   (KAJO_E_HIP) can leave some planes restored and others not, under the pass count of before: reset or destroy such a handle. It accepts a section of the handle's own layout (tile
+   shape, index and count), or a WHOLE-FRAME section (tileCount 1), of which it takes its own pixels. A section with an ADAPT block restores
+   into the same layout only (units are launch blocks). Afterwards the pass count, the AOVs' pass count, the carry, the owed baseline and
+   the adaptive state are the saved ones; the composed frame, the composed AOVs and the launch order are invalid, the guide planes gone.
+   kajo_hip_checkpoint_merge, pure host: the n sections of one frame's owners (tileCount n, every tileIndex once, the same fingerprint,
+   pass counts and planes) into one whole-frame section, whose digests are the sums of the sections' and which its own info accepts.
+   COUNTERS are added. Sections with an ADAPT block are refused. An owner without a pixel may lack CARRY. */
+#define KAJO_CKPT_VERSION 1u
+#define KAJO_CKPT_SUM 1u
+#define KAJO_CKPT_CARRY 2u
+#define KAJO_CKPT_AOV 3u
+#define KAJO_CKPT_MATTE 4u
+#define KAJO_CKPT_NOISE_BASE 5u
+#define KAJO_CKPT_NOISE_MOMENTS 6u
+#define KAJO_CKPT_ADAPT 7u
+#define KAJO_CKPT_COUNTERS 8u
+#define KAJO_CKPT_KINDS 9          /* kinds are 1 .. 8 */
+#define KAJO_CKPT_ADAPT_WORDS 16   /* words of the ADAPT block in front of the units' state words */
+typedef struct KajoCheckpointPlane {
+    uint32_t kind;          /* KAJO_CKPT_* */
+    uint32_t wordsPerPixel; /* 0: not per pixel */
+    uint64_t offset;        /* from the blob's start, a multiple of 16 */
+    uint64_t bytes;
+    uint64_t digest;
+} KajoCheckpointPlane;      /* 32 bytes */
+typedef struct KajoCheckpointHeader {
+    char magic[8];          /* "KAJOCKPT" */
+    uint32_t version;       /* KAJO_CKPT_VERSION */
+    uint32_t nPlanes;
+    int32_t width, height, tileW, tileH, tileIndex, tileCount;
+    uint32_t flags;         /* KajoParams.flags */
+    int32_t samplesPerPass, depthLimit;
+    int32_t passesDone;
+    uint64_t seed;
+    uint64_t fingerprint;
+    uint64_t pixels;        /* the section's pixels: the owner's in-image pixels */
+    int64_t aovPasses;
+    int32_t noiseRebase;    /* 1: a noise baseline is owed (kajo_hip_set_pass_count) */
+    int32_t reserved;       /* 0 */
+    uint64_t bytes;         /* of the whole section, the trailer included */
+} KajoCheckpointHeader;     /* 104 bytes */
+typedef struct KajoCheckpointTrailer {
+    double kernelMs;
+    uint64_t launches;
+} KajoCheckpointTrailer;    /* 16 bytes */
+typedef struct KajoCheckpointInfo {
+    KajoCheckpointHeader header;
+    KajoCheckpointTrailer trailer;
+    KajoCheckpointPlane planes[KAJO_CKPT_KINDS]; /* the first header.nPlanes of them, in the blob's order */
+} KajoCheckpointInfo;       /* 408 bytes */
+typedef struct KajoDigest {
+    uint64_t plane[KAJO_CKPT_KINDS]; /* by kind; 0 where the handle does not keep the plane */
+    uint32_t present;                /* bit k: the handle keeps plane k */
+    uint32_t reserved;
+} KajoDigest;               /* 80 bytes */
+int kajo_hip_checkpoint_bytes(kajo_hip_t h, size_t* bytes);
+int kajo_hip_checkpoint_save(kajo_hip_t h, void* blob, size_t capacity, size_t* written);
+int kajo_hip_checkpoint_restore(kajo_hip_t h, const void* blob, size_t bytes);
+int kajo_hip_checkpoint_info(const void* blob, size_t bytes, KajoCheckpointInfo* out);
+int kajo_hip_checkpoint_merge(const void* const* blobs, const size_t* bytes, int n, void* out, size_t capacity, size_t* written);
+/* The planes' digests of the live handle, no blob involved: two handles hold the same frame bit for bit exactly when their SUM words
+   agree (up to the 2^-64 of a 64-bit hash). */
+int kajo_hip_digest(kajo_hip_t h, KajoDigest* out);
 
 /* Use an existing HIP stream (hipStream_t passed as void*) instead of the handle's own; NULL is the null stream. The call waits for the
    stream the handle leaves, so work enqueued before it is complete before anything enqueued after it starts, whichever streams the two

@@ -59,6 +59,12 @@ KAJO_TRANSFER_GAMMA22, KAJO_TRANSFER_SRGB, KAJO_TRANSFER_PQ, KAJO_TRANSFER_LINEA
 KAJO_TRANSFERS = {"gamma22": KAJO_TRANSFER_GAMMA22, "srgb": KAJO_TRANSFER_SRGB, "pq": KAJO_TRANSFER_PQ, "linear": KAJO_TRANSFER_LINEAR}
 KAJO_ENCODE_DITHER, KAJO_ENCODE_SCENE = 1, 2  # KajoEncodeParams.flags
 KAJO_ENCODE_TABLE_WORDS = 8194  # floats of a transfer table (kajo_hip_encode_table)
+KAJO_CKPT_VERSION = 1  # checkpoints (kajo_hip_checkpoint_*): the version of a section, its planes' kinds, the words of an ADAPT block's head
+KAJO_CKPT_KINDS = 9
+KAJO_CKPT_NAMES = ("?", "SUM", "CARRY", "AOV", "MATTE", "NOISE_BASE", "NOISE_MOMENTS", "ADAPT", "COUNTERS")
+(KAJO_CKPT_SUM, KAJO_CKPT_CARRY, KAJO_CKPT_AOV, KAJO_CKPT_MATTE, KAJO_CKPT_NOISE_BASE, KAJO_CKPT_NOISE_MOMENTS, KAJO_CKPT_ADAPT,
+ KAJO_CKPT_COUNTERS) = range(1, 9)
+KAJO_CKPT_ADAPT_WORDS = 16
 KAJO_LOCAL_PIVOT_METERED = 1  # KajoLocalParams.flags: the pivot is the frame's own pivotPercentile-th luminance
 
 # every symbol include/kajo_hip.h declares
@@ -89,6 +95,8 @@ EXPORTS = [
     "kajo_hip_denoise_guide_planes",
     "kajo_hip_default_encode_params", "kajo_hip_encode_bytes", "kajo_hip_encode_table", "kajo_hip_encode_pixels", "kajo_hip_encode",
     "kajo_hip_encode_present", "kajo_hip_encode_present_gathered_device",
+    "kajo_hip_checkpoint_bytes", "kajo_hip_checkpoint_save", "kajo_hip_checkpoint_restore", "kajo_hip_checkpoint_info",
+    "kajo_hip_checkpoint_merge", "kajo_hip_digest",
 ]
 
 
@@ -181,6 +189,30 @@ class KajoGradeRegion(C.Structure):
 class KajoGradeParams(C.Structure):
     _fields_ = [("global_", KajoGradeOp), ("nRegions", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2),
                 ("regions", KajoGradeRegion * KAJO_GRADE_MAX_REGIONS)]  # (global_: the header's `global`, a keyword here)
+
+
+class KajoCheckpointPlane(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("wordsPerPixel", C.c_uint32), ("offset", C.c_uint64), ("bytes", C.c_uint64), ("digest", C.c_uint64)]
+
+
+class KajoCheckpointHeader(C.Structure):
+    _fields_ = [("magic", C.c_char * 8), ("version", C.c_uint32), ("nPlanes", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32),
+                ("tileW", C.c_int32), ("tileH", C.c_int32), ("tileIndex", C.c_int32), ("tileCount", C.c_int32), ("flags", C.c_uint32),
+                ("samplesPerPass", C.c_int32), ("depthLimit", C.c_int32), ("passesDone", C.c_int32), ("seed", C.c_uint64),
+                ("fingerprint", C.c_uint64), ("pixels", C.c_uint64), ("aovPasses", C.c_int64), ("noiseRebase", C.c_int32),
+                ("reserved", C.c_int32), ("bytes", C.c_uint64)]
+
+
+class KajoCheckpointTrailer(C.Structure):
+    _fields_ = [("kernelMs", C.c_double), ("launches", C.c_uint64)]
+
+
+class KajoCheckpointInfo(C.Structure):
+    _fields_ = [("header", KajoCheckpointHeader), ("trailer", KajoCheckpointTrailer), ("planes", KajoCheckpointPlane * KAJO_CKPT_KINDS)]
+
+
+class KajoDigest(C.Structure):
+    _fields_ = [("plane", C.c_uint64 * KAJO_CKPT_KINDS), ("present", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class KajoParams(C.Structure):
@@ -395,6 +427,14 @@ def lib():
             L.kajo_hip_adapt_evaluate.argtypes = [C.c_void_p, C.c_int64, C.POINTER(KajoAdaptParams), C.c_void_p, C.POINTER(C.c_int64)]
             L.kajo_hip_adapt_order.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_size_t]
             L.kajo_hip_adapt_order.restype = C.c_int64
+        if hasattr(L, "kajo_hip_checkpoint_save"):  # (nor checkpoints)
+            L.kajo_hip_checkpoint_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
+            L.kajo_hip_checkpoint_save.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+            L.kajo_hip_checkpoint_restore.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+            L.kajo_hip_checkpoint_info.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(KajoCheckpointInfo)]
+            L.kajo_hip_checkpoint_merge.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_void_p, C.c_size_t,
+                                                    C.POINTER(C.c_size_t)]
+            L.kajo_hip_digest.argtypes = [C.c_void_p, C.POINTER(KajoDigest)]
         L.kajo_hip_kat_trace.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
         L.kajo_hip_kat_shade.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         L.kajo_hip_kat_strictmath.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]

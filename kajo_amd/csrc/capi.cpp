@@ -799,6 +799,7 @@ int kajo_hip_create(const KajoScene* scene, int width, int height, const KajoPar
     h->W = width;
     h->H = height;
     h->numerics = kajoNumerics(p.flags);
+    h->sceneHash = kajoCkptSceneHash(*scene); // (the checkpoints' fingerprint: the handle does not keep the scene it was given)
     h->k = h->numerics == Numerics::Strict ? &kStrictKernels : h->numerics == Numerics::Exact ? &kExactKernels : &kFastKernels;
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
@@ -1631,3 +1632,6 @@ int kajo_hip_counters(kajo_hip_t h, KajoCounters* out)
 }
 
 } // extern "C"
+
+// checkpoints: kajo_hip_checkpoint_*, kajo_hip_digest
+#include "checkpoint.cpp"

@@ -30,6 +30,7 @@
 #include "view_weights.h"
 #include "grade_math.h"
 #include "adapt_math.h"
+#include "checkpoint_host.h"
 
 // launchers defined next to their kernels (kernel_fast.hip, kernel_strict.hip, kernel_exact.hip, aux_kernels.hip)
 extern "C" {
@@ -93,6 +94,14 @@ int kajo_matte_mask_launch(const void* ids, const void* counts, int W, int H, co
                            void* dominant, void* stream);
 int kajo_tone_fast_launch(const void* src, const TileMap* map, int fromTiles, float passes, const ToneArgs* t, void* scratch, void* dst, void* stream);
 int kajo_tone_strict_launch(const void* src, const TileMap* map, int fromTiles, float passes, const ToneArgs* t, void* scratch, void* dst, void* stream);
+// checkpoint_kernels.cpp: a plane between the handle's layout and canonical order (parts arrays of elems pieces of vecs 16-byte vectors), its digest
+int kajo_ckpt_pack_launch(const void* src, const KajoCkptGeom* g, const void* prefix, uint32_t pixels, uint32_t parts, uint32_t vecs, uint32_t elems,
+                          int tiled, void* staged, void* stream);
+int kajo_ckpt_unpack_launch(const void* staged, const KajoCkptGeom* g, const void* prefix, uint32_t parts, uint32_t vecs, uint32_t elems, int tiled,
+                            void* dst, void* stream);
+unsigned kajo_ckpt_digest_groups(uint32_t pixels);
+int kajo_ckpt_digest_launch(const void* staged, const KajoCkptGeom* g, const void* prefix, uint32_t pixels, uint32_t vecs, void* partials, void* out,
+                            void* stream);
 }
 
 static_assert(KAJO_TONE_CLAMP == KAJO_TONE_CURVE_CLAMP && KAJO_TONE_REINHARD == KAJO_TONE_CURVE_REINHARD && KAJO_TONE_ACES == KAJO_TONE_CURVE_ACES,
@@ -304,6 +313,12 @@ struct KajoHip : KajoFramePlan
     unsigned adaptRetired = 0;
     long long adaptPixels = 0, adaptActivePixels = 0, adaptPaths = 0;
     int adaptLastDecision = 0;
+    // checkpoints (checkpoint.cpp; kajo_hip_checkpoint_*, kajo_hip_digest): the hash of the scene create() was given; on the first call the
+    // staging buffer of one plane in canonical order, sized for the widest the handle can keep and reused plane by plane, the owner's
+    // prefix table (checkpoint_math.h) and the digests with the workgroups' partial sums behind them
+    uint64_t sceneHash = 0;
+    DeviceBuffer ckptStaging, ckptPrefix, ckptSums;
+    std::vector<uint32_t> ckptPrefixHost; // [tilesY + 1]; its last word: the owner's pixels
     int toneScaleState = 0; // the s of the most recent tone mapping: 0 none yet, 1 toneScale, 2 the scale word (auto exposure)
     float toneScale = 1.0f;
 };

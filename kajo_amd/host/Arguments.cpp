@@ -22,6 +22,7 @@ struct Raw
     std::string glareStrength, glareLevels, glareThreshold;
     std::string despeckleFactor, despeckleRank, despeckleFloor;
     std::string untilNoise, noiseQuantile, noiseFloor, maxPasses;
+    std::string checkpointEvery;
     std::string adaptiveE, adaptiveAllowance, adaptiveMinPasses, adaptiveEvery;
     std::string meterExposure, meterWhite;
     std::string localContrast, localDetail, localRange, localIterations, localPivot;
@@ -282,6 +283,12 @@ int help(const char* program)
                 "    --adaptive-min-passes N  --adaptive: no unit retires before pass N (16)\n"
                 "    --adaptive-every B  --adaptive: batches of four passes between decisions (4)\n"
                 "    --sample-map FILE.pfm  with --adaptive: also write the per-pixel pass count as a 1-channel PFM\n"
+                "    --checkpoint FILE  write the whole accumulated state (include/kajo_hip.h \"Checkpoints\"; any --gpus) to FILE when the run ends, through a\n"
+                "                    temporary name (--json: checkpoint_file, checkpoint_passes, resumed_from_passes, frame_digest)\n"
+                "    --checkpoint-every N  --checkpoint: also after the refresh that reaches each multiple of N passes, N >= 1\n"
+                "    --resume FILE   continue the session of FILE: --passes (--max-passes) is then the total of the whole session. A file written with\n"
+                "                    another --gpus is merged into one whole frame first; an --adaptive file resumes only with the --gpus it was\n"
+                "                    written with and is refused otherwise\n"
                 "    --noise-map FILE  also write the noise map as a 3-channel PFM: mean luminance per pass, its standard error, the relative\n"
                 "                    error (-1 where a pixel has fewer than two batches); any --gpus\n"
                 "    --png16 FILE.png  also write the image of the whole chain as a 16-bit RGB PNG (include/kajo_hip.h \"The encode\": RGBA16 words\n"
@@ -315,6 +322,7 @@ int commandLine(const std::vector<std::string>& args, Raw& r, Arguments& a)
         {"--despeckle-factor", &r.despeckleFactor}, {"--despeckle-rank", &r.despeckleRank}, {"--despeckle-floor", &r.despeckleFloor},
         {"--until-noise", &r.untilNoise}, {"--noise-quantile", &r.noiseQuantile}, {"--noise-floor", &r.noiseFloor}, {"--max-passes", &r.maxPasses},
         {"--noise-map", &a.noiseMapOut},
+        {"--checkpoint", &opt.checkpointPath}, {"--checkpoint-every", &r.checkpointEvery}, {"--resume", &opt.resumePath},
         {"--adaptive", &r.adaptiveE}, {"--adaptive-allowance", &r.adaptiveAllowance}, {"--adaptive-min-passes", &r.adaptiveMinPasses},
         {"--adaptive-every", &r.adaptiveEvery}, {"--sample-map", &a.sampleMapOut},
         {"--meter-exposure", &r.meterExposure}, {"--meter-white", &r.meterWhite},
@@ -479,6 +487,18 @@ int noiseAndAdaptiveOptions(const Raw& r, Arguments& a) // kajo_hip_set_adaptive
         return refuse("--max-passes must be a whole number >= 1, with --until-noise");
     if (rule)
         opt.passes = opt.maxPasses; // (the preview's pass budget and the scheduler's: the rule ends the run before it, or it does)
+    return 0;
+}
+
+int checkpointOptions(const Raw& r, Arguments& a) // kajo_hip_checkpoint_save and kajo_hip_checkpoint_restore
+{
+    hip::Options& opt = a.opt;
+    if (opt.checkpointPath.empty() && opt.resumePath.empty() && r.checkpointEvery.empty())
+        return 0;
+    if (a.threeArg)
+        return refuseThreeArg("checkpoint");
+    if (!r.checkpointEvery.empty() && (opt.checkpointPath.empty() || !wholeIn(r.checkpointEvery, 1, 0x7ffffffe, &opt.checkpointEvery)))
+        return refuse("--checkpoint-every must be a whole number >= 1, with --checkpoint");
     return 0;
 }
 
@@ -791,7 +811,7 @@ int parseArguments(int argc, char** argv, Arguments* out)
     a.matteGiven = !a.matteMaskOut.empty() || !a.matteIdsOut.empty();
     // (in this order: a later stage reads what an earlier one set -- the meter the tone's key and curve, the lens and the grade the size
     // the view left)
-    for (auto stage : {toneOptions, glareOptions, despeckleOptions, noiseAndAdaptiveOptions, meterOptions, localOptions, encodeOptions, viewOptions,
+    for (auto stage : {toneOptions, glareOptions, despeckleOptions, noiseAndAdaptiveOptions, checkpointOptions, meterOptions, localOptions, encodeOptions, viewOptions,
                        lensOptions, gradeOptions, aovMatteDenoiseOptions})
         if (int rc = stage(r, a))
             return rc;

@@ -6,8 +6,11 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
+#include <iterator>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -772,6 +775,69 @@ void Scheduler::readSamplePasses(uint32_t* plane)
         check(kajo_hip_adapt_passes(h, plane), "kajo_hip_adapt_passes");
 }
 
+namespace
+{
+
+// The checkpoint file: "KAJOCKPF", a version word, the number of sections, their sizes (64-bit), then the sections as
+// kajo_hip_checkpoint_save wrote them, each from a multiple of 16. Little-endian, as the sections are.
+const char kFileMagic[8] = {'K', 'A', 'J', 'O', 'C', 'K', 'P', 'F'};
+
+void writeCheckpointFile(const std::string& path, const std::vector<std::vector<unsigned char>>& sections)
+{
+    const std::string tmp = path + ".tmp";
+    {
+        std::ofstream f(tmp, std::ios::binary | std::ios::trunc);
+        const uint32_t head[2] = {1u, (uint32_t)sections.size()};
+        f.write(kFileMagic, 8);
+        f.write(reinterpret_cast<const char*>(head), sizeof head);
+        uint64_t at = 16 + 8 * (uint64_t)sections.size();
+        for (const auto& s : sections) {
+            const uint64_t n = s.size();
+            f.write(reinterpret_cast<const char*>(&n), 8);
+        }
+        const char zeros[16] = {};
+        for (const auto& s : sections) {
+            f.write(zeros, (std::streamsize)((16 - at % 16) % 16));
+            at += (16 - at % 16) % 16;
+            f.write(reinterpret_cast<const char*>(s.data()), (std::streamsize)s.size());
+            at += s.size();
+        }
+        f.flush();
+        if (!f)
+            throw std::runtime_error("hip::Scheduler: cannot write the checkpoint " + tmp);
+    }
+    if (std::rename(tmp.c_str(), path.c_str()) != 0)
+        throw std::runtime_error("hip::Scheduler: cannot rename " + tmp + " to " + path);
+}
+
+std::vector<std::vector<unsigned char>> readCheckpointFile(const std::string& path)
+{
+    std::ifstream f(path, std::ios::binary);
+    std::vector<unsigned char> all((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    if (!f && all.empty())
+        throw std::runtime_error("hip::Scheduler: cannot read the checkpoint " + path);
+    uint32_t head[2] = {0, 0};
+    if (all.size() < 16 || std::memcmp(all.data(), kFileMagic, 8) != 0)
+        throw std::runtime_error("hip::Scheduler: " + path + " is not a checkpoint file");
+    std::memcpy(head, all.data() + 8, sizeof head);
+    if (head[0] != 1u || head[1] < 1 || head[1] > 4096 || all.size() < 16 + 8 * (size_t)head[1])
+        throw std::runtime_error("hip::Scheduler: " + path + ": unknown version or truncated table of sections");
+    std::vector<std::vector<unsigned char>> sections;
+    uint64_t at = 16 + 8 * (uint64_t)head[1];
+    for (uint32_t i = 0; i < head[1]; i++) {
+        uint64_t n;
+        std::memcpy(&n, all.data() + 16 + 8 * (size_t)i, 8);
+        at += (16 - at % 16) % 16;
+        if (n > all.size() || at > all.size() - n)
+            throw std::runtime_error("hip::Scheduler: " + path + ": truncated inside section " + std::to_string(i));
+        sections.emplace_back(all.begin() + (std::ptrdiff_t)at, all.begin() + (std::ptrdiff_t)(at + n));
+        at += n;
+    }
+    return sections;
+}
+
+} // namespace
+
 void Scheduler::run()
 {
     Impl& d = *m_impl;
@@ -783,7 +849,63 @@ void Scheduler::run()
     int stoppedAt = 0;
     const std::thread::id self = std::this_thread::get_id();
     const auto t0 = std::chrono::steady_clock::now();
-    int done = 0;
+    int done = 0, resumedFrom = 0, checkpointed = 0;
+    // Options::checkpointPath: every owner's section into one file
+    const auto checkpoint = [&]() {
+        std::vector<std::vector<unsigned char>> sections;
+        for (kajo_hip_t h : d.handles) {
+            size_t bytes = 0, written = 0;
+            check(kajo_hip_checkpoint_bytes(h, &bytes), "kajo_hip_checkpoint_bytes");
+            sections.emplace_back(bytes);
+            check(kajo_hip_checkpoint_save(h, sections.back().data(), bytes, &written), "kajo_hip_checkpoint_save");
+            sections.back().resize(written);
+        }
+        writeCheckpointFile(o.checkpointPath, sections);
+        checkpointed = done;
+    };
+    if (!o.resumePath.empty()) {
+        // the file's sections as they are where they are the handles' own (same number of owners: restore refuses another layout), else
+        // merged into one whole-frame section of which every handle takes its pixels
+        std::vector<std::vector<unsigned char>> sections = readCheckpointFile(o.resumePath);
+        KajoCheckpointInfo info;
+        check(kajo_hip_checkpoint_info(sections[0].data(), sections[0].size(), &info), "kajo_hip_checkpoint_info");
+        if (sections.size() != d.handles.size() || info.header.tileCount != (int)d.handles.size()) {
+            for (uint32_t i = 0; i < info.header.nPlanes; i++)
+                if (info.planes[i].kind == KAJO_CKPT_ADAPT)
+                    throw std::runtime_error("hip::Scheduler: " + o.resumePath + " is an adaptive session of " + std::to_string(sections.size()) +
+                                             " GPU(s): it resumes with that many only (units are launch blocks)");
+            std::vector<const void*> ptrs;
+            std::vector<size_t> sizes;
+            for (const auto& s : sections) {
+                ptrs.push_back(s.data());
+                sizes.push_back(s.size());
+            }
+            size_t bytes = 0;
+            check(kajo_hip_checkpoint_merge(ptrs.data(), sizes.data(), (int)ptrs.size(), nullptr, 0, &bytes), "kajo_hip_checkpoint_merge");
+            std::vector<unsigned char> merged(bytes);
+            check(kajo_hip_checkpoint_merge(ptrs.data(), sizes.data(), (int)ptrs.size(), merged.data(), merged.size(), &bytes), "kajo_hip_checkpoint_merge");
+            sections.assign(d.handles.size(), merged);
+        } else {
+            // (in the order of the tile indices, whatever order the file has them in)
+            std::vector<std::vector<unsigned char>> byIndex(sections.size());
+            for (auto& s : sections) {
+                check(kajo_hip_checkpoint_info(s.data(), s.size(), &info), "kajo_hip_checkpoint_info");
+                if (info.header.tileCount != (int)sections.size())
+                    throw std::runtime_error("hip::Scheduler: " + o.resumePath + ": a section of " + std::to_string(info.header.tileCount) +
+                                             " owners in a file of " + std::to_string(sections.size()) + " sections");
+                if (!byIndex[(size_t)info.header.tileIndex].empty())
+                    throw std::runtime_error("hip::Scheduler: " + o.resumePath + ": owner " + std::to_string(info.header.tileIndex) + " is there twice");
+                byIndex[(size_t)info.header.tileIndex].swap(s);
+            }
+            sections.swap(byIndex);
+        }
+        for (size_t g = 0; g < d.handles.size(); g++)
+            check(kajo_hip_checkpoint_restore(d.handles[g], sections[g].data(), sections[g].size()), "kajo_hip_checkpoint_restore");
+        done = resumedFrom = info.header.passesDone;
+        d.aovComposed = false;
+        if (done > 0 && budget != 0 && done >= budget)
+            d.gatherAndResolve(); // (nothing left to render: the image of the restored frame)
+    }
     std::vector<double> batchMs;
     std::vector<int> batchPasses;
     // Passes between two refreshes. Fusing passes into one launch evens out the lanes' trip counts (38 G paths/s at
@@ -848,7 +970,11 @@ void Scheduler::run()
         if (d.preview)
             for (int p = done - now + 1; p <= done; p++)
                 d.preview->update(self, p, o.samplesPerPass, 0, 0, d.image->width, d.image->height);
+        if (!o.checkpointPath.empty() && o.checkpointEvery > 0 && done / o.checkpointEvery > (done - now) / o.checkpointEvery)
+            checkpoint();
     }
+    if (!o.checkpointPath.empty() && checkpointed != done)
+        checkpoint();
 
     d.stats = Statistics();
     d.stats.passes = done;
@@ -875,6 +1001,14 @@ void Scheduler::run()
         d.stats.clamped = c[0];
         d.stats.repaired = c[1];
     }
+    d.stats.checkpointPasses = checkpointed;
+    d.stats.resumedFromPasses = resumedFrom;
+    if (!o.checkpointPath.empty() || !o.resumePath.empty())
+        for (kajo_hip_t h : d.handles) { // (digests add over owners)
+            KajoDigest dg;
+            check(kajo_hip_digest(h, &dg), "kajo_hip_digest");
+            d.stats.frameDigest += dg.plane[KAJO_CKPT_SUM];
+        }
     d.stats.wallSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     for (kajo_hip_t h : d.handles) {
         KajoCounters c;

@@ -12,6 +12,7 @@
 
 #include <cstdint>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "Scheduler.h"
@@ -139,6 +140,14 @@ struct Options
     // to the first handle (kajo_hip_denoise_guide_planes) before the filter runs. Off by default: every run then makes exactly the calls
     // it made without this field.
     bool denoiseNoiseGuided = false;
+    // Checkpoint and resume (include/kajo_hip.h "Checkpoints"). checkpointPath: run() writes the owners' sections -- a small container, one
+    // section per GPU -- at its end and, with checkpointEvery > 0, after the refresh that reaches or passes each multiple of that many
+    // passes; to a temporary name beside the file, then renamed, so that a kill during the write leaves the file of before. resumePath:
+    // run() restores the handles from such a file before its first pass and counts on from the file's pass count (`passes` is the total
+    // of the whole session); a file of another number of GPUs goes through kajo_hip_checkpoint_merge, which an adaptive file is refused
+    // by. All empty by default: every run then makes exactly the calls it made without these fields.
+    std::string checkpointPath, resumePath;
+    int checkpointEvery = 0;
 };
 
 struct Statistics
@@ -162,6 +171,10 @@ struct Statistics
     // paths actually traced (`paths` above stays the nominal count), and the pass run() ended at because no unit was active (0: it did not)
     long long adaptiveUnits = 0, adaptiveActiveUnits = 0, adaptivePaths = 0;
     int adaptiveStoppedAtPass = 0;
+    // checkpoints (Options::checkpointPath / resumePath): the pass count of the last file written (0: none), the pass count run() resumed
+    // from, and the whole frame's SUM digest at the end of run() (the owners' kajo_hip_digest words added), taken only with one of the two
+    int checkpointPasses = 0, resumedFromPasses = 0;
+    unsigned long long frameDigest = 0;
 };
 
 class Scheduler : public ::Scheduler

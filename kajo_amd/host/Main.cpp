@@ -315,6 +315,22 @@ void printJson(const Arguments& a, const hip::Statistics& s, const Preview& prev
     if (a.noiseGiven || a.adaptiveGiven)
         std::printf(", \"noise_quantile_value\": %.9g, \"noise_known_px\": %lld, \"noise_bad_px\": %lld, \"noise_stopped_at_pass\": %d",
                     (double)s.noiseQuantileValue, s.noiseKnownPx, s.noiseBadPx, s.noiseStoppedAtPass);
+    if (!opt.checkpointPath.empty() || !opt.resumePath.empty())
+    {
+        // (the one file name in the line: its quotes, backslashes and control characters escaped)
+        std::string name;
+        for (unsigned char c : opt.checkpointPath) {
+            char u[8];
+            if (c == '"' || c == '\\')
+                name += '\\', name += (char)c;
+            else if (c < 0x20)
+                std::snprintf(u, sizeof u, "\\u%04x", c), name += u;
+            else
+                name += (char)c;
+        }
+        std::printf(", \"checkpoint_file\": \"%s\", \"checkpoint_passes\": %d, \"resumed_from_passes\": %d, \"frame_digest\": \"%016llx\"",
+                    name.c_str(), s.checkpointPasses, s.resumedFromPasses, s.frameDigest);
+    }
     if (opt.aovTiled)
         std::printf(", \"aov_tiled\": true");
     if (opt.denoiseNoiseGuided)

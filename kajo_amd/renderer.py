@@ -69,6 +69,38 @@ def adapt_order(order, state, waves_per_block: int, split: bool) -> np.ndarray:
     return out[:n]
 
 
+def checkpoint_info(blob) -> dict:
+    """What a checkpoint section says about itself, after every check that needs no handle -- magic, version, sizes, offsets and every
+    plane's digest recomputed (kajo_hip_checkpoint_info; pure host). The header's and the trailer's fields, and `planes`: a dict per plane
+    in the section's order (kind, name, wordsPerPixel, offset, bytes, digest). A truncated or altered blob raises KajoError."""
+    blob = bytes(blob)
+    info = capi.KajoCheckpointInfo()
+    capi.check(capi.lib().kajo_hip_checkpoint_info(blob, len(blob), C.byref(info)))
+    out = {k: getattr(info.header, k) for k, _ in capi.KajoCheckpointHeader._fields_ if k not in ("magic", "reserved")}
+    out.update({k: getattr(info.trailer, k) for k, _ in capi.KajoCheckpointTrailer._fields_})
+    out["planes"] = [dict(kind=p.kind, name=capi.KAJO_CKPT_NAMES[p.kind], wordsPerPixel=p.wordsPerPixel, offset=p.offset, bytes=p.bytes,
+                          digest=p.digest) for p in info.planes[:info.header.nPlanes]]
+    return out
+
+
+def checkpoint_merge(blobs) -> bytes:
+    """The sections of one frame's owners as one whole-frame section (kajo_hip_checkpoint_merge; pure host), which any handle of the same
+    scene and parameters restores its own pixels from, whatever its tile layout."""
+    blobs = [bytes(b) for b in blobs]
+    n = len(blobs)
+    if n < 1:
+        raise ValueError("no sections to merge")
+    keep = [C.create_string_buffer(b, len(b)) for b in blobs]
+    ptrs = (C.c_void_p * n)(*[C.cast(k, C.c_void_p) for k in keep])
+    sizes = (C.c_size_t * n)(*[len(b) for b in blobs])
+    written = C.c_size_t()
+    L = capi.lib()
+    capi.check(L.kajo_hip_checkpoint_merge(ptrs, sizes, n, None, 0, C.byref(written)))
+    out = C.create_string_buffer(written.value)
+    capi.check(L.kajo_hip_checkpoint_merge(ptrs, sizes, n, out, written.value, C.byref(written)))
+    return out.raw[:written.value]
+
+
 class HipRenderer:
     def __init__(self, scene: Scene, width: int, height: int, spp: int = 32, depth_limit: int = 8,
                  seed: int = 0o715517, strict: bool = False, exact: bool = False, counters: bool = False, device: int = 0,
@@ -151,6 +183,32 @@ class HipRenderer:
 
     def set_stream(self, stream_ptr: int):
         capi.check(self._L.kajo_hip_set_stream(self._h, C.c_void_p(stream_ptr)))
+
+    # -- checkpoints -----------------------------------------------------------------------
+    def checkpoint(self) -> bytes:
+        """The handle's whole accumulated state as one section (kajo_hip_checkpoint_save): a function of (scene, parameters, passes)
+        but for its last 16 bytes, the trailer. Waits."""
+        size = C.c_size_t()
+        capi.check(self._L.kajo_hip_checkpoint_bytes(self._h, C.byref(size)))
+        blob = C.create_string_buffer(size.value)
+        written = C.c_size_t()
+        capi.check(self._L.kajo_hip_checkpoint_save(self._h, blob, size.value, C.byref(written)))
+        return blob.raw[:written.value]
+
+    def restore(self, blob):
+        """Continue from a section of this handle's layout, or from a whole-frame section (kajo_hip_checkpoint_restore). Every later
+        pass and every reader gives what the uninterrupted handle gives. A refused section (KajoError) leaves the handle as it was."""
+        blob = bytes(blob)
+        capi.check(self._L.kajo_hip_checkpoint_restore(self._h, blob, len(blob)))
+        self.passes = checkpoint_info(blob)["passesDone"]
+        return self
+
+    def digest(self) -> dict:
+        """The 64-bit digests of the planes the handle keeps, by name (kajo_hip_digest): computed on the device, no read-back of the
+        planes. The digests of the owners of one frame add up, modulo 2^64, to the whole frame's."""
+        d = capi.KajoDigest()
+        capi.check(self._L.kajo_hip_digest(self._h, C.byref(d)))
+        return {capi.KAJO_CKPT_NAMES[k]: int(d.plane[k]) for k in range(1, capi.KAJO_CKPT_KINDS) if d.present >> k & 1}
 
     # -- outputs ---------------------------------------------------------------------------
     def radiance(self) -> np.ndarray:
