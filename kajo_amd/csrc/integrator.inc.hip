@@ -53,6 +53,11 @@
 #endif
 
 #define KDEV __device__ __forceinline__
+// in front of the two loops of trace()'s SIMPLE STRICT / EXACT walk: nothing, unless the including unit instantiates the walk with
+// compile-time counts and asks for straight-line code (kernel_exact_fixed.cpp)
+#ifndef KAJO_FIXED_UNROLL
+#define KAJO_FIXED_UNROLL
+#endif
 typedef __attribute__((address_space(3))) volatile uint32_t KajoLdsWord; // a word of LDS that other lanes of the wave write
 // A float4 of global memory behind a pointer that waited in two LDS words (renderBody GROUPS): the address space spelled out -- a
 // pointer made from an integer is generic, and stores through it would be flat_store instructions.
@@ -535,14 +540,19 @@ KDEV void gridWalk(const DSceneView& sc, const LdsScene& lds, F3 O, F3 d, float 
 // SIMPLE: the scene is known to have rigid planes and nothing but (centre, radius) spheres (launch.inc.hip picks the kernel): a small-scene
 // kernel instantiated with it carries one plane loop and one sphere loop (kernel_exact_simple.cpp); every other scene runs the kernels
 // that carry the general loops beside them.
-template <bool GRID, int GHOME = 0, bool LISTS_SCENE = false, bool SIMPLE = false>
+// NP, NS >= 0 (SIMPLE instances only): the scene has NP planes and NS spheres, known when the kernel was compiled (launch.inc.hip picks it
+// by the handle's counts, fixed_counts.h): the SIMPLE STRICT / EXACT walk is then straight-line code (KAJO_FIXED_UNROLL) -- no counter,
+// compare or branch per primitive, hit ids that are literals, record reads at constant offsets that can be issued ahead of their use.
+// The same operations on the same operands in the same order. -1: the counts are read at run time.
+template <bool GRID, int GHOME = 0, bool LISTS_SCENE = false, bool SIMPLE = false, int NP = -1, int NS = -1>
 KDEV Hit trace(const DSceneView& sc, const LdsScene& lds, F3 O, F3 d, bool hasRay = true)
 {
+    static_assert((NP < 0 && NS < 0) || (NP >= 0 && NS >= 0 && SIMPLE && KAJO_STRICT), "compile-time counts: the SIMPLE STRICT / EXACT walk only");
     float tMax = __builtin_inff(); // Ray.cpp:10-13; minDistance = 0
     int best = 0;
     float bestT0 = 0.0f;
 
-    const int np = sc.nPlanes;
+    const int np = NP >= 0 ? NP : sc.nPlanes;
 #if !KAJO_STRICT
     // FAST selection arithmetic. On gfx950 compares, selects and min/max issue at half the rate of
     // FMA/ADD/MUL/integer add (tools/valu_rate.hip), so the closest-hit bookkeeping is kept to one compare
@@ -577,6 +587,7 @@ KDEV Hit trace(const DSceneView& sc, const LdsScene& lds, F3 O, F3 d, bool hasRa
         // Every determinant within 2^-20 of 1 (all of the reference's data/ scenes: rotations and translations): t * det has the sign
         // of t -- a positive factor cannot make a product negative, and -0 stays -0, which `< 0` does not hold for either -- so
         // Raytracer.cpp:115's `t < ray.min` repeats :85-86's `t < 0` and is not asked again. The same t, the same t * det.
+        KAJO_FIXED_UNROLL
         for (int i = 0; i < np; i++) {
             const DFloat4 r = lds.planeRow[i];
             const float det = lds.planeDet[i];
@@ -606,7 +617,7 @@ KDEV Hit trace(const DSceneView& sc, const LdsScene& lds, F3 O, F3 d, bool hasRa
         best = ok ? i + 1 : best;
     }
 
-    const int ns = sc.nSpheres;
+    const int ns = NS >= 0 ? NS : sc.nSpheres;
     const float aT = dot(d, d); // a of every translated sphere (mat3(inverse) = identity)
 #if !KAJO_STRICT
     const float iaT = krcp(aT);
@@ -676,6 +687,7 @@ KDEV Hit trace(const DSceneView& sc, const LdsScene& lds, F3 O, F3 d, bool hasRa
         const float m4a = -4.0f * aT; // b^2 - (4a)c == b^2 + (-(4a))c: negation is exact
         float y = __builtin_amdgcn_rcpf(aT);
         y = __builtin_fmaf(__builtin_fmaf(-aT, y, 1.0f), y, y);
+        KAJO_FIXED_UNROLL
         for (int i = 0; i < ns; i++) { // Raytracer.cpp:21-72
             const DFloat4 s = lds.sphereHot[i];
             const F3 o = f3(O.x + s.x, O.y + s.y, O.z + s.z);
@@ -983,14 +995,15 @@ KDEV void sphereFrame(F3 n, F3& tg, F3& bn) // Raytracer.cpp:55-65
     bn = cross(n, tg);
 }
 
-template <bool ALLT = false>
+template <bool ALLT = false, int NP = -1>
 KDEV F3 hitNormal(const DSceneView& sc, const LdsScene& lds, const Hit& h, F3 O, F3 d)
 {
-    if (h.id <= sc.nPlanes) {
+    const int np = NP >= 0 ? NP : sc.nPlanes; // (NP: trace())
+    if (h.id <= np) {
         const DFloat4 n = lds.planeFrame[3 * (h.id - 1)];
         return f3(n.x, n.y, n.z);
     }
-    const int si = h.id - 1 - sc.nPlanes;
+    const int si = h.id - 1 - np;
     const uint32_t off = (ALLT || sc.allTranslated) ? (uint32_t)si : lds.sphereHotOffset[si];
     if (ALLT || !(off & KAJO_SPHERE_GENERAL)) {
 #if KAJO_STRICT
@@ -1309,18 +1322,21 @@ KDEV void stage16(DFloat4* dst, const void* src, int count)
 // COLD_LDS (small scenes): shading frames, sphere centres, materials and the light list are staged
 // into LDS next to the hot records and every sphere is tested. !COLD_LDS (large scenes): the cold
 // records are read from global memory (L2) and the spheres are reached through the uniform grid.
-template <bool COLD_LDS>
+// NP, NS >= 0: the scene's plane and sphere counts, known when the kernel was compiled (trace(): such a scene is a SIMPLE one, every
+// sphere one hot record) -- the arrays behind the hot records then lie at constant offsets.
+template <bool COLD_LDS, int NP = -1, int NS = -1>
 KDEV LdsScene stageToLds(const DSceneView& sc, unsigned char* ldsRaw)
 {
-    const int np = sc.nPlanes, ns = sc.nSpheres;
+    const int np = NP >= 0 ? NP : sc.nPlanes, ns = NS >= 0 ? NS : sc.nSpheres;
+    const int nSphereHot = NS >= 0 ? NS : sc.nSphereHot;
     // layout: [planeRow np x16][sphereHot nHot x16]{[planeFrame 3np x16][sphereCold ns x64]
     //         [material (np+ns) x96]}[planeDet np x4][sphereHotOffset ns x4][light nL x4] (pad to 16)
     //         [lightCold nL x64][lightEmission nL x16][lightPlaneSide nL*np x4 (pad to 16)][camera 8 x16]{[grid header 4 x16][grid cell starts][grid items]}
     DFloat4* ldsPlaneRow = reinterpret_cast<DFloat4*>(ldsRaw);
     DFloat4* ldsSphereHot = ldsPlaneRow + np;
-    DFloat4* cursor = ldsSphereHot + sc.nSphereHot;
+    DFloat4* cursor = ldsSphereHot + nSphereHot;
     stage16(ldsPlaneRow, sc.planeRow, np);
-    stage16(ldsSphereHot, sc.sphereHot, sc.nSphereHot);
+    stage16(ldsSphereHot, sc.sphereHot, nSphereHot);
     LdsScene lds;
 #ifdef KAJO_COUNT_SPHERE_TESTS
     lds.testCounter = nullptr;
@@ -1428,18 +1444,19 @@ KDEV LdsScene stageToLds(const DSceneView& sc, unsigned char* ldsRaw)
 // light's visibility lists (lightReached) instead of costing the lane a trip of its own through the grid: the light loop of a
 // vertex runs to its end in ONE trip, as Shader::sampleLights does (Shader.cpp:50-86), and every trip's walk carries camera and
 // extension rays only. Same draws, same tests, same sums in the same order: the buffer does not change by a bit.
-template <bool COLD_LDS, bool KAT, bool SPLIT = false, bool LISTS = false, bool ONE_LIGHT = false, int GHOME = 0, bool SIMPLE = false>
+// NP, NS >= 0: trace()'s compile-time counts.
+template <bool COLD_LDS, bool KAT, bool SPLIT = false, bool LISTS = false, bool ONE_LIGHT = false, int GHOME = 0, bool SIMPLE = false, int NP = -1, int NS = -1>
 KDEV void renderBody(const RenderArgs& args, unsigned char* ldsRaw)
 {
     const DSceneView& sc = args.scene;
-    const int np = sc.nPlanes;
+    const int np = NP >= 0 ? NP : sc.nPlanes;
 
     // ---- stage the scene into LDS (one copy per workgroup) ------------------------------------
 #ifdef KAJO_COUNT_SPHERE_TESTS
-    LdsScene lds = stageToLds<COLD_LDS>(sc, ldsRaw);
+    LdsScene lds = stageToLds<COLD_LDS, NP, NS>(sc, ldsRaw);
     lds.testCounter = args.counters ? args.counters + 29 : nullptr;
 #else
-    const LdsScene lds = stageToLds<COLD_LDS>(sc, ldsRaw);
+    const LdsScene lds = stageToLds<COLD_LDS, NP, NS>(sc, ldsRaw);
 #endif
     // GROUPS (FAST / EXACT, small scenes): the pixel's total takes the passes in groups of KAJO_GROUP_PASSES = 4 by their ABSOLUTE numbers
     // (passes 1-4, 5-8, ...; render_args.h): every group is summed from zero in pass order, the group sums are added to the total in
@@ -1820,7 +1837,7 @@ KDEV void renderBody(const RenderArgs& args, unsigned char* ldsRaw)
 
         KAJO_STAMP(0); // camera-ray block
         // ---- one ray per lane through the whole scene ------------------------------------------
-        const Hit hit = trace<!COLD_LDS, GHOME, LISTS, SIMPLE>(sc, lds, O, d, mode == MODE_EXTEND || mode == MODE_SHADOW);
+        const Hit hit = trace<!COLD_LDS, GHOME, LISTS, SIMPLE, NP, NS>(sc, lds, O, d, mode == MODE_EXTEND || mode == MODE_SHADOW);
         KAJO_STAMP(1); // traversal
         if (counting) {
             ctrTraversals += __builtin_popcountll(activeMask);
@@ -1874,7 +1891,7 @@ KDEV void renderBody(const RenderArgs& args, unsigned char* ldsRaw)
                 ctrVertices += 1; // (unconditionally: an inline constant, where `counting` as an addend would be one more live register)
                 const F3 view = d;
                 vP = O + d * hit.t; // Raytracer.cpp:134-135
-                vN = hitNormal<LISTS || SIMPLE>(sc, lds, hit, O, d);
+                vN = hitNormal<LISTS || SIMPLE, NP>(sc, lds, hit, O, d);
                 vId = hit.id;
                 vE = collectEmission ? f3(m1.x, m1.y, m1.z) : f3(0.0f, 0.0f, 0.0f); // Shader.cpp:121
                 float pc;
@@ -2392,7 +2409,7 @@ KDEV void renderBody(const RenderArgs& args, unsigned char* ldsRaw)
                     // with three lights (profiles/r04_inline_shadow.txt). The FAST loop does not have the registers for it: at
                     // five waves per SIMD it spills 47 (-26 %), at four it loses the fifth wave (-10 %).
                     ctrShadow += 1;
-                    const Hit sh = trace<false, 0, false, SIMPLE>(sc, lds, O, l);
+                    const Hit sh = trace<false, 0, false, SIMPLE, NP, NS>(sc, lds, O, l);
                     if (sh.id == np + 1 + si) {
 #if KAJO_RSTRICT
                         vLd = vLd + pendContrib;
@@ -2612,7 +2629,18 @@ KDEV void renderBody(const RenderArgs& args, unsigned char* ldsRaw)
 
 } // namespace
 
-#ifdef KAJO_SIMPLE_KERNEL_NAME
+#if defined(KAJO_FIXED_KERNELS)
+// A unit of the SIMPLE kernel's instances with compile-time plane and sphere counts (kernel_exact_fixed.cpp): KAJO_FIXED_KERNELS(X) lists
+// them as X(planes, spheres), fixed_counts.h names them. launch.inc.hip sends a SIMPLE scene of such counts here.
+#define KAJO_FIXED_KERNEL(P, S) \
+    extern "C" __global__ void __launch_bounds__(256, KAJO_WAVES_PER_SIMD) KAJO_FIXED_NAME(P, S)(const RenderArgs args) \
+    { \
+        extern __shared__ __attribute__((aligned(16))) unsigned char ldsRaw[]; \
+        renderBody<true, false, false, false, true, 0, true, P, S>(args, ldsRaw); \
+    }
+KAJO_FIXED_KERNELS(KAJO_FIXED_KERNEL)
+#undef KAJO_FIXED_KERNEL
+#elif defined(KAJO_SIMPLE_KERNEL_NAME)
 // A unit of one kernel (kernel_exact_simple.cpp): the one-light small-scene kernel for scenes of rigid planes and (centre, radius) spheres
 // (trace SIMPLE), without the loops for general records. launch.inc.hip sends such scenes here; the kernels below, in the build's own unit,
 // stay what they were and serve every other scene.
@@ -2773,4 +2801,4 @@ extern "C" __global__ void __launch_bounds__(256) KAJO_RESOLVE_TILES_NAME(const 
     dst[(size_t)y * map.W + x] = ((uint32_t)al << 24) | ((uint32_t)out[0] << 16) | ((uint32_t)out[1] << 8) | (uint32_t)out[2];
 }
 #endif
-#endif // KAJO_SIMPLE_KERNEL_NAME
+#endif // KAJO_FIXED_KERNELS, KAJO_SIMPLE_KERNEL_NAME

@@ -11,6 +11,7 @@
 #endif
 #define KAJO_KERNEL_NAME kajo_render_exact
 #define KAJO_SIMPLE_LAUNCH kajo_render_exact_simple // (launch.inc.hip: scenes of rigid planes and (centre, radius) spheres; kernel_exact_simple.cpp)
+#define KAJO_FIXED_LAUNCH kajo_render_exact_fixed // (... those of them whose counts are in fixed_counts.h: kernel_exact_fixed.cpp)
 #define KAJO_KERNEL_NAME_LIGHTS kajo_render_exact_lights
 #define KAJO_KERNEL_NAME_BIG kajo_render_exact_big
 #define KAJO_KERNEL_NAME_BIGLIST kajo_render_exact_biglist

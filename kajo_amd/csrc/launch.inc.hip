@@ -7,6 +7,12 @@
 // the build's one-light small-scene kernel without the loops for general records, in a unit of its own (kernel_exact_simple.cpp)
 extern "C" int KAJO_CAT(KAJO_SIMPLE_LAUNCH, _launch)(const RenderArgs* args, unsigned grid, unsigned block, size_t ldsBytes, void* stream);
 extern "C" int KAJO_CAT(KAJO_SIMPLE_LAUNCH, _set_lds)(size_t ldsBytes);
+#ifdef KAJO_FIXED_LAUNCH
+// ... and its instances for scenes whose plane and sphere counts are in fixed_counts.h's table, in another (kernel_exact_fixed.cpp)
+#include "fixed_counts.h"
+extern "C" int KAJO_CAT(KAJO_FIXED_LAUNCH, _launch)(const RenderArgs* args, unsigned grid, unsigned block, size_t ldsBytes, void* stream);
+extern "C" int KAJO_CAT(KAJO_FIXED_LAUNCH, _set_lds)(size_t ldsBytes);
+#endif
 #endif
 
 // coldInLds: 1 = whole scene staged in LDS (KAJO_KERNEL_NAME; FAST: its one-light instance for scenes of one light, 2 = never that one),
@@ -21,9 +27,14 @@ extern "C" int KAJO_CAT(KAJO_KERNEL_NAME, _launch)(const RenderArgs* args, int c
 #endif
 #ifdef KAJO_SIMPLE_LAUNCH
     // a one-light scene of rigid planes and (centre, radius) spheres: the kernel that carries no other loops (integrator.inc.hip trace SIMPLE)
-    if (coldInLds && args->scene.allTranslated && args->scene.planesRigid)
+    if (coldInLds && args->scene.allTranslated && args->scene.planesRigid) {
+#ifdef KAJO_FIXED_LAUNCH
+        // ... of counts the build has an instance for: the same kernel with the walk compiled for them (fixed_counts.h)
+        if (kajoFixedKernelName(args->scene.nPlanes, args->scene.nSpheres))
+            return KAJO_CAT(KAJO_FIXED_LAUNCH, _launch)(args, grid, block, ldsBytes, stream);
+#endif
         return KAJO_CAT(KAJO_SIMPLE_LAUNCH, _launch)(args, grid, block, ldsBytes, stream);
-    else
+    } else
 #endif
     if (coldInLds)
         hipLaunchKernelGGL(KAJO_KERNEL_NAME, dim3(grid), dim3(block), ldsBytes, static_cast<hipStream_t>(stream), *args);
@@ -71,6 +82,10 @@ extern "C" int KAJO_CAT(KAJO_KERNEL_NAME, _set_lds)(int coldInLds, size_t ldsByt
 #ifdef KAJO_SIMPLE_LAUNCH
         if (e == hipSuccess)
             e = (hipError_t)KAJO_CAT(KAJO_SIMPLE_LAUNCH, _set_lds)(ldsBytes);
+#ifdef KAJO_FIXED_LAUNCH
+        if (e == hipSuccess)
+            e = (hipError_t)KAJO_CAT(KAJO_FIXED_LAUNCH, _set_lds)(ldsBytes);
+#endif
 #endif
 #ifdef KAJO_KERNEL_NAME_LIGHTS
         if (e == hipSuccess)

@@ -1,0 +1,181 @@
+"""The EXACT build's one-light small-scene kernel instances with compile-time plane and sphere counts (kajo_amd/csrc/kernel_exact_fixed.cpp,
+fixed_counts.h; integrator.inc.hip trace NP / NS), checked without a GPU: what the compiler made of each instance -- the budgets of
+kajo_render_exact_simple (tests/test_simple_kernel_resources_cpu.py), whose arithmetic they repeat, but for the static instruction count,
+which unrolling raises and which is pinned where it was measured so that drift shows --, that the Makefile compiles the unit with
+kernel_exact.hip's flags and links it, that fixed_counts.h's table, the unit's kernels and the launcher's choice agree one to one, and which
+kernel tools/host_san.cpp `plan kernel` names for scenes with and without a table entry. (That no kernel from before moved is
+tests/test_noise_cpu.py's and tests/test_adaptive_cpu.py's digest comparison, and the simple kernel's own budgets its own test.)"""
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "kajo_amd", "csrc")
+# static vector instructions per instance as measured (the simple kernel: 1959; the walk of 6 planes and 5 spheres written out: 16
+# correctly rounded divisions where the loops held 3), held within 3 % either way
+VALU_MEASURED = {(6, 5): 2258}
+VALU_SLACK = 0.03
+
+
+def table():
+    """fixed_counts.h's pairs, from its text: the X(planes, spheres) entries of KAJO_FIXED_COUNTS"""
+    text = open(os.path.join(CSRC, "fixed_counts.h")).read()
+    body = re.search(r"^#define KAJO_FIXED_COUNTS\(X\)(.*)$", text, re.M).group(1)
+    pairs = [(int(p), int(s)) for p, s in re.findall(r"X\((\d+), (\d+)\)", body)]
+    assert re.sub(r"X\(\d+, \d+\)", "", body).strip() == "", body
+    return pairs
+
+
+def name_of(pair):
+    return "kajo_render_exact_p%ds%d" % pair
+
+
+def _make_line(target_src):
+    plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, "all"], capture_output=True, text=True, check=True).stdout
+    return plan, next(l for l in plan.splitlines() if l.startswith("hipcc") and target_src in l and " -c " in l)
+
+
+def _need_tools():
+    if shutil.which("hipcc") is None or shutil.which("make") is None:
+        pytest.skip("hipcc / make not available")
+
+
+@pytest.fixture(scope="module")
+def compiled():
+    """(resource remarks per kernel, device assembly) of the unit, by the Makefile's own command"""
+    _need_tools()
+    cmd = _make_line("kernel_exact_fixed.cpp")[1].split()
+    tmp = tempfile.mkdtemp(prefix="kajo_fixed_")
+    asm = os.path.join(tmp, "k.s")
+    i = cmd.index("-c")
+    cmd = cmd[:i] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + cmd[i + 1:]
+    cmd[cmd.index("-o") + 1] = asm
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    res, name = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"remark: Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            res[name] = {}
+            continue
+        m = re.search(r"remark:\s+(VGPRs|SGPRs Spill|VGPRs Spill|Occupancy \[waves/SIMD\]|ScratchSize \[bytes/lane\]): (\d+)", line)
+        if m and name:
+            res[name][m.group(1).split(" [")[0]] = int(m.group(2))
+    text = open(asm).read()
+    shutil.rmtree(tmp, ignore_errors=True)
+    return res, text
+
+
+def test_the_table_is_small_and_holds_the_benchmarked_scene(scenes):
+    pairs = table()
+    assert 1 <= len(pairs) <= 3 and len(set(pairs)) == len(pairs) and sorted(VALU_MEASURED) == sorted(pairs)
+    # taken from the golden set's simple one-light scenes (tests/test_one_light_routing_cpu.py SIMPLE_GOLDEN), all of them one room
+    golden = {(scenes[k].n_planes, scenes[k].n_spheres) for k in ("spheres_a1", "spheres_a43", "spheres_a169", "test_a1")}
+    assert golden == {(6, 5)} and golden <= set(pairs)
+
+
+def test_the_unit_holds_exactly_the_tables_kernels_within_the_budgets(compiled):
+    res, asm = compiled
+    pairs = table()
+    assert sorted(res) == sorted(name_of(p) for p in pairs), sorted(res)
+    for pair in pairs:
+        kernel = name_of(pair)
+        r = res[kernel]
+        assert r["Occupancy"] == 5 and r["VGPRs"] <= 96 and r["VGPRs Spill"] == 0 and r["ScratchSize"] == 0, (kernel, r)
+        body = asm[asm.index("\n" + kernel + ":"):]
+        body = body[:body.index("s_endpgm")]
+        assert not re.search(r"\n\s+flat_(load|store|atomic)", body) and not re.search(r"\n\s+scratch_", body), kernel
+        assert "v_div_scale_f32" not in body and "v_div_fmas_f32" not in body and "v_div_fixup_f32" in body, kernel
+        n = len(re.findall(r"\n\s+v_\w+", body))
+        print("%s: %d static VALU instructions, %d v_div_fixup_f32" % (kernel, n, body.count("v_div_fixup_f32")))
+        want = VALU_MEASURED[pair]
+        assert (1 - VALU_SLACK) * want <= n <= (1 + VALU_SLACK) * want, "%s: %d VALU instructions, measured %d" % (kernel, n, want)
+
+
+def test_the_walk_is_straight_line_code(compiled):
+    """One correctly rounded division per plane and two per sphere are written out between the kernel's label and its end -- the loops held
+    one and two -- beside the eight of the rest of the kernel (camera block 1, vertex and shadow result 3, light and BSDF 4: the blocks of
+    tools/isa_blocks.sh, the same eight in kajo_render_exact_simple)."""
+    _, asm = compiled
+    elsewhere = 8
+    for p, s in table():
+        kernel = name_of((p, s))
+        body = asm[asm.index("\n" + kernel + ":"):]
+        body = body[:body.index("s_endpgm")]
+        assert body.count("v_div_fixup_f32") == elsewhere + p + 2 * s, (kernel, body.count("v_div_fixup_f32"))
+
+
+def test_the_makefile_compiles_it_with_the_exact_units_flags_and_links_it():
+    _need_tools()
+    plan, fixed = _make_line("kernel_exact_fixed.cpp")
+    strip = lambda l, src, obj: [w for w in l.split() if w not in ("-x", "hip") and not w.endswith(src) and not w.endswith(obj)]
+    exact = next(l for l in plan.splitlines() if l.startswith("hipcc") and l.rstrip().split()[-3].endswith("kernel_exact.hip"))
+    assert strip(exact, "kernel_exact.hip", "kernel_exact.o") == strip(fixed, "kernel_exact_fixed.cpp", "kernel_exact_fixed.o")
+    assert "-ffp-contract=off" in fixed.split()
+    link = next(l for l in plan.splitlines() if l.startswith("hipcc") and " -shared " in l and l.split()[l.split().index("-o") + 1].endswith("libkajo_hip.so"))
+    assert any(w.endswith("kernel_exact_fixed.o") for w in link.split()) and any(w.endswith("kernel_exact_simple.o") for w in link.split())
+    # the launcher of the EXACT unit, and of no other, is told of it
+    for unit, told in (("kernel_exact.hip", True), ("kernel_strict.hip", False), ("kernel_fast.hip", False)):
+        assert ("#define KAJO_FIXED_LAUNCH kajo_render_exact_fixed" in open(os.path.join(CSRC, unit)).read()) == told, unit
+
+
+@pytest.fixture(scope="module")
+def kernel_name(tmp_path_factory):
+    """kernel_name(scene) -> what `host_san plan kernel` prints for it"""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    d = tmp_path_factory.mktemp("fixed_routing")
+    exe = str(d / "host_plan")
+    src = [os.path.join(ROOT, "tools", "host_san.cpp"), os.path.join(CSRC, "stage.cpp"), os.path.join(ROOT, "kajo_amd", "host", "scene", "SceneLoader.cpp")]
+    r = subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
+                        "-I" + os.path.join(ROOT, "kajo_amd", "host"), *src, "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+
+    def run(sc):
+        pod = str(d / "scene.pod")
+        sc.write_pod(pod)
+        line = subprocess.run([exe, "plan", "kernel", pod], capture_output=True, text=True, check=True).stdout.strip()
+        got = dict(kv.split("=") for kv in line.split(": ", 1)[1].split())
+        assert (int(got["nPlanes"]), int(got["nSpheres"]), int(got["nLights"])) == (sc.n_planes, sc.n_spheres, sc.n_lights), line
+        return got["kernel"]
+
+    return run
+
+
+def test_which_scenes_reach_a_fixed_instance(kernel_name, scenes):
+    from fixed_instance_scenes import far_sphere_twin, without_a_sphere
+    from one_light_scenes import scaled_plane_twin, turned_twin
+    pairs = table()
+    for k in ("spheres_a1", "spheres_a43", "spheres_a169", "test_a1"):
+        assert kernel_name(scenes[k]) == "kajo_render_exact_p6s5", k
+    base = scenes["spheres_a169"]
+    # one sphere more, one sphere fewer: simple scenes still, of counts without an entry
+    more, fewer = far_sphere_twin(base)[0], without_a_sphere(base)
+    assert (more.n_planes, more.n_spheres) == (6, 6) and (fewer.n_planes, fewer.n_spheres) == (6, 4)
+    assert (6, 6) not in pairs and (6, 4) not in pairs
+    assert kernel_name(more) == "kajo_render_exact_simple" and kernel_name(fewer) == "kajo_render_exact_simple"
+    # the counts alone do not send a scene there: a general record or a scaled plane goes where it went, whatever it counts
+    turned = turned_twin(without_a_sphere(base))[0]
+    assert (turned.n_planes, turned.n_spheres) == (6, 5) and kernel_name(turned) == "kajo_render_exact"
+    assert kernel_name(scaled_plane_twin(base)[0]) == "kajo_render_exact"
+    # ... nor do they for a scene of several lights
+    assert kernel_name(scenes["caustics_a169"]) == "kajo_render_exact_lights"
+
+
+def test_the_launcher_picks_by_the_function_the_printout_calls():
+    """launch.inc.hip asks fixed_counts.h's kajoFixedKernelName inside the simple scenes' branch, before the simple kernel's launch; the unit's
+    launcher and its LDS opt-in are stamped from the same table"""
+    text = open(os.path.join(CSRC, "launch.inc.hip")).read()
+    branch = text[text.index("args->scene.allTranslated && args->scene.planesRigid"):]
+    pick, simple = branch.index("kajoFixedKernelName(args->scene.nPlanes, args->scene.nSpheres)"), branch.index("KAJO_CAT(KAJO_SIMPLE_LAUNCH, _launch)(args")
+    assert 0 < pick < simple
+    unit = open(os.path.join(CSRC, "kernel_exact_fixed.cpp")).read()
+    assert unit.count("KAJO_FIXED_COUNTS(") == 2 and "#define KAJO_FIXED_KERNELS KAJO_FIXED_COUNTS" in unit
+    # (the printed name and the kernel's symbol are spelled from the same two numbers: name_of() above restates both)
+    header = open(os.path.join(CSRC, "fixed_counts.h")).read()
+    assert 'return "kajo_render_exact_p" #P "s" #S;' in header and "#define KAJO_FIXED_NAME(P, S) kajo_render_exact_p##P##s##S" in header

@@ -17,6 +17,8 @@
 //                                        numerics build, the grid's cells per axis against the cells it wanted, the visibility lists' bins
 //                                        and their longest row of 16-bit offsets; and the staged scene's allTranslated, planesRigid and
 //                                        roomClosed beside nLights (tests/test_one_light_routing_cpu.py: which small-scene kernel it runs)
+//   host_san plan kernel a.pod ...       the render kernel an EXACT handle of the scene launches, by name: launch.inc.hip's choice with
+//                                        fixed_counts.h's table (tests/test_fixed_kernel_cpu.py, tests/test_hip_fixed_instance.py)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -27,6 +29,7 @@
 
 #include "kajo_hip.h"
 #include "kajo_scene.h"
+#include "fixed_counts.h"
 #include "launch_order.h"
 #include "launch_plan.h"
 #include "render_args.h"
@@ -318,10 +321,30 @@ static int planCuts(int argc, char** argv)
     return 0;
 }
 
+// Which render kernel an EXACT handle of each scene file launches when the whole scene is staged in LDS and no flag says otherwise:
+// launch.inc.hip's choice restated over the staged scene, its last step through the function the launcher itself calls
+// (fixed_counts.h kajoFixedKernelName). One line "<file>: nPlanes=.. nSpheres=.. nLights=.. coldInLds=.. kernel=<name>".
+static int planKernel(int argc, char** argv)
+{
+    for (int a = 0; a < argc; a++) {
+        Pod pod;
+        if (int rc = pod.read(argv[a])) return rc;
+        kajo::StagedScene st;
+        kajo::stageScene(pod.sc, st, 48, true);
+        const KajoLdsPlan p = kajoLdsPlan(st, Numerics::Exact);
+        const char* fixed = kajoFixedKernelName(st.nPlanes, st.nSpheres);
+        const char* name = !p.coldInLds ? "large-scene" : st.light.size() != 1 ? "kajo_render_exact_lights"
+                         : !(st.allTranslated && st.planesRigid) ? "kajo_render_exact" : fixed ? fixed : "kajo_render_exact_simple";
+        printf("%s: nPlanes=%d nSpheres=%d nLights=%zu coldInLds=%d kernel=%s\n", argv[a], st.nPlanes, st.nSpheres, st.light.size(), p.coldInLds, name);
+    }
+    return 0;
+}
+
 static int plan(int argc, char** argv)
 {
     if (argc < 1) return 2;
     const std::string what = argv[0];
+    if (what == "kernel") return planKernel(argc - 1, argv + 1);
     if (what == "lds") return planLds(argc - 1, argv + 1);
     if (what == "cuts") return planCuts(argc - 1, argv + 1);
     if (what == "shape" && argc - 1 > 2) return planShapeOf(argc - 1, argv + 1);
