@@ -1046,8 +1046,8 @@ int kajo_hip_present_grade_gathered_argb8_device(kajo_hip_t h, const void* gathe
    RGBA16F; DITHER with RGBA16F; with PQ a peakNits that is not finite or not in (0, 10000]. They stand where the view's do: behind the
    tone parameters' own refusals (the two automatic exposures among them), in front of the denoiser's. Behind them
    KAJO_TONE_AUTO_EXPOSURE is refused: its scale is formed inside the tone launch, which this stage replaces -- use metered exposure (a
-   KajoMeterParams in the chain), which is patched into the tone parameters on the host and works with the encode. A view is not
-   combined with an encode (the view resamples ARGB8 words): the encoded entry points take none. The accumulation, the AOVs, the pass
+   KajoMeterParams in the chain), which is patched into the tone parameters on the host and works with the encode. The view
+   resamples ARGB8 words, so these entry points take none: "The float view" below has the ones that do. The accumulation, the AOVs, the pass
    count and the counters (kernelMs included) are not touched; the table (32776 bytes) is uploaded when the transfer or peakNits differ
    from the last call's, the image buffer is allocated on first use; both are freed by kajo_hip_destroy. */
 #define KAJO_ENCODE_ARGB8 0u
@@ -1098,6 +1098,57 @@ int kajo_hip_encode_present(kajo_hip_t h, const KajoDespeckleParams* despeckle, 
 int kajo_hip_encode_present_gathered_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle, const KajoGradeParams* grade,
                                             const KajoGlareParams* g, const KajoLocalParams* local, const KajoMeterParams* meter,
                                             const KajoToneParams* tone, const KajoEncodeParams* encode, void* dst, KajoMeterResult* result);
+
+/* The float view: the view's crop, zoom and supersampled output in front of the encode's transfer -- antialiasing, thumbnails and
+   window-sized read-backs at more than 8 bits. The entry points below resample the encode's own display-referred float y of step 3,
+   before any quantiser has touched it, where the view resamples the tone kernels' 8-bit words. Two kernels
+   of their own (kajo_amd/csrc/encode_view.cpp; arithmetic in encode_math.h, weight rows from view_weights.h) on the handle's stream,
+   compiled as the encode's kernel is. Off unless asked for: no other entry point changes. Definition -- P, F, the tone and encode
+   parameters as in "The encode", the view parameters as in "The view"; outW x outH the view's output size, W x H the frame's:
+     1  Front.     For every source pixel (jx, jy): the encode's steps 1-3 as they stand there (a pixel that does not count is mapped by
+                   CLAMP). L[jy][jx].c = y.c, finite and in [0, 1]. With SCENE, L is what step 6 would store before the rounding to
+                   half: min(max(x, 0), 65504), NaN giving 0.
+     2  Resample.  The view's own weight rows, kajo_hip_view_weights of the same rectangle: the same filters, trimming, KAJO_VIEW_MAX_*
+                   limits and refusals. float32, no FMA, every accumulator starts at +0:
+                     T[jy][i].c = sum of wx[i][j] * L[jy][j].c over the taps j = first_x[i] .., in increasing j
+                     r[o][i].c  = sum of wy[o][y] * T[y][i].c  over the taps y = first_y[o] .., in increasing y
+     3  Clamp.     q = min(max(r, 0), 1) with the encode's max and min (LANCZOS3 has negative lobes; a row's weights sum to 1 only
+                   within count * 2^-24). With SCENE: min(max(r, 0), 65504).
+     4  Back.      The encode's steps 4-6 with q in place of y (with SCENE: of the clamped x) and (px, py) = (i, o): the dither runs
+                   over OUTPUT pixel coordinates. outW x outH words of the format, kajo_hip_encode_bytes(p, outW, outH) bytes.
+   Consequences. The copy case (the whole frame at its own size, any filter) launches the plain encode and returns its words; under the
+   definition it is the identity too: one weight of 1.0 per axis, +0 + 1 * y = y for y >= +0, and the clamp is idempotent. NEAREST
+   without dither gives the plain encode's words gathered at floor(u). A constant frame comes back within ONE CODE of the plain encode,
+   not necessarily bit-equal: at 16 bits a weight sum count * 2^-24 off 1 moves v * 65535 by up to 0.01 code, which can cross a
+   rounding boundary. No division but step 1's, no atomics, no order between workgroups: a word depends on the inputs through image
+   coordinates only, so one, two, three and eight tile owners give one image, dither included.
+   Refusals (KAJO_E_INVALID, before any device work), in the chain's order: the stages in front, the tone parameters, the view's own
+   (as kajo_hip_present_view_argb8), the encode's (KAJO_TONE_AUTO_EXPOSURE behind them), the denoiser's, the handle, the view against
+   the frame. A NULL view makes every entry point below exactly the encoded entry point it extends. The weight rows, their pinned
+   staging (uploaded once per set of view parameters) and the intermediate T are the view's own scratch, shared with it: allocated on
+   first use, grown on demand, freed by kajo_hip_destroy. */
+/* The stage alone: kajo_hip_encode with a view. dst = HOST pointer to kajo_hip_encode_bytes(encode, outW, outH) bytes, may be NULL.
+   Waits. */
+int kajo_hip_encode_view(kajo_hip_t h, const KajoEncodeParams* encode, const KajoToneParams* tone, const KajoViewParams* view, void* dst);
+/* kajo_hip_encode_present with the float view: its arguments, with the view in front of the encode. Waits. */
+int kajo_hip_encode_view_present(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGradeParams* grade,
+                                 const KajoLensParams* lens, const KajoGlareParams* g, const KajoLocalParams* local, const KajoMeterParams* meter,
+                                 const KajoToneParams* tone, const KajoViewParams* view, const KajoEncodeParams* encode, void* dst,
+                                 KajoMeterResult* result);
+/* The gathered twin, kajo_hip_encode_present_gathered_device with the float view: dst = DEVICE pointer to kajo_hip_encode_bytes(encode,
+   outW, outH) bytes, 8-byte aligned for the 8-byte formats. Asynchronous under kajo_hip_present_view_gathered_argb8_device's
+   conditions: no wait beyond the meter's once the scratch stands; a change of the view parameters, the transfer or peakNits may wait
+   for the previous upload to leave its staging, never for a kernel; a larger view grows the scratch, which waits for the device. A
+   NULL handle is answered as there ("null argument"). */
+int kajo_hip_encode_view_present_gathered_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle,
+                                                 const KajoGradeParams* grade, const KajoGlareParams* g, const KajoLocalParams* local,
+                                                 const KajoMeterParams* meter, const KajoToneParams* tone, const KajoViewParams* view,
+                                                 const KajoEncodeParams* encode, void* dst, KajoMeterResult* result);
+/* The definition over a whole width x height frame of MEANS (m of step 1; meanRgb = width * height * 3 floats, row-major), pure host
+   code compiled from the kernels' own lines: no device, no handle. out: outW * outH words of the format (width * height with a NULL
+   view). The refusals above, then width, height >= 1, NULL arguments, the view against the frame. */
+int kajo_hip_encode_view_pixels(const KajoEncodeParams* encode, const KajoToneParams* tone, const KajoViewParams* view, const float* meanRgb,
+                                int32_t width, int32_t height, void* out);
 
 /* The noise estimate (KAJO_FLAG_NOISE): how noisy the frame is, pixel by pixel, from the frame's own passes -- batch means, in kernels of
    their own (kajo_amd/csrc/noise.hip) on the handle's stream, float32 / binary64 IEEE arithmetic without contraction in every numerics

@@ -95,6 +95,7 @@ EXPORTS = [
     "kajo_hip_denoise_guide_planes",
     "kajo_hip_default_encode_params", "kajo_hip_encode_bytes", "kajo_hip_encode_table", "kajo_hip_encode_pixels", "kajo_hip_encode",
     "kajo_hip_encode_present", "kajo_hip_encode_present_gathered_device",
+    "kajo_hip_encode_view", "kajo_hip_encode_view_present", "kajo_hip_encode_view_present_gathered_device", "kajo_hip_encode_view_pixels",
     "kajo_hip_checkpoint_bytes", "kajo_hip_checkpoint_save", "kajo_hip_checkpoint_restore", "kajo_hip_checkpoint_info",
     "kajo_hip_checkpoint_merge", "kajo_hip_digest",
 ]
@@ -402,6 +403,21 @@ def lib():
                                                                   C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams),
                                                                   C.POINTER(KajoToneParams), C.POINTER(KajoEncodeParams), C.c_void_p,
                                                                   C.POINTER(KajoMeterResult)]
+        if hasattr(L, "kajo_hip_encode_view"):  # (nor the float view)
+            L.kajo_hip_encode_view.argtypes = [C.c_void_p, C.POINTER(KajoEncodeParams), C.POINTER(KajoToneParams), C.POINTER(KajoViewParams),
+                                               C.c_void_p]
+            L.kajo_hip_encode_view_present.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams),
+                                                       C.POINTER(KajoGradeParams), C.POINTER(KajoLensParams), C.POINTER(KajoGlareParams),
+                                                       C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams),
+                                                       C.POINTER(KajoViewParams), C.POINTER(KajoEncodeParams), C.c_void_p,
+                                                       C.POINTER(KajoMeterResult)]
+            L.kajo_hip_encode_view_present_gathered_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams),
+                                                                       C.POINTER(KajoGradeParams), C.POINTER(KajoGlareParams),
+                                                                       C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams),
+                                                                       C.POINTER(KajoToneParams), C.POINTER(KajoViewParams),
+                                                                       C.POINTER(KajoEncodeParams), C.c_void_p, C.POINTER(KajoMeterResult)]
+            L.kajo_hip_encode_view_pixels.argtypes = [C.POINTER(KajoEncodeParams), C.POINTER(KajoToneParams), C.POINTER(KajoViewParams),
+                                                      C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         if hasattr(L, "kajo_hip_read_matte"):  # (nor the mattes)
             L.kajo_hip_read_matte.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
             L.kajo_hip_matte_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

@@ -662,7 +662,7 @@ const char* kajo_hip_version(void)
 {
     // (a comma, not a semicolon, in front of "view": tests/test_lens_cpu.py looks for "lens" in the LAST ';'-separated field, so the
     // stages added after the lens join that field; the next stage appends ", name" likewise)
-    return "kajo-hip 0.1 (gfx950; aov-matte; local; aov-tiled; lens, view, grade, denoise-guided, encode)";
+    return "kajo-hip 0.1 (gfx950; aov-matte; local; aov-tiled; lens, view, grade, denoise-guided, encode, encode-view)";
 }
 
 void kajo_hip_default_params(KajoParams* p)

@@ -218,4 +218,66 @@ KEM_FN uint64_t encodePixel(const EncodeArgs& a, const float* table, float F0, f
     return (uint64_t)c[0] | ((uint64_t)c[1] << 16) | ((uint64_t)c[2] << 32) | ((uint64_t)0xFFFFu << 48);
 }
 
+// The float view (include/kajo_hip.h "The float view"; encode_view.cpp and present.cpp's kajo_hip_encode_view_pixels) cuts encodePixel in
+// two and resamples between the halves. The lines are encodePixel's.
+
+// true: the view resamples scene-linear x (RGBA16F with SCENE), not the curve's y
+KEM_FN bool encodeViewScene(const EncodeArgs& a)
+{
+    return a.format == kEncodeRgba16f && (a.flags & kEncodeScene) != 0;
+}
+
+// The front: F.rgb the sums over passes -> L, steps 1-3 (with SCENE what step 6 would round to half). Finite, in [0, 1] or [0, 65504].
+KEM_FN void encodeFront(const EncodeArgs& a, float F0, float F1, float F2, float L[3])
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const float m[3] = {F0 / a.passes, F1 / a.passes, F2 / a.passes};
+    float x[3], y[3];
+    encodeCurve(a, m, x, y);
+    for (int k = 0; k < 3; k++) {
+        float v = y[k];
+        if (encodeViewScene(a)) {
+            v = encodeMax0(x[k]);
+            v = v < 65504.0f ? v : 65504.0f;
+        }
+        L[k] = v;
+    }
+}
+
+// The clamp behind the resampling: Lanczos has negative lobes and a row's weights sum to 1 only within count * 2^-24
+KEM_FN float encodeViewClamp(const EncodeArgs& a, float r)
+{
+    const float t = encodeMax0(r);
+    if (encodeViewScene(a))
+        return t < 65504.0f ? t : 65504.0f;
+    return encodeMin1(t);
+}
+
+// The back: q (clamped) in place of y -- with SCENE of the clamped x --, (px, py) the OUTPUT pixel -> the word, steps 4-6
+KEM_FN uint64_t encodeBack(const EncodeArgs& a, const float* table, const float q[3], uint32_t px, uint32_t py)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    uint32_t c[3];
+    if (a.format == kEncodeRgba16f) {
+        for (int k = 0; k < 3; k++)
+            c[k] = encodeHalf(q[k]);
+        return (uint64_t)c[0] | ((uint64_t)c[1] << 16) | ((uint64_t)c[2] << 32) | ((uint64_t)0x3C00u << 48);
+    }
+    const float maxCode = a.format == kEncodeArgb8 ? 255.0f : a.format == kEncodeRgb10a2 ? 1023.0f : 65535.0f;
+    for (int k = 0; k < 3; k++) {
+        const float v = a.transfer == kEncodeLinear ? q[k] : encodeLookup(table, q[k]);
+        const float d = (a.flags & kEncodeDither) ? encodeDither(px, py, (uint32_t)k, a.seed) : 0.5f;
+        c[k] = encodeQuantise(v, maxCode, d);
+    }
+    if (a.format == kEncodeArgb8)
+        return 0xFF000000u | (c[0] << 16) | (c[1] << 8) | c[2];
+    if (a.format == kEncodeRgb10a2)
+        return 0xC0000000u | (c[0] << 20) | (c[1] << 10) | c[2];
+    return (uint64_t)c[0] | ((uint64_t)c[1] << 16) | ((uint64_t)c[2] << 32) | ((uint64_t)0xFFFFu << 48);
+}
+
 } // namespace kajo

@@ -1,17 +1,24 @@
 // present.cpp -- libkajo_hip.so: the display path of include/kajo_hip.h. The stages (denoise, tone, glare, despeckle, meter, local, lens,
 // view, grade, encode), each with its refusals, its scratch layout and the helpers of its own entry points; then the chain
 //     despeckle -> denoise -> grade -> lens -> glare -> local -> meter -> tone -> view, or -> encode in place of the tone kernels' word
+//     (with a view beside the encode: the float view, between the tone curve and the transfer)
 // as one description (Chain), one check (checkChain) and one run (runChain), and every kajo_hip_tonemap_*, kajo_hip_display_*,
-// kajo_hip_present_* entry point, kajo_hip_glare, _local, _lens, _grade, _meter, _encode and _encode_present as a wrapper that fills the
-// description. The handle and what it shares with capi.cpp: handle.h. The encode's host half: encode_host.h.
+// kajo_hip_present_* entry point, kajo_hip_glare, _local, _lens, _grade, _meter, _encode, _encode_present, _encode_view and
+// _encode_view_present as a wrapper that fills the description. The handle and what it shares with capi.cpp: handle.h. The encode's host
+// half: encode_host.h; the float view's: encode_view_host.h.
 #include "handle.h"
 
 #include "encode_host.h"
+#include "encode_view_host.h"
 
 // encode.cpp's launcher (its argument block is encode_math.h's)
 extern "C" {
 size_t kajo_encode_table_words(void);
 int kajo_encode_launch(const void* src, const TileMap* map, int fromTiles, const kajo::EncodeArgs* a, const void* table, void* dst, void* stream);
+// encode_view.cpp's
+int kajo_encode_view_launch(const void* src, const TileMap* map, int fromTiles, const kajo::EncodeArgs* a, const void* table, const void* firstX,
+                            const void* countX, const void* wxT, const void* firstY, const void* countY, const void* wy, int strideY, int outW,
+                            int outH, int row0, int rows, void* T, void* dst, void* stream);
 }
 
 extern "C" {
@@ -752,19 +759,25 @@ struct ViewRect
     bool copy; // the copy case: the whole frame at its own size
 };
 
-// ... and those that need the frame's size: last of all, behind the null handle
+// ... and those that need the frame's size
+int checkViewFrame(int W, int H, const KajoViewParams* p, ViewRect* r)
+{
+    const bool whole = p->x0 == 0.0f && p->y0 == 0.0f && p->x1 == 0.0f && p->y1 == 0.0f;
+    *r = ViewRect{p->x0, p->y0, whole ? (double)W : (double)p->x1, whole ? (double)H : (double)p->y1, false};
+    if (r->x1 > W || r->y1 > H)
+        return fail(KAJO_E_INVALID, "view rectangle must lie inside the frame");
+    if ((r->x1 - r->x0) / p->outW > KAJO_VIEW_MAX_SCALE || (r->y1 - r->y0) / p->outH > KAJO_VIEW_MAX_SCALE)
+        return fail(KAJO_E_INVALID, "view minification must be at most 64");
+    r->copy = p->outW == W && p->outH == H && r->x0 == 0.0 && r->y0 == 0.0 && r->x1 == W && r->y1 == H;
+    return KAJO_OK;
+}
+
+// ... of a handle's frame: last of all, behind the null handle
 int checkViewHandle(kajo_hip_t h, const KajoViewParams* p, ViewRect* r)
 {
     if (!h)
         return fail(KAJO_E_INVALID, "null handle");
-    const bool whole = p->x0 == 0.0f && p->y0 == 0.0f && p->x1 == 0.0f && p->y1 == 0.0f;
-    *r = ViewRect{p->x0, p->y0, whole ? (double)h->W : (double)p->x1, whole ? (double)h->H : (double)p->y1, false};
-    if (r->x1 > h->W || r->y1 > h->H)
-        return fail(KAJO_E_INVALID, "view rectangle must lie inside the frame");
-    if ((r->x1 - r->x0) / p->outW > KAJO_VIEW_MAX_SCALE || (r->y1 - r->y0) / p->outH > KAJO_VIEW_MAX_SCALE)
-        return fail(KAJO_E_INVALID, "view minification must be at most 64");
-    r->copy = p->outW == h->W && p->outH == h->H && r->x0 == 0.0 && r->y0 == 0.0 && r->x1 == h->W && r->y1 == h->H;
-    return KAJO_OK;
+    return checkViewFrame(h->W, h->H, p, r);
 }
 
 // Form the weight rows of *p and upload them with the tables, unless they are the last call's. One block: lin[256], thresholds[255 + 1
@@ -1244,6 +1257,31 @@ int encodeLaunch(KajoHip* h, Image img, const ToneArgs& t, const KajoEncodeParam
     return KAJO_OK;
 }
 
+// Enqueue the float view of an image (tiles through h->map's geometry, or a row-major frame) into dst (device, outW * outH words of the
+// format): the view's own rows (viewPlan: its pinned staging, uploaded once per set of parameters) and its intermediate, the encode's
+// table. Checked by checkView, checkEncode and checkViewHandle, device bound. The copy case launches the plain encode.
+int encodeViewImage(KajoHip* h, Image img, const ToneArgs& t, const KajoEncodeParams* p, const KajoViewParams* view, const ViewRect& r, void* dst)
+{
+    if (r.copy)
+        return encodeLaunch(h, img, t, p, dst);
+    int rc;
+    if (encodeTabled(p) && (rc = encodePlan(h, p)))
+        return rc;
+    if ((rc = viewPlan(h, view, r)))
+        return rc;
+    const auto& pl = h->viewPlan;
+    HIP_TRY(growBuffer(h->viewMid, &h->viewMidBytes, (size_t)view->outW * pl.rows * 16));
+    const kajo::EncodeArgs a = encodeArgsOf(p, t, (float)h->passesDone);
+    const char* rows = h->viewRows.as<char>();
+    hipError_t le = (hipError_t)kajo_encode_view_launch(img.src, &h->map, img.fromTiles ? 1 : 0, &a, encodeTabled(p) ? h->encodeTable.p : nullptr,
+                                                        rows + pl.firstX, rows + pl.countX, rows + pl.wx, rows + pl.firstY, rows + pl.countY,
+                                                        rows + pl.wy, pl.strideY, view->outW, view->outH, pl.row0, pl.rows, h->viewMid.p, dst,
+                                                        h->stream);
+    if (le != hipSuccess)
+        return failHip(le, "encode view kernel launch");
+    return KAJO_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1309,6 +1347,41 @@ int kajo_hip_encode_pixels(const KajoEncodeParams* encode, const KajoToneParams*
     return KAJO_OK;
 }
 
+int kajo_hip_encode_view_pixels(const KajoEncodeParams* encode, const KajoToneParams* tone, const KajoViewParams* view, const float* meanRgb,
+                                int32_t width, int32_t height, void* out)
+{
+    ToneArgs t{};
+    int rc = toneArgsOf(tone, &t);
+    if (rc)
+        return rc;
+    if (view && (rc = checkView(view)))
+        return rc;
+    if ((rc = checkEncode(encode)) || (rc = checkEncodeTone(tone)))
+        return rc;
+    if (width < 1 || height < 1)
+        return fail(KAJO_E_INVALID, "width and height must be at least 1");
+    if (!meanRgb || !out)
+        return fail(KAJO_E_INVALID, "null argument");
+    ViewRect r{};
+    if (view && (rc = checkViewFrame(width, height, view, &r)))
+        return rc;
+    std::vector<float> table;
+    if (encodeTabled(encode)) {
+        table.resize(kajo::kEncodeTableWords);
+        kajo::encodeTable(encode->transfer, encode->transfer == KAJO_TRANSFER_PQ ? encode->peakNits : 0.0f, table.data());
+    }
+    const kajo::EncodeArgs a = encodeArgsOf(encode, t, 1.0f);
+    if (!view || r.copy) {
+        kajo::encodePixels(a, table.data(), meanRgb, (int64_t)width * height, 0, 0, width, out);
+        return KAJO_OK;
+    }
+    kajo::ViewAxis ax, ay;
+    if (!kajo::viewAxis(width, r.x0, r.x1, view->outW, view->filter, &ax) || !kajo::viewAxis(height, r.y0, r.y1, view->outH, view->filter, &ay))
+        return fail(KAJO_E_INVALID, "view row longer than 384 taps");
+    kajo::encodeViewPixels(a, table.data(), meanRgb, width, ax, ay, out);
+    return KAJO_OK;
+}
+
 } // extern "C"
 
 namespace
@@ -1348,7 +1421,7 @@ struct Chain
     const KajoMeterParams* meter = nullptr;
     const KajoToneParams* tone = nullptr;
     const KajoViewParams* view = nullptr;
-    const KajoEncodeParams* encode = nullptr; // the encoded sinks: in place of the tone kernels' word; no view beside it
+    const KajoEncodeParams* encode = nullptr; // the encoded sinks: in place of the tone kernels' word; a view beside it is the float view
     unsigned need = 0;
     // the source: the handle's own frame, or gathered tile buffers (tiles null: the handle's own tiles, which must be the whole frame)
     bool gathered = false;
@@ -1366,7 +1439,7 @@ struct Chain
 };
 
 // Every refusal of a chain, before any device work, in the header's order: the stages' parameters (despeckle, grade, lens, glare, local,
-// meter, tone, the two automatic exposures, view or encode), the denoiser's parameters and its handle rules, then the handle (null, the grade's
+// meter, tone, the two automatic exposures, view, encode), the denoiser's parameters and its handle rules, then the handle (null, the grade's
 // state, the lens's, the view against the frame). -> c.toneArgs, c.rect
 int checkChain(kajo_hip_t h, Chain& c)
 {
@@ -1461,11 +1534,11 @@ int runChain(KajoHip* h, const Chain& c)
     if (c.meter && (rc = meterAndPatch(h, img, c.meter, c.tone, c.result, &t)))
         return rc;
     if (c.sink == kSinkDeviceEncoded)
-        return encodeLaunch(h, img, t, c.encode, c.dst);
+        return c.view ? encodeViewImage(h, img, t, c.encode, c.view, c.rect, c.dst) : encodeLaunch(h, img, t, c.encode, c.dst);
     if (c.sink == kSinkHostEncoded) {
-        const size_t encodedBytes = count * kajo::encodePixelBytes(c.encode->format);
+        const size_t encodedBytes = (c.view ? (size_t)c.view->outW * c.view->outH : count) * kajo::encodePixelBytes(c.encode->format);
         HIP_TRY(growBuffer(h->encodeOut, &h->encodeOutBytes, encodedBytes));
-        if ((rc = encodeLaunch(h, img, t, c.encode, h->encodeOut.p)))
+        if ((rc = c.view ? encodeViewImage(h, img, t, c.encode, c.view, c.rect, h->encodeOut.p) : encodeLaunch(h, img, t, c.encode, h->encodeOut.p)))
             return rc;
         if (c.dst)
             HIP_TRY(hipMemcpyAsync(c.dst, h->encodeOut.p, encodedBytes, hipMemcpyDeviceToHost, h->stream));
@@ -1821,6 +1894,57 @@ int kajo_hip_encode_present_gathered_device(kajo_hip_t h, const void* gathered, 
     c.local = local;
     c.meter = meter;
     c.tone = tone;
+    c.encode = encode;
+    return present(h, c);
+}
+
+int kajo_hip_encode_view(kajo_hip_t h, const KajoEncodeParams* encode, const KajoToneParams* tone, const KajoViewParams* view, void* dst)
+{
+    Chain c;
+    c.sink = kSinkHostEncoded;
+    c.dst = dst;
+    c.tone = tone;
+    c.view = view;
+    c.encode = encode;
+    return present(h, c);
+}
+
+int kajo_hip_encode_view_present(kajo_hip_t h, const KajoDespeckleParams* despeckle, const KajoDenoiseParams* denoise, const KajoGradeParams* grade,
+                                 const KajoLensParams* lens, const KajoGlareParams* g, const KajoLocalParams* local, const KajoMeterParams* meter,
+                                 const KajoToneParams* tone, const KajoViewParams* view, const KajoEncodeParams* encode, void* dst,
+                                 KajoMeterResult* result)
+{
+    Chain c;
+    c.sink = kSinkHostEncoded;
+    c.dst = dst;
+    c.result = result;
+    c.despeckle = despeckle;
+    c.denoise = denoise;
+    c.grade = grade;
+    c.lens = lens;
+    c.glare = g;
+    c.local = local;
+    c.meter = meter;
+    c.tone = tone;
+    c.view = view;
+    c.encode = encode;
+    return present(h, c);
+}
+
+int kajo_hip_encode_view_present_gathered_device(kajo_hip_t h, const void* gathered, const KajoDespeckleParams* despeckle,
+                                                 const KajoGradeParams* grade, const KajoGlareParams* g, const KajoLocalParams* local,
+                                                 const KajoMeterParams* meter, const KajoToneParams* tone, const KajoViewParams* view,
+                                                 const KajoEncodeParams* encode, void* dst, KajoMeterResult* result)
+{
+    Chain c = gatheredChain(gathered, dst, result);
+    c.sink = kSinkDeviceEncoded;
+    c.despeckle = despeckle;
+    c.grade = grade;
+    c.glare = g;
+    c.local = local;
+    c.meter = meter;
+    c.tone = tone;
+    c.view = view;
     c.encode = encode;
     return present(h, c);
 }

@@ -299,7 +299,11 @@ int help(const char* program)
                 "    --peak-nits N   --png16 --transfer pq: the luminance a display value of 1 is shown at, 0 < N <= 10000 (1000)\n"
                 "    --dither        write -o through the encode's ARGB8 words with dither instead of the undithered resolve; any --gpus. Not with\n"
                 "                    a view option or --auto-exposure\n"
-                "    --dither-seed N  --dither: the seed of the pattern, 0 .. 4294967295 (0)\n",
+                "    --dither-seed N  --dither: the seed of the pattern, 0 .. 4294967295 (0)\n"
+                "    --encode-view   with a view option and --png16 or --dither: write --png16 and --dither's -o at the view's output size through\n"
+                "                    the float view (include/kajo_hip.h \"The float view\": resampled between the tone curve and the transfer, the\n"
+                "                    dither over output pixels); --dither then goes with a view option; any --gpus. --supersample K --png16 F\n"
+                "                    --encode-view is the antialiased 16-bit image (--json: encode_view_out_w, encode_view_out_h)\n",
                 program);
     return 1;
 }
@@ -370,6 +374,7 @@ int commandLine(const std::vector<std::string>& args, Raw& r, Arguments& a)
         else if (s == "--auto-exposure") r.toneAuto = a.toneGiven = true;
         else if (s == "--despeckle") opt.despeckleOn = true;
         else if (s == "--dither") a.dither = true;
+        else if (s == "--encode-view") a.encodeView = true;
         else if (s == "--grade-region" && more) r.gradeRegions.push_back(args[++i]);
         else if (s == "--aov-specular") opt.aovSpecular = true;
         else if (s == "--aov-tiled") opt.aovTiled = true;
@@ -561,6 +566,12 @@ int encodeOptions(const Raw& r, Arguments& a)
 {
     kajo_hip_default_encode_params(&a.encode16);
     kajo_hip_default_encode_params(&a.encode8);
+    if (a.encodeView && a.threeArg)
+        return refuseThreeArg("encode", "the options constructor");
+    if (a.encodeView && !a.viewGiven)
+        return refuse("--encode-view needs a view option (--output-size, --view, --view-filter or --supersample)");
+    if (a.encodeView && a.png16Out.empty() && !a.dither)
+        return refuse("--encode-view needs --png16 or --dither: it is the encoded images it resamples");
     if (!a.encodeGiven)
         return 0;
     if (a.threeArg)
@@ -571,7 +582,7 @@ int encodeOptions(const Raw& r, Arguments& a)
         return refuse("--dither-seed belongs to --dither");
     if (r.toneAuto)
         return refuse("--png16 and --dither take no --auto-exposure (its scale is formed inside the tone mapping they replace): use --meter-exposure");
-    if (a.dither && a.viewGiven)
+    if (a.dither && a.viewGiven && !a.encodeView)
         return refuse("--dither and a view option are not combined: the view resamples 8-bit words");
     a.encode16.format = KAJO_ENCODE_RGBA16;
     if (!r.transferName.empty()) {

@@ -20,6 +20,7 @@ struct Arguments
     // what the output stage needs beside the backend's options
     KajoEncodeParams encode16, encode8; // of --png16 and of -o through --dither
     bool dither = false;
+    bool encodeView = false; // --encode-view: --png16 and --dither's -o through the float view, at the view's output size
     std::vector<int32_t> matteObjects;
     int denoiseIterations = 5;
     bool whiteBalanceGiven = false;

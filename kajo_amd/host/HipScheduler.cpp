@@ -702,6 +702,19 @@ void Scheduler::readViewed(uint32_t* dst)
 
 void Scheduler::readEncoded(const KajoEncodeParams* encode, void* dst)
 {
+    readEncodedThrough(encode, nullptr, dst);
+}
+
+void Scheduler::readEncodedViewed(const KajoEncodeParams* encode, void* dst)
+{
+    if (!m_impl->opt.viewOn)
+        throw std::runtime_error("hip::Scheduler: readEncodedViewed needs Options::viewOn");
+    readEncodedThrough(encode, &m_impl->opt.view, dst);
+}
+
+// readEncoded (view null: the calls it has always made) and readEncodedViewed
+void Scheduler::readEncodedThrough(const KajoEncodeParams* encode, const KajoViewParams* view, void* dst)
+{
     Impl& d = *m_impl;
     const KajoDespeckleParams* despeckle = d.despeckleOrNull();
     const KajoLocalParams* local = d.localOrNull();
@@ -710,7 +723,7 @@ void Scheduler::readEncoded(const KajoEncodeParams* encode, void* dst)
     if (d.gathered && !wholeFrame) {
         // several owners: straight from the gathered tile buffers, as run()'s refreshes
         size_t bytes = 0;
-        check(kajo_hip_encode_bytes(encode, d.image->width, d.image->height, &bytes), "kajo_hip_encode_bytes");
+        check(kajo_hip_encode_bytes(encode, view ? view->outW : d.image->width, view ? view->outH : d.image->height, &bytes), "kajo_hip_encode_bytes");
         checkHip(hipSetDevice(d.devices[0]), "hipSetDevice");
         if (d.encodedBytes < bytes) {
             if (d.encodedDevice)
@@ -722,9 +735,14 @@ void Scheduler::readEncoded(const KajoEncodeParams* encode, void* dst)
         }
         if (d.opt.gradeOn)
             d.gradeParams(despeckle, nullptr, &grade);
-        check(kajo_hip_encode_present_gathered_device(d.handles[0], d.gathered, despeckle, d.opt.gradeOn ? &grade : nullptr, d.glareOrNull(), local,
-                                                      d.meterOrNull(), &d.opt.tone, encode, d.encodedDevice, &d.metered),
-              "kajo_hip_encode_present_gathered_device");
+        if (view)
+            check(kajo_hip_encode_view_present_gathered_device(d.handles[0], d.gathered, despeckle, d.opt.gradeOn ? &grade : nullptr, d.glareOrNull(),
+                                                               local, d.meterOrNull(), &d.opt.tone, view, encode, d.encodedDevice, &d.metered),
+                  "kajo_hip_encode_view_present_gathered_device");
+        else
+            check(kajo_hip_encode_present_gathered_device(d.handles[0], d.gathered, despeckle, d.opt.gradeOn ? &grade : nullptr, d.glareOrNull(), local,
+                                                          d.meterOrNull(), &d.opt.tone, encode, d.encodedDevice, &d.metered),
+                  "kajo_hip_encode_present_gathered_device");
         if (local)
             d.notePivot();
         checkHip(hipMemcpyAsync(dst, d.encodedDevice, bytes, hipMemcpyDeviceToHost, d.streams[0]), "hipMemcpyAsync(encoded image)");
@@ -733,9 +751,14 @@ void Scheduler::readEncoded(const KajoEncodeParams* encode, void* dst)
     }
     Impl::ChainStages c;
     d.prepareChain(despeckle, nullptr, false, c);
-    check(kajo_hip_encode_present(d.handles[0], despeckle, nullptr, c.grade, c.lens, d.glareOrNull(), local, d.meterOrNull(), &d.opt.tone, encode, dst,
-                                  &d.metered),
-          "kajo_hip_encode_present");
+    if (view)
+        check(kajo_hip_encode_view_present(d.handles[0], despeckle, nullptr, c.grade, c.lens, d.glareOrNull(), local, d.meterOrNull(), &d.opt.tone, view,
+                                           encode, dst, &d.metered),
+              "kajo_hip_encode_view_present");
+    else
+        check(kajo_hip_encode_present(d.handles[0], despeckle, nullptr, c.grade, c.lens, d.glareOrNull(), local, d.meterOrNull(), &d.opt.tone, encode, dst,
+                                      &d.metered),
+              "kajo_hip_encode_present");
     if (local)
         d.notePivot();
     if (c.lens)

@@ -238,6 +238,11 @@ public:
     // regions, gradeNeutralAt) the frame is composed on the first handle, as readViewed does, and kajo_hip_encode_present runs there. The
     // view takes no part. The library's refusals (the tone parameters' automatic exposure among them) are thrown.
     void readEncoded(const KajoEncodeParams* encode, void* dst);
+    // ... and through Options::view as the float view, between the tone curve and the encode's transfer (include/kajo_hip.h "The float
+    // view"): dst = kajo_hip_encode_bytes bytes of a view.outW x view.outH image. It composes first where readViewed and readEncoded do;
+    // with several owners the gathered tile buffers go through kajo_hip_encode_view_present_gathered_device. Throws where Options::viewOn
+    // is not set.
+    void readEncodedViewed(const KajoEncodeParams* encode, void* dst);
     // the noise map after run() (Options::noise or noiseTarget; include/kajo_hip.h kajo_hip_noise on every owner, into the same planes):
     // W*H floats each -- mean luminance per pass, its standard error, the relative error -- any may be null. Any number of GPUs, no gather
     void readNoise(float* mean, float* stderror, float* relative);
@@ -249,6 +254,7 @@ public:
     void readSamplePasses(uint32_t* plane);
 
 private:
+    void readEncodedThrough(const KajoEncodeParams* encode, const KajoViewParams* view, void* dst);
     struct Impl;
     std::unique_ptr<Impl> m_impl;
 };

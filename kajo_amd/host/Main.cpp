@@ -216,6 +216,8 @@ void readViewedImage(hip::Scheduler& s, const Arguments& a, std::unique_ptr<Imag
     if (!a.viewGiven || a.out.empty())
         return;
     viewed.reset(new Image(a.opt.view.outW, a.opt.view.outH));
+    if (a.dither && a.encodeView)
+        return; // (readDitheredImage fills it, through the float view)
     s.readViewed(viewed->pixels.get());
     if (a.gradeGiven)
         facts.gradeRan = s.lastGrade(facts.gradeSlopeUsed);
@@ -226,7 +228,10 @@ void readDitheredImage(hip::Scheduler& s, const Arguments& a, Image& image, RunF
 {
     if (!a.dither || a.out.empty())
         return;
-    s.readEncoded(&a.encode8, image.pixels.get());
+    if (a.encodeView)
+        s.readEncodedViewed(&a.encode8, image.pixels.get());
+    else
+        s.readEncoded(&a.encode8, image.pixels.get());
     if (a.gradeGiven)
         facts.gradeRan = s.lastGrade(facts.gradeSlopeUsed);
 }
@@ -235,9 +240,14 @@ bool writeEncoded16(hip::Scheduler& s, const Arguments& a)
 {
     if (a.png16Out.empty())
         return true;
-    std::vector<uint16_t> words((size_t)a.width * a.height * 4);
-    s.readEncoded(&a.encode16, words.data());
-    return writePng16(a.png16Out, a.width, a.height, words.data(), a.encode16.transfer == KAJO_TRANSFER_PQ);
+    // (--encode-view: at the view's output size, through the float view)
+    const int w = a.encodeView ? a.opt.view.outW : a.width, h = a.encodeView ? a.opt.view.outH : a.height;
+    std::vector<uint16_t> words((size_t)w * h * 4);
+    if (a.encodeView)
+        s.readEncodedViewed(&a.encode16, words.data());
+    else
+        s.readEncoded(&a.encode16, words.data());
+    return writePng16(a.png16Out, w, h, words.data(), a.encode16.transfer == KAJO_TRANSFER_PQ);
 }
 
 void printJson(const Arguments& a, const hip::Statistics& s, const Preview& preview, const RunFacts& f)
@@ -308,6 +318,8 @@ void printJson(const Arguments& a, const hip::Statistics& s, const Preview& prev
         else
             std::printf("null");
         std::printf(", \"encode_dither\": %s", a.dither ? "true" : "false");
+        if (a.encodeView)
+            std::printf(", \"encode_view_out_w\": %d, \"encode_view_out_h\": %d", (int)opt.view.outW, (int)opt.view.outH);
     }
     if (a.adaptiveGiven)
         std::printf(", \"adaptive_active_units\": %lld, \"adaptive_units\": %lld, \"adaptive_paths\": %lld, \"adaptive_stopped_at_pass\": %d",
@@ -373,7 +385,7 @@ int main(int argc, char** argv)
             !writeDenoised(s, a, facts))
             return 3;
         readViewedImage(s, a, viewed, facts);
-        readDitheredImage(s, a, *image, facts);
+        readDitheredImage(s, a, viewed && a.encodeView ? *viewed : *image, facts); // (--encode-view: -o at the view's size)
         if (!writeEncoded16(s, a))
             return 3;
     } catch (const std::exception& e) {

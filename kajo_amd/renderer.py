@@ -580,19 +580,27 @@ class HipRenderer:
         capi.check(self._L.kajo_hip_grade(self._h, ref(s), ref(d), C.byref(p), out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def _encoded_array(self, e):
+    def _encoded_array(self, e, v=None):
+        h, w = (self.height, self.width) if v is None else (max(v.outH, 0), max(v.outW, 0))
         if e.format in (capi.KAJO_ENCODE_ARGB8, capi.KAJO_ENCODE_RGB10A2):
-            return np.empty((self.height, self.width), np.uint32)
-        return np.empty((self.height, self.width, 4), np.float16 if e.format == capi.KAJO_ENCODE_RGBA16F else np.uint16)
+            return np.empty((h, w), np.uint32)
+        return np.empty((h, w, 4), np.float16 if e.format == capi.KAJO_ENCODE_RGBA16F else np.uint16)
 
-    def encode(self, encode: dict = None, **tone) -> np.ndarray:
+    def encode(self, encode: dict = None, view: dict = None, **tone) -> np.ndarray:
         """The encode stage alone over the handle's frame (include/kajo_hip.h kajo_hip_encode): exposure and tone curve as tonemap()'s
         (no automatic exposure), then the transfer, the dither and the format of encode_params(**encode) -> (H, W) uint32 for "argb8"
-        and "rgb10a2", (H, W, 4) uint16 for "rgba16", (H, W, 4) float16 for "rgba16f". Nothing of the handle's state is touched."""
+        and "rgb10a2", (H, W, 4) uint16 for "rgba16", (H, W, 4) float16 for "rgba16f". view: a dict of view()'s params puts the float
+        view between the tone curve and the transfer (kajo_hip_encode_view): the array then has the view's shape (out_h, out_w).
+        Nothing of the handle's state is touched."""
         e = encode_params(**(encode or {}))
         t = self._tone_params(**tone)
-        out = self._encoded_array(e)
-        capi.check(self._L.kajo_hip_encode(self._h, C.byref(e), C.byref(t), out.ctypes.data_as(C.c_void_p)))
+        if view is None:
+            out = self._encoded_array(e)
+            capi.check(self._L.kajo_hip_encode(self._h, C.byref(e), C.byref(t), out.ctypes.data_as(C.c_void_p)))
+            return out
+        v = self._view_params(**view)
+        out = self._encoded_array(e, v)
+        capi.check(self._L.kajo_hip_encode_view(self._h, C.byref(e), C.byref(t), C.byref(v), out.ctypes.data_as(C.c_void_p)))
         return out
 
     def present(self, despeckle: dict = None, denoise: dict = None, glare: dict = None, meter: dict = None, local: dict = None,
@@ -607,12 +615,11 @@ class HipRenderer:
         (kajo_hip_present_lens_argb8; likewise routed there only when it is given). view: a dict of view()'s params puts the view behind
         the tone curves (kajo_hip_present_view_argb8; likewise): the array returned then has the view's shape (out_h, out_w). grade: a dict of
         grade()'s params puts the grade between the denoiser and the lens (kajo_hip_present_grade_argb8; likewise). encode: a dict of
-        encode_params()'s arguments puts the encode in place of the 8-bit word (kajo_hip_encode_present; no view beside it): the array
-        returned is encode()'s, the second value the result dict of meter() with a meter and None without."""
+        encode_params()'s arguments puts the encode in place of the 8-bit word (kajo_hip_encode_present): the array returned is
+        encode()'s, the second value the result dict of meter() with a meter and None without. With a view beside the encode the float
+        view runs between the tone curve and the transfer (kajo_hip_encode_view_present) and the array has the view's shape."""
         t = self._tone_params(**tone)
         if encode is not None:
-            if view is not None:
-                raise ValueError("a view and an encode are not combined: the view resamples ARGB8 words")
             ref = lambda p: None if p is None else C.byref(p)
             e = encode_params(**encode)
             s = None if despeckle is None else self._despeckle_params(**despeckle)
@@ -623,6 +630,12 @@ class HipRenderer:
             l = None if local is None else self._local_params(**local)
             m = None if meter is None else self._meter_params(**meter)
             result = capi.KajoMeterResult()
+            if view is not None:
+                v = self._view_params(**view)
+                out = self._encoded_array(e, v)
+                capi.check(self._L.kajo_hip_encode_view_present(self._h, ref(s), ref(d), ref(c), ref(f), ref(g), ref(l), ref(m), C.byref(t),
+                                                                C.byref(v), C.byref(e), out.ctypes.data_as(C.c_void_p), C.byref(result)))
+                return out, (None if m is None else self._meter_result(result))
             out = self._encoded_array(e)
             capi.check(self._L.kajo_hip_encode_present(self._h, ref(s), ref(d), ref(c), ref(f), ref(g), ref(l), ref(m), C.byref(t), C.byref(e),
                                                        out.ctypes.data_as(C.c_void_p), C.byref(result)))
@@ -859,6 +872,42 @@ def encode_pixels(mean_rgb, encode: dict = None, x0: int = 0, y0: int = 0, row_w
     out = np.zeros(len(m), np.uint64 if wide else np.uint32)
     capi.check(capi.lib().kajo_hip_encode_pixels(C.byref(e), C.byref(t), m.ctypes.data_as(C.c_void_p), len(m), int(x0), int(y0),
                                                  int(row_width or max(len(m), 1)), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def view_params(width: int, height: int, out_w: int = None, out_h: int = None, rect=None, filter=None):
+    """KajoViewParams (include/kajo_hip.h "The view") for a width x height frame, as HipRenderer.view()'s params: out_w, out_h (the frame's
+    size where left out), rect (x0, y0, x1, y1) in source pixels (the whole frame where left out), filter (a name or a KAJO_VIEW_* value)."""
+    p = capi.KajoViewParams()
+    capi.lib().kajo_hip_default_view_params(C.byref(p))
+    p.outW = int(width) if out_w is None else int(out_w)
+    p.outH = int(height) if out_h is None else int(out_h)
+    if rect is not None:
+        p.x0, p.y0, p.x1, p.y1 = (float(v) for v in rect)
+    if filter is not None:
+        p.filter = capi.KAJO_VIEW_FILTERS[filter] if isinstance(filter, str) else int(filter)
+    return p
+
+
+def encode_view_pixels(mean_rgb, encode: dict = None, view: dict = None, curve: str = "clamp", exposure: float = 0.0, white: float = 0.0) -> np.ndarray:
+    """The float view over a whole frame (H, W, 3) of MEANS on the host, the kernels' own lines (include/kajo_hip.h
+    kajo_hip_encode_view_pixels) -> (out_h, out_w) words, uint32 or uint64 by the format. view: view_params()'s arguments (or a
+    KajoViewParams); None is the plain encode of the frame."""
+    m = np.ascontiguousarray(mean_rgb, np.float32)
+    if m.ndim != 3 or m.shape[2] != 3:
+        raise ValueError("the means must be (H, W, 3)")
+    H, W = m.shape[:2]
+    e = encode if isinstance(encode, capi.KajoEncodeParams) else encode_params(**(encode or {}))
+    v = view if isinstance(view, capi.KajoViewParams) or view is None else view_params(W, H, **view)
+    curves = {"clamp": capi.KAJO_TONE_CLAMP, "reinhard": capi.KAJO_TONE_REINHARD, "aces": capi.KAJO_TONE_ACES}
+    t = capi.KajoToneParams()
+    capi.lib().kajo_hip_default_tone_params(C.byref(t))
+    t.curve, t.exposure, t.white = curves[curve], float(exposure), float(white)
+    wide = e.format in (capi.KAJO_ENCODE_RGBA16, capi.KAJO_ENCODE_RGBA16F)
+    shape = (H, W) if v is None else (max(v.outH, 0), max(v.outW, 0))
+    out = np.zeros(shape, np.uint64 if wide else np.uint32)
+    capi.check(capi.lib().kajo_hip_encode_view_pixels(C.byref(e), C.byref(t), None if v is None else C.byref(v), m.ctypes.data_as(C.c_void_p),
+                                                      W, H, out.ctypes.data_as(C.c_void_p)))
     return out
 
 
