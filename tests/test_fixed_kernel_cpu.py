@@ -179,3 +179,134 @@ def test_the_launcher_picks_by_the_function_the_printout_calls():
     # (the printed name and the kernel's symbol are spelled from the same two numbers: name_of() above restates both)
     header = open(os.path.join(CSRC, "fixed_counts.h")).read()
     assert 'return "kajo_render_exact_p" #P "s" #S;' in header and "#define KAJO_FIXED_NAME(P, S) kajo_render_exact_p##P##s##S" in header
+
+
+# ---- the family of 6 + 5 scenes (tests/fixed_instance_scenes.py family) the instance is rendered on (tests/test_hip_fixed_instance.py) ----
+FAMILY_FRAMES = [(64, 16), (72, 40)]
+FAMILY_S, FAMILY_PASSES, FAMILY_SEED = 4, 5, 0o715517
+FAMILY_NAMES = (["light_at_%d" % k for k in range(4)] + ["planes_reversed", "materials_1", "materials_2", "materials_19", "nested", "overlapping",
+                "coincident", "touching_floor", "light_in_ceiling", "camera_in_glass", "test_a1", "spheres_a1"])
+
+
+def _bits(a):
+    import numpy as np
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def test_the_family_is_what_it_says(scenes):
+    """the members by name, none missing; what each is built to be, from its records"""
+    import numpy as np
+    from fixed_instance_scenes import NAMES, family
+    fam = family(scenes)
+    assert list(fam) == NAMES == FAMILY_NAMES
+    base = scenes["spheres_a169"]
+    emits = lambda sc: np.flatnonzero((sc.spheres[:, 28:32] != 0).any(1)).tolist()
+    key = lambda recs: sorted(map(bytes, recs))
+    for name, sc in fam.items():
+        assert (sc.n_planes, sc.n_spheres, sc.n_lights) == (6, 5, 1), name
+        # (centre, radius) spheres: the transform is a translation
+        T = sc.spheres[:, :16].reshape(-1, 4, 4).copy()
+        T[:, 3, :3] = 0
+        assert (T == np.eye(4, dtype=np.float32)).all(), name
+    for k in range(4):
+        sc = fam["light_at_%d" % k]
+        assert emits(sc) == [k] and key(sc.spheres) == key(base.spheres)
+        assert np.array_equal(np.delete(sc.spheres, k, axis=0), base.spheres[:4])  # the other records in their order
+    assert np.array_equal(fam["planes_reversed"].planes, base.planes[::-1]) and np.array_equal(fam["planes_reversed"].spheres, base.spheres)
+    kinds = set()
+    for name in FAMILY_NAMES:
+        if name.startswith("materials_"):
+            sc = fam[name]
+            assert np.array_equal(sc.spheres[:, :16], base.spheres[:, :16]) and np.array_equal(sc.planes[:, :16], base.planes[:, :16]) and emits(sc) == [4]
+            for m in np.concatenate([sc.planes[:, 16:38], sc.spheres[:4, 16:38]]):
+                d, s, t, e = m[4:7].any(), m[8:11].any(), m[16:19].any(), m[20]
+                assert not (t and e == 0), name  # no glass over exponent 0
+                kinds.add((bool(d), bool(s), bool(t), bool(e == 0)))
+    assert len(kinds) == 5, kinds  # the five classes all occur among the three seeds
+    dist = lambda sc, i, j: float(np.linalg.norm(sc.spheres[i, 12:15].astype(np.float64) - sc.spheres[j, 12:15]))
+    sc = fam["nested"]
+    assert sc.spheres[0, 32:35].any() and sc.spheres[3, 20:23].any() and dist(sc, 0, 3) + sc.spheres[3, 38] < sc.spheres[0, 38]
+    sc = fam["overlapping"]
+    assert abs(sc.spheres[1, 38] - sc.spheres[2, 38]) < dist(sc, 1, 2) < sc.spheres[1, 38] + sc.spheres[2, 38]
+    sc = fam["coincident"]
+    assert dist(sc, 1, 3) == 0 and sc.spheres[1, 38] == sc.spheres[3, 38] and not np.array_equal(sc.spheres[1, 16:38], sc.spheres[3, 16:38])
+    sc = fam["touching_floor"]
+    cy, r, floor = sc.spheres[2, 13], sc.spheres[2, 38], sc.planes[0, 13]
+    assert np.float64(cy) + np.float64(r) == np.float64(floor) and np.float32(cy + r) == floor and r != 1.0
+    sc = fam["light_in_ceiling"]
+    assert emits(sc) == [4] and abs(sc.spheres[4, 13] - sc.planes[5, 13]) < sc.spheres[4, 38]
+    sc = fam["camera_in_glass"]
+    eye = np.linalg.inv(sc.view.reshape(4, 4).T.astype(np.float64))[:3, 3]
+    assert sc.spheres[0, 32:35].any() and np.linalg.norm(eye - sc.spheres[0, 12:15]) < sc.spheres[0, 38]
+    assert fam["test_a1"] is scenes["test_a1"] and fam["spheres_a1"] is scenes["spheres_a1"]
+    assert not np.array_equal(fam["test_a1"].proj, base.proj)
+
+
+def test_the_twin_before_the_last_sphere(scenes):
+    import numpy as np
+    from fixed_instance_scenes import far_sphere_twin
+    base = scenes["spheres_a169"]
+    last, ids_last = far_sphere_twin(base)
+    twin, ids = far_sphere_twin(base, before_last=True)
+    assert np.array_equal(ids_last, np.arange(12)) and np.array_equal(last.spheres[:5], base.spheres)
+    assert np.array_equal(ids, [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12])
+    assert np.array_equal(twin.spheres[[0, 1, 2, 3, 5]], base.spheres) and np.array_equal(twin.spheres[4], last.spheres[5])
+    assert twin.n_lights == 1 and np.array_equal(twin.planes, base.planes)
+
+
+@pytest.mark.parametrize("name", FAMILY_NAMES)
+def test_every_member_runs_the_instance_and_its_twin_the_simple_kernel(kernel_name, scenes, name):
+    from fixed_instance_scenes import family, far_sphere_twin
+    sc = family(scenes)[name]
+    twin, _ = far_sphere_twin(sc, before_last=True)
+    assert (twin.n_planes, twin.n_spheres, twin.n_lights) == (6, 6, 1)
+    assert kernel_name(sc) == "kajo_render_exact_p6s5", name
+    assert kernel_name(twin) == "kajo_render_exact_simple", name
+
+
+@pytest.mark.parametrize("name", FAMILY_NAMES)
+def test_the_oracle_renders_member_and_twin_alike(scenes, name):
+    """The precondition of the comparison of the kernels (tests/test_hip_fixed_instance.py): in the oracle the twin's frame is the member's
+    bit for bit, not-a-number where it is not a number -- no ray meets the far sphere, and a ray that is not a number ends on the same record
+    in both. A condition every member meets, at both frame sizes."""
+    import numpy as np
+    from oraclelib import OracleLib, available
+    from fixed_instance_scenes import family, far_sphere_twin
+    if not available("oracle"):
+        pytest.skip("oracle not built")
+    lib = OracleLib("oracle")
+    sc = family(scenes)[name]
+    twin, _ = far_sphere_twin(sc, before_last=True)
+    for w, h in FAMILY_FRAMES:
+        a = lib.create(sc, 1).render(w, h, S=FAMILY_S, passes=FAMILY_PASSES, seed=FAMILY_SEED)
+        b = lib.create(twin, 1).render(w, h, S=FAMILY_S, passes=FAMILY_PASSES, seed=FAMILY_SEED)
+        same = ((_bits(a) == _bits(b)) | (np.isnan(a) & np.isnan(b))).all(-1)
+        assert same.all(), "%s at %dx%d: %d pixels differ, first at %s" % (name, w, h, int((~same).sum()), np.argwhere(~same)[:4].tolist())
+        assert np.isfinite(a[..., :3]).all(-1).mean() > 0.99, (name, w, h)  # (a frame, not a field of NaN: there is something to compare)
+
+
+def test_every_sphere_id_is_some_pixels_first_hit(scenes):
+    """From the oracle's own first-hit ids (camera_ray and trace: tests/test_aov_oracle_cpu.py's path), pass 1 at 72 x 40: over the family every
+    sphere id 7 .. 11 is the first hit of some pixel, so no literal sphere id of the unrolled walk goes unexercised -- and the light is seen
+    as every one of them; the twin meets, ray for ray, the member's object under the twin's id map."""
+    import numpy as np
+    from oraclelib import OracleLib, available, camera_ray
+    from fixed_instance_scenes import family, far_sphere_twin
+    if not available("oracle"):
+        pytest.skip("oracle not built")
+    lib = OracleLib("oracle")
+    w, h = FAMILY_FRAMES[1]
+    seen, light_seen_as = set(), set()
+    for name, sc in family(scenes).items():
+        o = lib.create(sc, 1)
+        rays = [camera_ray(o, w, h, FAMILY_S, x, y, s, npass=1, seed=FAMILY_SEED)[:2] for y in range(h) for x in range(w) for s in range(FAMILY_S)]
+        O, D = np.array([r[0] for r in rays], np.float32), np.array([r[1] for r in rays], np.float32)
+        idx = o.trace(O, D)["idx"]
+        twin, ids = far_sphere_twin(sc, before_last=True)
+        assert np.array_equal(lib.create(twin, 1).trace(O, D)["idx"], ids[idx]), name
+        seen |= set(np.unique(idx).tolist())
+        light = 7 + int(np.flatnonzero((sc.spheres[:, 28:32] != 0).any(1))[0])
+        if (idx == light).any():
+            light_seen_as.add(light)
+    assert seen >= set(range(7, 12)) and seen >= set(range(1, 7)), sorted(seen)
+    assert light_seen_as == set(range(7, 12)), sorted(light_seen_as)
