@@ -60,6 +60,26 @@ def test_scene_staging(san, stage_pods):
     assert out.count(": ok") == 2 * len(stage_pods)
 
 
+def test_general_grid_staging(san, scenes):
+    """tests/general_grid_scenes.py's entries -- large scenes of general records that keep the grid: whole-box registration, four-word hot
+    records behind sphereHotOffset, no visibility lists --, the open twin and a nudged twin that gets no grid: staged and planned clean.
+    (Pods of their own: stage_pods' set is the key set of tests/golden/lds_plan.json.)"""
+    import general_grid_scenes as G
+    base = scenes["spheres_a169"]
+    made = {name: G.entry(base, name) for name in G.ENTRIES}
+    made["mixed_open"] = G.open_twin(made["mixed"])[0]
+    made["ellipsoids_nudged"] = G.nudged(made["ellipsoids"], 7, np.diag(np.array([2, .5, 1.0000001], np.float32)), "ellipsoids_nudged")
+    files = []
+    for name, sc in made.items():
+        files.append(str(san.dir / ("general_grid_%s.pod" % name)))
+        sc.write_pod(files[-1])
+    assert san("stage", *files).count(": ok") == 2 * len(files)
+    assert len(san("plan", "lds", *files).splitlines()) == 9 * len(files)
+    sizes = san("plan", "sizes", *files).splitlines()
+    assert [" grid=1 lists=0 allTranslated=0" in line for line in sizes] == [name != "ellipsoids_nudged" for name in made], sizes
+    assert " grid=0 lists=0 allTranslated=0" in sizes[-1]
+
+
 def test_scene_loader(san):
     files = [os.path.join(ROOT, "kajo_amd", "data", n) for n in ("caustics.json", "dialect.json")]
     files += [os.path.join(ROOT, "tests", "golden", "scenes", n) for n in ("spheres.json", "test.json")]  # the reference's own scene files
