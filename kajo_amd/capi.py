@@ -246,6 +246,43 @@ class KajoCounters(C.Structure):
     ]
 
 
+# The display chain. STAGES: a stage's name -> its parameter block, in chain order; kajo_hip_default_<stage>_params fills one.
+STAGES = {"despeckle": KajoDespeckleParams, "denoise": KajoDenoiseParams, "grade": KajoGradeParams, "lens": KajoLensParams,
+          "glare": KajoGlareParams, "local": KajoLocalParams, "meter": KajoMeterParams, "tone": KajoToneParams, "view": KajoViewParams,
+          "encode": KajoEncodeParams}
+
+# Every chain entry point and its arguments, both in the header's order: `h` the handle, `gathered` the owners' tile buffers, a stage's name
+# its parameter block (NULL = the stage is off), `dst` what the call fills (image, radiance or histogram), `scale` a float and `result` a
+# KajoMeterResult it writes. lib() sets the argtypes from these rows and HipRenderer lays its calls out by them: a new stage is a row here.
+CHAIN_ENTRIES = {
+    "kajo_hip_tonemap_argb8": "h tone denoise dst scale",
+    "kajo_hip_tonemap_gathered_argb8_device": "h gathered tone dst",
+    "kajo_hip_glare": "h glare denoise dst",
+    "kajo_hip_display_argb8": "h denoise glare tone dst scale",
+    "kajo_hip_display_gathered_argb8_device": "h gathered glare tone dst",
+    "kajo_hip_present_argb8": "h despeckle denoise glare tone dst scale",
+    "kajo_hip_present_gathered_argb8_device": "h gathered despeckle glare tone dst",
+    "kajo_hip_meter": "h despeckle denoise glare meter dst result",
+    "kajo_hip_present_metered_argb8": "h despeckle denoise glare meter tone dst result",
+    "kajo_hip_present_metered_gathered_argb8_device": "h gathered despeckle glare meter tone dst result",
+    "kajo_hip_local": "h despeckle denoise glare local dst",
+    "kajo_hip_present_local_argb8": "h despeckle denoise glare local meter tone dst result",
+    "kajo_hip_present_local_gathered_argb8_device": "h gathered despeckle glare local meter tone dst result",
+    "kajo_hip_lens": "h despeckle denoise lens dst",
+    "kajo_hip_present_lens_argb8": "h despeckle denoise lens glare local meter tone dst result",
+    "kajo_hip_present_view_argb8": "h despeckle denoise lens glare local meter tone view dst result",
+    "kajo_hip_present_view_gathered_argb8_device": "h gathered despeckle glare local meter tone view dst result",
+    "kajo_hip_grade": "h despeckle denoise grade dst",
+    "kajo_hip_present_grade_argb8": "h despeckle denoise grade lens glare local meter tone view dst result",
+    "kajo_hip_present_grade_gathered_argb8_device": "h gathered despeckle grade glare local meter tone view dst result",
+    "kajo_hip_encode": "h encode tone dst",
+    "kajo_hip_encode_present": "h despeckle denoise grade lens glare local meter tone encode dst result",
+    "kajo_hip_encode_present_gathered_device": "h gathered despeckle grade glare local meter tone encode dst result",
+    "kajo_hip_encode_view": "h encode tone view dst",
+    "kajo_hip_encode_view_present": "h despeckle denoise grade lens glare local meter tone view encode dst result",
+    "kajo_hip_encode_view_present_gathered_device": "h gathered despeckle grade glare local meter tone view encode dst result",
+}
+
 _lib = None
 
 
@@ -287,137 +324,50 @@ def lib():
             L.kajo_hip_aov_kernel.argtypes = [C.c_void_p]
             L.kajo_hip_aov_kernel.restype = C.c_char_p
         if hasattr(L, "kajo_hip_denoise"):  # (nor the denoiser)
-            L.kajo_hip_default_denoise_params.argtypes = [C.POINTER(KajoDenoiseParams)]
-            L.kajo_hip_default_denoise_params.restype = None
             L.kajo_hip_denoise.argtypes = [C.c_void_p, C.POINTER(KajoDenoiseParams), C.c_void_p, C.c_void_p]
-        if hasattr(L, "kajo_hip_tonemap_argb8"):  # (nor the tone mapping)
-            L.kajo_hip_default_tone_params.argtypes = [C.POINTER(KajoToneParams)]
-            L.kajo_hip_default_tone_params.restype = None
-            L.kajo_hip_tonemap_argb8.argtypes = [C.c_void_p, C.POINTER(KajoToneParams), C.POINTER(KajoDenoiseParams), C.c_void_p,
-                                                 C.POINTER(C.c_float)]
-            L.kajo_hip_tonemap_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoToneParams), C.c_void_p]
+        if hasattr(L, "kajo_hip_tone_scale"):  # (nor the tone mapping)
             L.kajo_hip_tone_scale.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        if hasattr(L, "kajo_hip_glare"):  # (nor the glare)
-            L.kajo_hip_default_glare_params.argtypes = [C.POINTER(KajoGlareParams)]
-            L.kajo_hip_default_glare_params.restype = None
-            L.kajo_hip_glare.argtypes = [C.c_void_p, C.POINTER(KajoGlareParams), C.POINTER(KajoDenoiseParams), C.c_void_p]
-            L.kajo_hip_display_argb8.argtypes = [C.c_void_p, C.POINTER(KajoDenoiseParams), C.POINTER(KajoGlareParams), C.POINTER(KajoToneParams),
-                                                 C.c_void_p, C.POINTER(C.c_float)]
-            L.kajo_hip_display_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoGlareParams), C.POINTER(KajoToneParams),
-                                                                 C.c_void_p]
         if hasattr(L, "kajo_hip_despeckle"):  # (nor the despeckle)
-            L.kajo_hip_default_despeckle_params.argtypes = [C.POINTER(KajoDespeckleParams)]
-            L.kajo_hip_default_despeckle_params.restype = None
             L.kajo_hip_despeckle.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.c_void_p, C.POINTER(C.c_int64)]
             L.kajo_hip_despeckle_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-            L.kajo_hip_present_argb8.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams), C.POINTER(KajoGlareParams),
-                                                 C.POINTER(KajoToneParams), C.c_void_p, C.POINTER(C.c_float)]
-            L.kajo_hip_present_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoGlareParams),
-                                                                 C.POINTER(KajoToneParams), C.c_void_p]
         if hasattr(L, "kajo_hip_meter"):  # (nor the metering)
-            L.kajo_hip_default_meter_params.argtypes = [C.POINTER(KajoMeterParams)]
-            L.kajo_hip_default_meter_params.restype = None
             L.kajo_hip_meter_evaluate.argtypes = [C.c_void_p, C.POINTER(KajoMeterParams), C.POINTER(KajoMeterResult)]
             L.kajo_hip_meter_tone.argtypes = [C.POINTER(KajoMeterResult), C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams),
                                               C.POINTER(KajoToneParams)]
-            L.kajo_hip_meter.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams), C.POINTER(KajoGlareParams),
-                                         C.POINTER(KajoMeterParams), C.c_void_p, C.POINTER(KajoMeterResult)]
-            L.kajo_hip_present_metered_argb8.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams),
-                                                         C.POINTER(KajoGlareParams), C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams),
-                                                         C.c_void_p, C.POINTER(KajoMeterResult)]
-            L.kajo_hip_present_metered_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams),
-                                                                         C.POINTER(KajoGlareParams), C.POINTER(KajoMeterParams),
-                                                                         C.POINTER(KajoToneParams), C.c_void_p, C.POINTER(KajoMeterResult)]
             L.kajo_meter_groups.argtypes = [C.c_int, C.c_int]
         if hasattr(L, "kajo_hip_local"):  # (nor the local tone mapping)
-            L.kajo_hip_default_local_params.argtypes = [C.POINTER(KajoLocalParams)]
-            L.kajo_hip_default_local_params.restype = None
-            L.kajo_hip_local.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams), C.POINTER(KajoGlareParams),
-                                         C.POINTER(KajoLocalParams), C.c_void_p]
-            L.kajo_hip_present_local_argb8.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams),
-                                                       C.POINTER(KajoGlareParams), C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams),
-                                                       C.POINTER(KajoToneParams), C.c_void_p, C.POINTER(KajoMeterResult)]
-            L.kajo_hip_present_local_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams),
-                                                                       C.POINTER(KajoGlareParams), C.POINTER(KajoLocalParams),
-                                                                       C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams), C.c_void_p,
-                                                                       C.POINTER(KajoMeterResult)]
             L.kajo_hip_local_pivot.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         if hasattr(L, "kajo_hip_lens"):  # (nor the depth of field)
-            L.kajo_hip_default_lens_params.argtypes = [C.POINTER(KajoLensParams)]
-            L.kajo_hip_default_lens_params.restype = None
-            L.kajo_hip_lens.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams), C.POINTER(KajoLensParams),
-                                        C.c_void_p]
             L.kajo_hip_lens_coc.argtypes = [C.c_void_p, C.POINTER(KajoLensParams), C.c_void_p, C.c_void_p]
             L.kajo_hip_lens_depth_at.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
-            L.kajo_hip_present_lens_argb8.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams),
-                                                      C.POINTER(KajoLensParams), C.POINTER(KajoGlareParams), C.POINTER(KajoLocalParams),
-                                                      C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams), C.c_void_p,
-                                                      C.POINTER(KajoMeterResult)]
         if hasattr(L, "kajo_hip_view_argb8"):  # (nor the view)
-            L.kajo_hip_default_view_params.argtypes = [C.POINTER(KajoViewParams)]
-            L.kajo_hip_default_view_params.restype = None
             L.kajo_hip_view_weights.argtypes = [C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_size_t]
             L.kajo_hip_view_tables.argtypes = [C.c_void_p, C.c_void_p]
             L.kajo_hip_view_tables.restype = None
             L.kajo_hip_view_argb8.argtypes = [C.c_void_p, C.POINTER(KajoViewParams), C.c_void_p, C.c_void_p]
-            L.kajo_hip_present_view_argb8.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams),
-                                                      C.POINTER(KajoLensParams), C.POINTER(KajoGlareParams), C.POINTER(KajoLocalParams),
-                                                      C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams), C.POINTER(KajoViewParams),
-                                                      C.c_void_p, C.POINTER(KajoMeterResult)]
-            L.kajo_hip_present_view_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams),
-                                                                      C.POINTER(KajoGlareParams), C.POINTER(KajoLocalParams),
-                                                                      C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams),
-                                                                      C.POINTER(KajoViewParams), C.c_void_p, C.POINTER(KajoMeterResult)]
         if hasattr(L, "kajo_hip_grade"):  # (nor the grade)
-            L.kajo_hip_default_grade_params.argtypes = [C.POINTER(KajoGradeParams)]
-            L.kajo_hip_default_grade_params.restype = None
             L.kajo_hip_grade_pixels.argtypes = [C.POINTER(KajoGradeParams), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
             L.kajo_hip_grade_white_balance.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_float * 3)]
             L.kajo_hip_grade_neutral.argtypes = [C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3)]
-            L.kajo_hip_grade.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams), C.POINTER(KajoGradeParams),
-                                         C.c_void_p]
-            L.kajo_hip_present_grade_argb8.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams),
-                                                       C.POINTER(KajoGradeParams), C.POINTER(KajoLensParams), C.POINTER(KajoGlareParams),
-                                                       C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams),
-                                                       C.POINTER(KajoViewParams), C.c_void_p, C.POINTER(KajoMeterResult)]
-            L.kajo_hip_present_grade_gathered_argb8_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams),
-                                                                       C.POINTER(KajoGradeParams), C.POINTER(KajoGlareParams),
-                                                                       C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams),
-                                                                       C.POINTER(KajoToneParams), C.POINTER(KajoViewParams), C.c_void_p,
-                                                                       C.POINTER(KajoMeterResult)]
         if hasattr(L, "kajo_hip_encode"):  # (nor the encode)
-            L.kajo_hip_default_encode_params.argtypes = [C.POINTER(KajoEncodeParams)]
-            L.kajo_hip_default_encode_params.restype = None
             L.kajo_hip_encode_bytes.argtypes = [C.POINTER(KajoEncodeParams), C.c_int, C.c_int, C.POINTER(C.c_size_t)]
             L.kajo_hip_encode_table.argtypes = [C.c_uint32, C.c_float, C.c_void_p, C.c_size_t]
             L.kajo_hip_encode_pixels.argtypes = [C.POINTER(KajoEncodeParams), C.POINTER(KajoToneParams), C.c_void_p, C.c_int64, C.c_int32,
                                                  C.c_int32, C.c_int32, C.c_void_p]
-            L.kajo_hip_encode.argtypes = [C.c_void_p, C.POINTER(KajoEncodeParams), C.POINTER(KajoToneParams), C.c_void_p]
-            L.kajo_hip_encode_present.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams),
-                                                  C.POINTER(KajoGradeParams), C.POINTER(KajoLensParams), C.POINTER(KajoGlareParams),
-                                                  C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams),
-                                                  C.POINTER(KajoEncodeParams), C.c_void_p, C.POINTER(KajoMeterResult)]
-            L.kajo_hip_encode_present_gathered_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams),
-                                                                  C.POINTER(KajoGradeParams), C.POINTER(KajoGlareParams),
-                                                                  C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams),
-                                                                  C.POINTER(KajoToneParams), C.POINTER(KajoEncodeParams), C.c_void_p,
-                                                                  C.POINTER(KajoMeterResult)]
         if hasattr(L, "kajo_hip_encode_view"):  # (nor the float view)
-            L.kajo_hip_encode_view.argtypes = [C.c_void_p, C.POINTER(KajoEncodeParams), C.POINTER(KajoToneParams), C.POINTER(KajoViewParams),
-                                               C.c_void_p]
-            L.kajo_hip_encode_view_present.argtypes = [C.c_void_p, C.POINTER(KajoDespeckleParams), C.POINTER(KajoDenoiseParams),
-                                                       C.POINTER(KajoGradeParams), C.POINTER(KajoLensParams), C.POINTER(KajoGlareParams),
-                                                       C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams), C.POINTER(KajoToneParams),
-                                                       C.POINTER(KajoViewParams), C.POINTER(KajoEncodeParams), C.c_void_p,
-                                                       C.POINTER(KajoMeterResult)]
-            L.kajo_hip_encode_view_present_gathered_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(KajoDespeckleParams),
-                                                                       C.POINTER(KajoGradeParams), C.POINTER(KajoGlareParams),
-                                                                       C.POINTER(KajoLocalParams), C.POINTER(KajoMeterParams),
-                                                                       C.POINTER(KajoToneParams), C.POINTER(KajoViewParams),
-                                                                       C.POINTER(KajoEncodeParams), C.c_void_p, C.POINTER(KajoMeterResult)]
             L.kajo_hip_encode_view_pixels.argtypes = [C.POINTER(KajoEncodeParams), C.POINTER(KajoToneParams), C.POINTER(KajoViewParams),
                                                       C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        # the display chain: the stages' defaults and the entry points' signatures from the two tables
+        slots = dict({stage: C.POINTER(pod) for stage, pod in STAGES.items()}, h=C.c_void_p, gathered=C.c_void_p, dst=C.c_void_p,
+                     scale=C.POINTER(C.c_float), result=C.POINTER(KajoMeterResult))
+        for stage in STAGES:
+            default = getattr(L, "kajo_hip_default_%s_params" % stage, None)
+            if default is not None:
+                default.argtypes, default.restype = [slots[stage]], None
+        for name, row in CHAIN_ENTRIES.items():
+            if hasattr(L, name):
+                getattr(L, name).argtypes = [slots[slot] for slot in row.split()]
         if hasattr(L, "kajo_hip_read_matte"):  # (nor the mattes)
             L.kajo_hip_read_matte.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
             L.kajo_hip_matte_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

@@ -313,13 +313,9 @@ class HipRenderer:
 
     def _denoise_params(self, iterations: int = 5, sigma_luminance: float = None, sigma_normal: float = None, sigma_depth: float = None,
                         demodulate: bool = True, noise_guided: bool = False):
-        p = capi.KajoDenoiseParams()
-        self._L.kajo_hip_default_denoise_params(C.byref(p))
+        p = _stage_params("denoise", sigmaLuminance=sigma_luminance, sigmaNormal=sigma_normal, sigmaDepth=sigma_depth)
         p.iterations = int(iterations)
         p.flags = (0 if demodulate else capi.KAJO_DENOISE_NO_DEMODULATE) | (capi.KAJO_DENOISE_NOISE_GUIDED if noise_guided else 0)
-        for field, value in (("sigmaLuminance", sigma_luminance), ("sigmaNormal", sigma_normal), ("sigmaDepth", sigma_depth)):
-            if value is not None:
-                setattr(p, field, float(value))
         return p
 
     def denoise(self, iterations: int = 5, sigma_luminance: float = None, sigma_normal: float = None, sigma_depth: float = None,
@@ -355,72 +351,35 @@ class HipRenderer:
         = (H, W) uint32 as argb8(), scale = the linear factor s applied to the mean radiance. curve: "clamp" | "reinhard" | "aces".
         denoise: None maps the accumulation; a dict of denoise()'s keyword arguments maps the frame denoise() would give (aov=True). The
         defaults are argb8() bit for bit. The accumulation, the AOVs and the counters are not touched."""
-        p = self._tone_params(curve, exposure, white, auto_exposure, key)
-        d = None
-        if denoise is not None:
-            d = self._denoise_params(**denoise)
-        argb8 = np.empty((self.height, self.width), np.uint32)
-        scale = C.c_float()
-        capi.check(self._L.kajo_hip_tonemap_argb8(self._h, C.byref(p), None if d is None else C.byref(d), argb8.ctypes.data_as(C.c_void_p),
-                                                  C.byref(scale)))
-        return argb8, scale.value
+        tone = dict(curve=curve, exposure=exposure, white=white, auto_exposure=auto_exposure, key=key)
+        return self._chain("kajo_hip_tonemap_argb8", tone=tone, denoise=denoise)
 
     def _tone_params(self, curve: str = "clamp", exposure: float = 0.0, white: float = 0.0, auto_exposure: bool = False, key: float = 0.18):
-        curves = {"clamp": capi.KAJO_TONE_CLAMP, "reinhard": capi.KAJO_TONE_REINHARD, "aces": capi.KAJO_TONE_ACES}
-        if curve not in curves:
-            raise ValueError("curve must be one of %s" % ", ".join(curves))
-        p = capi.KajoToneParams()
-        self._L.kajo_hip_default_tone_params(C.byref(p))
-        p.curve = curves[curve]
+        if curve not in _CURVES:
+            raise ValueError("curve must be one of %s" % ", ".join(_CURVES))
+        p = _tone_curve(curve, exposure, white)
         p.flags = capi.KAJO_TONE_AUTO_EXPOSURE if auto_exposure else 0
-        p.exposure, p.white, p.key = float(exposure), float(white), float(key)
+        p.key = float(key)
         return p
 
     def _glare_params(self, levels: int = None, strength: float = None, threshold: float = None):
-        p = capi.KajoGlareParams()
-        self._L.kajo_hip_default_glare_params(C.byref(p))
-        if levels is not None:
-            p.levels = int(levels)
-        if strength is not None:
-            p.strength = float(strength)
-        if threshold is not None:
-            p.threshold = float(threshold)
-        return p
+        return _stage_params("glare", levels=levels, strength=strength, threshold=threshold)
 
     def glare(self, levels: int = None, strength: float = None, threshold: float = None, denoise: dict = None) -> np.ndarray:
         """The frame after the glare (bloom) pyramid (include/kajo_hip.h kajo_hip_glare): (H, W, 4) float32 sums over passes, as
         radiance(). Arguments left None take kajo_hip_default_glare_params' values (6 levels, strength 0.1, threshold 0). denoise: None
         glares the accumulation; a dict of denoise()'s keyword arguments glares the frame denoise() would give (aov=True). The
         accumulation, the AOVs and the counters are not touched."""
-        g = self._glare_params(levels, strength, threshold)
-        d = None if denoise is None else self._denoise_params(**denoise)
-        out = np.empty((self.height, self.width, 4), np.float32)
-        capi.check(self._L.kajo_hip_glare(self._h, C.byref(g), None if d is None else C.byref(d), out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._chain("kajo_hip_glare", glare=dict(levels=levels, strength=strength, threshold=threshold), denoise=denoise)
 
     def display(self, denoise: dict = None, glare: dict = None, **tone):
         """The display chain (include/kajo_hip.h kajo_hip_display_argb8): denoise (optional) -> glare (optional) -> tone mapping ->
         (argb8, scale) as tonemap(). denoise: a dict of denoise()'s keyword arguments; glare: a dict of glare()'s levels / strength /
         threshold; tone: tonemap()'s curve, exposure, white, auto_exposure, key. With glare None it is tonemap(denoise=denoise, **tone)."""
-        t = self._tone_params(**tone)
-        d = None if denoise is None else self._denoise_params(**denoise)
-        g = None if glare is None else self._glare_params(**glare)
-        argb8 = np.empty((self.height, self.width), np.uint32)
-        scale = C.c_float()
-        capi.check(self._L.kajo_hip_display_argb8(self._h, None if d is None else C.byref(d), None if g is None else C.byref(g), C.byref(t),
-                                                  argb8.ctypes.data_as(C.c_void_p), C.byref(scale)))
-        return argb8, scale.value
+        return self._chain("kajo_hip_display_argb8", tone=tone, denoise=denoise, glare=glare)
 
     def _despeckle_params(self, factor: float = None, rank: int = None, floor: float = None):
-        p = capi.KajoDespeckleParams()
-        self._L.kajo_hip_default_despeckle_params(C.byref(p))
-        if factor is not None:
-            p.factor = float(factor)
-        if rank is not None:
-            p.rank = int(rank)
-        if floor is not None:
-            p.floor = float(floor)
-        return p
+        return _stage_params("despeckle", factor=factor, rank=rank, floor=floor)
 
     def despeckle(self, factor: float = None, rank: int = None, floor: float = None) -> dict:
         """The frame with its NaN / Inf pixels repaired and its fireflies clamped (include/kajo_hip.h kajo_hip_despeckle): radiance =
@@ -440,14 +399,7 @@ class HipRenderer:
         return int(counts[0]), int(counts[1])
 
     def _meter_params(self, percentile: float = None, key: float = None, white_percentile: float = None, auto_white: bool = False):
-        p = capi.KajoMeterParams()
-        self._L.kajo_hip_default_meter_params(C.byref(p))
-        if percentile is not None:
-            p.percentile = float(percentile)
-        if key is not None:
-            p.key = float(key)
-        if white_percentile is not None:
-            p.whitePercentile = float(white_percentile)
+        p = _stage_params("meter", percentile=percentile, key=key, whitePercentile=white_percentile)
         p.flags = capi.KAJO_METER_AUTO_WHITE if auto_white else 0
         return p
 
@@ -461,26 +413,12 @@ class HipRenderer:
         above -- and result = a dict of KajoMeterResult's fields (pixels, nonfinite, under, over, metered, anchorL, whiteL, exposure in
         stops, minBin, maxBin). params: percentile (0.5), key (0.18), white_percentile (0.995), auto_white. The accumulation, the AOVs
         and the counters are not touched."""
-        m = self._meter_params(**params)
-        s = None if despeckle is None else self._despeckle_params(**despeckle)
-        d = None if denoise is None else self._denoise_params(**denoise)
-        g = None if glare is None else self._glare_params(**glare)
-        hist = np.empty(capi.KAJO_METER_BINS, np.uint32)
-        result = capi.KajoMeterResult()
-        ref = lambda p: None if p is None else C.byref(p)
-        capi.check(self._L.kajo_hip_meter(self._h, ref(s), ref(d), ref(g), C.byref(m), hist.ctypes.data_as(C.c_void_p), C.byref(result)))
-        return hist, self._meter_result(result)
+        return self._chain("kajo_hip_meter", meter=params, despeckle=despeckle, denoise=denoise, glare=glare)
 
     def _local_params(self, compression: float = None, detail: float = None, sigma_range: float = None, iterations: int = None,
                       pivot: float = None, metered: bool = False, pivot_percentile: float = None):
-        p = capi.KajoLocalParams()
-        self._L.kajo_hip_default_local_params(C.byref(p))
-        for field, value in (("compression", compression), ("detail", detail), ("sigmaRange", sigma_range), ("pivot", pivot),
-                             ("pivotPercentile", pivot_percentile)):
-            if value is not None:
-                setattr(p, field, float(value))
-        if iterations is not None:
-            p.iterations = int(iterations)
+        p = _stage_params("local", compression=compression, detail=detail, sigmaRange=sigma_range, pivot=pivot,
+                          pivotPercentile=pivot_percentile, iterations=iterations)
         p.flags = capi.KAJO_LOCAL_PIVOT_METERED if metered else 0
         return p
 
@@ -489,14 +427,7 @@ class HipRenderer:
         params: compression (0.6), detail (1), sigma_range (2 stops), iterations (5), pivot (log2(0.18)), metered (the pivot is the
         frame's own pivot_percentile-th luminance, 0.5); those left out take kajo_hip_default_local_params' values. despeckle, denoise,
         glare: the stages in front, as present(). The accumulation, the AOVs and the counters are not touched."""
-        l = self._local_params(**params)
-        s = None if despeckle is None else self._despeckle_params(**despeckle)
-        d = None if denoise is None else self._denoise_params(**denoise)
-        g = None if glare is None else self._glare_params(**glare)
-        out = np.empty((self.height, self.width, 4), np.float32)
-        ref = lambda p: None if p is None else C.byref(p)
-        capi.check(self._L.kajo_hip_local(self._h, ref(s), ref(d), ref(g), C.byref(l), out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._chain("kajo_hip_local", local=params, despeckle=despeckle, denoise=denoise, glare=glare)
 
     def local_pivot(self) -> float:
         """The pivot (log2 luminance) of the most recent local tone mapping (include/kajo_hip.h kajo_hip_local_pivot)."""
@@ -505,28 +436,14 @@ class HipRenderer:
         return pivot.value
 
     def _lens_params(self, aperture: float = None, focus_distance: float = None, max_radius: int = None):
-        p = capi.KajoLensParams()
-        self._L.kajo_hip_default_lens_params(C.byref(p))
-        if aperture is not None:
-            p.aperture = float(aperture)
-        if focus_distance is not None:
-            p.focusDistance = float(focus_distance)
-        if max_radius is not None:
-            p.maxRadius = int(max_radius)
-        return p
+        return _stage_params("lens", aperture=aperture, focusDistance=focus_distance, maxRadius=max_radius)
 
     def lens(self, despeckle: dict = None, denoise: dict = None, **params) -> np.ndarray:
         """The frame after the depth of field (include/kajo_hip.h kajo_hip_lens): (H, W, 4) float32 sums over passes, as radiance().
         params: aperture (0.01, the circle of confusion's radius at infinite depth as a fraction of the frame's height), focus_distance
         (10, in the depth AOV's units), max_radius (16 pixels); those left out take kajo_hip_default_lens_params' values. despeckle,
         denoise: the stages in front, as present(). Needs aov=True. The accumulation, the AOVs and the counters are not touched."""
-        l = self._lens_params(**params)
-        s = None if despeckle is None else self._despeckle_params(**despeckle)
-        d = None if denoise is None else self._denoise_params(**denoise)
-        out = np.empty((self.height, self.width, 4), np.float32)
-        ref = lambda p: None if p is None else C.byref(p)
-        capi.check(self._L.kajo_hip_lens(self._h, ref(s), ref(d), C.byref(l), out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._chain("kajo_hip_lens", lens=params, despeckle=despeckle, denoise=denoise)
 
     def lens_coc(self, **params) -> dict:
         """The depth of field's decisions (include/kajo_hip.h kajo_hip_lens_coc): dict(radius=(H, W) float32 circle of confusion in pixels,
@@ -544,15 +461,7 @@ class HipRenderer:
         return z.value
 
     def _view_params(self, out_w: int = None, out_h: int = None, rect=None, filter=None):
-        p = capi.KajoViewParams()
-        self._L.kajo_hip_default_view_params(C.byref(p))
-        p.outW = self.width if out_w is None else int(out_w)
-        p.outH = self.height if out_h is None else int(out_h)
-        if rect is not None:
-            p.x0, p.y0, p.x1, p.y1 = (float(v) for v in rect)
-        if filter is not None:
-            p.filter = capi.KAJO_VIEW_FILTERS[filter] if isinstance(filter, str) else int(filter)
-        return p
+        return view_params(self.width, self.height, out_w, out_h, rect, filter)
 
     def view(self, image: np.ndarray, **params) -> np.ndarray:
         """The view of a caller's image (include/kajo_hip.h kajo_hip_view_argb8): crop, zoom or supersampled output of an (H, W) uint32
@@ -572,13 +481,7 @@ class HipRenderer:
         grade_params(): slope, offset, power (a number or three), saturation, white_balance (gains multiplied into the slope), regions
         (a list of dicts: objects, amount and the op's keys; they need aov=True, matte=True). despeckle, denoise: the stages in front, as
         present(). The accumulation, the AOVs, the matte tables and the counters are not touched."""
-        p = grade_params(**params)
-        s = None if despeckle is None else self._despeckle_params(**despeckle)
-        d = None if denoise is None else self._denoise_params(**denoise)
-        out = np.empty((self.height, self.width, 4), np.float32)
-        ref = lambda p: None if p is None else C.byref(p)
-        capi.check(self._L.kajo_hip_grade(self._h, ref(s), ref(d), C.byref(p), out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._chain("kajo_hip_grade", grade=params, despeckle=despeckle, denoise=denoise)
 
     def _encoded_array(self, e, v=None):
         h, w = (self.height, self.width) if v is None else (max(v.outH, 0), max(v.outW, 0))
@@ -592,105 +495,66 @@ class HipRenderer:
         and "rgb10a2", (H, W, 4) uint16 for "rgba16", (H, W, 4) float16 for "rgba16f". view: a dict of view()'s params puts the float
         view between the tone curve and the transfer (kajo_hip_encode_view): the array then has the view's shape (out_h, out_w).
         Nothing of the handle's state is touched."""
-        e = encode_params(**(encode or {}))
-        t = self._tone_params(**tone)
-        if view is None:
-            out = self._encoded_array(e)
-            capi.check(self._L.kajo_hip_encode(self._h, C.byref(e), C.byref(t), out.ctypes.data_as(C.c_void_p)))
-            return out
-        v = self._view_params(**view)
-        out = self._encoded_array(e, v)
-        capi.check(self._L.kajo_hip_encode_view(self._h, C.byref(e), C.byref(t), C.byref(v), out.ctypes.data_as(C.c_void_p)))
-        return out
+        return self._chain("kajo_hip_encode" if view is None else "kajo_hip_encode_view", tone=tone, encode=encode or {}, view=view)
 
     def present(self, despeckle: dict = None, denoise: dict = None, glare: dict = None, meter: dict = None, local: dict = None,
                 lens: dict = None, view: dict = None, grade: dict = None, encode: dict = None, **tone):
-        """The display chain with the despeckle in front (include/kajo_hip.h kajo_hip_present_argb8): despeckle -> denoise -> glare ->
-        tone mapping -> (argb8, scale) as tonemap(), every stage but the last optional. despeckle: a dict of despeckle()'s factor / rank /
-        floor; the rest as display(). With despeckle None it is display(denoise, glare, **tone). meter: a dict of meter()'s params puts
-        the metering in front of the tone curves (kajo_hip_present_metered_argb8: exposure becomes a compensation on top of the metered
-        one, auto_white sets Reinhard's white) and makes the second value the result dict of meter() instead of the scale. local: a dict
-        of local()'s params puts the local tone mapping between the glare and the meter (kajo_hip_present_local_argb8; the call is
-        routed there only when it is given). lens: a dict of lens()'s params puts the depth of field between the denoiser and the glare
-        (kajo_hip_present_lens_argb8; likewise routed there only when it is given). view: a dict of view()'s params puts the view behind
-        the tone curves (kajo_hip_present_view_argb8; likewise): the array returned then has the view's shape (out_h, out_w). grade: a dict of
-        grade()'s params puts the grade between the denoiser and the lens (kajo_hip_present_grade_argb8; likewise). encode: a dict of
-        encode_params()'s arguments puts the encode in place of the 8-bit word (kajo_hip_encode_present): the array returned is
-        encode()'s, the second value the result dict of meter() with a meter and None without. With a view beside the encode the float
-        view runs between the tone curve and the transfer (kajo_hip_encode_view_present) and the array has the view's shape."""
-        t = self._tone_params(**tone)
+        """The whole display chain over the handle's frame (include/kajo_hip.h kajo_hip_present_*_argb8, kajo_hip_encode_present), the
+        stages in its order, every one but the tone mapping optional (None = the stage is off):
+          despeckle  a dict of despeckle()'s factor / rank / floor: NaN / Inf pixels repaired, fireflies clamped
+          denoise    a dict of denoise()'s keyword arguments (the handle needs aov=True)
+          grade      a dict of grade()'s params (regions need aov=True, matte=True)
+          lens       a dict of lens()'s params: the depth of field (aov=True)
+          glare      a dict of glare()'s levels / strength / threshold
+          local      a dict of local()'s params: the local tone mapping
+          meter      a dict of meter()'s params: the frame the stages above leave is metered, `exposure` becomes a compensation on top
+                     of the metered one and auto_white sets Reinhard's white
+          tone       the keyword arguments left over, tonemap()'s curve, exposure, white, auto_exposure, key
+          view       a dict of view()'s params: crop, zoom or supersampled output; the array then has the view's shape (out_h, out_w)
+          encode     a dict of encode_params()'s arguments: the transfer, the dither and the format in place of the 8-bit word; a view
+                     then runs in float between the tone curve and the transfer
+        The call goes to the narrowest entry point that takes every stage given. Without encode -> (argb8, second): argb8 (H, W) uint32
+        as argb8(), second the result dict of meter() with a meter, else the scale s as tonemap()'s. With encode -> (array, second): the
+        array as encode()'s, second the result dict of meter() with a meter, else None. The accumulation, the AOVs and the counters are
+        not touched."""
+        stages = dict(tone=tone, encode=encode, despeckle=despeckle, denoise=denoise, grade=grade, lens=lens, glare=glare, local=local,
+                      meter=meter, view=view)
+        given = {stage for stage, spec in stages.items() if spec is not None}
         if encode is not None:
-            ref = lambda p: None if p is None else C.byref(p)
-            e = encode_params(**encode)
-            s = None if despeckle is None else self._despeckle_params(**despeckle)
-            d = None if denoise is None else self._denoise_params(**denoise)
-            c = None if grade is None else grade_params(**grade)
-            f = None if lens is None else self._lens_params(**lens)
-            g = None if glare is None else self._glare_params(**glare)
-            l = None if local is None else self._local_params(**local)
-            m = None if meter is None else self._meter_params(**meter)
-            result = capi.KajoMeterResult()
-            if view is not None:
-                v = self._view_params(**view)
-                out = self._encoded_array(e, v)
-                capi.check(self._L.kajo_hip_encode_view_present(self._h, ref(s), ref(d), ref(c), ref(f), ref(g), ref(l), ref(m), C.byref(t),
-                                                                C.byref(v), C.byref(e), out.ctypes.data_as(C.c_void_p), C.byref(result)))
-                return out, (None if m is None else self._meter_result(result))
-            out = self._encoded_array(e)
-            capi.check(self._L.kajo_hip_encode_present(self._h, ref(s), ref(d), ref(c), ref(f), ref(g), ref(l), ref(m), C.byref(t), C.byref(e),
-                                                       out.ctypes.data_as(C.c_void_p), C.byref(result)))
-            return out, (None if m is None else self._meter_result(result))
-        s = None if despeckle is None else self._despeckle_params(**despeckle)
-        d = None if denoise is None else self._denoise_params(**denoise)
-        g = None if glare is None else self._glare_params(**glare)
-        argb8 = np.empty((self.height, self.width), np.uint32)
-        scale = C.c_float()
-        ref = lambda p: None if p is None else C.byref(p)
-        if grade is not None:
-            c = grade_params(**grade)
-            v = None if view is None else self._view_params(**view)
-            f = None if lens is None else self._lens_params(**lens)
-            l = None if local is None else self._local_params(**local)
-            m = None if meter is None else self._meter_params(**meter)
-            result = capi.KajoMeterResult()
-            if v is not None:
-                argb8 = np.empty((max(v.outH, 0), max(v.outW, 0)), np.uint32)
-            capi.check(self._L.kajo_hip_present_grade_argb8(self._h, ref(s), ref(d), C.byref(c), ref(f), ref(g), ref(l), ref(m), C.byref(t),
-                                                            ref(v), argb8.ctypes.data_as(C.c_void_p), C.byref(result)))
-            return argb8, (self.tone_scale() if m is None else self._meter_result(result))
-        if view is not None:
-            v = self._view_params(**view)
-            f = None if lens is None else self._lens_params(**lens)
-            l = None if local is None else self._local_params(**local)
-            m = None if meter is None else self._meter_params(**meter)
-            result = capi.KajoMeterResult()
-            argb8 = np.empty((max(v.outH, 0), max(v.outW, 0)), np.uint32)
-            capi.check(self._L.kajo_hip_present_view_argb8(self._h, ref(s), ref(d), ref(f), ref(g), ref(l), ref(m), C.byref(t), C.byref(v),
-                                                           argb8.ctypes.data_as(C.c_void_p), C.byref(result)))
-            return argb8, (self.tone_scale() if m is None else self._meter_result(result))
-        if lens is not None:
-            f = self._lens_params(**lens)
-            l = None if local is None else self._local_params(**local)
-            m = None if meter is None else self._meter_params(**meter)
-            result = capi.KajoMeterResult()
-            capi.check(self._L.kajo_hip_present_lens_argb8(self._h, ref(s), ref(d), C.byref(f), ref(g), ref(l), ref(m), C.byref(t),
-                                                           argb8.ctypes.data_as(C.c_void_p), C.byref(result)))
-            return argb8, (self.tone_scale() if m is None else self._meter_result(result))
-        if local is not None:
-            l = self._local_params(**local)
-            m = None if meter is None else self._meter_params(**meter)
-            result = capi.KajoMeterResult()
-            capi.check(self._L.kajo_hip_present_local_argb8(self._h, ref(s), ref(d), ref(g), C.byref(l), ref(m), C.byref(t),
-                                                            argb8.ctypes.data_as(C.c_void_p), C.byref(result)))
-            return argb8, (self.tone_scale() if m is None else self._meter_result(result))
-        if meter is not None:
-            m = self._meter_params(**meter)
-            result = capi.KajoMeterResult()
-            capi.check(self._L.kajo_hip_present_metered_argb8(self._h, ref(s), ref(d), ref(g), C.byref(m), C.byref(t),
-                                                              argb8.ctypes.data_as(C.c_void_p), C.byref(result)))
-            return argb8, self._meter_result(result)
-        capi.check(self._L.kajo_hip_present_argb8(self._h, ref(s), ref(d), ref(g), C.byref(t), argb8.ctypes.data_as(C.c_void_p), C.byref(scale)))
-        return argb8, scale.value
+            entry = "kajo_hip_encode_present" if view is None else "kajo_hip_encode_view_present"
+        else:  # (the host present entries are nested: each takes the stages of the one before it and one more)
+            entry = next(name for name, row in capi.CHAIN_ENTRIES.items()
+                         if name.startswith("kajo_hip_present_") and name.endswith("_argb8") and given <= set(row.split()))
+        return self._chain(entry, **stages)
+
+    def _chain(self, entry: str, **stages):
+        """The one call site of the chain entry points (capi.CHAIN_ENTRIES): stages = a dict of its builder's arguments per stage (None =
+        the stage is off), built in the order given. The output is allocated by what the entry fills, the arguments laid out by the
+        entry's row. -> the array; with a `scale` slot (array, scale); with a `result` slot (array, the result dict of meter() with a
+        meter, else None for an encoded array and tone_scale() for an 8-bit one)."""
+        slots = capi.CHAIN_ENTRIES[entry].split()
+        builder = lambda stage: {"grade": grade_params, "encode": encode_params}.get(stage) or getattr(self, "_%s_params" % stage)
+        pods = {stage: builder(stage)(**spec) for stage, spec in stages.items() if spec is not None}
+        assert set(pods) <= set(slots), (entry, sorted(pods))
+        view = pods.get("view")
+        if "encode" in slots:
+            out = self._encoded_array(pods["encode"], view)
+        elif "tone" in slots:
+            out = np.empty((self.height, self.width) if view is None else (max(view.outH, 0), max(view.outW, 0)), np.uint32)
+        elif "result" in slots:  # (the meter alone)
+            out = np.empty(capi.KAJO_METER_BINS, np.uint32)
+        else:
+            out = np.empty((self.height, self.width, 4), np.float32)
+        scale, result = C.c_float(), capi.KajoMeterResult()
+        fixed = dict(h=self._h, dst=out.ctypes.data_as(C.c_void_p), scale=C.byref(scale), result=C.byref(result))
+        capi.check(getattr(self._L, entry)(*[fixed[slot] if slot in fixed else _ref(pods.get(slot)) for slot in slots]))
+        if "scale" in slots:
+            return out, scale.value
+        if "result" not in slots:
+            return out
+        if "meter" in pods:
+            return out, self._meter_result(result)
+        return out, (None if "encode" in slots else self.tone_scale())
 
     def tone_scale(self) -> float:
         """The scale s of the most recent tone mapping (include/kajo_hip.h kajo_hip_tone_scale)."""
@@ -763,6 +627,30 @@ class HipRenderer:
         capi.check(self._L.kajo_hip_compose_aov(self._h, C.c_void_p(gathered_aov_ptr), C.c_void_p(gathered_matte_ptr)))
 
 
+def _ref(p):
+    return None if p is None else C.byref(p)
+
+
+def _stage_params(stage, **fields):
+    """The stage's parameter block (capi.STAGES) at its defaults, with the fields that were given (not None) set."""
+    p = capi.STAGES[stage]()
+    getattr(capi.lib(), "kajo_hip_default_%s_params" % stage)(C.byref(p))
+    for field, value in fields.items():
+        if value is not None:
+            setattr(p, field, type(getattr(p, field))(value))  # int() or float(), by the field
+    return p
+
+
+_CURVES = {"clamp": capi.KAJO_TONE_CLAMP, "reinhard": capi.KAJO_TONE_REINHARD, "aces": capi.KAJO_TONE_ACES}
+
+
+def _tone_curve(curve, exposure, white):
+    """KajoToneParams of a curve's name (KeyError where unknown), an exposure and a white point: no automatic exposure."""
+    p = _stage_params("tone")
+    p.curve, p.exposure, p.white = _CURVES[curve], float(exposure), float(white)
+    return p
+
+
 def _grade_op(op, slope=None, offset=None, power=None, saturation=None):
     for field, value in (("slope", slope), ("offset", offset), ("power", power)):
         if value is not None:
@@ -776,8 +664,7 @@ def grade_params(slope=None, offset=None, power=None, saturation=None, white_bal
     1) and saturation (1); white_balance = gains (grade_white_balance(), grade_neutral()) multiplied into the slope in binary64 and
     rounded once; regions = up to four dicts of objects (ids as matte_mask() takes them), amount (1) and the op's keys. Nothing is
     checked here: the library refuses what is out of range."""
-    p = capi.KajoGradeParams()
-    capi.lib().kajo_hip_default_grade_params(C.byref(p))
+    p = _stage_params("grade")
     if white_balance is not None:
         base = np.broadcast_to(np.asarray(1.0 if slope is None else slope, np.float64), (3,))
         slope = base * np.asarray(white_balance, np.float64)
@@ -833,15 +720,12 @@ def encode_params(format="argb8", transfer=None, dither: bool = False, scene: bo
     """KajoEncodeParams (include/kajo_hip.h "The encode"): format "argb8" | "rgb10a2" | "rgba16" | "rgba16f", transfer "gamma22" | "srgb" |
     "pq" | "linear" (or the KAJO_ENCODE_* / KAJO_TRANSFER_* values; the transfer defaults to "linear" for "rgba16f", else to "gamma22"),
     dither, scene (scene-linear halves), peak_nits for "pq", dither_seed."""
-    p = capi.KajoEncodeParams()
-    capi.lib().kajo_hip_default_encode_params(C.byref(p))
+    p = _stage_params("encode", peakNits=peak_nits)
     p.format = capi.KAJO_ENCODE_FORMATS[format] if isinstance(format, str) else int(format)
     if transfer is None:
         transfer = "linear" if p.format == capi.KAJO_ENCODE_RGBA16F else "gamma22"
     p.transfer = capi.KAJO_TRANSFERS[transfer] if isinstance(transfer, str) else int(transfer)
     p.flags = (capi.KAJO_ENCODE_DITHER if dither else 0) | (capi.KAJO_ENCODE_SCENE if scene else 0)
-    if peak_nits is not None:
-        p.peakNits = float(peak_nits)
     p.ditherSeed = int(dither_seed) & 0xFFFFFFFF
     return p
 
@@ -863,10 +747,7 @@ def encode_pixels(mean_rgb, encode: dict = None, x0: int = 0, y0: int = 0, row_w
     words, uint32 or uint64 by the format. The pixels are row-major in a rectangle row_width wide (default: all in one row) whose first
     pixel is (x0, y0) of the frame; that matters to the dither only."""
     e = encode if isinstance(encode, capi.KajoEncodeParams) else encode_params(**(encode or {}))
-    curves = {"clamp": capi.KAJO_TONE_CLAMP, "reinhard": capi.KAJO_TONE_REINHARD, "aces": capi.KAJO_TONE_ACES}
-    t = capi.KajoToneParams()
-    capi.lib().kajo_hip_default_tone_params(C.byref(t))
-    t.curve, t.exposure, t.white = curves[curve], float(exposure), float(white)
+    t = _tone_curve(curve, exposure, white)
     m = np.ascontiguousarray(mean_rgb, np.float32).reshape(-1, 3)
     wide = e.format in (capi.KAJO_ENCODE_RGBA16, capi.KAJO_ENCODE_RGBA16F)
     out = np.zeros(len(m), np.uint64 if wide else np.uint32)
@@ -878,8 +759,7 @@ def encode_pixels(mean_rgb, encode: dict = None, x0: int = 0, y0: int = 0, row_w
 def view_params(width: int, height: int, out_w: int = None, out_h: int = None, rect=None, filter=None):
     """KajoViewParams (include/kajo_hip.h "The view") for a width x height frame, as HipRenderer.view()'s params: out_w, out_h (the frame's
     size where left out), rect (x0, y0, x1, y1) in source pixels (the whole frame where left out), filter (a name or a KAJO_VIEW_* value)."""
-    p = capi.KajoViewParams()
-    capi.lib().kajo_hip_default_view_params(C.byref(p))
+    p = _stage_params("view")
     p.outW = int(width) if out_w is None else int(out_w)
     p.outH = int(height) if out_h is None else int(out_h)
     if rect is not None:
@@ -899,10 +779,7 @@ def encode_view_pixels(mean_rgb, encode: dict = None, view: dict = None, curve: 
     H, W = m.shape[:2]
     e = encode if isinstance(encode, capi.KajoEncodeParams) else encode_params(**(encode or {}))
     v = view if isinstance(view, capi.KajoViewParams) or view is None else view_params(W, H, **view)
-    curves = {"clamp": capi.KAJO_TONE_CLAMP, "reinhard": capi.KAJO_TONE_REINHARD, "aces": capi.KAJO_TONE_ACES}
-    t = capi.KajoToneParams()
-    capi.lib().kajo_hip_default_tone_params(C.byref(t))
-    t.curve, t.exposure, t.white = curves[curve], float(exposure), float(white)
+    t = _tone_curve(curve, exposure, white)
     wide = e.format in (capi.KAJO_ENCODE_RGBA16, capi.KAJO_ENCODE_RGBA16F)
     shape = (H, W) if v is None else (max(v.outH, 0), max(v.outW, 0))
     out = np.zeros(shape, np.uint64 if wide else np.uint32)
