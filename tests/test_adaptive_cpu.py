@@ -4,17 +4,16 @@ kajo_hip_adapt_evaluate, against a float64 numpy restatement; the filter of the 
 model, and under AddressSanitizer + UBSan in a program of its own (tools/adapt_san.cpp); the Makefile's plan, what the compiler made of
 the three kernels, and that the device code of every kernel from before is what it was, against digests recorded from the parent commit."""
 import ctypes as C
-import importlib.util
 import json
 import os
 import re
 import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import devicecode
 from kajo_amd import capi
 from kajo_amd.renderer import NOISE_MOMENTS, AdaptParams, adapt_evaluate, adapt_order
 
@@ -337,13 +336,8 @@ def test_the_slot_to_pixel_arithmetic_is_the_exact_inverse_of_the_tile_map_at_ev
 
 # ---- the build -----------------------------------------------------------------------------------------------------------------------
 
-def _need_tools():
-    if shutil.which("hipcc") is None or shutil.which("make") is None:
-        pytest.skip("hipcc / make not available")
-
-
 def test_the_new_unit_is_in_both_link_lines_and_there_is_no_third_library():
-    _need_tools()
+    devicecode.need_tools()
     plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, "all", "tune"], capture_output=True, text=True, check=True).stdout
     links = [l for l in plan.splitlines() if l.startswith("hipcc") and " -shared " in l]
     assert len(links) == 2 and all("adapt_kernels.o" in l and "noise.o" in l for l in links), links
@@ -358,36 +352,14 @@ def test_the_new_unit_is_in_both_link_lines_and_there_is_no_third_library():
 
 
 def test_adaptive_kernels_spill_nothing_and_use_no_scratch_or_flat_access():
-    _need_tools()
-    obj = os.path.join(CSRC, "build", "adapt_kernels.o")
-    plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, obj], capture_output=True, text=True, check=True).stdout
-    cmd = next(l for l in plan.splitlines() if l.startswith("hipcc") and "/adapt_kernels.cpp" in l).split()
-    tmp = tempfile.mkdtemp(prefix="kajo_adapt_res_")
-    asm = os.path.join(tmp, "k.s")
-    i = cmd.index("-c")
-    cmd = cmd[:i] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + cmd[i + 1:]
-    cmd[cmd.index("-o") + 1] = asm
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" [")[0]] = int(m.group(2))
-    text = open(asm).read()
-    shutil.rmtree(tmp, ignore_errors=True)
+    b = devicecode.build("adapt_kernels.cpp")
+    res, text = b.resources, b.asm
     assert sorted(res) == sorted(KERNELS), sorted(res)
     for k in KERNELS:
         r = res[k]
         print(k, r)
         assert r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0 and r["ScratchSize"] == 0 and r["Occupancy"] == 8, (k, r)
-        body = text[text.index("\n" + k + ":"):]
-        body = body[:body.index(".Lfunc_end")]
+        body = devicecode.body(text, k, end=".Lfunc_end")
         assert not re.search(r"\n\s+flat_\w+", body) and not re.search(r"\n\s+scratch_\w+", body), k
         stores = re.findall(r"\n\s+(global_store_\w+)", body)
         loads = re.findall(r"\n\s+(global_load_\w+)", body)
@@ -412,16 +384,14 @@ def test_the_device_code_of_every_kernel_from_before_is_unchanged_function_by_fu
     """tests/golden/kernel_digests_before_adaptive.json: tools/kernel_digests.py over the parent commit -- all fourteen device units, the
     noise estimate's among them. The working tree must give the same functions with the same digests: adaptive sampling moved no kernel.
     (Its own unit is HIP source in a .cpp file, which the tool, made for the .hip units, does not list.)"""
-    _need_tools()
-    spec = importlib.util.spec_from_file_location("kernel_digests", os.path.join(ROOT, "tools", "kernel_digests.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+    devicecode.need_tools()
+    tool = devicecode.digest_tool()
     recorded = json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_digests_before_adaptive.json")))
     before = recorded["units"]
     assert sorted(before) == sorted(["kernel_fast", "kernel_exact", "kernel_strict", "aux_kernels", "denoise", "glare", "despeckle", "meter", "local",
                                      "lens", "view", "matte", "grade", "noise"])
     assert sorted(before["noise"]) == ["kajo_noise_map", "kajo_noise_update"] and sum(len(f) for f in before.values()) > 100
-    now = tool.digests(CSRC)
+    now = devicecode.digests_now()
     where = "(recorded with %s; this is %s)" % (recorded["compiler"], tool.compiler())
     assert sorted(now) == sorted(before), (sorted(now), where)
     for unit in before:

@@ -4,53 +4,23 @@ present in both kernel translation units, nothing spilled, no scratch, no FLAT m
 tests/test_kernel_resources_cpu.py). The compile command is the Makefile's own (`make -n`)."""
 import os
 import re
-import shutil
 import subprocess
-import tempfile
 
 import pytest
 
+import devicecode
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "kajo_amd", "csrc")
 BIN = os.path.join(ROOT, "kajo_amd", "host", "kajo_render")
 INSTANCES = ("", "_big", "_big_lg", "_biglist", "_biglist_lg")
 
 
 def _compile(unit):
     """(resource remarks per kernel, assembly) of kernel_<unit>.hip compiled as the Makefile compiles it (device code only)."""
-    if shutil.which("hipcc") is None or shutil.which("make") is None:
-        pytest.skip("hipcc / make not available")
-    obj = os.path.join(CSRC, "build", "kernel_%s.o" % unit)
-    plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, obj], capture_output=True, text=True, check=True).stdout
-    cmd = next(l for l in plan.splitlines() if l.startswith("hipcc") and "kernel_%s.hip" % unit in l).split()
-    tmp = tempfile.mkdtemp(prefix="kajo_aov_res_")
-    asm = os.path.join(tmp, "k.s")
-    i = cmd.index("-c")
-    cmd = cmd[:i] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + cmd[i + 1:]
-    cmd[cmd.index("-o") + 1] = asm
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|SGPRs Spill|VGPRs Spill|Occupancy \[waves/SIMD\]|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" [")[0]] = int(m.group(2))
-    text = open(asm).read()
-    shutil.rmtree(tmp, ignore_errors=True)
-    return res, text
-
-
-def _body(asm, kernel):
-    body = asm[asm.index("\n" + kernel + ":"):]
-    return body[:body.index("s_endpgm")]
+    b = devicecode.build("kernel_%s.hip" % unit)
+    return b.resources, b.asm
 
 
 def test_header_and_binding_agree_on_the_flag():
@@ -89,7 +59,7 @@ def test_aov_kernels_present_spill_nothing_and_use_no_scratch_or_flat(unit):
         assert k in res, (k, sorted(res))
         r = res[k]
         assert r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0 and r["ScratchSize"] == 0, (k, r)
-        body = _body(asm, k)
+        body = devicecode.body(asm, k)
         assert not re.search(r"\n\s+flat_\w+", body), (k, re.findall(r"\n\s+(flat_\w+)", body)[:5])
         assert not re.search(r"\n\s+scratch_\w+", body), k
         # the sums are written with plain vector stores to global memory

@@ -5,6 +5,7 @@ stratum sy * n + sx (np.sum would add pairwise: not that order). No GPU."""
 import numpy as np
 import pytest
 
+from framelib import bits
 from kajo_amd.scene import stress_scene
 from oraclelib import OracleLib, available, camera_ray
 
@@ -40,10 +41,6 @@ def replay_per_sample(sc, passes, w, h, spp, seed=SEED):
             B[:, :3] += normal
             B[:, 3] += depth
     return A.reshape(h, w, 4), B.reshape(h, w, 4)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _scene(scenes, which):

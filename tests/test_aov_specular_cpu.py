@@ -14,17 +14,14 @@ from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 from oraclelib import OracleLib, available
 
+import devicecode
 from aov_specular_replay import describe, material_tables, replay_specular, without_delta
-from test_aov_cpu import _body, _compile
+from framelib import bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "kajo_amd", "host", "kajo_render")
 INSTANCES = ("", "_big", "_big_lg", "_biglist", "_biglist_lg")
 SEED = 0o715517
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def test_header_and_binding_agree_on_the_flag():
@@ -61,7 +58,8 @@ def test_driver_refuses_the_modifier_alone(tmp_path):
 
 @pytest.mark.parametrize("unit", ["strict", "fast"])
 def test_new_instances_present_and_within_the_budget(unit):
-    res, asm = _compile(unit)
+    b = devicecode.build("kernel_%s.hip" % unit)
+    res, asm = b.resources, b.asm
     for suffix in INSTANCES:
         k = "kajo_aov_%s_spec%s" % (unit, suffix)
         assert k in res, (k, sorted(res))
@@ -69,13 +67,13 @@ def test_new_instances_present_and_within_the_budget(unit):
         print(k, r)
         assert r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0 and r["ScratchSize"] == 0, (k, r)
         assert r["Occupancy"] >= 5, (k, r)
-        body = _body(asm, k)
+        body = devicecode.body(asm, k)
         assert not re.search(r"\n\s+flat_\w+", body), (k, re.findall(r"\n\s+(flat_\w+)", body)[:5])
         assert not re.search(r"\n\s+scratch_\w+", body), k
         assert not re.search(r"\n\s+\w*atomic\w*", body), k
         assert re.search(r"\n\s+global_store_dwordx4", body), k
     if unit == "strict":  # EXACT handles run the STRICT instances
-        res_e, _ = _compile("exact")
+        res_e = devicecode.build("kernel_exact.hip").resources
         assert not [k for k in res_e if k.startswith("kajo_aov")]
 
 

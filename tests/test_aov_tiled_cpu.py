@@ -9,9 +9,9 @@ import subprocess
 
 import pytest
 
+import devicecode
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
-from test_aov_cpu import _compile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "kajo_amd", "host", "kajo_render")
@@ -86,7 +86,7 @@ def test_aov_kernels_spill_nothing_and_take_no_more_registers_than_before(unit):
     """The tiled shape is a run-time argument of the existing instances, which are every AOV kernel the library can launch: none uses
     scratch or spills a vector register, and none has more VGPRs than before the argument was added."""
     before = json.load(open(os.path.join(ROOT, "tests", "golden", "aov_kernel_vgprs.json")))
-    res, _ = _compile(unit)
+    res = devicecode.build("kernel_%s.hip" % unit).resources
     names = ["kajo_aov_%s%s%s" % (unit, v, c) for v in VARIANTS for c in CLASSES]
     assert sorted(k for k in res if k.startswith("kajo_aov_")) == sorted(names)
     for k in names:

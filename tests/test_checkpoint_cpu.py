@@ -8,12 +8,12 @@ import os
 import re
 import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import checkpointlib as ck
+import devicecode
 from kajo_amd import capi
 from kajo_amd.renderer import checkpoint_info, checkpoint_merge
 from kajo_amd.tiles import TileLayout
@@ -255,32 +255,9 @@ def test_merge_refusals():
 # ---- the kernels ------------------------------------------------------------------------------------------------------------------------
 
 def _compile():
-    if shutil.which("hipcc") is None or shutil.which("make") is None:
-        pytest.skip("hipcc / make not available")
-    obj = os.path.join(CSRC, "build", "checkpoint_kernels.o")
-    plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, obj], capture_output=True, text=True, check=True).stdout
-    cmd = next(l for l in plan.splitlines() if l.startswith("hipcc") and "checkpoint_kernels.cpp" in l).split()
-    assert "--offload-arch=gfx950" in cmd
-    tmp = tempfile.mkdtemp(prefix="kajo_ckpt_res_")
-    asm = os.path.join(tmp, "k.s")
-    i = cmd.index("-c")
-    cmd = cmd[:i] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + cmd[i + 1:]
-    cmd[cmd.index("-o") + 1] = asm
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" [")[0]] = int(m.group(2))
-    text = open(asm).read()
-    shutil.rmtree(tmp, ignore_errors=True)
-    return res, text
+    b = devicecode.build("checkpoint_kernels.cpp")
+    assert "--offload-arch=gfx950" in b.cmd
+    return b.resources, b.asm
 
 
 def test_checkpoint_kernels_spill_nothing_and_use_no_scratch_flat_or_atomics():
@@ -289,15 +266,13 @@ def test_checkpoint_kernels_spill_nothing_and_use_no_scratch_flat_or_atomics():
     for k in KERNELS:
         r = res[k]
         assert r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0 and r["ScratchSize"] == 0, (k, r)
-        body = asm[asm.index("\n" + k + ":"):]
-        body = body[:body.index("s_endpgm")]
+        body = devicecode.body(asm, k)
         assert not re.search(r"\n\s+flat_\w+", body), (k, re.findall(r"\n\s+(flat_\w+)", body)[:5])
         assert not re.search(r"\n\s+scratch_\w+", body), k
         assert not re.search(r"\n\s+\w*atomic\w*", body), k
     # the records move as 16-byte vectors
     for k in ("kajo_ckpt_pack", "kajo_ckpt_unpack"):
-        body = asm[asm.index("\n" + k + ":"):]
-        body = body[:body.index("s_endpgm")]
+        body = devicecode.body(asm, k)
         assert re.search(r"\n\s+global_load_dwordx4", body) and re.search(r"\n\s+global_store_dwordx4", body), k
 
 

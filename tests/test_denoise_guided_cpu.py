@@ -6,12 +6,11 @@ instruction, no atomic), and the driver's refusal of --denoise-noise-guided with
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
-import tempfile
 
 import pytest
 
+import devicecode
 from kajo_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,59 +68,25 @@ def test_the_flag_with_out_of_range_iterations_is_refused_for_the_iterations(ite
     assert L.kajo_hip_last_error().decode() == "null handle"
 
 
-def _make_plan(*targets):
-    if shutil.which("hipcc") is None or shutil.which("make") is None:
-        pytest.skip("hipcc / make not available")
-    return subprocess.run(["make", "-n", "-B", "-C", CSRC, *targets], capture_output=True, text=True, check=True).stdout
-
-
-def _unit_command():
-    plan = _make_plan(os.path.join(CSRC, "build", "denoise_guided.o"))
-    return next(l for l in plan.splitlines() if l.startswith("hipcc") and "denoise_guided.cpp" in l).split()
-
-
 def test_makefile_compiles_the_unit_as_hip_without_contraction_and_links_it_into_the_product_and_the_tools_twin():
-    cmd = _unit_command()
+    devicecode.need_tools()
+    cmd = devicecode.compile_command("denoise_guided.cpp")
     assert "-ffp-contract=off" in cmd and "-ffp-contract=fast" not in cmd
     assert cmd[cmd.index("-x") + 1] == "hip" and "--offload-arch=gfx950" in cmd
-    plan = _make_plan("all", "tune")
+    plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, "all", "tune"], capture_output=True, text=True, check=True).stdout
     links = [l for l in plan.splitlines() if l.startswith("hipcc") and " -shared " in l]
     assert len(links) == 2 and all("denoise_guided.o" in l and "denoise.o" in l for l in links), links
 
 
-def _compile():
-    cmd = _unit_command()
-    tmp = tempfile.mkdtemp(prefix="kajo_denoise_guided_res_")
-    asm = os.path.join(tmp, "k.s")
-    i = cmd.index("-c")
-    cmd = cmd[:i] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + cmd[i + 1:]
-    cmd[cmd.index("-o") + 1] = asm
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" [")[0]] = int(m.group(2))
-    text = open(asm).read()
-    shutil.rmtree(tmp, ignore_errors=True)
-    return res, text
-
-
 def test_the_units_kernels_spill_nothing_and_use_no_scratch_flat_or_atomics():
-    res, asm = _compile()
+    b = devicecode.build("denoise_guided.cpp")
+    res, asm = b.resources, b.asm
     assert sorted(res) == sorted(KERNELS), sorted(res)
     for k in KERNELS:
         r = res[k]
         print(k, r)
         assert r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0 and r["ScratchSize"] == 0, (k, r)
-        body = asm[asm.index("\n" + k + ":"):]
-        body = body[:body.index("s_endpgm")]
+        body = devicecode.body(asm, k)
         assert not re.search(r"\n\s+flat_\w+", body), (k, re.findall(r"\n\s+(flat_\w+)", body)[:5])
         assert not re.search(r"\n\s+scratch_\w+", body), k
         assert not re.search(r"\n\s+\w*atomic\w*", body), k

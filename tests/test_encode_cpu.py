@@ -16,6 +16,7 @@ import zlib
 import numpy as np
 import pytest
 
+import devicecode
 from kajo_amd import capi
 from kajo_amd.renderer import encode_params, encode_pixels, encode_table
 import encode_replay as R
@@ -335,30 +336,8 @@ def test_makefile_compiles_the_stage_once_and_links_it_twice():
 
 def test_the_kernel_keeps_its_budget():
     """no scratch, no spill, and the LDS the source's comment states: the table, 8194 floats"""
-    if shutil.which("hipcc") is None or shutil.which("make") is None:
-        pytest.skip("hipcc / make not available")
-    obj = os.path.join(CSRC, "build", "encode.o")
-    plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, obj], capture_output=True, text=True, check=True).stdout
-    cmd = next(l for l in plan.splitlines() if l.startswith("hipcc") and "/encode.cpp" in l).split()
-    tmp = tempfile.mkdtemp(prefix="kajo_encode_res_")
-    i = cmd.index("-c")
-    cmd = cmd[:i] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + cmd[i + 1:]
-    asm = os.path.join(tmp, "k.s")
-    cmd[cmd.index("-o") + 1] = asm
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    body = open(asm).read() if os.path.exists(asm) else ""
-    shutil.rmtree(tmp, ignore_errors=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" [")[0]] = int(m.group(2))
+    b = devicecode.build("encode.cpp")
+    res, body = b.resources, b.asm
     assert sorted(res) == ["kajo_encode"], sorted(res)
     k = res["kajo_encode"]
     print(k)

@@ -12,6 +12,7 @@ import tempfile
 import numpy as np
 import pytest
 
+import devicecode
 from kajo_amd import capi
 from kajo_amd.renderer import encode_params, encode_pixels, encode_view_pixels, view_params
 import encode_view_replay as R
@@ -257,30 +258,8 @@ def test_the_kernels_keep_their_budgets():
     """no scratch, no spill; the LDS the source's comment states: rows 3 planes x 4 rows x 256 floats + 64 (first, end) pairs = 12800 bytes,
     columns the table, 32776 bytes; the registers and the occupancy of this build (gfx950, -O3), pinned as tests/test_view_cpu.py pins
     the view's"""
-    if shutil.which("hipcc") is None or shutil.which("make") is None:
-        pytest.skip("hipcc / make not available")
-    obj = os.path.join(CSRC, "build", "encode_view.o")
-    plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, obj], capture_output=True, text=True, check=True).stdout
-    cmd = next(l for l in plan.splitlines() if l.startswith("hipcc") and "/encode_view.cpp" in l).split()
-    tmp = tempfile.mkdtemp(prefix="kajo_encode_view_res_")
-    i = cmd.index("-c")
-    cmd = cmd[:i] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + cmd[i + 1:]
-    asm = os.path.join(tmp, "k.s")
-    cmd[cmd.index("-o") + 1] = asm
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    body = open(asm).read() if os.path.exists(asm) else ""
-    shutil.rmtree(tmp, ignore_errors=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" [")[0]] = int(m.group(2))
+    b = devicecode.build("encode_view.cpp")
+    res, body = b.resources, b.asm
     assert sorted(res) == ["kajo_encode_view_columns", "kajo_encode_view_rows"], sorted(res)
     print(res)
     for k in res.values():

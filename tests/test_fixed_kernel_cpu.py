@@ -9,9 +9,11 @@ import os
 import re
 import shutil
 import subprocess
-import tempfile
 
 import pytest
+
+import devicecode
+from framelib import bits as _bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "kajo_amd", "csrc")
@@ -39,36 +41,11 @@ def _make_line(target_src):
     return plan, next(l for l in plan.splitlines() if l.startswith("hipcc") and target_src in l and " -c " in l)
 
 
-def _need_tools():
-    if shutil.which("hipcc") is None or shutil.which("make") is None:
-        pytest.skip("hipcc / make not available")
-
-
 @pytest.fixture(scope="module")
 def compiled():
     """(resource remarks per kernel, device assembly) of the unit, by the Makefile's own command"""
-    _need_tools()
-    cmd = _make_line("kernel_exact_fixed.cpp")[1].split()
-    tmp = tempfile.mkdtemp(prefix="kajo_fixed_")
-    asm = os.path.join(tmp, "k.s")
-    i = cmd.index("-c")
-    cmd = cmd[:i] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + cmd[i + 1:]
-    cmd[cmd.index("-o") + 1] = asm
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|SGPRs Spill|VGPRs Spill|Occupancy \[waves/SIMD\]|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" [")[0]] = int(m.group(2))
-    text = open(asm).read()
-    shutil.rmtree(tmp, ignore_errors=True)
-    return res, text
+    b = devicecode.build("kernel_exact_fixed.cpp")
+    return b.resources, b.asm
 
 
 def test_the_table_is_small_and_holds_the_benchmarked_scene(scenes):
@@ -87,8 +64,7 @@ def test_the_unit_holds_exactly_the_tables_kernels_within_the_budgets(compiled):
         kernel = name_of(pair)
         r = res[kernel]
         assert r["Occupancy"] == 5 and r["VGPRs"] <= 96 and r["VGPRs Spill"] == 0 and r["ScratchSize"] == 0, (kernel, r)
-        body = asm[asm.index("\n" + kernel + ":"):]
-        body = body[:body.index("s_endpgm")]
+        body = devicecode.body(asm, kernel)
         assert not re.search(r"\n\s+flat_(load|store|atomic)", body) and not re.search(r"\n\s+scratch_", body), kernel
         assert "v_div_scale_f32" not in body and "v_div_fmas_f32" not in body and "v_div_fixup_f32" in body, kernel
         n = len(re.findall(r"\n\s+v_\w+", body))
@@ -105,13 +81,12 @@ def test_the_walk_is_straight_line_code(compiled):
     elsewhere = 8
     for p, s in table():
         kernel = name_of((p, s))
-        body = asm[asm.index("\n" + kernel + ":"):]
-        body = body[:body.index("s_endpgm")]
+        body = devicecode.body(asm, kernel)
         assert body.count("v_div_fixup_f32") == elsewhere + p + 2 * s, (kernel, body.count("v_div_fixup_f32"))
 
 
 def test_the_makefile_compiles_it_with_the_exact_units_flags_and_links_it():
-    _need_tools()
+    devicecode.need_tools()
     plan, fixed = _make_line("kernel_exact_fixed.cpp")
     strip = lambda l, src, obj: [w for w in l.split() if w not in ("-x", "hip") and not w.endswith(src) and not w.endswith(obj)]
     exact = next(l for l in plan.splitlines() if l.startswith("hipcc") and l.rstrip().split()[-3].endswith("kernel_exact.hip"))
@@ -186,11 +161,6 @@ FAMILY_FRAMES = [(64, 16), (72, 40)]
 FAMILY_S, FAMILY_PASSES, FAMILY_SEED = 4, 5, 0o715517
 FAMILY_NAMES = (["light_at_%d" % k for k in range(4)] + ["planes_reversed", "materials_1", "materials_2", "materials_19", "nested", "overlapping",
                 "coincident", "touching_floor", "light_in_ceiling", "camera_in_glass", "test_a1", "spheres_a1"])
-
-
-def _bits(a):
-    import numpy as np
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def test_the_family_is_what_it_says(scenes):

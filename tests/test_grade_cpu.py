@@ -9,11 +9,11 @@ import os
 import re
 import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import devicecode
 from kajo_amd import capi
 from kajo_amd.renderer import grade_neutral, grade_params, grade_pixels, grade_white_balance
 from grade_replay import XYZ_TO_SRGB, fill, illuminant_rgb, planckian_xy, restate32, restate64
@@ -463,31 +463,9 @@ KERNELS = {"kajo_grade_global": (22, 8), "kajo_grade_regions": (42, 8)}
 
 
 def test_grade_kernels_keep_their_budgets():
-    if shutil.which("hipcc") is None or shutil.which("make") is None:
-        pytest.skip("hipcc / make not available")
-    obj = os.path.join(CSRC, "build", "grade.o")
-    plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, obj], capture_output=True, text=True, check=True).stdout
-    cmd = next(l for l in plan.splitlines() if l.startswith("hipcc") and "grade.hip" in l).split()
-    assert "-ffp-contract=off" in cmd and "--offload-arch=gfx950" in cmd
-    tmp = tempfile.mkdtemp(prefix="kajo_grade_res_")
-    i = cmd.index("-c")
-    cmd = cmd[:i] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + cmd[i + 1:]
-    asm = os.path.join(tmp, "k.s")
-    cmd[cmd.index("-o") + 1] = asm
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    text = open(asm).read() if os.path.exists(asm) else ""
-    shutil.rmtree(tmp, ignore_errors=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" [")[0]] = int(m.group(2))
+    b = devicecode.build("grade.hip")
+    assert "-ffp-contract=off" in b.cmd and "--offload-arch=gfx950" in b.cmd
+    res, text = b.resources, b.asm
     assert sorted(res) == sorted(KERNELS), sorted(res)
     for k, (vgprs, waves) in KERNELS.items():
         r = res[k]

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from framelib import read_pfm
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 from kajo_amd.scene import Scene, stress_scene
@@ -213,17 +214,6 @@ def test_state_and_errors(scenes):
     with pytest.raises(capi.KajoError) as e:
         HipRenderer(sc, W, H, spp=S, seed=SEED, aov=True, tile_index=1, tile_count=2)
     assert e.value.code == capi.KAJO_E_INVALID
-
-
-def read_pfm(path):
-    with open(path, "rb") as f:
-        kind = f.readline().strip()
-        w, h = (int(v) for v in f.readline().split())
-        scale = float(f.readline())
-        data = np.frombuffer(f.read(), "<f4" if scale < 0 else ">f4")
-    c = 3 if kind == b"PF" else 1
-    assert kind in (b"PF", b"Pf") and data.size == w * h * c
-    return data.reshape(h, w, c)[::-1]  # (rows are stored bottom to top)
 
 
 @pytest.mark.skipif(not os.path.exists(BIN), reason="kajo_render not built")

@@ -16,7 +16,8 @@ from kajo_amd.scene import stress_scene
 from oraclelib import available
 
 from aov_specular_replay import describe, replay_specular, with_delta_balls, without_delta
-from test_hip_aov import crowded_scene, open_floor, read_pfm
+from framelib import read_pfm
+from test_hip_aov import crowded_scene, open_floor
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not available("oracle"), reason="oracle not built")]
 SEED = 0o715517

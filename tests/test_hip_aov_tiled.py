@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from framelib import bits
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 from kajo_amd.scene import stress_scene
@@ -27,10 +28,6 @@ FRAMES = [(130, 70, (64, 16)), (130, 70, (32, 8)), (72, 130, (8, 32))]
 FLAGS = [dict(), dict(aov_specular=True), dict(matte=True), dict(matte=True, aov_specular=True)]
 BUILDS = {"strict": dict(strict=True), "exact": dict(exact=True), "fast": dict()}
 OBJECTS = [3, 4, 7]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def same(a, b):

@@ -6,6 +6,7 @@ The call must leave the handle exactly as a twin that never denoised."""
 import numpy as np
 import pytest
 
+from framelib import bits
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 from kajo_amd.scene import stress_scene
@@ -115,10 +116,6 @@ def compare(got, want, passes):
     d = np.abs(got[..., :3].astype(np.float64) - want[..., :3])[fw & fg]
     rel = d / np.maximum(np.abs(want[..., :3][fw & fg]), 1e-2 * passes)
     return float(rel.mean()), float(rel.max()), bool(np.array_equal(fg, fw))
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _build(exact=False, strict=False):

@@ -19,6 +19,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from framelib import bits, read_pfm, read_png, upload_frame
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 from kajo_amd.scene import Scene
@@ -31,10 +32,6 @@ BUILDS = {"fast": dict(), "exact": dict(exact=True), "strict": dict(strict=True)
 REL_TOL, ABS_TOL = 1e-5, 1e-30
 F32 = np.float32
 RING = [(dx, dy) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if (dx, dy) != (0, 0)]  # row-major
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _mean_and_luminance(F, passes):
@@ -137,20 +134,9 @@ def check_against(got, F, passes, **params):
 
 
 def _upload(r, frame, passes, tile=(64, 16)):
-    """Write `frame` (H, W, 4) float32 into the handle's accumulation through its tile buffer and declare it the sum of `passes`;
-    tile = the tile shape the handle was created with."""
-    import torch
-    from bench import DevicePtr
-    H, W = frame.shape[:2]
+    """framelib.upload_frame behind a wait for the handle's own work (this file writes into handles that have just rendered or filtered)"""
     r.wait()
-    ptr, nbytes = r.tile_buffer()
-    buf = torch.as_tensor(DevicePtr(ptr, nbytes // 4), device="cuda").view(-1, 4)
-    ys, xs = np.mgrid[0:H, 0:W]
-    _, slots = TileLayout(W, H, 1, tile).owner_and_slot(xs, ys)
-    buf[torch.as_tensor(slots.reshape(-1).astype(np.int64), device="cuda")] = torch.as_tensor(frame.reshape(-1, 4), device="cuda")
-    torch.cuda.synchronize()
-    r.set_pass_count(passes)
-    assert np.array_equal(bits(r.radiance()), bits(frame))
+    upload_frame(r, frame, passes, tile)
 
 
 SPIKE = F32([900.0, 450.0, 120.0])
@@ -602,7 +588,6 @@ def test_quality_against_a_converged_frame(scenes):
 def test_driver_despeckles_as_the_c_abi(tmp_path, gpus):
     """kajo_render --despeckle --despeckle-factor 2 --glare 0.2 --tonemap reinhard: the pixels of HipRenderer.present on the same frame,
     one owner and three gathered on one device; --hdr stays the accumulation / P; without the option, the image written today."""
-    from test_hip_tonemap import read_pfm, read_png
     scene = os.path.join(ROOT, "kajo_amd", "data", "caustics.json")
     out, raw, hdr = str(tmp_path / "o.png"), str(tmp_path / "o.raw"), str(tmp_path / "o.pfm")
     base = [BIN, "-w", "96", "-h", "54", "-r", "hip", "--passes", "2", "--json", *gpus]
@@ -636,7 +621,6 @@ def test_driver_despeckles_as_the_c_abi(tmp_path, gpus):
 @pytest.mark.skipif(not os.path.exists(BIN), reason="kajo_render not built")
 def test_driver_despeckles_in_front_of_the_denoiser(tmp_path):
     """--denoise FILE with --despeckle, --glare and a tone option writes HipRenderer.present(despeckle=..., denoise=..., glare=..., tone)."""
-    from test_hip_tonemap import read_png
     scene = os.path.join(ROOT, "kajo_amd", "data", "caustics.json")
     dn = str(tmp_path / "d.png")
     p = subprocess.run([BIN, "-w", "96", "-h", "54", "-r", "hip", "--passes", "2", "-o", "", "--denoise", dn, "--despeckle", "--despeckle-factor", "2", "--despeckle-rank", "2", "--despeckle-floor", "0.01",

@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from framelib import read_png
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer, encode_params, encode_pixels, grade_params
 from kajo_amd.tiles import TileLayout
@@ -339,7 +340,6 @@ def test_driver_writes_the_c_abi_s_words(tmp_path, driver_reference, owners):
     """kajo_render --png16 / --dither write the words HipRenderer.present(encode=...) gives on the same frame, for one GPU and for three
     owners on one device (the gathered twin); --json reports the encode; without the options the plain PNG"""
     from test_encode_cpu import read_png16
-    from test_hip_tonemap import read_png
     assert os.path.exists(BIN), BIN
     gpus = {"1": ["--gpus", "1"], "3-on-one-device": ["--gpus", "3", "--same-device"]}[owners]
     ref = driver_reference

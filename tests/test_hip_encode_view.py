@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from framelib import read_png
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer, encode_params, encode_view_pixels
 import encode_view_replay as R
@@ -345,7 +346,6 @@ def test_driver_writes_the_c_abi_s_words(tmp_path, driver_reference, owners):
     for one GPU and for three owners on one device; the same command without the switch writes the file it has always written, the
     16-bit image at the rendered size; --dither goes with the view under the switch"""
     from test_encode_cpu import read_png16
-    from test_hip_tonemap import read_png
     assert os.path.exists(BIN), BIN
     gpus = {"1": ["--gpus", "1"], "3-on-one-device": ["--gpus", "3", "--same-device"]}[owners]
     ref = driver_reference

@@ -15,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from framelib import bits
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 from fixed_instance_scenes import far_sphere_twin, without_a_sphere
@@ -28,10 +29,6 @@ S = 4
 PASSES = 5  # crosses the boundary of the group of passes 1-4
 FRAMES = [(64, 16), (16, 16), (72, 40)]  # one block row; less than a tile; a height that is no multiple of 16, several blocks
 frames = pytest.mark.parametrize("size", FRAMES, ids=["%dx%d" % f for f in FRAMES])
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @pytest.fixture(scope="module")

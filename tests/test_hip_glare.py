@@ -16,10 +16,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from framelib import bits, read_pfm, read_png
+from framelib import upload_frame as _upload
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 from kajo_amd.scene import Scene
-from kajo_amd.tiles import TileLayout
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -85,10 +86,6 @@ def restate(F, passes, levels=6, strength=0.1, threshold=0.0):
     return dict(out=out, counts=counts, m=m, G=G, B0=B[0], n=n)
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def check_against(got, F, passes, **params):
     """The assertion of the module docstring; -> the largest |out - ref| / P over the allowance (1 = at the bound)."""
     want = restate(F, passes, **params)
@@ -102,21 +99,6 @@ def check_against(got, F, passes, **params):
     ratio = float((err[c] / allow[c]).max()) if c.any() else 0.0
     assert ratio <= 1.0, (params, ratio, np.argwhere((err > allow) & c[..., None])[:5])
     return ratio
-
-
-def _upload(r, frame, passes):
-    """Write `frame` (H, W, 4) float32 into the handle's accumulation through its tile buffer and declare it the sum of `passes`."""
-    import torch
-    from bench import DevicePtr
-    H, W = frame.shape[:2]
-    ptr, nbytes = r.tile_buffer()
-    buf = torch.as_tensor(DevicePtr(ptr, nbytes // 4), device="cuda").view(-1, 4)
-    ys, xs = np.mgrid[0:H, 0:W]
-    _, slots = TileLayout(W, H, 1).owner_and_slot(xs, ys)
-    buf[torch.as_tensor(slots.reshape(-1).astype(np.int64), device="cuda")] = torch.as_tensor(frame.reshape(-1, 4), device="cuda")
-    torch.cuda.synchronize()
-    r.set_pass_count(passes)
-    assert np.array_equal(bits(r.radiance()), bits(frame))
 
 
 def synthetic_frames(W, H, passes):
@@ -405,7 +387,6 @@ def test_refusals_and_states_on_a_device(scenes):
 def test_driver_glares_as_the_c_abi(tmp_path, gpus):
     """kajo_render --glare 0.2 --glare-levels 4 --tonemap reinhard: the pixels of HipRenderer.display on the same frame, one owner and
     three gathered on one device; --hdr stays the accumulation / P; --glare 0 writes the image written without the option."""
-    from test_hip_tonemap import read_pfm, read_png
     scene = os.path.join(ROOT, "kajo_amd", "data", "caustics.json")
     out, raw, hdr = str(tmp_path / "o.png"), str(tmp_path / "o.raw"), str(tmp_path / "o.pfm")
     base = [BIN, "-w", "96", "-h", "54", "-r", "hip", "--passes", "2", "--json", *gpus]
@@ -439,7 +420,6 @@ def test_driver_glares_as_the_c_abi(tmp_path, gpus):
 @pytest.mark.skipif(not os.path.exists(BIN), reason="kajo_render not built")
 def test_driver_glares_the_denoised_image(tmp_path):
     """--denoise FILE with --glare and a tone option writes HipRenderer.display(denoise=..., glare=..., tone)."""
-    from test_hip_tonemap import read_png
     scene = os.path.join(ROOT, "kajo_amd", "data", "caustics.json")
     dn = str(tmp_path / "d.png")
     p = subprocess.run([BIN, "-w", "96", "-h", "54", "-r", "hip", "--passes", "2", "-o", "", "--denoise", dn, "--glare", "0.2", "--glare-levels", "4",

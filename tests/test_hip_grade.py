@@ -13,6 +13,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from framelib import bits, read_png
+from framelib import upload_frame as _upload
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer, grade_neutral, grade_params, grade_pixels, grade_white_balance
 from kajo_amd.scene import Scene, stress_scene
@@ -40,10 +42,6 @@ def specs(objects):
         "one_region": dict(slope=[1.1, 1.0, 0.9], regions=[dict(objects=objects[0], amount=1.0, **OPS[0])]),
         "four_regions": dict(saturation=1.3, regions=[dict(objects=o, amount=a, **op) for o, a, op in zip(objects, (0.0, 0.5, 1.0, 0.5), OPS)]),
     }
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _masks(r, spec):
@@ -114,11 +112,6 @@ def test_mirrors_select_the_object_seen_in_them(scenes):
                 check(r, specs(objects)[name], "grid60 %s %s" % (build, name))
             covered = r.matte_mask(objects[1])[0]
             assert 0 < (covered > 0).mean() < 1
-
-
-def _upload(r, frame, passes):
-    from test_hip_lens import _upload as up
-    up(r, frame, passes)
 
 
 def test_pixels_that_do_not_count_keep_their_bits_and_reach_no_neighbour(scenes):
@@ -435,7 +428,6 @@ def driver_reference():
 
 
 def _run_driver(tmp_path, extra):
-    from test_hip_tonemap import read_png
     out = str(tmp_path / "o.png")
     p = subprocess.run(DRIVER + ["-o", out, "--glare", "0.1", "--tonemap", "aces"] + extra + [SCENE], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0, p.stderr

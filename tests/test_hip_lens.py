@@ -18,10 +18,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from framelib import bits, read_png, upload_aov, upload_frame
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 from kajo_amd.scene import Scene, stress_scene
-from kajo_amd.tiles import TileLayout
 from lens_replay import aov_of, bound, counting, depth_fields, planes, restate
 from local_replay import synthetic_frames
 
@@ -35,50 +35,6 @@ FOCUS = 10.0
 SHAPES = [(1, 1), (2, 1), (7, 5), (41, 23), (65, 9), (130, 70)]
 PARAMS = [dict(max_radius=R, aperture=a) for R in (1, 5, 16) for a in (0.01, 0.1, 1.0)]
 SEEN = dict(share=0.0)  # the largest share of the allowance seen in the session, printed by every test that compares
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _tile_view(ptr, nbytes):
-    import torch
-    from bench import DevicePtr
-    return torch.as_tensor(DevicePtr(ptr, nbytes // 4), device="cuda").view(-1, 4)
-
-
-def _slots(W, H):
-    import torch
-    ys, xs = np.mgrid[0:H, 0:W]
-    _, slots = TileLayout(W, H, 1).owner_and_slot(xs, ys)
-    return torch.as_tensor(slots.reshape(-1).astype(np.int64), device="cuda")
-
-
-def _upload(r, frame, passes):
-    """Write `frame` (H, W, 4) float32 into the handle's accumulation through its tile buffer and declare it the sum of `passes`."""
-    import torch
-    H, W = frame.shape[:2]
-    buf = _tile_view(*r.tile_buffer())
-    buf[_slots(W, H)] = torch.as_tensor(np.ascontiguousarray(frame).reshape(-1, 4), device="cuda")
-    torch.cuda.synchronize()
-    r.set_pass_count(passes)
-    assert np.array_equal(bits(r.radiance()), bits(frame))
-
-
-def _upload_aov(r, A, B):
-    """Write the AOV sums into the AOV tile buffer of a one-owner handle with tiled AOVs, then compose them."""
-    import torch
-    H, W = A.shape[:2]
-    ptr, nbytes, _, _ = r.aov_tile_buffers()
-    buf = _tile_view(ptr, nbytes)
-    per_owner = buf.shape[0] // 2
-    slots = _slots(W, H)
-    buf[slots] = torch.as_tensor(np.ascontiguousarray(A).reshape(-1, 4), device="cuda")
-    buf[per_owner + slots] = torch.as_tensor(np.ascontiguousarray(B).reshape(-1, 4), device="cuda")
-    torch.cuda.synchronize()
-    r.compose_aov()
-    a, b = r.aov()["raw"]
-    assert np.array_equal(bits(a), bits(A)) and np.array_equal(bits(b), bits(B))
 
 
 def check_against(got, F, A, B, passes, what="", **params):
@@ -131,9 +87,9 @@ def test_synthetic_frames_and_depths_match_the_restatement(scenes, shape, chunk,
                 continue
             A, B = aov_of(fields[fn])
             if loaded != gn:
-                _upload(r, frames[gn], passes)
+                upload_frame(r, frames[gn], passes)
                 loaded = gn
-            _upload_aov(r, A, B)
+            upload_aov(r, A, B)
             params = dict(PARAMS[(i // chunks + 4 * chunk) % len(PARAMS)], focus_distance=FOCUS)
             check_against(r.lens(**params), frames[gn], A, B, passes, "%dx%d %s %s" % (W, H, fn, gn), **params)
             if gn == "constant":
@@ -150,8 +106,8 @@ def test_copy_and_in_focus_cases(scenes):
     with HipRenderer(scenes["spheres_a43"], W, H, spp=4, exact=True, aov=True, aov_tiled=True) as r:
         A, B = aov_of(depth_fields(W, H, FOCUS)["focus"])
         for name, frame in _frames(W, H, passes).items():
-            _upload(r, frame, passes)
-            _upload_aov(r, A, B)
+            upload_frame(r, frame, passes)
+            upload_aov(r, A, B)
             assert np.array_equal(bits(r.lens(aperture=0.0, focus_distance=3.0, max_radius=7)), bits(frame)), name
             got = r.lens(aperture=1.0, focus_distance=FOCUS)
             m, c = counting(frame, passes)
@@ -275,7 +231,6 @@ LENS = dict(aperture=0.08, focus_distance=6.0, max_radius=12)
 def test_chain_is_the_local_chain_over_the_stage_s_own_frame(scenes):
     """present(lens=L, glare, local, meter, **tone) = kajo_hip_present_local_argb8 over kajo_hip_lens's own frame written into a twin's
     accumulation: the blur sits in front of the glare, behind the despeckle and the denoiser."""
-    from test_hip_local import _upload as upload_frame
     sc = scenes["spheres_a169"]
     gl, lc, mt = dict(levels=4, strength=0.25), dict(iterations=3, compression=0.5), dict(percentile=0.4, auto_white=True)
     with HipRenderer(sc, 130, 70, spp=4, exact=True, aov=True) as r, HipRenderer(sc, 130, 70, spp=4, exact=True) as twin:
@@ -440,7 +395,6 @@ SCENE = os.path.join(ROOT, "kajo_amd", "data", "caustics.json")
 def test_driver_writes_the_c_abi_s_image(tmp_path, driver_reference, owners):
     """kajo_render --lens-aperture 0.05 --lens-max-radius 12 --glare 0.1 --tonemap aces writes the PNG HipRenderer.present gives on the
     same frame focused on the centre pixel; --json reports the focus and the largest radius; --raw stays the accumulation."""
-    from test_hip_tonemap import read_png
     gpus = {"1": ["--gpus", "1"], "3-on-one-device-tiled": ["--gpus", "3", "--same-device", "--aov-tiled"]}[owners]
     ref = driver_reference
     out, raw = str(tmp_path / "o.png"), str(tmp_path / "o.raw")

@@ -13,10 +13,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from framelib import bits, read_pfm, read_png
+from framelib import upload_frame as _upload
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 from kajo_amd.scene import Scene, stress_scene
-from kajo_amd.tiles import TileLayout
 from local_replay import DEFAULTS, base_layer, compare, mean_and_mask, restate, synthetic_frames
 
 pytestmark = pytest.mark.gpu
@@ -41,25 +42,6 @@ COMPRESSIONS = (0.4, 1.0)
 DETAILS = (0.0, 1.0, 2.0)
 SIGMAS = (0.5, 2.0)
 SEEN = dict(mean=0.0, max=0.0)  # the largest figures of the session, printed by every test that compares
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _upload(r, frame, passes):
-    """Write `frame` (H, W, 4) float32 into the handle's accumulation through its tile buffer and declare it the sum of `passes`."""
-    import torch
-    from bench import DevicePtr
-    H, W = frame.shape[:2]
-    ptr, nbytes = r.tile_buffer()
-    buf = torch.as_tensor(DevicePtr(ptr, nbytes // 4), device="cuda").view(-1, 4)
-    ys, xs = np.mgrid[0:H, 0:W]
-    _, slots = TileLayout(W, H, 1).owner_and_slot(xs, ys)
-    buf[torch.as_tensor(slots.reshape(-1).astype(np.int64), device="cuda")] = torch.as_tensor(np.ascontiguousarray(frame).reshape(-1, 4), device="cuda")
-    torch.cuda.synchronize()
-    r.set_pass_count(passes)
-    assert np.array_equal(bits(r.radiance()), bits(frame))
 
 
 def check_against(got, F, passes, what="", want=None, **params):
@@ -443,7 +425,6 @@ def test_driver_maps_as_the_c_abi(tmp_path, driver_reference, owners):
     frame: one owner, three gathered on one device, and two -- on two GPUs where the box shows more than one, else on one device;
     --json reports the pivot and the parameters; --hdr stays the accumulation / P."""
     import torch
-    from test_hip_tonemap import read_pfm, read_png
     gpus = {"1": ["--gpus", "1"], "3-on-one-device": ["--gpus", "3", "--same-device"],
             "2": ["--gpus", "2"] + ([] if torch.cuda.device_count() > 1 else ["--same-device"])}[owners]
     ref = driver_reference
@@ -465,7 +446,6 @@ def test_driver_maps_as_the_c_abi(tmp_path, driver_reference, owners):
 
 @pytest.mark.skipif(not os.path.exists(BIN), reason="kajo_render not built")
 def test_driver_with_contrast_one_writes_the_plain_image(tmp_path, driver_reference):
-    from test_hip_tonemap import read_png
     one, none = str(tmp_path / "1.png"), str(tmp_path / "n.png")
     for path, extra in ((one, ["--local-contrast", "1", "--local-pivot", "metered"]), (none, [])):
         p = subprocess.run(DRIVER + ["--gpus", "1", "-o", path, "--meter-exposure", "0.5", *extra, SCENE], capture_output=True, text=True, timeout=120)

@@ -19,7 +19,8 @@ from oraclelib import available
 
 from aov_specular_replay import material_tables, replay_specular, with_delta_balls, without_delta
 from matte_replay import mask_of, restate
-from test_hip_aov import crowded_scene, open_floor, read_pfm
+from framelib import read_pfm
+from test_hip_aov import crowded_scene, open_floor
 from test_matte_cpu import OVERFLOW
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not available("oracle"), reason="oracle not built")]

@@ -16,6 +16,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from framelib import bits, read_pfm, read_png
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 from kajo_amd.scene import Scene
@@ -31,10 +32,6 @@ BASE = (127 - 16) << 4
 FLT_MAX = np.finfo(F32).max
 RESULT_INTS = ("pixels", "nonfinite", "under", "over", "metered", "minBin", "maxBin")
 RESULT_FLOATS = ("anchorL", "whiteL", "exposure")
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def luminance(F, passes):
@@ -458,7 +455,6 @@ def test_driver_meters_as_the_c_abi(tmp_path, gpus):
     """kajo_render --meter-exposure 0.5 --meter-white 0.995 --tonemap reinhard: the pixels of HipRenderer.present(meter=...) on the same
     frame, one owner and three gathered on one device; the --json fields are the result's; --hdr stays the accumulation / P; without
     the options, the image written today."""
-    from test_hip_tonemap import read_pfm, read_png
     scene = os.path.join(ROOT, "kajo_amd", "data", "caustics.json")
     out, raw, hdr = str(tmp_path / "o.png"), str(tmp_path / "o.raw"), str(tmp_path / "o.pfm")
     base = [BIN, "-w", "96", "-h", "54", "-r", "hip", "--passes", "2", "--json", *gpus]

@@ -16,6 +16,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from framelib import read_pfm
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer, NOISE_MOMENTS, noise_evaluate
 from kajo_amd.tiles import TileLayout
@@ -320,15 +321,6 @@ def driver(tmp_path, *extra, passes=None):
     p = subprocess.run(cmd + [os.path.join(ROOT, "kajo_amd", "data", "caustics.json")], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0, p.stderr
     return json.loads(p.stdout.strip().splitlines()[-1])
-
-
-def read_pfm(path):
-    with open(path, "rb") as f:
-        assert f.readline().strip() == b"PF"
-        w, h = map(int, f.readline().split())
-        scale = float(f.readline())
-        a = np.frombuffer(f.read(), "<f4" if scale < 0 else ">f4").reshape(h, w, 3)
-    return a
 
 
 @pytest.mark.skipif(not os.path.exists(BIN), reason="kajo_render not built")

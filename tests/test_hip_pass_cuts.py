@@ -15,6 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from framelib import bits
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 
@@ -24,10 +25,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "kajo_amd", "host", "kajo_render")
 SEED = 0o715517
 CUTS = [(16,), (8, 8), (4, 12), (1, 2, 13), (3, 5, 8)]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def render_cuts(sc, w, h, cuts, owners=1, warm=0, **kw):

@@ -15,6 +15,7 @@ id maps."""
 import numpy as np
 import pytest
 
+from framelib import bits
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 from adaptive_shape_cases import CASES as SHAPE_CASES, PASSES as ADAPT_PASSES, create_keywords
@@ -28,10 +29,6 @@ BASES = ["spheres_a169", "spheres_a1"]  # spheres_a1: the golden one-light scene
 TWINS = {"turned": turned_twin, "scaled-plane": scaled_plane_twin, "both": both_twin}
 FRAMES = [(72, 40), (130, 70)]
 frames_and_bases = lambda f: pytest.mark.parametrize("size", FRAMES, ids=["72x40", "130x70"])(pytest.mark.parametrize("base", BASES)(f))
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def twins(scenes, base):

@@ -31,6 +31,7 @@ tests/test_hip_noise_tile_shapes.py, which takes TILES, `same` and `bits` from h
 import numpy as np
 import pytest
 
+from framelib import bits
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 from kajo_amd.scene import stress_scene
@@ -46,10 +47,6 @@ W, H = 100, 75
 PASSES = 3
 F32 = np.float32
 tile_id = lambda t: "%dx%d" % t
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def same(a, b):

@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from framelib import bits, read_pfm, read_png
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 from kajo_amd.scene import Scene, stress_scene
@@ -56,10 +57,6 @@ def restate(acc, passes, curve="clamp", exposure=0.0, white=0.0, auto_exposure=F
 
 def channels(argb8):
     return np.stack([(argb8 >> 16) & 255, (argb8 >> 8) & 255, argb8 & 255], -1).astype(np.int64)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _gathered(owners):
@@ -319,34 +316,6 @@ def test_refusals_and_states_on_a_device(scenes):
         assert e.value.code == capi.KAJO_E_STATE
         with pytest.raises(capi.KajoError, match="gathered"):
             _gathered_image(part, None, 64, 48)
-
-
-def read_png(path):
-    import struct
-    import zlib
-    data = open(path, "rb").read()
-    pos, idat, w, h = 8, b"", 0, 0
-    while pos < len(data):
-        n, typ = struct.unpack(">I4s", data[pos:pos + 8])
-        body = data[pos + 8:pos + 8 + n]
-        if typ == b"IHDR":
-            w, h = struct.unpack(">II", body[:8])
-        elif typ == b"IDAT":
-            idat += body
-        pos += 12 + n
-    raw = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(h, 1 + 4 * w)
-    assert (raw[:, 0] == 0).all()
-    return raw[:, 1:].reshape(h, w, 4)
-
-
-def read_pfm(path):
-    with open(path, "rb") as f:
-        kind = f.readline().strip()
-        w, h = (int(v) for v in f.readline().split())
-        scale = float(f.readline())
-        data = np.frombuffer(f.read(), "<f4" if scale < 0 else ">f4")
-    assert kind == b"PF" and data.size == w * h * 3
-    return data.reshape(h, w, 3)[::-1]  # (rows are stored bottom to top)
 
 
 @pytest.mark.skipif(not os.path.exists(BIN), reason="kajo_render not built")

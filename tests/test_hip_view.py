@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from framelib import bits, read_png
 from kajo_amd import capi
 from kajo_amd.renderer import HipRenderer
 from view_replay import FILTERS, restate, test_images as images_of
@@ -22,10 +23,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "kajo_amd", "host", "kajo_render")
 BUILDS = {"fast": dict(), "exact": dict(exact=True), "strict": dict(strict=True)}
 SHAPES = [(1, 1), (2, 1), (7, 5), (41, 23), (65, 9), (130, 70)]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _views(W, H):
@@ -259,7 +256,6 @@ def driver_reference():
 
 
 def _run_driver(tmp_path, name, args):
-    from test_hip_tonemap import read_png
     out = str(tmp_path / name)
     p = subprocess.run([BIN, "-r", "hip", "--passes", "2", "--json", "--tonemap", "aces", "-o", out] + args + [SCENE], capture_output=True,
                        text=True, timeout=120)

@@ -2,37 +2,17 @@
 driven by the headless kajo_render binary, must give exactly the frame the C ABI gives directly."""
 import json
 import os
-import struct
 import subprocess
-import zlib
 
 import numpy as np
 import pytest
 
+from framelib import read_png
 from kajo_amd.renderer import HipRenderer
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "kajo_amd", "host", "kajo_render")
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not os.path.exists(BIN), reason="kajo_render not built")]
-
-
-def read_png(path):
-    data = open(path, "rb").read()
-    assert data[:8] == b"\x89PNG\r\n\x1a\n"
-    pos, idat, w, h = 8, b"", 0, 0
-    while pos < len(data):
-        n, typ = struct.unpack(">I4s", data[pos:pos + 8])
-        body = data[pos + 8:pos + 8 + n]
-        assert zlib.crc32(typ + body) == struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])[0]
-        if typ == b"IHDR":
-            w, h, depth, ctype = struct.unpack(">IIBB", body[:10])
-            assert depth == 8 and ctype == 6
-        elif typ == b"IDAT":
-            idat += body
-        pos += 12 + n
-    raw = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(h, 1 + 4 * w)
-    assert (raw[:, 0] == 0).all()
-    return raw[:, 1:].reshape(h, w, 4)
 
 
 def run(tmp_path, *extra):

@@ -6,44 +6,17 @@ Why a test: both have regressed silently before. A `volatile` access through a g
 the large-scene kernels' list walk carried five of those per round for most of round 4 -- and one more scalar value live across the
 small-scene loop spills five registers (-1.4 %, profiles/HISTORY.md section 4.2). The command is the Makefile's own (`make -n`), with the
 assembly and the resource remarks asked for instead of an object file."""
-import os
 import re
-import shutil
-import subprocess
-import tempfile
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "kajo_amd", "csrc")
+import devicecode
+from devicecode import body as _body
 
 
 def _compile(unit):
-    if shutil.which("hipcc") is None or shutil.which("make") is None:
-        pytest.skip("hipcc / make not available")
-    obj = os.path.join(CSRC, "build", "kernel_%s.o" % unit)
-    plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, obj], capture_output=True, text=True, check=True).stdout
-    cmd = next(l for l in plan.splitlines() if l.startswith("hipcc") and "kernel_%s.hip" % unit in l).split()
-    tmp = tempfile.mkdtemp(prefix="kajo_res_")
-    asm = os.path.join(tmp, "k.s")
-    i = cmd.index("-c")
-    cmd = cmd[:i] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + cmd[i + 1:]
-    cmd[cmd.index("-o") + 1] = asm
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|SGPRs Spill|VGPRs Spill|Occupancy \[waves/SIMD\]|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" [")[0]] = int(m.group(2))
-    text = open(asm).read()
-    shutil.rmtree(tmp, ignore_errors=True)
-    return res, text
+    b = devicecode.build("kernel_%s.hip" % unit)
+    return b.resources, b.asm
 
 
 def test_fast_kernels_keep_their_register_budgets_and_use_no_flat_accesses():
@@ -63,8 +36,7 @@ def test_fast_kernels_keep_their_register_budgets_and_use_no_flat_accesses():
     flat = [l.strip() for l in asm.splitlines() if re.match(r"\s+flat_(load|store|atomic)", l)]
     assert not flat, flat[:5]
     # ... and the cross-lane words of the list walk are LDS instructions, not scratch or global ones
-    body = asm[asm.index("kajo_render_fast_biglist:"):]
-    body = body[:body.index("s_endpgm")]
+    body = _body(asm, "kajo_render_fast_biglist")
     assert "ds_bpermute_b32" in body and "ds_write_b32" in body
 
 
@@ -75,33 +47,24 @@ def test_strict_kernels_keep_their_register_budgets():
         assert k in res, sorted(res)
         r = res[k]
         assert r["Occupancy"] == 4 and r["VGPRs"] <= 128 and r["VGPRs Spill"] == 0 and r["ScratchSize"] == 0, (k, r)
-        body = asm[asm.index(k + ":"):]
-        body = body[:body.index("s_endpgm")]
+        body = _body(asm, k)
         assert not re.search(r"\n\s+flat_(load|store|atomic)", body), k
     # large scenes: an instance per home of the grid's cell lists (LDS: _lg), typed loads in each
     for k in ("kajo_render_strict_big", "kajo_render_strict_biglist", "kajo_render_strict_big_lg", "kajo_render_strict_biglist_lg"):
         r = res[k]
         assert r["Occupancy"] == 4 and r["VGPRs"] <= 128 and r["VGPRs Spill"] <= 16, (k, r)
-        body = asm[asm.index(k + ":"):]
-        body = body[:body.index("s_endpgm")]
+        body = _body(asm, k)
         assert not re.search(r"\n\s+flat_(load|store|atomic)", body), k
     # the sweep of the strict math over every binary32 (kajo_hip_kat_strictmath_sweep): plain C++ around the header, measured 38 VGPRs,
     # eight waves per SIMD, nothing spilled; its only memory accesses are the LDS reduction and one pair of global stores a workgroup
     r = res["kajo_kat_math_sweep"]
     assert r["Occupancy"] == 8 and r["VGPRs"] <= 48 and r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0 and r["ScratchSize"] == 0, r
-    body = asm[asm.index("kajo_kat_math_sweep:"):]
-    body = body[:body.index("s_endpgm")]
+    body = _body(asm, "kajo_kat_math_sweep")
     assert not re.search(r"\n\s+(flat_|global_load|global_atomic|scratch_)", body)
     # (the known-answer kernels walk the grid through a pointer of either home: the only flat accesses of the unit)
     for k in ("kajo_kat_shade_strict", "kajo_kat_trace_strict"):
-        body = asm[asm.index(k + ":"):]
-        body = body[:body.index("s_endpgm")]
+        body = _body(asm, k)
         assert sorted(re.findall(r"\n\s+(flat_\w+)", body)) == ["flat_load_dwordx2", "flat_load_ushort"], k
-
-
-def _body(asm, kernel):
-    body = asm[asm.index(kernel + ":"):]
-    return body[:body.index("s_endpgm")]
 
 
 def _valu(asm, kernel):

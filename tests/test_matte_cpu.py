@@ -7,9 +7,7 @@ and on the overflow fixture. The compile commands are the Makefile's own (`make 
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -20,8 +18,8 @@ from kajo_amd.scene import stress_scene
 from oraclelib import available
 
 from matte_replay import mask_of, ranked, restate, tables
-from test_aov_cpu import _body
-from test_aov_cpu import _compile as _compile_unit
+import devicecode
+from devicecode import body as _body
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "kajo_amd", "csrc")
@@ -119,32 +117,14 @@ def test_driver_help_lists_the_matte_options():
 
 
 def _compile_matte():
-    if shutil.which("hipcc") is None or shutil.which("make") is None:
-        pytest.skip("hipcc / make not available")
-    obj = os.path.join(CSRC, "build", "matte.o")
-    plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, obj], capture_output=True, text=True, check=True).stdout
-    cmd = next(l for l in plan.splitlines() if l.startswith("hipcc") and "matte.hip" in l).split()
-    assert "-ffp-contract=off" in cmd and "--offload-arch=gfx950" in cmd
-    tmp = tempfile.mkdtemp(prefix="kajo_matte_res_")
-    asm = os.path.join(tmp, "k.s")
-    i = cmd.index("-c")
-    cmd = cmd[:i] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + cmd[i + 1:]
-    cmd[cmd.index("-o") + 1] = asm
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" [")[0]] = int(m.group(2))
-    text = open(asm).read()
-    shutil.rmtree(tmp, ignore_errors=True)
-    return res, text
+    b = devicecode.build("matte.hip")
+    assert "-ffp-contract=off" in b.cmd and "--offload-arch=gfx950" in b.cmd
+    return b.resources, b.asm
+
+
+def _compile_unit(unit):
+    b = devicecode.build("kernel_%s.hip" % unit)
+    return b.resources, b.asm
 
 
 def test_matte_kernels_spill_nothing_and_use_no_scratch_lds_flat_or_atomics():

@@ -8,13 +8,12 @@ command is the Makefile's own (`make -n`)."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import devicecode
 from kajo_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -352,32 +351,9 @@ def test_the_plan_is_exported_and_the_partials_stay_under_a_megabyte():
 
 
 def _compile():
-    if shutil.which("hipcc") is None or shutil.which("make") is None:
-        pytest.skip("hipcc / make not available")
-    obj = os.path.join(CSRC, "build", "meter.o")
-    plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, obj], capture_output=True, text=True, check=True).stdout
-    cmd = next(l for l in plan.splitlines() if l.startswith("hipcc") and "meter.hip" in l).split()
-    assert "-ffp-contract=off" in cmd and "--offload-arch=gfx950" in cmd
-    tmp = tempfile.mkdtemp(prefix="kajo_meter_res_")
-    asm = os.path.join(tmp, "k.s")
-    i = cmd.index("-c")
-    cmd = cmd[:i] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + cmd[i + 1:]
-    cmd[cmd.index("-o") + 1] = asm
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" [")[0]] = int(m.group(2))
-    text = open(asm).read()
-    shutil.rmtree(tmp, ignore_errors=True)
-    return res, text
+    b = devicecode.build("meter.hip")
+    assert "-ffp-contract=off" in b.cmd and "--offload-arch=gfx950" in b.cmd
+    return b.resources, b.asm
 
 
 def test_meter_kernels_spill_nothing_and_use_no_scratch_flat_or_global_atomics():
@@ -388,8 +364,7 @@ def test_meter_kernels_spill_nothing_and_use_no_scratch_flat_or_global_atomics()
         print(k, r)
         assert r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0 and r["ScratchSize"] == 0, (k, r)
         assert abs(r["VGPRs"] - vgprs) <= VGPR_ROOM and r["Occupancy"] == 8 and r["LDS Size"] == lds, (k, r)  # (full occupancy; LDS: 515 counters, the sum's 8 x 32 shares)
-        body = asm[asm.index("\n" + k + ":"):]
-        body = body[:body.index("s_endpgm")]
+        body = devicecode.body(asm, k)
         assert not re.search(r"\n\s+flat_\w+", body), (k, re.findall(r"\n\s+(flat_\w+)", body)[:5])
         assert not re.search(r"\n\s+scratch_\w+", body), k
         assert not re.search(r"\n\s+\w*atomic\w*", body), k  # (global_atomic_*, buffer_atomic_*: the LDS adds are ds_add_u32)

@@ -6,17 +6,15 @@ device code of every kernel from before is what it was, function by function, ag
 kernels live in a translation unit of their own, which no other unit includes; the driver's refusals; and the DEFINITION against the
 CPU oracle: over K seeds the variance the estimate predicts for the mean must be the variance the means show."""
 import ctypes as C
-import importlib.util
 import json
 import os
 import re
-import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import devicecode
 from kajo_amd import capi
 from kajo_amd.renderer import noise_evaluate
 from oraclelib import OracleLib, available
@@ -177,32 +175,9 @@ def test_evaluate_hand_made_histograms_against_numpy():
 
 
 def _compile():
-    if shutil.which("hipcc") is None or shutil.which("make") is None:
-        pytest.skip("hipcc / make not available")
-    obj = os.path.join(CSRC, "build", "noise.o")
-    plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, obj], capture_output=True, text=True, check=True).stdout
-    cmd = next(l for l in plan.splitlines() if l.startswith("hipcc") and "/noise.hip" in l).split()
-    assert "-ffp-contract=off" in cmd and "--offload-arch=gfx950" in cmd
-    tmp = tempfile.mkdtemp(prefix="kajo_noise_res_")
-    asm = os.path.join(tmp, "k.s")
-    i = cmd.index("-c")
-    cmd = cmd[:i] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + cmd[i + 1:]
-    cmd[cmd.index("-o") + 1] = asm
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" [")[0]] = int(m.group(2))
-    text = open(asm).read()
-    shutil.rmtree(tmp, ignore_errors=True)
-    return res, text
+    b = devicecode.build("noise.hip")
+    assert "-ffp-contract=off" in b.cmd and "--offload-arch=gfx950" in b.cmd
+    return b.resources, b.asm
 
 
 def test_noise_kernels_spill_nothing_and_use_no_scratch_or_flat_access():
@@ -212,8 +187,7 @@ def test_noise_kernels_spill_nothing_and_use_no_scratch_or_flat_access():
         r = res[k]
         print(k, r)
         assert r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0 and r["ScratchSize"] == 0 and r["Occupancy"] == 8, (k, r)
-        body = asm[asm.index("\n" + k + ":"):]
-        body = body[:body.index("s_endpgm")]
+        body = devicecode.body(asm, k)
         assert not re.search(r"\n\s+flat_\w+", body), (k, re.findall(r"\n\s+(flat_\w+)", body)[:5])
         assert not re.search(r"\n\s+scratch_\w+", body), k
         loads = re.findall(r"\n\s+(global_load_\w+)", body)
@@ -234,28 +208,20 @@ def test_noise_kernels_spill_nothing_and_use_no_scratch_or_flat_access():
             assert atomics == {"global_atomic_add"} and "ds_add_u32" in body and "ds_add_rtn" not in body, atomics
 
 
-def _digest_tool():
-    spec = importlib.util.spec_from_file_location("kernel_digests", os.path.join(ROOT, "tools", "kernel_digests.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
-    return tool
-
-
 def test_the_device_code_of_every_kernel_from_before_is_unchanged_function_by_function():
     """tests/golden/kernel_digests_before_noise.json: a SHA-256 per function of every device unit, recorded from the commit in front of the
     noise estimate (tools/kernel_digests.py: the Makefile's own commands, -S --cuda-device-only; a function is its label to its .Lfunc_end,
     comments dropped). The working tree, compiled the same way, must give the same functions with the same digests in the same units, and
     one unit more, noise, with the two kernels and nothing else. A shared header (render_args.h, device_scene.h), a flag of the Makefile or
     a source that moved a kernel shows here, whatever its text looks like."""
-    if shutil.which("hipcc") is None or shutil.which("make") is None:
-        pytest.skip("hipcc / make not available")
-    tool = _digest_tool()
+    devicecode.need_tools()
+    tool = devicecode.digest_tool()
     recorded = json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_digests_before_noise.json")))
     before = recorded["units"]
     assert sorted(before) == sorted(["kernel_fast", "kernel_exact", "kernel_strict", "aux_kernels", "denoise", "glare", "despeckle", "meter", "local",
                                      "lens", "view", "matte", "grade"])
     assert sum(len(f) for f in before.values()) > 100 and all(re.fullmatch(r"[0-9a-f]{64}", d) for f in before.values() for d in f.values())
-    now = tool.digests(CSRC)
+    now = devicecode.digests_now()
     assert sorted(now) == sorted(list(before) + ["noise"]), sorted(now)
     assert sorted(now.pop("noise")) == sorted(KERNELS)
     where = "(recorded with %s; this is %s)" % (recorded["compiler"], tool.compiler())

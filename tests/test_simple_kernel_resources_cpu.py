@@ -4,11 +4,9 @@ exists to carry FEWER instructions than that kernel -- the loops for general sph
 the instruction budget is the point: measured 1959 static vector instructions against kajo_render_exact's 2278."""
 import os
 import re
-import shutil
 import subprocess
-import tempfile
 
-import pytest
+import devicecode
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "kajo_amd", "csrc")
@@ -17,31 +15,8 @@ VALU_BUDGET = 2000
 
 
 def _compile():
-    if shutil.which("hipcc") is None or shutil.which("make") is None:
-        pytest.skip("hipcc / make not available")
-    obj = os.path.join(CSRC, "build", "kernel_exact_simple.o")
-    plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, obj], capture_output=True, text=True, check=True).stdout
-    cmd = next(l for l in plan.splitlines() if l.startswith("hipcc") and "kernel_exact_simple.cpp" in l).split()
-    tmp = tempfile.mkdtemp(prefix="kajo_res_")
-    asm = os.path.join(tmp, "k.s")
-    i = cmd.index("-c")
-    cmd = cmd[:i] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + cmd[i + 1:]
-    cmd[cmd.index("-o") + 1] = asm
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|SGPRs Spill|VGPRs Spill|Occupancy \[waves/SIMD\]|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" [")[0]] = int(m.group(2))
-    text = open(asm).read()
-    shutil.rmtree(tmp, ignore_errors=True)
-    return res, text
+    b = devicecode.build("kernel_exact_simple.cpp")
+    return b.resources, b.asm
 
 
 def test_the_unit_holds_one_kernel_within_the_exact_kernels_budgets():
@@ -49,8 +24,7 @@ def test_the_unit_holds_one_kernel_within_the_exact_kernels_budgets():
     assert sorted(res) == [KERNEL], sorted(res)
     r = res[KERNEL]
     assert r["Occupancy"] == 5 and r["VGPRs"] <= 96 and r["VGPRs Spill"] == 0 and r["ScratchSize"] == 0 and r["SGPRs Spill"] <= 10, r
-    body = asm[asm.index(KERNEL + ":"):]
-    body = body[:body.index("s_endpgm")]
+    body = devicecode.body(asm, KERNEL)
     assert not re.search(r"\n\s+flat_(load|store|atomic)", body)
     assert "v_div_scale_f32" not in body and "v_div_fmas_f32" not in body and "v_div_fixup_f32" in body
     n = len(re.findall(r"\n\s+v_\w+", body))

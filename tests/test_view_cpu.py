@@ -8,13 +8,12 @@ import ctypes as C
 import math
 import os
 import re
-import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import devicecode
 from kajo_amd import capi
 from kajo_amd.renderer import view_tables, view_weights
 import view_replay
@@ -417,29 +416,9 @@ KERNELS = {"kajo_view_rows": (35, 8, 5120), "kajo_view_columns": (11, 8, 1024)}
 
 
 def test_view_kernels_keep_their_budgets():
-    if shutil.which("hipcc") is None or shutil.which("make") is None:
-        pytest.skip("hipcc / make not available")
-    obj = os.path.join(CSRC, "build", "view.o")
-    plan = subprocess.run(["make", "-n", "-B", "-C", CSRC, obj], capture_output=True, text=True, check=True).stdout
-    cmd = next(l for l in plan.splitlines() if l.startswith("hipcc") and "view.hip" in l).split()
-    assert "-ffp-contract=off" in cmd and "--offload-arch=gfx950" in cmd
-    tmp = tempfile.mkdtemp(prefix="kajo_view_res_")
-    i = cmd.index("-c")
-    cmd = cmd[:i] + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage"] + cmd[i + 1:]
-    cmd[cmd.index("-o") + 1] = os.path.join(tmp, "k.s")
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    shutil.rmtree(tmp, ignore_errors=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            res[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and name:
-            res[name][m.group(1).split(" [")[0]] = int(m.group(2))
+    b = devicecode.build("view.hip")
+    assert "-ffp-contract=off" in b.cmd and "--offload-arch=gfx950" in b.cmd
+    res = b.resources
     assert sorted(res) == sorted(KERNELS), sorted(res)
     for k, (vgprs, waves, lds) in KERNELS.items():
         r = res[k]
